@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the MI355X-native RTFS-Net separator forward.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment, one rank per GPU over RCCL), or started plainly as `python bench.py --gpus N ...`:
@@ -11,7 +11,8 @@ relays rank 0's JSON line and exits non-zero if any rank failed.
 Metric (BASELINE.json): mixtures/s of the RTFS-Net-4 forward on synthetic 2 s @16 kHz 2-speaker mixtures with
 dummy lip embeddings, batch 32 per GPU (configs[1]); inputs and weights are resident in HBM before the timed
 region.  One "step" = one forward over one batch.  Weak scaling: every rank runs its own batch, there is no
-data-path collective (utterances are independent in the forward).  Rank 0 prints ONE JSON line that also carries
+data-path collective (utterances are independent in the forward).  --dump-outputs DIR: after the timed steps, rank 0 writes what
+its last timed step returned as DIR/<name>.npy (`dump_outputs`).  Rank 0 prints ONE JSON line that also carries
   roofline      the fused dual-path sweep kernel: algorithmic bytes (20*L*N*64 per SRU layer, 4 layers per
                 launch) / its launch duration measured live with HIP events on the launch stream, vs 8 TB/s HBM
   cpu_baseline  the CPU oracle (oracle/rtfs_oracle.py, numpy) timed on this box's host cores on a bounded sample
@@ -204,6 +205,26 @@ def throughput(world, B, steps, dt):
     return world * B * steps / dt
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  The inputs and weights are seeded, so two builds run with the same
+    arguments can be compared output for output.  An array past its share of DUMP_BYTES is replaced by the same seeded sample of its
+    flattened elements (sorted indices) in every run.  Returns what was written, for the JSON line."""
+    os.makedirs(path, exist_ok=True)
+    budget = (DUMP_BYTES - 4096) // 4 // len(arrays)  # floats per array; 4096 bytes left for the .npy headers
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        info[name] = {"shape": list(a.shape), "sampled_elements": None}
+        if a.size > budget:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, budget, replace=False))]
+            info[name]["sampled_elements"] = budget
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": info}
+
+
 def spawn_ranks(n, argv, timeout=3000):
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes of THIS process, which has not
     touched the GPU (no HIP call, no torch.cuda.is_available()) and never will: it only waits, relays rank 0's JSON line (its stdout)
@@ -301,10 +322,13 @@ def dry_run_main(args):
     assert bool(torch.isfinite(chk))
     ev = dist_evidence(dist, world)
     if rank == 0:
-        print(json.dumps({"metric": "dry run (launcher + rendezvous + timing protocol only; NOT a measurement)", "dist": ev, "value": round(throughput(world, B, args.steps, dt), 3),
-                          "unit": "mixtures/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-                          "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-                          "config": {"workload": "stand-in step on CPU over gloo", "per_gpu_batch": B, "global_batch": B * world}}), flush=True)
+        res = {"metric": "dry run (launcher + rendezvous + timing protocol only; NOT a measurement)", "dist": ev, "value": round(throughput(world, B, args.steps, dt), 3),
+               "unit": "mixtures/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "config": {"workload": "stand-in step on CPU over gloo", "per_gpu_batch": B, "global_batch": B * world}}
+        if args.dump_outputs:
+            res["dump_outputs"] = dump_outputs(args.dump_outputs, {"out": chk})
+        print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -351,6 +375,8 @@ def train_main(args):
         extra = {"roofline": train_roofline(dev, B, L)}
         if cpu_res is not None:
             extra["cpu_baseline"] = cpu_res
+        if args.dump_outputs:
+            extra["dump_outputs"] = dump_outputs(args.dump_outputs, {"loss": last})
         print(json.dumps({
             "metric": f"mixtures/sec trained ({args.seconds:g} s@16 kHz) RTFS-Net-{args.repeats} training step", "value": round(throughput(world, B, args.steps, dt), 3),
             "unit": "mixtures/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -383,9 +409,16 @@ def main():
                     help="measure the training step instead (forward_train + PIT loss + HIP backward + one flattened gradient all-reduce "
                          "over RCCL + clip + AdamW; SyncBatchNorm at N > 1); not the contract metric, a separate JSON line")
     ap.add_argument("--dist-dry-run", action="store_true", help="CPU/gloo rehearsal of the multi-rank protocol with a stand-in step (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the separated waveforms; the loss with --train) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        return spawn_ranks(args.gpus, sys.argv[1:])  # this process never touches the GPU
+        # the ranks start in ROOT: a relative --dump-outputs is passed on as the directory it names here (the last occurrence wins)
+        argv = sys.argv[1:] + (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
+        return spawn_ranks(args.gpus, argv)  # this process never touches the GPU
     if args.dist_dry_run:
         return dry_run_main(args)
     if args.train:
@@ -425,6 +458,7 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
     assert bool(torch.isfinite(out).all())
+    last_step = {"out": out.cpu()} if args.dump_outputs else None  # what the last timed forward returned: (B, 1, L) separated waveforms
 
     # per-launch durations of the dominant kernel, recorded during the timed region
     cap = 4096
@@ -507,6 +541,8 @@ def main():
             res["batch_split_2"] = split2
         if cpu_res is not None:
             res["cpu_baseline"] = cpu_res
+        if args.dump_outputs:
+            res["dump_outputs"] = dump_outputs(args.dump_outputs, last_step)
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()

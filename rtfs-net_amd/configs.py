@@ -2,7 +2,7 @@
 
 config/lrs2_RTFSNet_{4,6,12}_layer.yaml differ only in `audio_params.repeats` (the block weights are shared, `shared: true`), so one
 dictionary + the repeat count covers the BASELINE configurations; bench.py, __graft_entry__.smoke() and the tests build their models
-from here (tests/test_host.py checks the dictionary against the reference's yaml when /root/reference is mounted).
+from here (tests/test_host.py checks the dictionary against the reference yaml's section, stored as tests/golden/config_R4_audionet.json).
 """
 import copy
 

@@ -6,6 +6,9 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
+import torch
+
 from tests.util import ROOT
 
 WORKER = r"""
@@ -170,3 +173,54 @@ def test_bench_self_launch_with_the_real_forward_on_one_gpu():
     assert r["n_gpus"] == 2 and r["config"]["global_batch"] == 4 and r["value"] > 0 and "cpu_baseline" not in r
     # 2 steps x 8 sweep launches, every third one timed (bench.py: rtfs_sweep_timing_enable(3))
     assert r["roofline"]["launches_timed"] == len(range(0, 2 * 8, 3)) and 0 < r["roofline"]["frac"] < 2
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: rank 0 writes what the last timed step returned as DIR/<name>.npy in float32 and names it in the JSON line.  A
+    relative DIR is the caller's directory also when the parent spawns the ranks (they start in the repository root)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--dist-dry-run",
+                         "--dump-outputs", "dump"], cwd=tmp_path, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert pr.returncode == 0, pr.stderr[-2000:]
+    rec = json.loads([l for l in pr.stdout.splitlines() if l.startswith("{")][0])
+    assert rec["steps"] == 2 and rec["dump_outputs"]["arrays"] == {"out": {"shape": [], "sampled_elements": None}}
+    out = np.load(tmp_path / "dump" / "out.npy")
+    assert out.dtype == np.float32 and out.shape == () and np.isfinite(out)
+    pr = _bench("--steps", "0", "--dist-dry-run")
+    assert pr.returncode != 0 and "--steps" in pr.stderr
+
+
+def test_bench_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """Past DUMP_BYTES in all, an array is replaced by a seeded sample of its elements: the same one in every run, in index order."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 4 * 2 * 100)  # 100 floats for each of two arrays
+    x = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    for d in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / d), {"x": x, "y": torch.ones(50)})
+        assert info["arrays"] == {"x": {"shape": [10, 100], "sampled_elements": 100}, "y": {"shape": [50], "sampled_elements": None}}
+        assert sum(os.path.getsize(tmp_path / d / f) for f in ("x.npy", "y.npy")) <= bench.DUMP_BYTES
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "y.npy"), np.ones(50, np.float32))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_forward(tmp_path):
+    """bench.py --dump-outputs with the real forward: out.npy is the separator's output for bench.py's seeded inputs and weights (the
+    torch.manual_seed(0) initialisation), against the CPU oracle with the same weights."""
+    import bench
+    import rtfs_net_amd as R
+    from oracle import rtfs_oracle as O
+    from tests.util import rel_err
+    pr = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--seconds", "0.25", "--repeats", "2", "--no-cpu-baseline",
+                "--dump-outputs", str(tmp_path))
+    assert pr.returncode == 0, pr.stderr[-2000:]
+    rec = json.loads([l for l in pr.stdout.splitlines() if l.startswith("{")][0])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["dump_outputs"]["arrays"]["out"]["shape"] == [2, 1, 4000]
+    got = np.load(tmp_path / "out.npy")
+    torch.manual_seed(0)
+    m = R.AVNet(print_macs=False, **bench.audionet_config(2)).eval()
+    wav, emb = bench.rank_inputs(0, 2, 4000, 6)
+    ref = O.avnet_forward(wav.numpy(), emb.numpy(), {k: v.numpy() for k, v in m.state_dict().items()}, repeats=2)
+    assert got.dtype == np.float32 and got.shape == ref.shape == (2, 1, 4000)
+    assert rel_err(got, ref) <= 1e-4, rel_err(got, ref)
