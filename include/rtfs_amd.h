@@ -23,8 +23,9 @@
  *     the diagnostic sweep-timing log (off by default), so the
  *     library may be driven from several host threads / devices in one process (one thread per stream).
  *   - length limits of the FUSED entry points (they keep a whole sweep / score row / video pyramid on chip and return -1 beyond):
- *       sweep axis of rtfs_dualpath_* / rtfs_block_f32 / rtfs_separator_forward_f32   <= 250 positions (T/2 <= 250: 4 s of audio)
- *       keys of rtfs_tf_attention_f32                                                 <= 256
+ *       time sweep (dim 3) of rtfs_dualpath_sru_f32                                   <= 512 positions (8.2 s of audio)
+ *       frequency sweep, rtfs_dualpath_lstm_f32, rtfs_block_f32, rtfs_separator_forward_f32  <= 250 positions (T/2 <= 250: 4 s of audio)
+ *       keys of rtfs_tf_attention_f32                                                 <= 512
  *       video frames of rtfs_vp_block_f32                                             <= 120
  *     The reference has no length limit (rnn_layers.py:136-162, attention.py:149-189; infer_any_video.py:86 feeds whole files): longer
  *     inputs go through the UNFUSED entry points below (rtfs_*_forward_train_f32 and friends: GEMM + scan + GEMM sweeps, batched-GEMM
@@ -82,7 +83,9 @@ int rtfs_block_f32(const float* x, const float* x_res, const float* pack, float*
                    size_t ws_bytes, void* stream, int rnn_kind /* 0 = SRU pack, 1 = LSTM pack */);
 
 /* DualPathRNN.forward with rnn_type SRU, kernel 8, stride 1, 4 layers, bidirectional, hidden 32
- * (src/models/layers/rnn_layers.py:136-162).  x, out (B,64,T,F); dim = 4 sweeps along F, 3 along T. */
+ * (src/models/layers/rnn_layers.py:136-162).  x, out (B,64,T,F); dim = 4 sweeps along F (F <= 250), 3 along T (T <= 512).  Past
+ * T = 256 the batch runs in consecutive sub-batches of < 4 GB each (the sweep kernel's 32-bit offsets), any B; past T = 250 the sweep is
+ * the f16x3 kernel whatever RTFS_GEMM_F32 says (the exact-f32 A/B kernels stop at 250). */
 size_t rtfs_dualpath_workspace_bytes(int B, int T, int F);
 int rtfs_dualpath_sru_f32(const float* x, const float* pack, float* out, int B, int T, int F, int dim, void* ws,
                           size_t ws_bytes, void* stream);

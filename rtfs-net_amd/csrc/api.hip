@@ -249,9 +249,19 @@ int dualpath(const DpPack& p, const float* x, float* out, int B, int T, int F, i
         if (!gemm_f32() && !p.whh) return launch_dualpath16(dp16_args(p, x, out, B * T, T, F, CH * plane, F, plane), st);
         return launch_dualpath(dp_args(p, x, out, T, F, CH * plane, F, plane), B * T, st);
     }
-    RTFS_RETURN_IF(T < 8 || T > 250, RTFS_ERR_SHAPE);
+    // along T: the SRU cell's fused sweep takes T <= 512 (k_dualpath16s.hip, two passes past 256; there the exact-f32 switch has no kernel of
+    // its own and does not apply), the LSTM cell 250
+    RTFS_RETURN_IF(T < 8 || T > (p.whh ? 250 : 512), RTFS_ERR_SHAPE);
     CHECK(launch_transpose(x, tA, B * CH, T, F, st));
-    if (!gemm_f32() && !p.whh) {
+    if (T > 256 && !p.whh) {
+        // the two-pass kernel addresses a launch's tensor with 32-bit byte offsets and has no 64-bit fall-back: consecutive sub-batches of
+        // samples, each spanning < 4 GB (T = 512, F = 64: 511 samples)
+        const int nb = (int)std::min<size_t>((size_t)B, (((size_t)1 << 32) - 1) / (CH * plane * sizeof(float)));
+        for (int b0 = 0; b0 < B; b0 += nb) {
+            const int n = std::min(nb, B - b0);
+            CHECK(launch_dualpath16(dp16_args(p, tA + (size_t)b0 * CH * plane, tB + (size_t)b0 * CH * plane, n * F, F, T, CH * plane, T, plane), st));
+        }
+    } else if ((!gemm_f32() || T > 250) && !p.whh) {
         CHECK(launch_dualpath16(dp16_args(p, tA, tB, B * F, F, T, CH * plane, T, plane), st));
     } else {
         CHECK(launch_dualpath(dp_args(p, tA, tB, F, T, CH * plane, T, plane), B * F, st));
@@ -761,7 +771,7 @@ size_t rtfs_tf_attention_workspace_bytes(int B, int T) { return (size_t)B * T * 
 
 int rtfs_tf_attention_f32(const float* x, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, void* stream) {
     RTFS_RETURN_IF(!x || !pack || !out || B < 1, RTFS_ERR_ARG);
-    RTFS_RETURN_IF(T < 1 || T > 256, RTFS_ERR_SHAPE);
+    RTFS_RETURN_IF(T < 1 || T > 512, RTFS_ERR_SHAPE);
     Arena ar(ws, ws_bytes);
     float* q = ar.take<float>((size_t)B * 4 * T * 256);
     float* k = ar.take<float>((size_t)B * 4 * T * 256);

@@ -192,17 +192,17 @@ __global__ __launch_bounds__(256) void attn_core_kernel(AttnArgs a) {
     const float* __restrict__ K = a.k + ((size_t)b * 4 + hd) * T * 256;
     const float* __restrict__ V = a.v + ((size_t)b * 4 + hd) * T * 1024;
 
-    // ---- scores S = Q K^T / 16: wave w owns key tiles w and w + 4
-    {
+    // ---- scores S = Q K^T / 16: wave w owns key tiles w and w + 4 of every group of eight (T <= 512: two groups)
+    for (int kg = 0; kg < NKT; kg += 8) {
         f32x16 acc[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
         const float* __restrict__ qp = Q + (size_t)min(q0 + r, T - 1) * 256 + 8 * h;
-        const float* __restrict__ kp0 = K + (size_t)min(wave * 32 + r, T - 1) * 256 + 8 * h;
-        const float* __restrict__ kp1 = K + (size_t)min((wave + 4) * 32 + r, T - 1) * 256 + 8 * h;
-        const bool two = wave + 4 < NKT;
+        const float* __restrict__ kp0 = K + (size_t)min((kg + wave) * 32 + r, T - 1) * 256 + 8 * h;
+        const float* __restrict__ kp1 = K + (size_t)min((kg + wave + 4) * 32 + r, T - 1) * 256 + 8 * h;
+        const bool two = kg + wave + 4 < NKT;
 #pragma unroll 4
         for (int ks = 0; ks < 16; ++ks) {
             float qv[8], k0[8], k1[8];
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void attn_core_kernel(AttnArgs a) {
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int kt = wave + 4 * j;
+            const int kt = kg + wave + 4 * j;
             if (kt < NKT) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) S[((q & 3) + 8 * (q >> 2) + 4 * h) * ldp + kt * 32 + r] = acc[j][q] * a.scale;
@@ -333,7 +333,7 @@ int launch_row_can_proj(const RowCanArgs& a_, int B, hipStream_t st) {
     return rtfs_launch_status();
 }
 int launch_attn_core(const AttnArgs& a, int B, hipStream_t st) {
-    if (a.T < 1 || a.T > 256) return RTFS_ERR_SHAPE;
+    if (a.T < 1 || a.T > 512) return RTFS_ERR_SHAPE;  // (the score tile: 66 KB at 512 keys)
     const size_t lds = attn_core_lds_bytes(a.T);
     if (rtfs_set_max_lds((const void*)attn_core_kernel, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
     AttnArgs a2 = a;

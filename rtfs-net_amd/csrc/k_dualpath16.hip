@@ -441,15 +441,17 @@ static int launch_dp16_t(const Dp16Args& a, hipStream_t st) {
 
 int launch_dualpath16(const Dp16Args& a, hipStream_t st) {
     const int L = a.Ls - 7;
-    if (L < 1 || a.Ls > 256) return RTFS_ERR_SHAPE;
-    // (all routing is by Ls = L + 7: the load phase and the conv-transpose output cover Ls rows - 64 / 128 / 256 per configuration)
+    if (L < 1 || a.Ls > 512) return RTFS_ERR_SHAPE;
+    // (all routing is by Ls = L + 7: the load phase and the conv-transpose output cover Ls rows - 64 / 128 / 256 per configuration; 257 .. 512:
+    // generation 3 only)
     // generation 3 (k_dualpath16s.hip: two workgroups per CU up to Ls = 128, its 512-thread variant above); RTFS_SWEEP_GEN2=1 keeps this file's
     // kernels for A/B
     static const bool gen2 = getenv("RTFS_SWEEP_GEN2") != nullptr;
-    if (!gen2) {
+    if (!gen2 || a.Ls > 256) {  // (past 256 positions there is no generation-2 kernel: the switch applies to the shorter sweeps)
         const int rc = launch_dualpath16s(a, st);
         if (rc != RTFS_ERR_SHAPE) return rc;  // (a tensor spanning >= 4 GB: this file's kernels address with 64 bits)
     }
+    if (a.Ls > 256) return RTFS_ERR_SHAPE;
     if (a.stamps) {
         if (a.Ls <= 64) return launch_dp16_stamp_t<4, 2, true>(a, st);
         if (a.Ls <= 128) return launch_dp16_stamp_t<2, 4, true>(a, st);

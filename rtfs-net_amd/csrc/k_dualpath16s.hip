@@ -23,7 +23,12 @@
 //   * T sweep (Ls <= 128): 1 sequence per workgroup, wave = (time part of 64 steps, direction): the A-operand rows of a tile are
 //     ordered so that lane half h holds 16 CONSECUTIVE steps (16 h + q); the halves take turns 16 steps at a time (one
 //     v_permlane32_swap per hand-off), the resting half masked by EXEC;
-//   * Ls <= 256 (the 4 s time sweep): the same single-sequence program with FOUR time parts - 512 threads, 102 KB, one workgroup per CU.
+//   * Ls <= 256 (the 4 s time sweep): the same single-sequence program with FOUR time parts - 512 threads, 102 KB, one workgroup per CU;
+//   * Ls <= 512 (the 8 s time sweep): the 4 s program walked in TWO passes of 256 steps per layer (NPASS = 2).  The plane of 512 rows is
+//     142 KB, so the weight stream has ONE 16 KB buffer (158 KB in all): a K step reads its fragments, meets the other waves at a barrier,
+//     then overwrites the buffer with the next step.  A pass's GEMM reads rows the other pass writes (the layer input is every channel of a
+//     position, the two directions write back their halves from opposite ends), so the hidden outputs of pass 0 wait in registers, packed
+//     hi|lo (32 per lane), until pass 1's GEMM has read the plane; the cell state is handed from part 3 of pass 0 to part 0 of pass 1.
 // Both variants keep the generation-2 tricks: only the cell-state chain c_t = u0 + (c_{t-1} - u0) sigmoid(u1 + v_f c_{t-1}) is
 // serial, the reset gate / highway output are evaluated after the hand-off; sigmoid = rcp(1 + exp2(z)) with -log2(e) folded into
 // the gate weights; the highway input of layers 1-3 comes out of the same MFMAs through an identity block in the weight image (whose
@@ -93,20 +98,24 @@ __device__ __forceinline__ float sum_halves(float v) {
 // and, with the CU's second workgroup, four per SIMD.
 // NP = time parts per workgroup (default 4 / NT: 128 covered steps unpaired, 64 paired).  NT = 2 with NP = 4 is the LONG variant for the 4 s
 // shapes (Ls <= 256: one sequence, 4 time parts x 2 directions = 512 threads, 102 KB of LDS, ONE workgroup per CU with two of its own waves per
-// SIMD): the same program, the chain handed through four parts.
-template <int NSEQ, bool PAIRED, int NT, bool STAMP = false, int NP = 4 / NT>
+// SIMD): the same program, the chain handed through four parts.  NPASS = 2 on top of that is the 8 s variant (Ls <= 512): every layer and the
+// conv-transpose walk the 256 covered steps twice, the weight stream single-buffered.
+template <int NSEQ, bool PAIRED, int NT, bool STAMP = false, int NP = 4 / NT, int NPASS = 1>
 __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Args a) {
     static_assert((NSEQ == 2 && PAIRED) || (NSEQ == 1 && !PAIRED), "F sweep: one sequence pair; T sweep: one sequence");
     static_assert(NT == 1 || NT == 2, "row tiles per wave");
     static_assert(NP == 2 || NP == 4, "time parts");
+    static_assert(NPASS == 1 || (NPASS == 2 && NSEQ == 1 && NT == 2 && NP == 4), "two passes: the 4 s program only");
     constexpr int STEPS = (PAIRED ? 16 : 32) * NT;  // time steps covered by one wave
     constexpr int NPART = NP;                       // time parts per workgroup
     constexpr int NTHR = 128 * NPART;               // 2 directions x NPART waves
     constexpr int NPIECE = 1024 / NTHR;             // 16-byte pieces of a staged K step per thread
+    constexpr int PSTEPS = STEPS * NPART;           // time steps of one pass
+    constexpr bool WB1 = NPASS > 1;                 // one weight buffer (the 8 s plane leaves no room for two)
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int Ls = a.Ls, L = Ls - 7, rowsH = Ls + 1 + PADR;  // per sequence: PADR scratch rows (-PADR .. -1), rows 0 .. Ls - 1, row Ls all zero (conv-transpose borders)
-    half8* Wst = reinterpret_cast<half8*>(smem);                          // [2 buffers][1024 pieces of 16 B], fragment order
-    _Float16* Hh = reinterpret_cast<_Float16*>(smem + 2 * WBUF) + PADR * HLD;  // row 0 of sequence 0; [NSEQ][rowsH][HLD]: hi halves of a row, then its lo halves
+    half8* Wst = reinterpret_cast<half8*>(smem);                          // [2 buffers (WB1: 1)][1024 pieces of 16 B], fragment order
+    _Float16* Hh = reinterpret_cast<_Float16*>(smem + (WB1 ? 1 : 2) * WBUF) + PADR * HLD;  // row 0 of sequence 0; [NSEQ][rowsH][HLD]: hi halves of a row, then its lo halves
     _Float16* Hl = Hh + HLO;
     float* chand = reinterpret_cast<float*>(Hh + (NSEQ * rowsH - PADR) * HLD);  // [NSEQ][2 dirs][32]
 
@@ -161,7 +170,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
     auto stage_write = [&](auto set_c, int buf) {
         constexpr int S = decltype(set_c)::value;
 #pragma unroll
-        for (int j = 0; j < NPIECE; ++j) Wst[buf * 1024 + tid + NTHR * j] = pre[S][j];
+        for (int j = 0; j < NPIECE; ++j) Wst[(WB1 ? 0 : buf) * 1024 + tid + NTHR * j] = pre[S][j];
     };
     const std::integral_constant<int, 0> S0;
     const std::integral_constant<int, 1> S1;
@@ -169,8 +178,10 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
 
     // ---------------- phase 0: load rows, LayerNorm over channels, split to f16 planes (normalizations.py:33-37).
     // lane = (position, channel half): 32 consecutive positions x 2 halves per wave, the halves meet in one permlane swap
-    if (wave * 32 < NSEQ * Ls) {  // (uniform; 32 rows a wave: Ls <= 64 paired, <= 128 / 256 unpaired - the launcher routes by Ls)
-        const int task = wave * 32 + r, ntask = NSEQ * Ls;
+#pragma unroll 1
+    for (int rb = 0; rb < NPASS; ++rb)  // (NPASS blocks of NTHR / 2 rows)
+    if (rb * (NTHR / 2) + wave * 32 < NSEQ * Ls) {  // (uniform; 32 rows a wave: Ls <= 64 paired, <= 128 / 256 / 512 unpaired - the launcher routes by Ls)
+        const int task = rb * (NTHR / 2) + wave * 32 + r, ntask = NSEQ * Ls;
         const bool live = task < ntask;
         const int tk = live ? task : ntask - 1;
         const int s = (NSEQ == 2 && tk >= Ls) ? 1 : 0, pos = tk - s * Ls;
@@ -217,13 +228,16 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
     //                            unpaired -> step 32 t + 16 ((r >> 2) & 1) + (r & 3) + 4 (r >> 3)
     // either way accumulator register q of lane half h (row (q & 3) + 8 (q >> 2) + 4 h) is step q of that half's 16-step run
     int rowbase[NT];
+    auto set_rows = [&](int pass) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int rs = PAIRED ? (r >> 2) & 1 : 0;
-        int tau = STEPS * part + (r & 3) + 4 * (r >> 3) + (PAIRED ? 16 * t : 32 * t + 16 * ((r >> 2) & 1));
-        tau = tau < L ? tau : L - 1;
-        rowbase[t] = (rs * rowsH + (dir ? L - 1 - tau : tau)) * HLD + 8 * h;
-    }
+        for (int t = 0; t < NT; ++t) {
+            const int rs = PAIRED ? (r >> 2) & 1 : 0;
+            int tau = PSTEPS * pass + STEPS * part + (r & 3) + 4 * (r >> 3) + (PAIRED ? 16 * t : 32 * t + 16 * ((r >> 2) & 1));
+            tau = tau < L ? tau : L - 1;
+            rowbase[t] = (rs * rowsH + (dir ? L - 1 - tau : tau)) * HLD + 8 * h;
+        }
+    };
+    set_rows(0);
     stamp();  // 1: after load + LN issue (before first barrier)
     stage_write(S0, 0);
     stage_load(S0, a.wf_l0 + 1024);      // step 1 -> set 0 (written to LDS during step 0)
@@ -239,6 +253,11 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         const int nchunk = FIRST ? 32 : 4;
         const float vf = a.wc16[layer * 128 + dir * 32 + r], vr = a.wc16[layer * 128 + 64 + dir * 32 + r];
         const float bf = a.bias16[layer * 128 + dir * 32 + r] * 256.f, br = a.bias16[layer * 128 + 64 + dir * 32 + r] * 256.f;
+        unsigned hold[NT][16];  // NPASS = 2: pass 0's hidden outputs (hi | lo << 16) until pass 1's GEMM has read the plane
+        (void)hold;
+#pragma unroll
+        for (int pass = 0; pass < NPASS; ++pass) {
+        if (NPASS > 1) set_rows(pass);
         f32x16 acc[NT][4];
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -251,7 +270,8 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
             }
         const half8* const gsrc = FIRST ? a.wf_l0 : a.wf_l + (size_t)(layer - 1) * 4 * 1024;
         // what follows this layer in the stream: the next layer's steps, then the conv-transpose's taps
-        const half8* const gnext = layer < 3 ? a.wf_l + (size_t)layer * 4 * 1024 : a.wf_ct;
+        // (NPASS = 2: pass 0 is followed by the same layer's steps again)
+        const half8* const gnext = pass + 1 < NPASS ? gsrc : layer < 3 ? a.wf_l + (size_t)layer * 4 * 1024 : a.wf_ct;
         // (MFMA order: tools/mfma_rate.hip measures 32.5 ticks per v_mfma_f32_32x32x16_f16 whether 1, 2, 4 or 8 accumulators rotate - a
         // dependent chain costs nothing, so the order of the three split-precision terms is free; term-major is kept, it is harmless.)
         // `tiles` consecutive gate tiles from m0, term-major: NT = 2 issues pairs (4 accumulators), NT = 1 all four gate tiles at once
@@ -284,7 +304,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         // rotated - and only through the two terms with the hi weights: 4 MFMAs there, none in steps 2, 3 (the skipped products are
         // exact zeros): 80 instead of 96 MFMAs per layer and wave.
         auto kstep = [&](int q, auto set_c, auto n3_c) {
-            constexpr int N3 = (NT == 2 && DP16S_SGB) ? decltype(n3_c)::value : 6;
+            constexpr int N3 = (NT == 2 && (DP16S_SGB || WB1)) ? decltype(n3_c)::value : 6;
             // (layers 1-3: the backward direction's K steps come rotated by two, packing.frag_image_gate_rot)
             const int aoff = FIRST ? (q >> 2) * HLD + (q & 3) * 16 : ((q + 2 * dir) & 3) * 16;
             half8 ah[NT], al[NT];
@@ -293,8 +313,27 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
                 ah[t] = *reinterpret_cast<const half8*>(Hh + rowbase[t] + aoff);
                 al[t] = *reinterpret_cast<const half8*>(Hl + rowbase[t] + aoff);
             }
-            const half8* wb = Wst + (g & 1) * 1024 + dir * 512 + lane;
-            if (NT == 2 && DP16S_SGB) {
+            const half8* wb = Wst + (WB1 ? 0 : (g & 1)) * 1024 + dir * 512 + lane;
+            if constexpr (WB1) {
+                // one buffer: the step's fragments are read gate tile by gate tile into the MFMAs, the waves meet at a barrier, then the
+                // buffer takes step g + 1 (its write exposed; holding all eight B fragments across the barrier instead spilled)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    if (m == 3 && N3 == 0) continue;
+                    const half8 bh = wb[m * 128];
+                    const half8 bl = (m < 3 || N3 == 6) ? wb[m * 128 + 64] : bh;
+#pragma unroll
+                    for (int term = 0; term < 3; ++term) {
+                        if (m == 3 && N3 == 4 && term == 1) continue;  // (the identity block's lo half is zero)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t)
+                            acc[t][m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 2 ? al[t] : ah[t], term == 1 ? bl : bh, acc[t][m], 0, 0, 0);
+                    }
+                }
+                __syncthreads();  // every wave has read step g: the buffer is free
+                stage_write(set_c, 0);
+                stage_load(set_c, q + 3 < nchunk ? gsrc + (size_t)(q + 3) * 1024 : gnext + (size_t)(q + 3 - nchunk) * 1024);
+            } else if (NT == 2 && DP16S_SGB) {
                 // Hand-pinned issue order (sched_group_barrier): the wave's 12 fragment reads, 4 staging writes and 4 prefetch loads are
                 // spread over the gaps between its 24 MFMAs instead of clustered in front of them (an MFMA holds the issue port for 8 of
                 // its 32 cycles): only the first six reads and the barrier stay exposed.
@@ -394,8 +433,41 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
                     asm volatile("" : "+v"(acc[t][m]));
                 }
         };
+        // pass 0's held outputs go into the plane now that pass 1's GEMM has read it (time part 0: behind its chain)
+        auto flush = [&](auto bw_c) {
+            constexpr bool BW = decltype(bw_c)::value;
+            constexpr int ROWB = HLD * 2, KMAX = (NT - 1) * 32 + 15;
+            const int lane_t0 = PSTEPS * (pass - 1) + STEPS * part + 16 * h;
+            int base = (dir * 32 + r) * 2 + (BW ? L - 1 - lane_t0 - KMAX : lane_t0) * ROWB;
+            asm volatile("" : "+v"(base));
+            char* const Hb = reinterpret_cast<char*>(Hh);
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int q4 = 0; q4 < 16; q4 += DP16S_WBG)
+                    if (lane_t0 + 32 * t + q4 < L) {
+#pragma unroll
+                        for (int i = 0; i < DP16S_WBG; ++i) {
+                            const int k = 32 * t + q4 + i;
+                            char* const o = Hb + base + (BW ? KMAX - k : k) * ROWB;
+                            *reinterpret_cast<unsigned short*>(o) = (unsigned short)hold[t][q4 + i];
+                            *reinterpret_cast<unsigned short*>(o + HLO * 2) = (unsigned short)(hold[t][q4 + i] >> 16);
+                        }
+                    }
+        };
+        auto flush_held = [&]() {
+            if (NPASS > 1 && pass > 0) {
+                if (dir)
+                    flush(std::true_type());
+                else
+                    flush(std::false_type());
+            }
+        };
         unscale(0);
-        if (part != 0) unscale(2);
+        if (part != 0) {
+            unscale(2);
+            flush_held();
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (layer == 1) stamp_at(12);  // prescale undone
         float cin[NT];  // c_{t-1} of register 0 of tile t (this lane's run)
@@ -403,7 +475,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         for (int t = 0; t < NT; ++t) cin[t] = 0.f;
         for (int hp = 0; hp < NPART; ++hp) {
             if (part == hp) {
-                float c = hp > 0 ? chand[(seq * 2 + dir) * 32 + r] : 0.f;
+                float c = (hp > 0 || pass > 0) ? chand[(seq * 2 + dir) * 32 + r] : 0.f;
                 if (PAIRED) {
                     // register q of tile t = time step 16 t + q of this lane's own sequence.  Only the cell-state chain is serial; it
                     // overwrites u0 in place.  The reset gate and the hidden output depend on c_{t-1}, c_t but nothing depends on
@@ -413,7 +485,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
                         cin[t] = c;
 #pragma unroll
                         for (int q4 = 0; q4 < 16; q4 += 4) {
-                            if (STEPS * hp + 16 * t + q4 < L) {  // (uniform: groups of four steps behind the sequence end are not walked)
+                            if (PSTEPS * pass + STEPS * hp + 16 * t + q4 < L) {  // (uniform: groups of four steps behind the sequence end are not walked)
 #pragma unroll
                                 for (int q = q4; q < q4 + 4; ++q) {
                                     const float u0 = acc[t][0][q];
@@ -436,7 +508,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
                                 cin[t] = c;
 #pragma unroll
                                 for (int q4 = 0; q4 < 16; q4 += 4) {
-                                    if (STEPS * hp + 32 * t + 16 * ph + q4 < L) {  // (uniform)
+                                    if (PSTEPS * pass + STEPS * hp + 32 * t + 16 * ph + q4 < L) {  // (uniform)
 #pragma unroll
                                         for (int q = q4; q < q4 + 4; ++q) {
                                             const float u0 = acc[t][0][q];
@@ -457,7 +529,10 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
             if (hp + 1 < NPART) __syncthreads();  // cell state published: the next time part starts while this one writes back
             if (layer == 1 && hp == 0) stamp_at(14);
             if (part == hp) {
-                if (hp == 0) unscale(2);
+                if (hp == 0) {
+                    unscale(2);
+                    flush_held();
+                }
                 // deferred reset gate + highway: h = x' + (c_t - x') r(c_{t-1}); hidden outputs (this wave's direction half of the
                 // channels) go back into the planes in place: 9 vector instructions + 2 two-byte stores a step, no branch per step (that
                 // made every step its own basic block - exp, rcp, converts and stores at their full latencies, ~125 cycles a step).
@@ -466,7 +541,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
                 // time, stage by stage (a step is a chain of dependent instructions with two transcendentals in it); a group is skipped when
                 // its first step lies beyond the sequence end, the up to WBG - 1 steps behind the end inside a group land in rows L .. L + WBG - 2
                 // (forward; free since layer 0's GEMM) or in the PADR rows in front of the plane (backward).
-                const int tau0 = STEPS * part;
+                const int tau0 = PSTEPS * pass + STEPS * part;
                 char* const Hb = reinterpret_cast<char*>(Hh);
                 constexpr int ROWB = HLD * 2, TSTEP = PAIRED ? 16 : 32, KMAX = (NT - 1) * TSTEP + 15, WBG = DP16S_WBG;
                 static_assert(WBG <= PADR && WBG <= 8 && 16 % WBG == 0, "overshoot of a group: at most WBG - 1 rows, 7 free rows behind the sequence end");
@@ -506,6 +581,10 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
                                     asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lo[i]) : "v"(hv[i]), "v"(hh[i]));
 #pragma unroll
                                 for (int i = 0; i < WBG; ++i) {
+                                    if (pass + 1 < NPASS) {  // (NPASS = 2, pass 0: held, flush() stores them)
+                                        hold[t][q4 + i] = (unsigned)__builtin_bit_cast(unsigned short, hh[i]) | ((lo[i] & 0xffffu) << 16);
+                                        continue;
+                                    }
                                     const int k = TSTEP * t + q4 + i;
                                     char* const o = Hb + base + (BW ? KMAX - k : k) * ROWB;
                                     *reinterpret_cast<_Float16*>(o) = hh[i];
@@ -525,13 +604,16 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         if (layer == 1) stamp_at(15);  // part 0's write-back done and the loop's last barrier passed: waiting for part 1's write-back
         __syncthreads();  // all hidden outputs of this layer are in the planes
         stamp();  // 3,5,7,9: scan of layer done
+        }  // pass
     };
     do_layer(0, std::true_type());
     for (int layer = 1; layer < 4; ++layer) do_layer(layer, std::false_type());
 
     // ---------------- ConvTranspose1d(64->64, k=8) + bias + residual (rnn_layers.py:153-156), transposed:
-    //   y[co][t] = bt[co] + sum_{kk,ci} Wt[co][kk*64+ci] * H[t-kk][ci];  wave = (sequence, co tile, position part)
-    {
+    //   y[co][t] = bt[co] + sum_{kk,ci} Wt[co][kk*64+ci] * H[t-kk][ci];  wave = (sequence, co tile, position part); NPASS passes of PSTEPS positions,
+    //   the eight taps streamed once per pass
+#pragma unroll 1
+    for (int cp = 0; cp < NPASS; ++cp) {
         // one accumulator per position tile (a dependent MFMA chain issues at the full rate, tools/mfma_rate.hip: separate partial sums
         // per k-step parity bought nothing and cost 32 registers)
         f32x16 acc[NT];
@@ -546,7 +628,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         const size_t rbase = seq_base(cseq) + (size_t)(ccot * 32) * a.cstride;  // uniform
         unsigned eoff[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) eoff[t] = (unsigned)(rbase + (size_t)(4 * h) * a.cstride + min(32 * NT * cpart + 32 * t + r, Ls - 1)) * 4u;
+        for (int t = 0; t < NT; ++t) eoff[t] = (unsigned)(rbase + (size_t)(4 * h) * a.cstride + min(PSTEPS * cp + 32 * NT * cpart + 32 * t + r, Ls - 1)) * 4u;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int cq = (q & 3) + 8 * (q >> 2);
@@ -560,10 +642,10 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
             int hrow[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                const int p = 32 * NT * cpart + 32 * t + r - q;
+                const int p = PSTEPS * cp + 32 * NT * cpart + 32 * t + r - q;
                 hrow[t] = (cseq * rowsH + ((p >= 0 && p < L) ? p : Ls)) * HLD + 8 * h;
             }
-            const half8* wb = Wst + (g & 1) * 1024 + ccot * 512 + lane;
+            const half8* wb = Wst + (WB1 ? 0 : (g & 1)) * 1024 + ccot * 512 + lane;
             // all fragment reads of the tap first in program order, in the order they are needed (the staging write below may alias the
             // weight reads as far as the compiler knows, so it can only be scheduled behind the last of them); two k steps x two position
             // tiles = four accumulators.  Term order (wh xh), (wl xh), (wh xl): xh and wl are dead after eight of a block's twelve MFMAs,
@@ -584,6 +666,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
 #pragma unroll
                     for (int t = 0; t < NT; ++t) xl[kk][t] = *reinterpret_cast<const half8*>(Hl + hrow[t] + kk * 16);
             }
+            if (WB1) __syncthreads();  // (one buffer: every wave holds the tap's fragments before it is overwritten)
             stage_write(set_c, (g + 1) & 1);  // (the last tap rewrites tap 7's neighbour with a clamped copy: never read)
 #pragma unroll
             for (int k2 = 0; k2 < 4; k2 += 2) {
@@ -596,8 +679,8 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
                             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 1 ? wl[kk] : wh[kk], term == 2 ? xl[kk][t] : xh[kk][t], acc[t], 0, 0, 0);
                 }
             }
-            stage_load(set_c, a.wf_ct + (size_t)(q + 3 < 8 ? q + 3 : 7) * 1024);  // unconditional, clamped
-            if (NT == 2 && DP16S_SGB_CT) {
+            stage_load(set_c, a.wf_ct + (size_t)(min(8 * cp + q + 3, 8 * NPASS - 1) & 7) * 1024);  // unconditional, clamped; the next pass's taps follow
+            if (NT == 2 && DP16S_SGB_CT && !WB1) {
                 // issue order of a tap pinned like a gate step's: 24 fragment reads (a tap reads twice a gate step's - each fragment feeds
                 // six MFMAs, not twelve), 4 staging writes and 4 prefetch loads in the gaps between the 24 MFMAs
                 __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);  // k2 = 0: hi fragments
@@ -625,7 +708,7 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         if (n0 + cseq < a.nseq) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                const int p = 32 * NT * cpart + 32 * t + r;
+                const int p = PSTEPS * cp + 32 * NT * cpart + 32 * t + r;
                 if (p < Ls) {  // (then the clamped position of eoff is p itself)
 #pragma unroll
                     for (int q = 0; q < 16; ++q)
@@ -638,38 +721,39 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
 }
 
 size_t dp16s_lds_bytes(int Ls, int nseq_per_wg) {
-    return (size_t)2 * WBUF + (size_t)nseq_per_wg * (Ls + 1 + PADR) * HLD * 2 + (size_t)nseq_per_wg * 2 * 32 * 4;
+    return (size_t)(Ls > 256 ? 1 : 2) * WBUF + (size_t)nseq_per_wg * (Ls + 1 + PADR) * HLD * 2 + (size_t)nseq_per_wg * 2 * 32 * 4;
 }
 
-template <int NSEQ, bool PAIRED, int NT, int NP = 4 / NT>
+template <int NSEQ, bool PAIRED, int NT, int NP = 4 / NT, int NPASS = 1>
 static int launch_dp16s_t(const Dp16Args& a, hipStream_t st) {
     const size_t lds = dp16s_lds_bytes(a.Ls, NSEQ);
     constexpr bool LONG = NT == 2 && NP == 4;             // one 512-thread workgroup per CU
     if (lds > (LONG ? 160 : 80) * 1024) return RTFS_ERR_SHAPE;  // (else: two workgroups per CU)
     constexpr int NTHR = 128 * NP;
     if (a.stamps) {
-        if (rtfs_set_max_lds((const void*)dp16s_kernel<NSEQ, PAIRED, NT, true, NP>, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
-        hipLaunchKernelGGL((dp16s_kernel<NSEQ, PAIRED, NT, true, NP>), dim3(cdiv(a.nseq, NSEQ)), dim3(NTHR), lds, st, a);
+        if (rtfs_set_max_lds((const void*)dp16s_kernel<NSEQ, PAIRED, NT, true, NP, NPASS>, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
+        hipLaunchKernelGGL((dp16s_kernel<NSEQ, PAIRED, NT, true, NP, NPASS>), dim3(cdiv(a.nseq, NSEQ)), dim3(NTHR), lds, st, a);
         return rtfs_launch_status();
     }
-    if (rtfs_set_max_lds((const void*)dp16s_kernel<NSEQ, PAIRED, NT, false, NP>, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
+    if (rtfs_set_max_lds((const void*)dp16s_kernel<NSEQ, PAIRED, NT, false, NP, NPASS>, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
     void* slot = dualpath_timing_begin(a.Ls, a.nseq, st);
-    hipLaunchKernelGGL((dp16s_kernel<NSEQ, PAIRED, NT, false, NP>), dim3(cdiv(a.nseq, NSEQ)), dim3(NTHR), lds, st, a);
+    hipLaunchKernelGGL((dp16s_kernel<NSEQ, PAIRED, NT, false, NP, NPASS>), dim3(cdiv(a.nseq, NSEQ)), dim3(NTHR), lds, st, a);
     dualpath_timing_end(slot, st);
     return rtfs_launch_status();
 }
 
 // Ls <= 64 (the F sweep: 64): one sequence pair per workgroup; Ls <= 128 (the 2 s T sweep: 125): one sequence per workgroup; Ls <= 256 (the
-// 4 s T sweep: 250): one sequence per 512-thread workgroup.  The limits are
+// 4 s T sweep: 250): one sequence per 512-thread workgroup; Ls <= 512 (the 8 s T sweep: 512): the same workgroup in two passes.  The limits are
 // on Ls = L + 7, the row count of the load phase and of the conv-transpose output (routing by L left Ls = 65 .. 71 and 129 .. 135 with their
 // last positions unwritten - found by tests/test_hip_parity.py::test_dualpath_sweep_lengths)
 int launch_dualpath16s(const Dp16Args& a0, hipStream_t st) {
     const int L = a0.Ls - 7;
-    if (L < 1 || a0.Ls > 256) return RTFS_ERR_SHAPE;
+    if (L < 1 || a0.Ls > 512) return RTFS_ERR_SHAPE;
     // 32-bit byte offsets from the tensor base inside the kernel
     if ((((size_t)(a0.nseq - 1) / a0.R) * a0.bstride + (size_t)(a0.R - 1) * a0.rstride + 63 * a0.cstride + a0.Ls) * 4 >= ((size_t)1 << 32)) return RTFS_ERR_SHAPE;
     const Dp16Args& a = a0;
     const bool pair = a0.Ls <= 64;
+    if (a0.Ls > 256) return launch_dp16s_t<1, false, 2, 4, 2>(a, st);  // the 8 s shapes: the same, two passes
     if (a0.Ls > 128) return launch_dp16s_t<1, false, 2, 4>(a, st);  // the 4 s shapes: four time parts, one workgroup per CU
     return pair ? launch_dp16s_t<2, true, 2>(a, st) : launch_dp16s_t<1, false, 2>(a, st);
 }

@@ -52,12 +52,14 @@ class PackedModule(nn.Module):
 
 _FORCE_TRAIN_KERNELS = [False]
 
-# Fused inference kernels keep a whole sweep / score row / video pyramid on chip: a sweep axis of 250 positions (4 s of audio, BASELINE
-# config 5), 256 attention keys, 120 video frames.  The reference's forward has no length limit (rnn_layers.py:136-162, attention.py:149-189;
-# infer_any_video.py:86 feeds whole files): longer inputs run on the UNFUSED HIP kernels (GEMM + scan + GEMM, batched-GEMM attention,
-# per-layer video block) that also serve training - same arithmetic, tensors through HBM between the steps, any length.
-FUSED_MAX_SWEEP = 250
-FUSED_MAX_KEYS = 256
+# Fused inference kernels keep a whole sweep / score row / video pyramid on chip: an SRU time sweep of 512 positions (8.2 s of audio), 512
+# attention keys, 120 video frames; the fused block and separator, the LSTM cell's sweep and the frequency sweep stop at 250 positions (4 s,
+# BASELINE config 5).  The reference's forward has no length limit (rnn_layers.py:136-162, attention.py:149-189; infer_any_video.py:86 feeds
+# whole files): longer inputs run on the UNFUSED HIP kernels (GEMM + scan + GEMM, batched-GEMM attention, per-layer video block) that also
+# serve training - same arithmetic, tensors through HBM between the steps, any length.
+FUSED_MAX_SWEEP = 512
+FUSED_MAX_BLOCK_SWEEP = 250
+FUSED_MAX_KEYS = 512
 FUSED_MAX_VIDEO_FRAMES = 120
 
 
@@ -775,7 +777,8 @@ class DualPathRNN(PackedModule):
         B, C, T, Fq = x.shape
         if (T if self.dim == 3 else Fq) < self.kernel_size:
             raise ValueError(f"sweep axis shorter than kernel_size {self.kernel_size}")  # nn.Unfold raises in the reference
-        long_axis = (T if self.dim == 3 else Fq) > FUSED_MAX_SWEEP  # past the fused kernel's on-chip sweep: the unfused kernels, any length
+        # past the fused kernel's on-chip sweep (SRU along T: 512, else 250): the unfused kernels, any length
+        long_axis = (T if self.dim == 3 else Fq) > (FUSED_MAX_SWEEP if self.dim == 3 and self.rnn_type == "SRU" else FUSED_MAX_BLOCK_SWEEP)
         if _recording(x, self) or self.rnn_type == "GRU" or long_axis:  # GRU: no fused inference kernel, the GEMM + scan kernels serve both
             if self.rnn_type in ("LSTM", "GRU"):
                 cell = [getattr(self.rnn, n) for n in packing.lstm_param_names()]
