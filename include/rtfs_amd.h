@@ -24,9 +24,11 @@
  *     library may be driven from several host threads / devices in one process (one thread per stream).
  *   - length limits of the FUSED entry points (they keep a whole sweep / score row / video pyramid on chip and return -1 beyond):
  *       time sweep (dim 3) of rtfs_dualpath_sru_f32                                   <= 512 positions (8.2 s of audio)
- *       frequency sweep, rtfs_dualpath_lstm_f32, rtfs_block_f32, rtfs_separator_forward_f32  <= 250 positions (T/2 <= 250: 4 s of audio)
+ *       rtfs_block_f32, rtfs_separator_forward_f32 with the SRU cell (rnn_kind 0)      T/2 <= 512 (T <= 1025 frames: 8.2 s of audio)
+ *       frequency sweep, rtfs_dualpath_lstm_f32, rtfs_block_f32 / rtfs_separator_forward_f32 with the LSTM cell (rnn_kind 1)
+ *                                                                                     <= 250 positions (T/2 <= 250: 4 s of audio)
  *       keys of rtfs_tf_attention_f32                                                 <= 512
- *       video frames of rtfs_vp_block_f32                                             <= 120
+ *       video frames of rtfs_vp_block_f32                                             <= 256 (10.2 s at 25 fps)
  *     The reference has no length limit (rnn_layers.py:136-162, attention.py:149-189; infer_any_video.py:86 feeds whole files): longer
  *     inputs go through the UNFUSED entry points below (rtfs_*_forward_train_f32 and friends: GEMM + scan + GEMM sweeps, batched-GEMM
  *     attention, per-layer video block), which take any length; rtfs-net_amd/{models,layers}.py route by length (FUSED_MAX_*).
@@ -112,7 +114,9 @@ int rtfs_caf_f32(const float* audio, const float* video, const float* pack, floa
                  void* ws, size_t ws_bytes, void* stream);
 
 /* VP block = the video-side 1-D TDANetBlock.forward (upsampling_depth 4, kernel 3, BatchNorm1d, GlobalAttention;
- * src/models/separators/tdanet.py:104-131 with yaml video_params): video (B,512,Tv) -> (B,512,Tv), Tv <= 120 (see the conventions).
+ * src/models/separators/tdanet.py:104-131 with yaml video_params): video (B,512,Tv) -> (B,512,Tv), Tv <= 256 (see the conventions).
+ * One launch, one workgroup per sample: Tv <= 120 runs entirely in LDS; 121 <= Tv <= 256 stages its three full-rate 64 x Tv tensors in
+ * out's own slice for the sample (so `out` must not alias `video`) and keeps the rest in LDS.
  * pack = rtfs-net_amd/packing.py:pack_vp (eval BatchNorm folded); rtfs_vp_pack_floats() returns its length. */
 size_t rtfs_vp_pack_floats(void);
 int rtfs_vp_block_f32(const float* video, const float* pack, float* out, int B, int Tv, void* stream);

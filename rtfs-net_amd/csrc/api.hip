@@ -648,7 +648,11 @@ size_t pack_size() {
     return c.off;
 }
 
-bool shape_ok_block(int B, int T, int F) { return B >= 1 && F / 2 == FQ && T / 2 >= 8 && T / 2 <= 250; }
+// The fused block's only length-bound launches are the time sweep (dualpath dim 3) and the attention core: T/2 <= 512 with the SRU cell
+// (8.2 s of audio; k_dualpath16s.hip, k_attn.hip), 250 with the LSTM cell (k_dualpath.hip).  Every other kernel the block and the separator
+// reach forms its sample base in 64 bits and checks its own per-sample span (e.g. 256 * cs * 4 < 2^31: ~16,000 frames), so no length
+// below these two limits needs a sub-batch split.
+bool shape_ok_block(int B, int T, int F, int rnn_kind) { return B >= 1 && F / 2 == FQ && T / 2 >= 8 && T / 2 <= (rnn_kind == 0 ? 512 : 250); }
 
 }  // namespace
 
@@ -731,7 +735,7 @@ size_t rtfs_block_workspace_bytes(int B, int T, int F) {
 
 int rtfs_block_f32(const float* x, const float* x_res, const float* pack, float* out, int B, int T, int F, void* ws, size_t ws_bytes, void* stream, int rnn_kind) {
     RTFS_RETURN_IF(!x || !pack || !out, RTFS_ERR_ARG);
-    RTFS_RETURN_IF(!shape_ok_block(B, T, F), RTFS_ERR_SHAPE);
+    RTFS_RETURN_IF(!shape_ok_block(B, T, F, rnn_kind), RTFS_ERR_SHAPE);
     Arena ar(ws, ws_bytes);
     BlockWs w(ar, B, T, F);
     RTFS_RETURN_IF(!ws || !ar.ok(), RTFS_ERR_WORKSPACE);
@@ -870,7 +874,7 @@ size_t rtfs_vp_pack_floats(void) {
     auto t = [&](size_t k) { n += (k + 63) / 64 * 64; };
     t(512); t(512); t(1); t(512 * 64); t(64);
     for (int i = 0; i < 4; ++i) { t(192); t(64); t(64); }
-    t(64); t(64); t(16 * 64); t(192 * 64); t(192); t(64 * 64); t(64); t(64); t(64);
+    t(64); t(64); t(32 * 64); t(192 * 64); t(192); t(64 * 64); t(64); t(64); t(64);
     t(128 * 64); t(128); t(128); t(128 * 3); t(128); t(64 * 128); t(64); t(64);
     for (int i = 0; i < 7; ++i) for (int j = 0; j < 3; ++j) { t(192); t(64); t(64); }
     t(64 * 512); t(512);
@@ -1110,7 +1114,7 @@ int rtfs_separator_forward_ex_f32(const float* wav, const float* video_vp, const
     RTFS_RETURN_IF(!wav || !video_vp || !pack_enc || !pack_bn || !pack_block || !pack_caf || !pack_s3 || !pack_dec || !out, RTFS_ERR_ARG);
     RTFS_RETURN_IF(B < 1 || L <= 128 || Tv < 1 || repeats < 1, RTFS_ERR_ARG);
     const int T = rtfs_num_frames(L);
-    RTFS_RETURN_IF(!shape_ok_block(B, T, NF), RTFS_ERR_SHAPE);
+    RTFS_RETURN_IF(!shape_ok_block(B, T, NF, rnn_kind), RTFS_ERR_SHAPE);
     RTFS_RETURN_IF(rnn_kind != 0 && rnn_kind != 1, RTFS_ERR_ARG);
     const int np = separator_parts(B, split);
     Arena ar(ws, ws_bytes);

@@ -3,12 +3,21 @@
 // layers/attention.py:28-73,192-220; layers/conv_layers.py:218-259; layers/fusion.py:54-69).
 // 0.004 GMAC per sample: one workgroup per sample runs the whole block out of LDS, stage by stage.
 // Eval-mode BatchNorm (and the conv bias in front of it) is folded into (scale, shift) at pack time.
+//
+// Two instances of the one kernel body: LONG = false for Tv <= 120 (every tensor in LDS, 150 KB at 120 frames) and LONG = true for
+// 121 <= Tv <= 256 (8.2 s of video at 25 fps is 205 frames; global length Lg <= 32).  All-LDS needs ~1,248 B per frame, 320 KB at 256,
+// so the long instance keeps the three full-rate 64 x Tv tensors that are read by other waves (x_enc, d0 = the pyramid's level 0, and
+// x_fused[0]) in the sample's own slice of `out` (512 x Tv floats, written by step 7 only, when all three are dead), and everything at
+// half rate or below in LDS (152 KB at 256 frames).  The level-0 `expanded` goes straight to LDS over the dead pyramid.  Same launch
+// geometry (one workgroup per sample, VP_NT threads) and the same arithmetic in the same order as the short instance.
 #include "common.h"
 #include "kernels.h"
 
 #define VC 64     // hidden channels
 #define VIN 512   // embedding channels
 #define VDEPTH 4
+#define VP_SHORT_MAX 120  // frames of the all-LDS instance
+#define VP_LONG_MAX 256   // frames of the long instance (Lg <= 32)
 #define VP_NT 512  // threads per workgroup (one workgroup per sample: at small batches this kernel is the forward's critical path, and
                     // every stage below is a short loop over at most 64 x Tv items between two barriers - 256 threads took 0.5 ms)
 
@@ -35,8 +44,22 @@ __device__ __forceinline__ float dw3(const float* x, int n, int t, const float* 
 }
 }  // namespace
 
+// Store -> barrier -> load of the long instance's staging tensors (global memory, slice out[b], read back by other waves of the same
+// workgroup): (1) every wave drains its own stores (s_waitcnt vmcnt(0)) before the barrier, so they have reached the L2 the readers'
+// misses go to; (2) no staged address is read before it is written in this launch (the slots are written once each, and the vector L1
+// starts the launch invalid), so no reader holds a stale L1 line of it; (3) the staging pointers are derived from `out`, which the kernel
+// writes, so the compiler cannot turn their loads into scalar-cache (s_load) reads - the .s has s_load only on the kernel arguments and
+// the (read-only) parameter pack.  The short instance keeps the plain barrier.
+template <bool LONG>
+__device__ __forceinline__ void vp_sync() {
+    if (LONG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+template <bool LONG>
 __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict__ video, const float* __restrict__ pack,
                                                        float* __restrict__ out, int Tv) {
+    constexpr int LGM = LONG ? 32 : 16;  // capacity of the global length Lg (rows of pe, score tile edge)
     extern __shared__ float lds[];
     __shared__ double red[2 * (VP_NT / 64)];
     __shared__ float stat[2];
@@ -51,7 +74,7 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
     const float* proj_wt = take(p, VIN * VC); const float* proj_b = take(p, VC);
     const float *dsw[VDEPTH], *dss[VDEPTH], *dsb[VDEPTH];
     for (int i = 0; i < VDEPTH; ++i) { dsw[i] = take(p, VC * 3); dss[i] = take(p, VC); dsb[i] = take(p, VC); }
-    const float* ln1w = take(p, VC); const float* ln1b = take(p, VC); const float* pe = take(p, 16 * VC);
+    const float* ln1w = take(p, VC); const float* ln1b = take(p, VC); const float* pe = take(p, 32 * VC);
     const float* inw = take(p, 192 * VC); const float* inb = take(p, 192);
     const float* ow = take(p, VC * VC); const float* ob = take(p, VC);
     const float* ln2w = take(p, VC); const float* ln2b = take(p, VC);
@@ -66,27 +89,34 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
 
     // ---- LDS carve-up (floats).  R2 is two 64 x Tv buffers for the projection chunk / `expanded` pong / lazily
     // computed x_fused[i]; while the attention + FFN run (nothing else is live there) it holds their work buffers.
+    // Long instance (see the top of the file): D[0], XE and x_fused[0] are slots 0-2 of the sample's slice of `out`; LDS holds
+    // D[1..3] | G | XF3 | R2, and R2 = the projection chunk (step 1), the attention / FFN buffers (4-5), then E2 | TMP | E1 (step 6):
+    // `expanded` of levels 2 and 1 and the x_fused[i] in flight.  The level-0 `expanded` is written to lds[0] over D[1..3] | G | XF3, which
+    // are dead by then (64 Tv <= 64 (len1 + len2 + len3 + 2 LGM) for every Tv <= 512).
+    float* stage = out + (size_t)b * VIN * Tv;
     float* D[VDEPTH];  // downsampled pyramids d_i (64 x len_i)
     float* q = lds;
-    for (int i = 0; i < VDEPTH; ++i) { D[i] = q; q += VC * len[i]; }
-    float* XE = q; q += VC * Tv;           // x_enc, later `expanded` ping
-    float* G = q; q += VC * 16;            // global features (64 x Lg)
-    float* XF3 = q; q += VC * 16;          // x_fused[depth-1] (64 x Lg)
+    for (int i = LONG ? 1 : 0; i < VDEPTH; ++i) { D[i] = q; q += VC * len[i]; }
+    if (LONG) D[0] = stage + VC * Tv;
+    float* XE = q;                         // x_enc, later `expanded` ping
+    if (LONG) XE = stage; else q += VC * Tv;
+    float* G = q; q += VC * LGM;           // global features (64 x Lg)
+    float* XF3 = q; q += VC * LGM;         // x_fused[depth-1] (64 x Lg)
     float* R2 = q;
     float* EX = R2;                        // `expanded` pong; residual chunk RS during the projection
     float* TMP = R2 + VC * Tv;             // x_fused[i] for the concat step in flight
     float* RS = EX;
     float* Y = R2;                         // (Lg x 64) token-major work buffers
-    float* Y2 = Y + 16 * VC;
-    float* QKV = Y2 + 16 * VC;
-    float* SC = QKV + 16 * 192;
-    float* HID = SC + 8 * 16 * 16;
-    float* HID2 = HID + 128 * 16;
+    float* Y2 = Y + LGM * VC;
+    float* QKV = Y2 + LGM * VC;
+    float* SC = QKV + LGM * 192;
+    float* HID = LONG ? Y2 : SC + 8 * LGM * LGM;  // (long: the FFN's buffers over the attention's, which are dead by then)
+    float* HID2 = HID + 128 * LGM;
     const float* vb = video + (size_t)b * VIN * Tv;
 
     // ---- 1. gateway (dw 1x1 + PReLU) + projection 512 -> 64, K chunked by 64 input channels
     {
-        constexpr int NQ = VP_NT / 64, NJ = 128 / NQ;  // time slots tq + NQ j, j < NJ cover Tv <= 120
+        constexpr int NQ = VP_NT / 64, NJ = (LONG ? 256 : 128) / NQ;  // time slots tq + NQ j, j < NJ cover Tv <= 120 (long: 256)
         const int co = tid & 63, tq = tid >> 6;
         float acc[NJ];
 #pragma unroll
@@ -117,13 +147,13 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
             if (t < Tv) XE[co * Tv + t] = acc[j] + proj_b[co];
         }
     }
-    __syncthreads();
+    vp_sync<LONG>();
     // ---- 2. bottom-up pyramid: d0 = BN(dw3 s1 (x_enc)); d_i = BN(dw3 s2 pad1 (d_{i-1}))
     for (int i = tid; i < VC * Tv; i += VP_NT) {
         const int c = i / Tv, t = i - c * Tv;
         D[0][i] = fmaf(dw3(XE + c * Tv, Tv, t, dsw[0] + c * 3), dss[0][c], dsb[0][c]);
     }
-    __syncthreads();
+    vp_sync<LONG>();
     for (int lv = 1; lv < VDEPTH; ++lv) {
         const int n = len[lv - 1], m = len[lv];
         for (int i = tid; i < VC * m; i += VP_NT) {
@@ -173,11 +203,11 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
         const int hd = i / (Lg * Lg), r = i - hd * Lg * Lg, ti = r / Lg, tj = r - ti * Lg;
         float a = 0.f;
         for (int d = 0; d < 8; ++d) a = fmaf(QKV[ti * 192 + hd * 8 + d], QKV[tj * 192 + 64 + hd * 8 + d], a);
-        SC[(hd * 16 + ti) * 16 + tj] = a * 0.35355339059327373f;  // 1/sqrt(8)
+        SC[(hd * LGM + ti) * LGM + tj] = a * 0.35355339059327373f;  // 1/sqrt(8)
     }
     __syncthreads();
     for (int i = tid; i < 8 * Lg; i += VP_NT) {
-        float* row = SC + (size_t)(i / Lg * 16 + i % Lg) * 16;
+        float* row = SC + (size_t)(i / Lg * LGM + i % Lg) * LGM;
         float mx = -3.0e38f;
         for (int j = 0; j < Lg; ++j) mx = fmaxf(mx, row[j]);
         float s = 0.f;
@@ -188,7 +218,7 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
     for (int i = tid; i < Lg * VC; i += VP_NT) {  // attention output, token-major (t, head*8+d)
         const int t = i / VC, o = i - t * VC, hd = o >> 3;
         float a = 0.f;
-        for (int j = 0; j < Lg; ++j) a = fmaf(SC[(hd * 16 + t) * 16 + j], QKV[j * 192 + 128 + o], a);
+        for (int j = 0; j < Lg; ++j) a = fmaf(SC[(hd * LGM + t) * LGM + j], QKV[j * 192 + 128 + o], a);
         Y2[i] = a;
     }
     __syncthreads();
@@ -266,19 +296,33 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
             const float g = sigmoidf_(fmaf(dw3(glob + c * ng, ng, tg, m.gw + c * 3), m.gs[c], m.gb[c]));
             dst[i] = fmaf(l, g, e) + (add ? add[i] : 0.f);
         }
-        __syncthreads();
+        vp_sync<LONG>();
     };
     // x_fused[i] = fusion_layers[i](d_i, g) is computed right before the concat step that consumes it.
     // expanded = cat[2](xf2, xf3) + d2 ; then cat[1](xf1, expanded) + d1 ; cat[0](xf0, expanded) + d0
     float* cur = XE;
     float* nxt = EX;
-    ims(fus[VDEPTH - 1], D[VDEPTH - 1], Lg, G, Lg, nullptr, XF3);
-    ims(fus[VDEPTH - 2], D[VDEPTH - 2], len[VDEPTH - 2], G, Lg, nullptr, TMP);
-    ims(cat[VDEPTH - 2], TMP, len[VDEPTH - 2], XF3, Lg, D[VDEPTH - 2], cur);
-    for (int lv = VDEPTH - 3; lv >= 0; --lv) {
-        ims(fus[lv], D[lv], len[lv], G, Lg, nullptr, TMP);
-        ims(cat[lv], TMP, len[lv], cur, len[lv + 1], D[lv], nxt);
-        float* t = cur; cur = nxt; nxt = t;
+    if (LONG) {  // R2 = E2 (64 x len2) | TMP (64 x len1) | E1 (64 x len1); x_fused[0] in slot 2 of the slice; level 0 -> lds[0]
+        float* E2 = R2;
+        float* TMPL = E2 + VC * len[2];
+        float* E1 = TMPL + VC * len[1];
+        ims(fus[VDEPTH - 1], D[VDEPTH - 1], Lg, G, Lg, nullptr, XF3);
+        ims(fus[2], D[2], len[2], G, Lg, nullptr, TMPL);
+        ims(cat[2], TMPL, len[2], XF3, Lg, D[2], E2);
+        ims(fus[1], D[1], len[1], G, Lg, nullptr, TMPL);
+        ims(cat[1], TMPL, len[1], E2, len[2], D[1], E1);
+        ims(fus[0], D[0], len[0], G, Lg, nullptr, stage + 2 * VC * Tv);
+        ims(cat[0], stage + 2 * VC * Tv, len[0], E1, len[1], D[0], lds);
+        cur = lds;
+    } else {
+        ims(fus[VDEPTH - 1], D[VDEPTH - 1], Lg, G, Lg, nullptr, XF3);
+        ims(fus[VDEPTH - 2], D[VDEPTH - 2], len[VDEPTH - 2], G, Lg, nullptr, TMP);
+        ims(cat[VDEPTH - 2], TMP, len[VDEPTH - 2], XF3, Lg, D[VDEPTH - 2], cur);
+        for (int lv = VDEPTH - 3; lv >= 0; --lv) {
+            ims(fus[lv], D[lv], len[lv], G, Lg, nullptr, TMP);
+            ims(cat[lv], TMP, len[lv], cur, len[lv + 1], D[lv], nxt);
+            float* t = cur; cur = nxt; nxt = t;
+        }
     }
     // ---- 7. residual_conv 64 -> 512 + bias + gateway(video) (recomputed)
     {
@@ -299,11 +343,22 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
     }
 }
 
+// LDS bytes of the instance that serves Tv (the carve-up of vp_block_kernel<Tv > VP_SHORT_MAX>)
 size_t vp_lds_bytes(int Tv) {
     int len[VDEPTH];
     len[0] = Tv;
     int sum = Tv;
     for (int i = 1; i < VDEPTH; ++i) { len[i] = (len[i - 1] - 1) / 2 + 1; sum += len[i]; }
+    if (Tv > VP_SHORT_MAX) {
+        const size_t work = 32 * VC + 32 * VC + 32 * 192 + 8 * 32 * 32;        // Y | Y2 | QKV | SC (HID | HID2 alias Y2..)
+        const size_t lev = (size_t)VC * (len[2] + 2 * len[1]);                 // E2 | TMP | E1
+        size_t r2 = (size_t)VC * Tv;                                           // projection chunk
+        r2 = r2 > work ? r2 : work;
+        r2 = r2 > lev ? r2 : lev;
+        const size_t below = (size_t)VC * (sum - Tv) + 2 * VC * 32;            // D[1..3] | G | XF3
+        const size_t e0 = (size_t)VC * Tv;                                     // level-0 `expanded` over lds[0] (never more than below + r2)
+        return ((below + r2) > e0 ? below + r2 : e0) * sizeof(float);
+    }
     const size_t work = 2 * 16 * VC + 16 * 192 + 8 * 16 * 16 + 2 * 128 * 16;  // attention + FFN buffers aliased onto R2
     const size_t r2 = (size_t)2 * VC * Tv > work ? (size_t)2 * VC * Tv : work;
     return ((size_t)VC * (sum + Tv) + 2 * VC * 16 + r2) * sizeof(float);
@@ -312,9 +367,11 @@ size_t vp_lds_bytes(int Tv) {
 int launch_vp_block(const float* video, const float* pack, float* out, int B, int Tv, hipStream_t st) {
     int Lg = Tv;
     for (int i = 1; i < VDEPTH; ++i) Lg = (Lg - 1) / 2 + 1;
-    if (Tv < 1 || Lg > 16 || Tv > 120) return RTFS_ERR_SHAPE;
+    if (Tv < 1 || Lg > 32 || Tv > VP_LONG_MAX) return RTFS_ERR_SHAPE;
     const size_t lds = vp_lds_bytes(Tv);
-    if (rtfs_set_max_lds((const void*)vp_block_kernel, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
-    hipLaunchKernelGGL(vp_block_kernel, dim3(B), dim3(VP_NT), lds, st, video, pack, out, Tv);
+    const void* k = Tv > VP_SHORT_MAX ? (const void*)vp_block_kernel<true> : (const void*)vp_block_kernel<false>;
+    if (rtfs_set_max_lds(k, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
+    if (Tv > VP_SHORT_MAX) hipLaunchKernelGGL(vp_block_kernel<true>, dim3(B), dim3(VP_NT), lds, st, video, pack, out, Tv);
+    else hipLaunchKernelGGL(vp_block_kernel<false>, dim3(B), dim3(VP_NT), lds, st, video, pack, out, Tv);
     return rtfs_launch_status();
 }

@@ -53,14 +53,21 @@ class PackedModule(nn.Module):
 _FORCE_TRAIN_KERNELS = [False]
 
 # Fused inference kernels keep a whole sweep / score row / video pyramid on chip: an SRU time sweep of 512 positions (8.2 s of audio), 512
-# attention keys, 120 video frames; the fused block and separator, the LSTM cell's sweep and the frequency sweep stop at 250 positions (4 s,
-# BASELINE config 5).  The reference's forward has no length limit (rnn_layers.py:136-162, attention.py:149-189; infer_any_video.py:86 feeds
-# whole files): longer inputs run on the UNFUSED HIP kernels (GEMM + scan + GEMM, batched-GEMM attention, per-layer video block) that also
-# serve training - same arithmetic, tensors through HBM between the steps, any length.
+# attention keys, 256 video frames (10.2 s at 25 fps); the fused block and separator take T/2 <= 512 with the SRU cell, while the LSTM
+# cell's sweep, the LSTM block and the frequency sweep stop at 250 positions (4 s, BASELINE config 5).  The reference's forward has no length
+# limit (rnn_layers.py:136-162, attention.py:149-189; infer_any_video.py:86 feeds whole files): longer inputs run on the UNFUSED HIP kernels
+# (GEMM + scan + GEMM, batched-GEMM attention, per-layer video block) that also serve training - same arithmetic, tensors through HBM
+# between the steps, any length.
 FUSED_MAX_SWEEP = 512
-FUSED_MAX_BLOCK_SWEEP = 250
+FUSED_MAX_BLOCK_SWEEP = 250       # LSTM cell (sweep and block), frequency sweep
+FUSED_MAX_BLOCK_SWEEP_SRU = 512   # fused RTFS block / separator with the SRU cell: T/2 (T = 1025 frames, 8.2 s of audio)
 FUSED_MAX_KEYS = 512
-FUSED_MAX_VIDEO_FRAMES = 120
+FUSED_MAX_VIDEO_FRAMES = 256
+
+
+def fused_max_block_sweep(rnn_kind):
+    """Longest T/2 the fused RTFS block and separator take with cell ``rnn_kind`` (0 SRU, 1 LSTM; 2 GRU has no fused block: 0)."""
+    return {0: FUSED_MAX_BLOCK_SWEEP_SRU, 1: FUSED_MAX_BLOCK_SWEEP}.get(rnn_kind, 0)
 
 
 class force_train_kernels:

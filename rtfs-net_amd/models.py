@@ -340,8 +340,9 @@ class TDANetBlock(PackedModule):
     def forward(self, x, x_res=None):
         if x.is_cuda and L_recording(x, x_res, self):  # audio (2-D) and video (1-D) blocks alike
             return self._forward_train(x, x_res)
-        if self._hip and (self.rnn_kind == 2 or x.shape[2] // 2 > layers.FUSED_MAX_BLOCK_SWEEP):
-            # GRU cells, or a time axis past the fused kernels' on-chip sweep (> 4 s): the block composed from the unfused HIP kernels
+        if self._hip and x.shape[2] // 2 > layers.fused_max_block_sweep(self.rnn_kind):
+            # GRU cells, or a time axis past the fused kernels' on-chip sweep (SRU > 8.2 s, LSTM > 4 s): the block composed from the unfused
+            # HIP kernels
             _lib.need_gpu(x, x_res)
             if self.training:
                 raise RuntimeError("TDANetBlock: call .eval() for inference")
@@ -613,10 +614,12 @@ class AVNet(BaseAVModel):
         if L_recording(self):
             return self.forward_train(audio_mixture, mouth_embedding)
         frames = int(_lib.load().rtfs_num_frames(int(wav.shape[-1])))
-        too_long = frames // 2 > layers.FUSED_MAX_BLOCK_SWEEP or (mouth_embedding is not None and mouth_embedding.shape[-1] > layers.FUSED_MAX_VIDEO_FRAMES)
-        if self.refinement_module.audio_net.get_block(0).rnn_kind == 2 or too_long:
-            # GRU cells, or an utterance past the fused kernels' on-chip limits (> 4 s of audio / > 120 video frames): the separator
-            # composed from the unfused HIP kernels - any length, like the reference (infer_any_video.py:86 feeds whole files)
+        # (the video length does not route the separator: the VP block routes itself - fused up to FUSED_MAX_VIDEO_FRAMES, per-layer past
+        # it - and the separator's CAF kernels take any Tv)
+        too_long = frames // 2 > layers.fused_max_block_sweep(self.refinement_module.audio_net.get_block(0).rnn_kind)
+        if too_long:
+            # GRU cells, or an utterance past the fused block's on-chip limit (SRU > 8.2 s, LSTM > 4 s of audio): the separator composed
+            # from the unfused HIP kernels - any length, like the reference (infer_any_video.py:86 feeds whole files)
             if self.training:
                 raise RuntimeError("AVNet: call .eval() for inference")
             with torch.no_grad(), layers.force_train_kernels():

@@ -532,7 +532,7 @@ def pack_vp(sd):
         sc, sh = _bn_fold(sd, p + "3", sd[p + "2.bias"])
         parts += [sd[p + "2.weight"].reshape(64, 3), sc, sh]
     m = "globalatt.0.MHSA."
-    parts += [sd[m + "norm1.weight"], sd[m + "norm1.bias"], sd[m + "pos_enc.pe"][0, :16], sd[m + "attention.in_proj_weight"],
+    parts += [sd[m + "norm1.weight"], sd[m + "norm1.bias"], sd[m + "pos_enc.pe"][0, :32], sd[m + "attention.in_proj_weight"],
               sd[m + "attention.in_proj_bias"], sd[m + "attention.out_proj.weight"], sd[m + "attention.out_proj.bias"],
               sd[m + "norm2.weight"], sd[m + "norm2.bias"]]
     f = "globalatt.0.FFN."
