@@ -185,9 +185,9 @@ def injection_multi_sum_torch(local, glob, p):
     return le * gate + ge
 
 
-def rtfs_block_torch(x, p):
+def rtfs_block_torch(x, p, att_masks=None):
     """rtfs_oracle.rtfs_block in torch (reference separators/tdanet.py:104-131; is2d, upsampling_depth 2, globalatt =
-    DualPathRNN(dim 4), DualPathRNN(dim 3), MultiHeadSelfAttention2D)."""
+    DualPathRNN(dim 4), DualPathRNN(dim 3), MultiHeadSelfAttention2D).  att_masks: the attention's PReLU sign pattern (mhsa2d_torch)."""
     import torch.nn.functional as F
     residual = _cna(x, _sub(p, "gateway"), depthwise=True, act=2)
     x_enc = _cna(residual, _sub(p, "projection"))
@@ -197,7 +197,7 @@ def rtfs_block_torch(x, p):
     dp = dualpath_lstm_torch if "globalatt.0.rnn.weight_ih_l0" in p else dualpath_rnn_torch  # yaml rnn_type LSTM / SRU
     g = dp(g, _sub(p, "globalatt.0"), 4)
     g = dp(g, _sub(p, "globalatt.1"), 3)
-    g = mhsa2d_torch(g, _sub(p, "globalatt.2"))
+    g = mhsa2d_torch(g, _sub(p, "globalatt.2"), masks=att_masks)
     xf0 = injection_multi_sum_torch(d0, g, _sub(p, "fusion_layers.0"))
     xf1 = injection_multi_sum_torch(d1, g, _sub(p, "fusion_layers.1"))
     expanded = injection_multi_sum_torch(xf0, xf1, _sub(p, "concat_layers.0")) + d0

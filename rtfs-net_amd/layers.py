@@ -63,11 +63,23 @@ FUSED_MAX_BLOCK_SWEEP = 250       # LSTM cell (sweep and block), frequency sweep
 FUSED_MAX_BLOCK_SWEEP_SRU = 512   # fused RTFS block / separator with the SRU cell: T/2 (T = 1025 frames, 8.2 s of audio)
 FUSED_MAX_KEYS = 512
 FUSED_MAX_VIDEO_FRAMES = 256
+# The training BACKWARD of every dual-path cell holds one whole sweep in LDS (api_train.hip DpGeom::ok_backward): a training segment's
+# coarsest time sweep (frames through the block's stride-2 pyramid) may be at most 256 positions, 4.1 s of audio.  Inference has no limit.
+TRAIN_MAX_SWEEP = 256
 
 
 def fused_max_block_sweep(rnn_kind):
     """Longest T/2 the fused RTFS block and separator take with cell ``rnn_kind`` (0 SRU, 1 LSTM; 2 GRU has no fused block: 0)."""
     return {0: FUSED_MAX_BLOCK_SWEEP_SRU, 1: FUSED_MAX_BLOCK_SWEEP}.get(rnn_kind, 0)
+
+
+def coarsest_sweep(n, block):
+    """Length ``n`` (frames or frequency bins) after the downsampling pyramid of RTFS block ``block``: what its dual-path sweeps run over."""
+    for d in block.downsample_layers:
+        conv = d.full_layer[2]
+        if conv.stride[0] > 1:  # strided levels pad (k - 1) // 2; the others are "same"
+            n = (n + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
+    return n
 
 
 class force_train_kernels:

@@ -676,6 +676,13 @@ class AVNet(BaseAVModel):
         of this rank's batch; eval: running statistics), the video-side VP block is differentiated when it is in train mode and has
         trainable parameters, and evaluated without a graph on its inference kernel otherwise (``freeze_for_finetune``)."""
         rm = self.refinement_module
+        blk = rm.audio_net.get_block(0)
+        if torch.is_grad_enabled() and L_recording(self):  # refuse before the first launch, not in the backward after a whole forward
+            L = int(audio_mixture.shape[-1])
+            sweep = layers.coarsest_sweep(int(_lib.load().rtfs_num_frames(L)), blk)
+            if sweep > layers.TRAIN_MAX_SWEEP:
+                raise ValueError(f"AVNet.forward_train: a {L}-sample segment sweeps {sweep} positions, the training backward takes at most "
+                                 f"TRAIN_MAX_SWEEP = {layers.TRAIN_MAX_SWEEP} (about 4.1 s at 16 kHz); use shorter training segments")
         vp_block = rm.video_net.get_block(0)
         # The VP block is ~1500 tiny launches that only feed the CAF block: it runs on the side stream under the encoder and the first RTFS
         # block, and - autograd replays every node on the stream its forward ran on - its backward runs under theirs as well.
@@ -690,7 +697,6 @@ class AVNet(BaseAVModel):
                 with torch.no_grad():
                     video = vp_block(video)
         emb = self.encoder(audio_mixture)
-        blk = rm.audio_net.get_block(0)
         # rows (B, T, F, C) from the bottleneck to the mask generator wherever the modules take them (the SRU block's rows pipeline); only
         # the CAF block and the S^3 product work channel-first (each layout change of a 256-channel tensor is a 50 us transpose, twice
         # per step with the backward)

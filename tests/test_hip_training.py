@@ -17,9 +17,12 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("kind,M,N,K,acc", [(0, 300, 192, 64, 0), (0, 1000, 512, 256, 1), (0, 37, 64, 512, 0), (1, 512, 256, 1237, 0),
-                                             (1, 64, 192, 5, 0), (1, 64, 64, 40000, 0)])
+                                             (1, 64, 192, 5, 0), (1, 64, 64, 40000, 0),
+                                             (0, 129516, 64, 256, 0), (1, 256, 64, 129516, 0), (1, 256, 256, 518064, 0)])
 def test_training_gemms(kind, M, N, K, acc):
-    """The two bf16x3 GEMM forms of the training path against float64 numpy (error budget ~2^-17 per product)."""
+    """The two bf16x3 GEMM forms of the training path against float64 numpy (error budget ~2^-17 per product).  The last three rows are
+    the 1x1 convolutions of a 2 s step: the forward over B.T.F = 4.251.129 rows (not a multiple of 256), and the weight gradients over
+    K = 4.251.129 and 16.251.129 (gemm_tn splits K into 506 chunks merged by f32 atomics)."""
     from rtfs_net_amd import _lib
     lib = _lib.load()
     rng = np.random.default_rng(M + N + K)

@@ -480,3 +480,21 @@ def test_batch_split_setter_and_workspace_layout():
         assert all(0 <= t - o < 704 * 1024 for t, o in zip(two, one))  # per part: padding + the 32 KB encoder fragment image + two 288 KB padded weight images
     finally:
         R.set_batch_split(0)
+
+
+def test_training_segment_past_the_backward_limit_refused_up_front():
+    """A training segment whose coarsest time sweep exceeds layers.TRAIN_MAX_SWEEP (the dual-path backward holds one sweep in LDS) is
+    refused by AVNet.forward_train with a ValueError before anything runs; 65663 samples (513 frames -> 256 positions) is the longest
+    accepted, 65664 (514 -> 257) the shortest refused."""
+    from rtfs_net_amd import layers
+    m = build(2).train()
+    blk = m.refinement_module.audio_net.get_block(0)
+    assert layers.TRAIN_MAX_SWEEP == 256
+    assert layers.coarsest_sweep(251, blk) == 125 and layers.coarsest_sweep(129, blk) == 64
+    assert layers.coarsest_sweep(513, blk) == 256 and layers.coarsest_sweep(514, blk) == 257
+    with pytest.raises(ValueError, match="TRAIN_MAX_SWEEP = 256"):
+        m.forward_train(torch.zeros(1, 65664), torch.zeros(1, 512, 103))
+    for L, grad in ((65663, True), (65664, False)):  # within the limit, or no gradient wanted: past the check, on to the CPU tensors' error
+        with torch.set_grad_enabled(grad), pytest.raises(Exception) as err:
+            m.forward_train(torch.zeros(1, L), torch.zeros(1, 512, 103))
+        assert "TRAIN_MAX_SWEEP" not in str(err.value)
