@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the MI355X-native RTFS-Net separator forward.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment, one rank per GPU over RCCL), or started plainly as `python bench.py --gpus N ...`:
@@ -15,8 +15,13 @@ data-path collective (utterances are independent in the forward).  --dump-output
 its last timed step returned as DIR/<name>.npy (`dump_outputs`).  Rank 0 prints ONE JSON line that also carries
   roofline      the fused dual-path sweep kernel: algorithmic bytes (20*L*N*64 per SRU layer, 4 layers per
                 launch) / its launch duration measured live with HIP events on the launch stream, vs 8 TB/s HBM
+
+A plain run does only what that line needs: set-up, W warm-up steps, K timed steps, the dump, the line.  --full adds what
+takes work of its own (each can still be skipped with its --no-* option), as further fields of the same line:
   cpu_baseline  the CPU oracle (oracle/rtfs_oracle.py, numpy) timed on this box's host cores on a bounded sample
-                (16 single-threaded worker processes, one mixture each, started before the GPU is touched).
+                (16 single-threaded worker processes, one mixture each, started before the GPU is touched)
+  batch_split_2 the same step as two half batches on two streams, timed after the timed region (--no-batch-split)
+and with --train the training CPU baseline and the roofline of the step's dominant GEMM, timed alone.
 """
 import argparse
 import ctypes
@@ -338,7 +343,7 @@ def train_main(args):
     """Training-step throughput, same timing protocol as the forward bench (W warm-up steps, K steps between barrier + synchronize on both
     sides, MAX over ranks, whole-job aggregate).  Per-GPU batch defaults to the reference's training batch_size 4 unless --batch is given."""
     rank, local_rank, world, dist = init_ranks(args)
-    cpu_res = train_cpu_baseline(args.repeats) if (world == 1 and not args.no_cpu_baseline) else None  # before the GPU is initialised
+    cpu_res = train_cpu_baseline(args.repeats) if (world == 1 and args.full and not args.no_cpu_baseline) else None  # before the GPU is initialised
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
     import rtfs_net_amd as R
@@ -372,7 +377,7 @@ def train_main(args):
     ev = dist_evidence(dist, world, dev)
     if rank == 0:
         peak_gib = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
-        extra = {"roofline": train_roofline(dev, B, L)}
+        extra = {"roofline": train_roofline(dev, B, L)} if args.full else {}
         if cpu_res is not None:
             extra["cpu_baseline"] = cpu_res
         if args.dump_outputs:
@@ -400,11 +405,15 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="mixtures per GPU per step (default: 32 forward, 4 training)")
     ap.add_argument("--repeats", type=int, default=4, help="RTFS-Net-R")
     ap.add_argument("--seconds", type=float, default=2.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes work of its own: the CPU baseline, the 'batch_split_2' mode and, with --train, the "
+                         "roofline of the step's dominant GEMM (a plain run times the steps and prints the line, nothing else)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--split", type=int, default=1,
-                    help="rtfs_set_batch_split for the timed region (default 1: one chain, per-kernel durations undisturbed); the two-part "
-                         "throughput mode is measured as well, after the timed region, and reported under 'batch_split_2'")
-    ap.add_argument("--no-batch-split", action="store_true", help="skip the extra 'batch_split_2' measurement (profiling runs: one mode per trace)")
+                    help="rtfs_set_batch_split for the timed region (default 1: one chain, per-kernel durations undisturbed); with --full "
+                         "the two-part throughput mode is measured as well, after the timed region, and reported under 'batch_split_2'")
+    ap.add_argument("--no-batch-split", action="store_true",
+                    help="with --full: skip the extra 'batch_split_2' measurement (profiling runs: one mode per trace)")
     ap.add_argument("--train", action="store_true",
                     help="measure the training step instead (forward_train + PIT loss + HIP backward + one flattened gradient all-reduce "
                          "over RCCL + clip + AdamW; SyncBatchNorm at N > 1); not the contract metric, a separate JSON line")
@@ -426,7 +435,7 @@ def main():
 
     rank, local_rank, world, dist = init_ranks(args)
     cpu_res = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu_res = cpu_baseline(args.repeats)  # child processes: started before this process initialises the GPU
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
@@ -471,9 +480,9 @@ def main():
     dt = max_over_ranks(dt, dist, dev)
 
     # the throughput option (two half batches as independent chains on forked streams), outside the contract's timed region: it makes every
-    # kernel share the chip with a kernel of the other half, so it is reported beside the contract numbers, not instead of them
+    # kernel share the chip with a kernel of the other half, so it is reported beside the contract numbers, not instead of them (--full only)
     split2 = None
-    if args.split == 1 and B >= 16 and not args.no_batch_split:
+    if args.full and args.split == 1 and B >= 16 and not args.no_batch_split:
         R.set_batch_split(2)
         with torch.no_grad():
             for _ in range(2):

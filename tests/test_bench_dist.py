@@ -175,6 +175,29 @@ def test_bench_self_launch_with_the_real_forward_on_one_gpu():
     assert r["roofline"]["launches_timed"] == len(range(0, 2 * 8, 3)) and 0 < r["roofline"]["frac"] < 2
 
 
+@pytest.mark.gpu
+def test_bench_full_adds_the_extra_measurements():
+    """A plain run prints the line of its timed steps (the live sweep roofline included) and measures nothing else; --full adds the
+    measurements that take runs of their own: the two-part batch split (B >= 16) and, with --train, the dominant GEMM timed alone.  The CPU
+    baselines are --full only as well; --no-cpu-baseline keeps them out of this test (they take minutes)."""
+    fwd = ("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16", "--seconds", "0.25", "--repeats", "2")
+    trn = ("--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "2", "--seconds", "0.256", "--repeats", "2", "--train")
+    recs = {}
+    for name, argv in (("plain", fwd), ("full", fwd + ("--full", "--no-cpu-baseline")), ("train", trn), ("train_full", trn + ("--full", "--no-cpu-baseline"))):
+        pr = _bench(*argv)
+        assert pr.returncode == 0, (name, pr.stderr[-2000:])
+        lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, (name, pr.stdout)
+        recs[name] = json.loads(lines[0])
+    p, f = recs["plain"], recs["full"]
+    assert "batch_split_2" not in p and "cpu_baseline" not in p and p["roofline"]["launches_timed"] > 0
+    assert f["batch_split_2"]["value"] > 0 and f["batch_split_2"]["same_outputs"] and "cpu_baseline" not in f
+    assert "roofline" not in recs["train"] and "cpu_baseline" not in recs["train"]
+    assert recs["train_full"]["roofline"]["avg_launch_ms"] > 0 and "cpu_baseline" not in recs["train_full"]
+    for r in recs.values():
+        assert r["value"] > 0 and r["ms_per_step"] > 0 and r["unit"] == "mixtures/s" and r["higher_is_better"] is True
+
+
 def test_bench_dump_outputs(tmp_path):
     """--dump-outputs DIR: rank 0 writes what the last timed step returned as DIR/<name>.npy in float32 and names it in the JSON line.  A
     relative DIR is the caller's directory also when the parent spawns the ranks (they start in the repository root)."""
