@@ -270,9 +270,11 @@ int dualpath(const DpPack& p, const float* x, float* out, int B, int T, int F, i
 }
 
 // ---------------------------------------------------------------- attention
-int attention(const AttnPack& p, const float* x, float* out, int B, int T, float* q, float* k, float* v, float* o, hipStream_t st) {
+// x: (B,64,T,64), or channel-last (B,T,64,64) with `cl` (the RTFS block's route from the time sweep); out (B,64,T,64) either way
+int attention(const AttnPack& p, const float* x, float* out, int B, int T, float* q, float* k, float* v, float* o, hipStream_t st, bool cl = false) {
     RowCanArgs a;
     a.x = x;
+    a.cl = cl;
     a.wt = p.qkv_wt;
     a.bias = p.qkv_b;
     a.slope = p.qkv_slope;
@@ -308,6 +310,7 @@ int attention(const AttnPack& p, const float* x, float* out, int B, int T, float
     r.group_start[1] = 64;
     r.T = T;
     r.res = x;
+    r.cl = cl;
     r.out = out;
     return launch_row_can_proj(r, B, st);
 }
@@ -428,10 +431,38 @@ int block_body(const BlockPack& p, int B, int T, int F, const BlockWs& w, hipStr
     // 4. g = pool(d0) + d1
     CHECK(launch_g_form(w.p0, w.c1, w.st(W::S_C1, B), icG, p.ds1_g, p.ds1_be, w.g, B, CH, Pg, st));
     // 5-8. dual-path sweeps along F then T                                                  yaml layer_1 / layer_2
-    CHECK(dualpath(p.dpF, w.g, w.gF, B, Tp, Fp, 4, w.tA, w.tB, st));
-    CHECK(dualpath(p.dpT, w.gF, w.gT, B, Tp, Fp, 3, w.tA, w.tB, st));
+    // Channel-last route (the SRU cell on the generation-3 sweep): the F sweep reads g channel-major and writes gF channel-last, (B,T',F',64);
+    // the T sweep reads gF and writes gT in that layout - a sequence (b, f') is T' rows of 256 bytes - and the attention reads it: no
+    // transposes.  Both sweeps address with 32-bit byte offsets: sub-batches of samples spanning < 4 GB (past T' = 256, as dualpath(); at or
+    // below it the route needs the whole batch in one span).  Otherwise (the LSTM cell, RTFS_GEMM_F32=1, RTFS_SWEEP_GEN2=1) the channel-major
+    // sweeps with the two transposes around the time sweep.
+    const size_t per = (size_t)CH * Pg;  // floats per sample, either layout
+    const int nb = (int)std::min<size_t>((size_t)B, (((size_t)1 << 32) - 1) / (per * sizeof(float)));
+    const bool cl = !p.dpF.whh && !p.dpT.whh && !gemm_f32() && !dualpath_gen2() && Fp >= 8 && Fp <= 64 && Tp >= 8 && Tp <= 512 &&
+                    nb >= 1 && (nb >= B || Tp > 256);
+    if (cl) {
+        for (int b0 = 0; b0 < B; b0 += nb) {
+            const int n = std::min(nb, B - b0);
+            Dp16Args f = dp16_args(p.dpF, w.g + b0 * per, w.gF + b0 * per, n * Tp, Tp, Fp, per, Fp, Pg);
+            f.layout = 2;
+            f.obstride = per;
+            f.orstride = (size_t)Fp * CH;
+            f.opstride = CH;
+            CHECK(launch_dualpath16(f, st));
+        }
+        for (int b0 = 0; b0 < B; b0 += nb) {
+            const int n = std::min(nb, B - b0);
+            Dp16Args t = dp16_args(p.dpT, w.gF + b0 * per, w.gT + b0 * per, n * Fp, Fp, Tp, per, CH, 1);
+            t.layout = 3;
+            t.pstride = (size_t)Fp * CH;
+            CHECK(launch_dualpath16(t, st));
+        }
+    } else {
+        CHECK(dualpath(p.dpF, w.g, w.gF, B, Tp, Fp, 4, w.tA, w.tB, st));
+        CHECK(dualpath(p.dpT, w.gF, w.gT, B, Tp, Fp, 3, w.tA, w.tB, st));
+    }
     // 9. TF self-attention                                                                  yaml layer_3
-    CHECK(attention(p.attn, w.gT, w.gA, B, Tp, w.q, w.k, w.v, w.o, st));
+    CHECK(attention(p.attn, w.gT, w.gA, B, Tp, w.q, w.k, w.v, w.o, st, cl));
     {  // 10. the four G-level convs on the attention output (fusion 0/1: global_embedding, global_gate)
        // 11. fusion 1 local_embedding on d1 = gLN(c1) - independent of step 10: one launch for the three jobs
         DwArgs a;

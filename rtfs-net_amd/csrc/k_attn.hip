@@ -18,7 +18,12 @@
 // kernel (few waves per CU: register-heavy) never waits on a cold load.
 #define RCAN_ROWS 8
 #define RCAN_LD 72  // Ys row stride: D-layout writes (rows +4 on the upper half-wave) land in the other 32 banks
-template <int NOUT>
+// CL (RowCanArgs::cl): NOUT == 96 reads X channel-last, (B,T,64 f,64 c) - lane (h, f) takes channels 16 ks + 8 h .. + 7 as two 16-byte loads per k
+// step; NOUT == 64 reads its residual channel-last.  A lane there needs channels 16 wave .. + 15 of position f: a quarter of a 256-byte row, so
+// every 128-byte line would be fetched by two waves.  Instead the workgroup loads the frame's 16 KB as four whole-line 16-byte loads per thread
+// and passes it through LDS (Rs, written behind the GEMM, read behind the barrier that follows it).  X of NOUT == 64 (attn_core's output) and
+// every output stay channel-major.
+template <int NOUT, bool CL = false>
 __global__ __launch_bounds__(256, 2) void row_can_kernel(RowCanArgs a) {
     constexpr int MT = NOUT / 32, MTW = (MT + 1) / 2;
     constexpr int NR = NOUT / 4;  // LayerNorm rows per wave: 96 -> Q_w (4) + K_w (4) + V_w (16); 64 -> 16 of the one group
@@ -26,6 +31,8 @@ __global__ __launch_bounds__(256, 2) void row_can_kernel(RowCanArgs a) {
     __shared__ float Ys[NOUT][RCAN_LD];
     __shared__ float bias_s[NOUT], slope_s[NOUT];
     __shared__ float red[8];
+    constexpr bool XCL = CL && NOUT == 96, RCL = CL && NOUT == 64;
+    __shared__ __attribute__((aligned(16))) float Rs[RCL ? AF : 1][RCL ? 68 : 4];  // RCL: the frame's residual, [f][c], rows padded to 68 floats
     const int T = a.T, b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -62,15 +69,24 @@ __global__ __launch_bounds__(256, 2) void row_can_kernel(RowCanArgs a) {
     }
     const int t0 = blockIdx.x * a.rpw;
     const int nrows = min(a.rpw, T - t0);
-    const float* __restrict__ X = a.x + (size_t)b * 64 * T * AF + nt * 32 + r;
-    const float* __restrict__ RES = NOUT == 64 ? a.res + ((size_t)b * 64 + wave * 16) * T * AF + lane : nullptr;
+    const float* __restrict__ X = XCL ? a.x + ((size_t)b * T * AF + nt * 32 + r) * 64 + 8 * h : a.x + (size_t)b * 64 * T * AF + nt * 32 + r;
+    const float* __restrict__ RES = NOUT == 64 ? (RCL ? a.res + (size_t)b * T * AF * 64 + 4 * tid : a.res + ((size_t)b * 64 + wave * 16) * T * AF + lane)
+                                               : nullptr;
     float v[4][8];
     float rs[NOUT == 64 ? 16 : 1];
     auto load_x = [&](int t) {
+        if constexpr (XCL) {
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
+            for (int ks = 0; ks < 4; ++ks) {
+                *reinterpret_cast<f32x4*>(&v[ks][0]) = *reinterpret_cast<const f32x4*>(X + (size_t)t * AF * 64 + ks * 16);
+                *reinterpret_cast<f32x4*>(&v[ks][4]) = *reinterpret_cast<const f32x4*>(X + (size_t)t * AF * 64 + ks * 16 + 4);
+            }
+        } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[ks][j] = X[((size_t)(ks * 16 + 8 * h + j) * T + t) * AF];
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[ks][j] = X[((size_t)(ks * 16 + 8 * h + j) * T + t) * AF];
+        }
     };
     load_x(t0);
     __syncthreads();
@@ -85,7 +101,10 @@ __global__ __launch_bounds__(256, 2) void row_can_kernel(RowCanArgs a) {
             bh[ks] = __builtin_bit_cast(half8, *reinterpret_cast<f32x4*>(hi));
             bl[ks] = __builtin_bit_cast(half8, *reinterpret_cast<f32x4*>(lo));
         }
-        if (NOUT == 64) {
+        if constexpr (RCL) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(&rs[4 * k]) = *reinterpret_cast<const f32x4*>(RES + (size_t)t * AF * 64 + 1024 * k);
+        } else if (NOUT == 64) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) rs[i] = RES[((size_t)i * T + t) * AF];
         }
@@ -109,6 +128,10 @@ __global__ __launch_bounds__(256, 2) void row_can_kernel(RowCanArgs a) {
                     Ys[o][nt * 32 + r] = preluf_(acc[q] * WINV, slope_s[o]);
                 }
             }
+        }
+        if constexpr (RCL) {  // thread tid's pieces: f = tid / 16 + 16 k, c = 4 (tid % 16)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(&Rs[tid / 16 + 16 * k][4 * (tid % 16)]) = *reinterpret_cast<const f32x4*>(&rs[4 * k]);
         }
         __syncthreads();
         float y[NR];
@@ -154,6 +177,10 @@ __global__ __launch_bounds__(256, 2) void row_can_kernel(RowCanArgs a) {
             __syncthreads();
             const float rstd = 1.0f / sqrtf((red[4] + red[5] + red[6] + red[7]) / (float)(64 * AF) + RTFS_EPS);
             float* __restrict__ O = a.out + ((size_t)b * 64 + wave * 16) * T * AF + lane;
+            if constexpr (RCL) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(&rs[4 * k]) = *reinterpret_cast<const f32x4*>(&Rs[lane][wave * 16 + 4 * k]);
+            }
 #pragma unroll
             for (int i = 0; i < 16; ++i) O[((size_t)i * T + t) * AF] = fmaf(y[i] * rstd, gam_s[ln_row(i)][lane], bet_s[ln_row(i)][lane]) + rs[i];
         }
@@ -322,14 +349,20 @@ int launch_row_can_qkv(const RowCanArgs& a_, int B, hipStream_t st) {
     RowCanArgs a = a_;
     a.rpw = rcan_rows(a.T, B);
     if (a.ngroups != 12 || a.group_start[8] != 32 || a.group_start[12] != 96) return RTFS_ERR_SHAPE;  // Q_h x4, K_h x4 (4 ch), V_h x4 (16 ch)
-    hipLaunchKernelGGL(row_can_kernel<96>, dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
+    if (a.cl)
+        hipLaunchKernelGGL((row_can_kernel<96, true>), dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((row_can_kernel<96, false>), dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
     return rtfs_launch_status();
 }
 int launch_row_can_proj(const RowCanArgs& a_, int B, hipStream_t st) {
     RowCanArgs a = a_;
     a.rpw = rcan_rows(a.T, B);
     if (a.ngroups != 1) return RTFS_ERR_SHAPE;
-    hipLaunchKernelGGL(row_can_kernel<64>, dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
+    if (a.cl)
+        hipLaunchKernelGGL((row_can_kernel<64, true>), dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((row_can_kernel<64, false>), dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
     return rtfs_launch_status();
 }
 int launch_attn_core(const AttnArgs& a, int B, hipStream_t st) {

@@ -439,6 +439,11 @@ static int launch_dp16_t(const Dp16Args& a, hipStream_t st) {
     return rtfs_launch_status();
 }
 
+bool dualpath_gen2() {
+    static const bool gen2 = getenv("RTFS_SWEEP_GEN2") != nullptr;
+    return gen2;
+}
+
 int launch_dualpath16(const Dp16Args& a, hipStream_t st) {
     const int L = a.Ls - 7;
     if (L < 1 || a.Ls > 512) return RTFS_ERR_SHAPE;
@@ -446,8 +451,8 @@ int launch_dualpath16(const Dp16Args& a, hipStream_t st) {
     // generation 3 only)
     // generation 3 (k_dualpath16s.hip: two workgroups per CU up to Ls = 128, its 512-thread variant above); RTFS_SWEEP_GEN2=1 keeps this file's
     // kernels for A/B
-    static const bool gen2 = getenv("RTFS_SWEEP_GEN2") != nullptr;
-    if (!gen2 || a.Ls > 256) {  // (past 256 positions there is no generation-2 kernel: the switch applies to the shorter sweeps)
+    if (a.layout != 0) return launch_dualpath16s(a, st);  // (channel-last sides: generation 3 only)
+    if (!dualpath_gen2() || a.Ls > 256) {  // (past 256 positions there is no generation-2 kernel: the switch applies to the shorter sweeps)
         const int rc = launch_dualpath16s(a, st);
         if (rc != RTFS_ERR_SHAPE) return rc;  // (a tensor spanning >= 4 GB: this file's kernels address with 64 bits)
     }

@@ -77,6 +77,15 @@ __device__ __forceinline__ void sto(float* __restrict__ base, unsigned boff, flo
     asm volatile("" : "+v"(boff));
     *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + boff) = v;
 }
+// four consecutive channels of a channel-last row: one 16-byte access, `imm` bytes behind the lane offset (an instruction immediate)
+__device__ __forceinline__ f32x4 ldo4(const float* __restrict__ base, unsigned boff, unsigned imm) {
+    asm volatile("" : "+v"(boff));
+    return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + boff + imm);
+}
+__device__ __forceinline__ void sto4(float* __restrict__ base, unsigned boff, unsigned imm, f32x4 v) {
+    asm volatile("" : "+v"(boff));
+    *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(base) + boff + imm) = v;
+}
 
 // sigmoid with the -log2(e) factor already folded into z
 __device__ __forceinline__ float sig2(float z) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z)); }
@@ -100,9 +109,14 @@ __device__ __forceinline__ float sum_halves(float v) {
 // shapes (Ls <= 256: one sequence, 4 time parts x 2 directions = 512 threads, 102 KB of LDS, ONE workgroup per CU with two of its own waves per
 // SIMD): the same program, the chain handed through four parts.  NPASS = 2 on top of that is the 8 s variant (Ls <= 512): every layer and the
 // conv-transpose walk the 256 covered steps twice, the weight stream single-buffered.
-template <int NSEQ, bool PAIRED, int NT, bool STAMP = false, int NP = 4 / NT, int NPASS = 1>
+// LAY = Dp16Args::layout: 0 channel-major in and out (a position's channels cstride apart, positions contiguous); 3 channel-last in and out (a
+// position's 64 channels are one 256-byte row, positions pstride apart: the RTFS block's time sweep); 2 channel-major in, channel-last out (the
+// block's frequency sweep).  Channel-last sides are read and written 16 bytes at a time; the arithmetic and its order do not depend on LAY.
+template <int NSEQ, bool PAIRED, int NT, bool STAMP = false, int NP = 4 / NT, int NPASS = 1, int LAY = 0>
 __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Args a) {
     static_assert((NSEQ == 2 && PAIRED) || (NSEQ == 1 && !PAIRED), "F sweep: one sequence pair; T sweep: one sequence");
+    static_assert(LAY == 0 || LAY == 2 || LAY == 3, "layouts: channel-major, channel-major -> channel-last, channel-last");
+    constexpr bool XCL = LAY & 1, OCL = LAY >> 1;   // channel-last input / output
     static_assert(NT == 1 || NT == 2, "row tiles per wave");
     static_assert(NP == 2 || NP == 4, "time parts");
     static_assert(NPASS == 1 || (NPASS == 2 && NSEQ == 1 && NT == 2 && NP == 4), "two passes: the 4 s program only");
@@ -154,6 +168,12 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         n = n < a.nseq ? n : a.nseq - 1;
         return (size_t)(n / a.R) * a.bstride + (size_t)(n % a.R) * a.rstride;
     };
+    auto out_seq_base = [&](int s) {  // (layout 2: the output's own strides; otherwise x's)
+        int n = n0 + s;
+        n = n < a.nseq ? n : a.nseq - 1;
+        return XCL == OCL ? (size_t)(n / a.R) * a.bstride + (size_t)(n % a.R) * a.rstride
+                          : (size_t)(n / a.R) * a.obstride + (size_t)(n % a.R) * a.orstride;
+    };
 
     // ---------------- weight stream.  Global images in fragment order, 1024 pieces (16 KB) per K step:
     //   gate step:  piece ((dir * 4 + m) * 2 + part) * 64 + lane      conv-transpose tap: piece ((co tile * 4 + ks) * 2 + part) * 64 + lane
@@ -185,10 +205,20 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
         const bool live = task < ntask;
         const int tk = live ? task : ntask - 1;
         const int s = (NSEQ == 2 && tk >= Ls) ? 1 : 0, pos = tk - s * Ls;
-        const unsigned xoff = (unsigned)(seq_base(s) + pos + (size_t)(32 * h) * a.cstride) * 4u;
         float v[32];
+        if constexpr (XCL) {  // the half's 32 channels: one 128-byte line, eight 16-byte loads
+            const unsigned xoff = (unsigned)(seq_base(s) + (size_t)pos * a.pstride + 32 * h) * 4u;
 #pragma unroll
-        for (int c = 0; c < 32; ++c) v[c] = ldo(a.x + (size_t)c * a.cstride, xoff);
+            for (int c4 = 0; c4 < 8; ++c4) {
+                const f32x4 q = ldo4(a.x, xoff, 16 * c4);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[4 * c4 + i] = q[i];
+            }
+        } else {
+            const unsigned xoff = (unsigned)(seq_base(s) + pos + (size_t)(32 * h) * a.cstride) * 4u;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) v[c] = ldo(a.x + (size_t)c * a.cstride, xoff);
+        }
         float sum = 0.f;
 #pragma unroll
         for (int c = 0; c < 32; ++c) sum += v[c];
@@ -623,18 +653,33 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
             for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
         // the residual rows of the epilogue are requested now and arrive under the GEMM (clamped addresses: dead
         // sequences / positions read a valid element that is never stored)
-        // channel co = 32 ccot + (q & 3) + 8 (q >> 2) + 4 h: the q part of the address is wave-uniform (scalar base), the rest one lane offset
+        // channel co = 32 ccot + (q & 3) + 8 (q >> 2) + 4 h: the q part of the address is wave-uniform (scalar base), the rest one lane offset;
+        // channel-last, the four channels (q & 3) of one q >> 2 are one 16-byte access at an immediate offset of 32 (q >> 2) bytes
         float res[NT][16];
-        const size_t rbase = seq_base(cseq) + (size_t)(ccot * 32) * a.cstride;  // uniform
-        unsigned eoff[NT];
+        unsigned eoff[NT];  // residual (x); layouts 0 and 3: the output too
 #pragma unroll
-        for (int t = 0; t < NT; ++t) eoff[t] = (unsigned)(rbase + (size_t)(4 * h) * a.cstride + min(PSTEPS * cp + 32 * NT * cpart + 32 * t + r, Ls - 1)) * 4u;
+        for (int t = 0; t < NT; ++t) {
+            const size_t p = min(PSTEPS * cp + 32 * NT * cpart + 32 * t + r, Ls - 1);
+            eoff[t] = XCL ? (unsigned)(seq_base(cseq) + p * a.pstride + ccot * 32 + 4 * h) * 4u
+                          : (unsigned)(seq_base(cseq) + (size_t)(ccot * 32) * a.cstride + (size_t)(4 * h) * a.cstride + p) * 4u;
+        }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int cq = (q & 3) + 8 * (q >> 2);
             const float btq = a.bt[ccot * 32 + cq + 4 * h];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) res[t][q] = ldo(a.x + (size_t)cq * a.cstride, eoff[t]) + btq;  // residual + conv-transpose bias, fetched under the GEMM
+            for (int t = 0; t < NT; ++t) {  // residual + conv-transpose bias, fetched under the GEMM
+                if constexpr (XCL) {
+                    if ((q & 3) == 0) {
+                        const f32x4 x4 = ldo4(a.x, eoff[t], 32 * (q >> 2));
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) res[t][q + i] = x4[i];
+                    }
+                    res[t][q] += btq;
+                } else {
+                    res[t][q] = ldo(a.x + (size_t)cq * a.cstride, eoff[t]) + btq;
+                }
+            }
         }
         __builtin_amdgcn_sched_barrier(0);  // (the residual requests stay out of the taps' pinned schedule)
         // tap 0 is staged in buffer g & 1, taps 1 and 2 in the register sets; 8 taps of 64 k' each
@@ -710,9 +755,20 @@ __global__ __launch_bounds__(128 * NP, NT == 2 ? 2 : 4) void dp16s_kernel(Dp16Ar
             for (int t = 0; t < NT; ++t) {
                 const int p = PSTEPS * cp + 32 * NT * cpart + 32 * t + r;
                 if (p < Ls) {  // (then the clamped position of eoff is p itself)
+                    if constexpr (OCL) {  // four 16-byte stores; the other pieces of their 128-byte lines come from the workgroup's other waves
+                        const unsigned ooff = XCL ? eoff[t] : (unsigned)(out_seq_base(cseq) + (size_t)p * a.opstride + ccot * 32 + 4 * h) * 4u;
 #pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        sto(a.out + (size_t)((q & 3) + 8 * (q >> 2)) * a.cstride, eoff[t], fmaf(acc[t][q], WINV, res[t][q]));
+                        for (int j = 0; j < 4; ++j) {
+                            f32x4 y;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) y[i] = fmaf(acc[t][4 * j + i], WINV, res[t][4 * j + i]);
+                            sto4(a.out, ooff, 32 * j, y);
+                        }
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 16; ++q)
+                            sto(a.out + (size_t)((q & 3) + 8 * (q >> 2)) * a.cstride, eoff[t], fmaf(acc[t][q], WINV, res[t][q]));
+                    }
                 }
             }
         }
@@ -724,36 +780,48 @@ size_t dp16s_lds_bytes(int Ls, int nseq_per_wg) {
     return (size_t)(Ls > 256 ? 1 : 2) * WBUF + (size_t)nseq_per_wg * (Ls + 1 + PADR) * HLD * 2 + (size_t)nseq_per_wg * 2 * 32 * 4;
 }
 
-template <int NSEQ, bool PAIRED, int NT, int NP = 4 / NT, int NPASS = 1>
+template <int NSEQ, bool PAIRED, int NT, int NP = 4 / NT, int NPASS = 1, int LAY = 0>
 static int launch_dp16s_t(const Dp16Args& a, hipStream_t st) {
     const size_t lds = dp16s_lds_bytes(a.Ls, NSEQ);
     constexpr bool LONG = NT == 2 && NP == 4;             // one 512-thread workgroup per CU
     if (lds > (LONG ? 160 : 80) * 1024) return RTFS_ERR_SHAPE;  // (else: two workgroups per CU)
     constexpr int NTHR = 128 * NP;
-    if (a.stamps) {
+    if (a.stamps) {  // (the diagnostic build: channel-major only)
+        if (LAY != 0) return RTFS_ERR_ARG;
         if (rtfs_set_max_lds((const void*)dp16s_kernel<NSEQ, PAIRED, NT, true, NP, NPASS>, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
         hipLaunchKernelGGL((dp16s_kernel<NSEQ, PAIRED, NT, true, NP, NPASS>), dim3(cdiv(a.nseq, NSEQ)), dim3(NTHR), lds, st, a);
         return rtfs_launch_status();
     }
-    if (rtfs_set_max_lds((const void*)dp16s_kernel<NSEQ, PAIRED, NT, false, NP, NPASS>, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
+    if (rtfs_set_max_lds((const void*)dp16s_kernel<NSEQ, PAIRED, NT, false, NP, NPASS, LAY>, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
     void* slot = dualpath_timing_begin(a.Ls, a.nseq, st);
-    hipLaunchKernelGGL((dp16s_kernel<NSEQ, PAIRED, NT, false, NP, NPASS>), dim3(cdiv(a.nseq, NSEQ)), dim3(NTHR), lds, st, a);
+    hipLaunchKernelGGL((dp16s_kernel<NSEQ, PAIRED, NT, false, NP, NPASS, LAY>), dim3(cdiv(a.nseq, NSEQ)), dim3(NTHR), lds, st, a);
     dualpath_timing_end(slot, st);
     return rtfs_launch_status();
+}
+
+// routing by Ls for one layout
+template <int LAY>
+static int launch_dp16s_lay(const Dp16Args& a, hipStream_t st) {
+    if (a.Ls > 256) return launch_dp16s_t<1, false, 2, 4, 2, LAY>(a, st);  // the 8 s shapes: the same, two passes
+    if (a.Ls > 128) return launch_dp16s_t<1, false, 2, 4, 1, LAY>(a, st);  // the 4 s shapes: four time parts, one workgroup per CU
+    return a.Ls <= 64 ? launch_dp16s_t<2, true, 2, 2, 1, LAY>(a, st) : launch_dp16s_t<1, false, 2, 2, 1, LAY>(a, st);
 }
 
 // Ls <= 64 (the F sweep: 64): one sequence pair per workgroup; Ls <= 128 (the 2 s T sweep: 125): one sequence per workgroup; Ls <= 256 (the
 // 4 s T sweep: 250): one sequence per 512-thread workgroup; Ls <= 512 (the 8 s T sweep: 512): the same workgroup in two passes.  The limits are
 // on Ls = L + 7, the row count of the load phase and of the conv-transpose output (routing by L left Ls = 65 .. 71 and 129 .. 135 with their
 // last positions unwritten - found by tests/test_hip_parity.py::test_dualpath_sweep_lengths)
-int launch_dualpath16s(const Dp16Args& a0, hipStream_t st) {
-    const int L = a0.Ls - 7;
-    if (L < 1 || a0.Ls > 512) return RTFS_ERR_SHAPE;
-    // 32-bit byte offsets from the tensor base inside the kernel
-    if ((((size_t)(a0.nseq - 1) / a0.R) * a0.bstride + (size_t)(a0.R - 1) * a0.rstride + 63 * a0.cstride + a0.Ls) * 4 >= ((size_t)1 << 32)) return RTFS_ERR_SHAPE;
-    const Dp16Args& a = a0;
-    const bool pair = a0.Ls <= 64;
-    if (a0.Ls > 256) return launch_dp16s_t<1, false, 2, 4, 2>(a, st);  // the 8 s shapes: the same, two passes
-    if (a0.Ls > 128) return launch_dp16s_t<1, false, 2, 4>(a, st);  // the 4 s shapes: four time parts, one workgroup per CU
-    return pair ? launch_dp16s_t<2, true, 2>(a, st) : launch_dp16s_t<1, false, 2>(a, st);
+int launch_dualpath16s(const Dp16Args& a, hipStream_t st) {
+    const int L = a.Ls - 7;
+    if (L < 1 || a.Ls > 512) return RTFS_ERR_SHAPE;
+    if (a.layout != 0 && a.layout != 2 && a.layout != 3) return RTFS_ERR_ARG;
+    // 32-bit byte offsets from the tensor base inside the kernel: the last element of either side lies below 4 GB
+    const bool xcl = a.layout & 1, ocl = a.layout >> 1;
+    const size_t nb = (size_t)(a.nseq - 1) / a.R, nr = (size_t)(a.R - 1), lp = (size_t)(a.Ls - 1);
+    const size_t xspan = nb * a.bstride + nr * a.rstride + (xcl ? lp * a.pstride + 63 : 63 * a.cstride + lp);
+    const size_t ospan = xcl == ocl ? xspan : nb * a.obstride + nr * a.orstride + lp * a.opstride + 63;
+    if ((std::max(xspan, ospan) + 1) * 4 >= ((size_t)1 << 32)) return RTFS_ERR_SHAPE;
+    if (a.layout == 3) return launch_dp16s_lay<3>(a, st);
+    if (a.layout == 2) return launch_dp16s_lay<2>(a, st);
+    return launch_dp16s_lay<0>(a, st);
 }

@@ -229,7 +229,8 @@ int launch_sru_standalone(const float* x, float* h, int L, int N, const float* W
 
 // TF attention
 struct RowCanArgs {
-    const float* x = nullptr;      // (B,64,T,64)
+    const float* x = nullptr;      // (B,64,T,64); cl: (B,T,64,64) channel-last (NOUT == 96)
+    int cl = 0;                    // channel-last X (NOUT == 96) / residual (NOUT == 64): the RTFS block's route from the time sweep
     const float* wt = nullptr;     // (64, NOUT) transposed 1x1 weights of every ConvActNorm in the call
     const float* bias = nullptr;   // (NOUT)
     const float* slope = nullptr;  // (ngroups) PReLU slope of each ConvActNorm
@@ -280,7 +281,13 @@ struct Dp16Args {
     const float* x = nullptr;
     float* out = nullptr;
     int nseq = 0, R = 0, Ls = 0;
-    size_t bstride = 0, rstride = 0, cstride = 0;
+    size_t bstride = 0, rstride = 0, cstride = 0;  // x: sequence n at (n / R) bstride + (n % R) rstride; channel stride (channel-major)
+    // Channel-last sides (generation 3 only, k_dualpath16s.hip): a position's 64 channels are contiguous, positions `pstride` floats apart.
+    // layout bit 0: x channel-last (cstride unused); bit 1: out channel-last.  Layouts 0 and 3: out shares x's strides; layout 2 (x channel-major,
+    // out channel-last - the F sweep feeding the T sweep) addresses out with its own ob / or / op strides.
+    int layout = 0;
+    size_t pstride = 0;
+    size_t obstride = 0, orstride = 0, opstride = 0;
     const float* ln_gamma = nullptr;
     const float* ln_beta = nullptr;
     const half8* w16_l0 = nullptr;  // [16 chunks][hi|lo][256 cols = dir*128 + gate*32 + j][32 k'], k' = kk*64 + c
@@ -299,6 +306,7 @@ int launch_dualpath16(const Dp16Args& a, hipStream_t st);
 // generation 3 (k_dualpath16s.hip): 256-thread workgroups, two per CU, L <= 128; launch_dualpath16 routes to it
 size_t dp16s_lds_bytes(int Ls, int nseq_per_wg);
 int launch_dualpath16s(const Dp16Args& a, hipStream_t st);
+bool dualpath_gen2();  // RTFS_SWEEP_GEN2=1: the sweeps up to Ls = 256 run on generation 2 (channel-major only)
 void* dualpath_timing_begin(int Ls, int nseq, hipStream_t st);
 void dualpath_timing_end(void* slot, hipStream_t st);
 
