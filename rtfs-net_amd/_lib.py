@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 
 import torch
 
@@ -158,7 +159,10 @@ def load():
 
 def check(code: int, what: str):
     if code != 0:
+        _guards().clear()
         raise RuntimeError(f"{what} failed: {_ERR.get(code, code)}")
+    if _POISON is not None:
+        _check_guards(what)
 
 
 def ptr(t):
@@ -187,13 +191,79 @@ def need_gpu(*tensors):
             raise RuntimeError(f"rtfs_net_amd kernels are float32; got {t.dtype}")
 
 
-_POISON = bool(os.environ.get("RTFS_POISON_WS"))
+def poison_byte(value):
+    """The fill byte an ``RTFS_POISON_WS`` value selects: None (unset, empty, "0": off), 0xFF ("1", "nan": NaN as f32 and f64) or
+    0x7F ("big": 3.4e38 as f32, 1.4e306 as f64; finite, so it survives the fmaxf of a ReLU or max-pool epilogue and blows up later)."""
+    v = (value or "").strip().lower()
+    if v in ("", "0"):
+        return None
+    if v in ("1", "nan"):
+        return 0xFF
+    if v == "big":
+        return 0x7F
+    raise ValueError(f"RTFS_POISON_WS={value!r}: expected 0, 1, nan or big")
+
+
+# read at call time (tests switch it in-process with monkeypatch.setattr(_lib, "_POISON", 0xFF))
+_POISON = poison_byte(os.environ.get("RTFS_POISON_WS"))
+GUARD_BYTES = 64 << 10
+_tls = threading.local()
+
+
+def _guards():
+    g = getattr(_tls, "guards", None)
+    if g is None:
+        g = _tls.guards = []
+    return g
+
+
+def _poison(t: torch.Tensor):
+    if t.is_floating_point():
+        t.untyped_storage().fill_(_POISON)
+    return t
+
+
+def empty(*size, device, dtype=torch.float32):
+    """torch.empty for the outputs and saved state a C call fills.  Off, it is exactly torch.empty; under RTFS_POISON_WS a floating
+    tensor comes back filled with the poison byte, so an element no kernel writes (or a kernel reads before writing) shows up."""
+    t = torch.empty(*size, device=device, dtype=dtype)
+    return t if _POISON is None else _poison(t)
+
+
+def empty_like(t: torch.Tensor):
+    """torch.empty_like with the poison fill of ``empty``."""
+    e = torch.empty_like(t)
+    return e if _POISON is None else _poison(e)
 
 
 def workspace(nbytes: int, device):
     """Caller-owned scratch for one C call.  The kernels must never read a workspace byte they have not written in the same call;
-    RTFS_POISON_WS=1 (tests) fills every workspace with 0xFF bytes (NaN as f32 / f64) so such a read shows up in the output."""
-    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-    if _POISON:
-        ws.fill_(0xFF)
-    return ws
+    RTFS_POISON_WS (tests) fills every workspace with the poison byte so such a read shows up in the output, and follows it with a
+    poisoned guard band of GUARD_BYTES that the next check() verifies: a write past the size the *_workspace_bytes query promised
+    raises there, naming the entry point."""
+    n = max(int(nbytes), 256)
+    if _POISON is None:
+        return torch.empty(n, dtype=torch.uint8, device=device)
+    buf = torch.empty(n + GUARD_BYTES, dtype=torch.uint8, device=device)
+    buf.fill_(_POISON)
+    _guards().append(buf[n:])
+    return buf[:n]
+
+
+def _check_guards(what: str):
+    """Verify (and forget) the guard bands this thread handed out since the previous check.  Skipped while the current stream is
+    capturing a graph: nothing has run yet."""
+    g = _guards()
+    if not g:
+        return
+    if any(t.is_cuda for t in g) and torch.cuda.is_current_stream_capturing():
+        g.clear()
+        return
+    pending = list(g)
+    g.clear()
+    if any(t.is_cuda for t in pending):
+        torch.cuda.synchronize()
+    bad = [t for t in pending if bool(t.ne(_POISON).any())]
+    if bad:
+        raise RuntimeError(f"{what} wrote past the end of {len(bad)} of its {len(pending)} workspace(s) "
+                           f"(guard band of {GUARD_BYTES} bytes changed)")

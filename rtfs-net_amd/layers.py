@@ -308,8 +308,8 @@ class _CNATrainFn(torch.autograd.Function):
             oshape = (B, ho_v, wo_v, cfg[1]) if x.dim() == 4 else (B, wo_v, cfg[1])
         else:
             oshape = (B, cfg[1], ho_v, wo_v) if x.dim() == 4 else (B, cfg[1], wo_v)
-        out = torch.empty(oshape, device=x.device, dtype=torch.float32)
-        saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
+        out = _lib.empty(oshape, device=x.device, dtype=torch.float32)
+        saved = _lib.empty(n_saved, device=x.device, dtype=torch.float32)
         ws = _lib.workspace(ws_bytes, x.device)
 
         def run(c):
@@ -341,8 +341,8 @@ class _CNATrainFn(torch.autograd.Function):
         world = ctx.world
         carr, _, _, _, ws_bytes, n_grad = _CNATrainFn._geom(ctx.cfg, world, B, H, W)
         dout = dout.contiguous().to(torch.float32)
-        dx = torch.empty(ctx.xshape, device=dout.device, dtype=torch.float32)
-        dpar = torch.empty(n_grad, device=dout.device, dtype=torch.float32)
+        dx = _lib.empty(ctx.xshape, device=dout.device, dtype=torch.float32)
+        dpar = _lib.empty(n_grad, device=dout.device, dtype=torch.float32)
         ws = _lib.workspace(ws_bytes, dout.device)
 
         def run(c):
@@ -383,7 +383,7 @@ class _GatewayFn(torch.autograd.Function):
         x = x.contiguous()
         x_res = None if x_res is None else x_res.contiguous()
         C = x.shape[-1]
-        out = torch.empty_like(x)
+        out = _lib.empty_like(x)
         _lib.check(lib.rtfs_gateway_forward_train_f32(_lib.ptr(x), _lib.ptr(x_res), _lib.ptr(w), _lib.ptr(b), _lib.ptr(slope), _lib.ptr(out),
                                                       x.numel() // C, C, _lib.stream_of(x)), "rtfs_gateway_forward_train_f32")
         ctx.save_for_backward(x, x_res, w, b, slope)
@@ -396,8 +396,8 @@ class _GatewayFn(torch.autograd.Function):
         x, x_res, w, b, slope = ctx.saved_tensors
         C = x.shape[-1]
         dout = dout.contiguous()
-        dx = torch.empty_like(x)
-        dpar = torch.empty(lib.rtfs_gateway_grad_floats(C), device=x.device, dtype=torch.float32)
+        dx = _lib.empty_like(x)
+        dpar = _lib.empty(lib.rtfs_gateway_grad_floats(C), device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_gateway_workspace_bytes(C), x.device)
         _lib.check(lib.rtfs_gateway_backward_f32(_lib.ptr(x), _lib.ptr(x_res), _lib.ptr(w), _lib.ptr(b), _lib.ptr(slope), _lib.ptr(dout), _lib.ptr(dx),
                                                  _lib.ptr(dpar), x.numel() // C, C, _lib.ptr(ws), ws.numel(), _lib.stream_of(x)),
@@ -612,8 +612,8 @@ class _SRUTrainFn(torch.autograd.Function):
         x = x.contiguous()
         L, N, _ = x.shape
         tpack = packing.cached_train_pack("sru", params, lambda: packing.pack_sru_train(params[0::3], params[1::3], params[2::3]))
-        h = torch.empty(L, N, 64, device=x.device, dtype=torch.float32)
-        saved = torch.empty(lib.rtfs_sru_saved_floats(L, N), device=x.device, dtype=torch.float32)
+        h = _lib.empty(L, N, 64, device=x.device, dtype=torch.float32)
+        saved = _lib.empty(lib.rtfs_sru_saved_floats(L, N), device=x.device, dtype=torch.float32)
         _lib.check(lib.rtfs_sru_forward_train_f32(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(h), _lib.ptr(saved), L, N, _lib.stream_of(x)),
                    "rtfs_sru_forward_train_f32")
         ctx.save_for_backward(x, tpack, saved)
@@ -625,8 +625,8 @@ class _SRUTrainFn(torch.autograd.Function):
         x, tpack, saved = ctx.saved_tensors
         L, N, _ = x.shape
         dh = dh.contiguous().to(torch.float32)
-        dx = torch.empty_like(x)
-        dpar = torch.empty(lib.rtfs_sru_grad_floats(), device=x.device, dtype=torch.float32)
+        dx = _lib.empty_like(x)
+        dpar = _lib.empty(lib.rtfs_sru_grad_floats(), device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_sru_backward_workspace_bytes(L, N), x.device)
         _lib.check(lib.rtfs_sru_backward_f32(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(saved), _lib.ptr(dh), _lib.ptr(dx), _lib.ptr(dpar), L, N,
                                              _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_sru_backward_f32")
@@ -658,7 +658,7 @@ class SRU(PackedModule):
             return _SRUTrainFn.apply(x, *params), None
         x = x.contiguous()
         L, N, _ = x.shape
-        h = torch.empty(L, N, 64, device=x.device, dtype=torch.float32)
+        h = _lib.empty(L, N, 64, device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_sru_workspace_bytes(L, N), x.device)
         _lib.check(lib.rtfs_sru_f32(_lib.ptr(x), _lib.ptr(self.pack()), _lib.ptr(h), L, N, _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_sru_f32")
         return h, None
@@ -680,8 +680,8 @@ class _DualPathTrainFn(torch.autograd.Function):
         sru, lin_w, lin_b = rest[:12], rest[12], rest[13]
         tpack = packing.cached_train_pack("dualpath", (gamma, beta) + tuple(rest),
                                           lambda: packing.pack_dualpath_train(gamma, beta, sru[0::3], sru[1::3], sru[2::3], lin_w, lin_b))
-        out = torch.empty_like(x)
-        saved = torch.empty(lib.rtfs_dualpath_saved_floats(B, T, Fq, dim % 10), device=x.device, dtype=torch.float32)
+        out = _lib.empty_like(x)
+        saved = _lib.empty(lib.rtfs_dualpath_saved_floats(B, T, Fq, dim % 10), device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_dualpath_train_workspace_bytes(B, T, Fq, dim % 10), x.device)
         _lib.check(lib.rtfs_dualpath_forward_train_f32(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(out), _lib.ptr(saved), B, T, Fq, dim,
                                                        _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_dualpath_forward_train_f32")
@@ -696,8 +696,8 @@ class _DualPathTrainFn(torch.autograd.Function):
         x, tpack, saved = ctx.saved_tensors
         B, T, Fq = ctx.geom
         dout = dout.contiguous().to(torch.float32)
-        dx = torch.empty_like(x)
-        dpar = torch.empty(lib.rtfs_dualpath_grad_floats(), device=x.device, dtype=torch.float32)
+        dx = _lib.empty_like(x)
+        dpar = _lib.empty(lib.rtfs_dualpath_grad_floats(), device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_dualpath_train_workspace_bytes(B, T, Fq, ctx.dim % 10), x.device)
         _lib.check(lib.rtfs_dualpath_backward_f32(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(saved), _lib.ptr(dout), _lib.ptr(dx), _lib.ptr(dpar),
                                                   B, T, Fq, ctx.dim, _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_dualpath_backward_f32")
@@ -737,8 +737,8 @@ class _DualPathLstmTrainFn(torch.autograd.Function):
         pack_fn = packing.pack_dualpath_lstm_train if kind == "lstm" else packing.pack_dualpath_gru_train
         tpack = packing.cached_train_pack("dualpath_" + kind, (gamma, beta) + tuple(rest), lambda: pack_fn(gamma, beta, cell, lin_w, lin_b))
         fn = lambda n: getattr(lib, f"rtfs_dualpath_{kind}_{n}")
-        out = torch.empty_like(x)
-        saved = torch.empty(fn("saved_floats")(B, T, Fq, dim), device=x.device, dtype=torch.float32)
+        out = _lib.empty_like(x)
+        saved = _lib.empty(fn("saved_floats")(B, T, Fq, dim), device=x.device, dtype=torch.float32)
         ws = _lib.workspace(fn("train_workspace_bytes")(B, T, Fq, dim), x.device)
         _lib.check(fn("forward_train_f32")(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(out), _lib.ptr(saved), B, T, Fq, dim, _lib.ptr(ws), ws.numel(),
                                            _lib.stream_of(x)), f"rtfs_dualpath_{kind}_forward_train_f32")
@@ -754,8 +754,8 @@ class _DualPathLstmTrainFn(torch.autograd.Function):
         kind = ctx.kind
         fn = lambda n: getattr(lib, f"rtfs_dualpath_{kind}_{n}")
         dout = dout.contiguous().to(torch.float32)
-        dx = torch.empty_like(x)
-        dpar = torch.empty(fn("grad_floats")(), device=x.device, dtype=torch.float32)
+        dx = _lib.empty_like(x)
+        dpar = _lib.empty(fn("grad_floats")(), device=x.device, dtype=torch.float32)
         ws = _lib.workspace(fn("train_workspace_bytes")(B, T, Fq, ctx.dim), x.device)
         _lib.check(fn("backward_f32")(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(saved), _lib.ptr(dout), _lib.ptr(dx), _lib.ptr(dpar), B, T, Fq, ctx.dim,
                                       _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), f"rtfs_dualpath_{kind}_backward_f32")
@@ -805,7 +805,7 @@ class DualPathRNN(PackedModule):
                                                   self.linear.bias)
             sru = [p for cell in self.rnn.rnn_lst for p in (cell.weight, cell.weight_c, cell.bias)]
             return dualpath_train(x, self.dim, self.norm.gamma, self.norm.beta, sru, self.linear.weight, self.linear.bias)
-        out = torch.empty_like(x)
+        out = _lib.empty_like(x)
         ws = _lib.workspace(lib.rtfs_dualpath_workspace_bytes(B, T, Fq), x.device)
         fn = lib.rtfs_dualpath_sru_f32 if self.rnn_type == "SRU" else lib.rtfs_dualpath_lstm_f32
         _lib.check(fn(_lib.ptr(x), _lib.ptr(self.pack()), _lib.ptr(out), B, T, Fq, self.dim, _lib.ptr(ws), ws.numel(), _lib.stream_of(x)),
@@ -823,8 +823,8 @@ class _AttentionTrainFn(torch.autograd.Function):
         x = x.contiguous()
         B, T = (x.shape[0], x.shape[1]) if rows else (x.shape[0], x.shape[2])
         tpack = packing.cached_train_pack("attention", params, lambda: packing.pack_attention_train(dict(zip(names, params))))
-        out = torch.empty_like(x)
-        saved = torch.empty(lib.rtfs_tf_attention_saved_floats(B, T), device=x.device, dtype=torch.float32)
+        out = _lib.empty_like(x)
+        saved = _lib.empty(lib.rtfs_tf_attention_saved_floats(B, T), device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_tf_attention_train_workspace_bytes(B, T), x.device)
         _lib.check(lib.rtfs_tf_attention_forward_train_f32(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(out), _lib.ptr(saved), B, T, int(rows),
                                                            _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_tf_attention_forward_train_f32")
@@ -838,8 +838,8 @@ class _AttentionTrainFn(torch.autograd.Function):
         tpack, saved, xrows = ctx.saved_tensors
         B, T = ctx.geom
         dout = dout.contiguous().to(torch.float32)
-        dx = torch.empty_like(dout)
-        dpar = torch.empty(lib.rtfs_tf_attention_grad_floats(), device=dout.device, dtype=torch.float32)
+        dx = _lib.empty_like(dout)
+        dpar = _lib.empty(lib.rtfs_tf_attention_grad_floats(), device=dout.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_tf_attention_train_workspace_bytes(B, T), dout.device)
         _lib.check(lib.rtfs_tf_attention_backward_f32(_lib.ptr(xrows), _lib.ptr(tpack), _lib.ptr(saved), _lib.ptr(dout), _lib.ptr(dx), _lib.ptr(dpar),
                                                       B, T, int(ctx.rows), _lib.ptr(ws), ws.numel(), _lib.stream_of(dout)),
@@ -886,7 +886,7 @@ class MultiHeadSelfAttention2D(PackedModule):
         if _recording(x, self) or T > FUSED_MAX_KEYS:  # more keys than the fused kernel's LDS score tile: batched-GEMM attention, any length
             names, params = zip(*self.named_parameters())
             return attention_train(x, names, False, params)
-        out = torch.empty_like(x)
+        out = _lib.empty_like(x)
         ws = _lib.workspace(lib.rtfs_tf_attention_workspace_bytes(B, T), x.device)
         _lib.check(lib.rtfs_tf_attention_f32(_lib.ptr(x), _lib.ptr(self.pack()), _lib.ptr(out), B, T, _lib.ptr(ws), ws.numel(),
                                              _lib.stream_of(x)), "rtfs_tf_attention_f32")
@@ -912,9 +912,9 @@ class _AdaptivePoolFn(torch.autograd.Function):
         N, H, W, C = _geom(x, rows)
         Ho, Wo = (size[0], size[1]) if x.dim() == 4 else (1, size[-1])
         if rows:
-            y = torch.empty((x.shape[0], Ho, Wo, C) if x.dim() == 4 else (x.shape[0], Wo, C), device=x.device, dtype=torch.float32)
+            y = _lib.empty((x.shape[0], Ho, Wo, C) if x.dim() == 4 else (x.shape[0], Wo, C), device=x.device, dtype=torch.float32)
         else:
-            y = torch.empty(x.shape[:2] + ((Ho, Wo) if x.dim() == 4 else (Wo,)), device=x.device, dtype=torch.float32)
+            y = _lib.empty(x.shape[:2] + ((Ho, Wo) if x.dim() == 4 else (Wo,)), device=x.device, dtype=torch.float32)
         _lib.check(lib.rtfs_adaptive_avg_pool2d_f32(_lib.ptr(x), _lib.ptr(y), N, H, W, Ho, Wo, C, _lib.stream_of(x)), "rtfs_adaptive_avg_pool2d_f32")
         ctx.geom, ctx.xshape = (N, H, W, Ho, Wo, C), x.shape
         return y
@@ -924,7 +924,7 @@ class _AdaptivePoolFn(torch.autograd.Function):
         lib = _lib.load()
         N, H, W, Ho, Wo, C = ctx.geom
         dy = dy.contiguous()
-        dx = torch.empty(ctx.xshape, device=dy.device, dtype=torch.float32)
+        dx = _lib.empty(ctx.xshape, device=dy.device, dtype=torch.float32)
         _lib.check(lib.rtfs_adaptive_avg_pool2d_backward_f32(_lib.ptr(dy), _lib.ptr(dx), N, H, W, Ho, Wo, C, _lib.stream_of(dy)),
                    "rtfs_adaptive_avg_pool2d_backward_f32")
         return dx, None, None
@@ -939,7 +939,7 @@ class _TfarCombineFn(torch.autograd.Function):
         local, gate, glob = local.contiguous(), gate.contiguous(), glob.contiguous()
         N, H, W, C = _geom(local, rows)
         _, Hg, Wg, _ = _geom(gate, rows)
-        out = torch.empty_like(local)
+        out = _lib.empty_like(local)
         _lib.check(lib.rtfs_tfar_combine_f32(_lib.ptr(local), _lib.ptr(gate), _lib.ptr(glob), _lib.ptr(out), N, H, W, Hg, Wg, C,
                                              _lib.stream_of(local)), "rtfs_tfar_combine_f32")
         ctx.save_for_backward(local, gate)
@@ -952,7 +952,7 @@ class _TfarCombineFn(torch.autograd.Function):
         local, gate = ctx.saved_tensors
         N, H, W, Hg, Wg, C = ctx.geom
         dout = dout.contiguous()
-        dl, dg, de = torch.empty_like(local), torch.empty_like(gate), torch.empty_like(gate)
+        dl, dg, de = _lib.empty_like(local), _lib.empty_like(gate), _lib.empty_like(gate)
         _lib.check(lib.rtfs_tfar_combine_backward_f32(_lib.ptr(dout), _lib.ptr(local), _lib.ptr(gate), _lib.ptr(dl), _lib.ptr(dg), _lib.ptr(de),
                                                       N, H, W, Hg, Wg, C, _lib.stream_of(dout)), "rtfs_tfar_combine_backward_f32")
         return dl, dg, de, None
@@ -968,10 +968,10 @@ class _LayoutFn(torch.autograd.Function):
         x = x.contiguous()
         if to_rows:
             B, C, sp = x.shape[0], x.shape[1], tuple(x.shape[2:])
-            y = torch.empty((B,) + sp + (C,), device=x.device, dtype=torch.float32)
+            y = _lib.empty((B,) + sp + (C,), device=x.device, dtype=torch.float32)
         else:
             B, C, sp = x.shape[0], x.shape[-1], tuple(x.shape[1:-1])
-            y = torch.empty((B, C) + sp, device=x.device, dtype=torch.float32)
+            y = _lib.empty((B, C) + sp, device=x.device, dtype=torch.float32)
         P = 1
         for d in sp:
             P *= d
@@ -1028,7 +1028,7 @@ class InjectionMultiSum(PackedModule):
         loc, glo = local_features.contiguous(), global_features.contiguous()
         B, _, H, W = loc.shape
         Hg, Wg = glo.shape[-2:]
-        out = torch.empty_like(loc)
+        out = _lib.empty_like(loc)
         ws = _lib.workspace(lib.rtfs_tfar_workspace_bytes(B, H, W, Hg, Wg), loc.device)
         _lib.check(lib.rtfs_tfar_f32(_lib.ptr(loc), _lib.ptr(glo), _lib.ptr(self.pack()), _lib.ptr(out), B, H, W, Hg, Wg, _lib.ptr(ws),
                                      ws.numel(), _lib.stream_of(loc)), "rtfs_tfar_f32")
@@ -1055,7 +1055,7 @@ class _CafAttentionFn(torch.autograd.Function):
         lib = _lib.load()
         emb = emb.contiguous()
         B, _, Tv = emb.shape
-        att = torch.empty(B, C, Tv, device=emb.device, dtype=torch.float32)
+        att = _lib.empty(B, C, Tv, device=emb.device, dtype=torch.float32)
         _lib.check(lib.rtfs_caf_attention_f32(_lib.ptr(emb), _lib.ptr(att), B, C, Tv, _lib.stream_of(emb)), "rtfs_caf_attention_f32")
         ctx.save_for_backward(att)
         return att
@@ -1066,7 +1066,7 @@ class _CafAttentionFn(torch.autograd.Function):
         (att,) = ctx.saved_tensors
         B, C, Tv = att.shape
         datt = datt.contiguous()
-        demb = torch.empty(B, 4 * C, Tv, device=att.device, dtype=torch.float32)
+        demb = _lib.empty(B, 4 * C, Tv, device=att.device, dtype=torch.float32)
         _lib.check(lib.rtfs_caf_attention_backward_f32(_lib.ptr(att), _lib.ptr(datt), _lib.ptr(demb), B, C, Tv, _lib.stream_of(att)),
                    "rtfs_caf_attention_backward_f32")
         return demb, None
@@ -1080,7 +1080,7 @@ class _CafCombineFn(torch.autograd.Function):
         lib = _lib.load()
         key, value, resized, att = key.contiguous(), value.contiguous(), resized.contiguous(), att.contiguous()
         Tv = resized.shape[-1]
-        out = torch.empty_like(key)
+        out = _lib.empty_like(key)
         if rows:  # key, value (B, T, F, C)
             B, T, Fq, C = key.shape
             _lib.check(lib.rtfs_caf_combine_rows_f32(_lib.ptr(key), _lib.ptr(value), _lib.ptr(resized), _lib.ptr(att), _lib.ptr(out), B, T, Fq, C, Tv,
@@ -1099,7 +1099,7 @@ class _CafCombineFn(torch.autograd.Function):
         key, value, resized, att = ctx.saved_tensors
         Tv = resized.shape[-1]
         dout = dout.contiguous()
-        dk, dv, dr, da = torch.empty_like(key), torch.empty_like(value), torch.empty_like(resized), torch.empty_like(att)
+        dk, dv, dr, da = _lib.empty_like(key), _lib.empty_like(value), _lib.empty_like(resized), _lib.empty_like(att)
         if ctx.rows:
             B, T, Fq, C = key.shape
             _lib.check(lib.rtfs_caf_combine_rows_backward_f32(_lib.ptr(dout), _lib.ptr(key), _lib.ptr(value), _lib.ptr(resized), _lib.ptr(att),
@@ -1151,7 +1151,7 @@ class ATTNFusionCell(PackedModule):
         a, v = tensor_a.contiguous(), tensor_b.contiguous()
         B, _, T, Fq = a.shape
         Tv = v.shape[-1]
-        out = torch.empty_like(a)
+        out = _lib.empty_like(a)
         ws = _lib.workspace(lib.rtfs_caf_workspace_bytes(B, Tv), a.device)
         _lib.check(lib.rtfs_caf_f32(_lib.ptr(a), _lib.ptr(v), _lib.ptr(self.pack()), _lib.ptr(out), B, T, Fq, Tv, _lib.ptr(ws), ws.numel(),
                                     _lib.stream_of(a)), "rtfs_caf_f32")
@@ -1185,7 +1185,7 @@ class _LnRowsFn(torch.autograd.Function):
         x = x.contiguous()
         C = x.shape[-1]
         N = x.numel() // C
-        y = torch.empty_like(x)
+        y = _lib.empty_like(x)
         _lib.check(lib.rtfs_layernorm_rows_f32(_lib.ptr(x), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(y), N, C, _lib.stream_of(x)), "rtfs_layernorm_rows_f32")
         ctx.save_for_backward(x, gamma)
         return y
@@ -1197,7 +1197,7 @@ class _LnRowsFn(torch.autograd.Function):
         C = x.shape[-1]
         N = x.numel() // C
         dy = dy.contiguous()
-        dx, dg, db = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
+        dx, dg, db = _lib.empty_like(x), _lib.empty_like(gamma), _lib.empty_like(gamma)
         _lib.check(lib.rtfs_layernorm_rows_backward_f32(_lib.ptr(x), _lib.ptr(gamma), _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(dg), _lib.ptr(db), N, C,
                                                         _lib.stream_of(x)), "rtfs_layernorm_rows_backward_f32")
         return dx, dg, db
@@ -1212,7 +1212,7 @@ class _LinearRowsFn(torch.autograd.Function):
         x, w = x.contiguous(), weight.contiguous()
         N, K = w.shape
         M = x.numel() // K
-        y = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=torch.float32)
+        y = _lib.empty(x.shape[:-1] + (N,), device=x.device, dtype=torch.float32)
         _lib.check(lib.rtfs_linear_rows_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y), M, N, K, _lib.stream_of(x)), "rtfs_linear_rows_f32")
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
@@ -1225,8 +1225,8 @@ class _LinearRowsFn(torch.autograd.Function):
         N, K = w.shape
         M = x.numel() // K
         dy = dy.contiguous()
-        dx, dw = torch.empty_like(x), torch.empty_like(w)
-        db = torch.empty(N, device=x.device, dtype=torch.float32) if ctx.has_bias else None
+        dx, dw = _lib.empty_like(x), _lib.empty_like(w)
+        db = _lib.empty(N, device=x.device, dtype=torch.float32) if ctx.has_bias else None
         ws = _lib.workspace(N * K * 4, x.device)
         _lib.check(lib.rtfs_linear_rows_backward_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(dy), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), M, N, K,
                                                      _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_linear_rows_backward_f32")
@@ -1242,7 +1242,7 @@ class _MhaCoreFn(torch.autograd.Function):
         qkv = qkv.contiguous()
         B, T, E3 = qkv.shape
         E = E3 // 3
-        o = torch.empty(B, T, E, device=qkv.device, dtype=torch.float32)
+        o = _lib.empty(B, T, E, device=qkv.device, dtype=torch.float32)
         pm = None if pmask is None else pmask.contiguous()
         _lib.check(lib.rtfs_mha_core_f32(_lib.ptr(qkv), _lib.ptr(pm), _lib.ptr(o), B, T, n_head, E // n_head, _lib.stream_of(qkv)), "rtfs_mha_core_f32")
         ctx.save_for_backward(qkv, pm)
@@ -1256,7 +1256,7 @@ class _MhaCoreFn(torch.autograd.Function):
         B, T, E3 = qkv.shape
         E = E3 // 3
         do = do.contiguous()
-        dqkv = torch.empty_like(qkv)
+        dqkv = _lib.empty_like(qkv)
         _lib.check(lib.rtfs_mha_core_backward_f32(_lib.ptr(qkv), _lib.ptr(pm), _lib.ptr(do), _lib.ptr(dqkv), B, T, ctx.n_head, E // ctx.n_head,
                                                   _lib.stream_of(qkv)), "rtfs_mha_core_backward_f32")
         return dqkv, None, None

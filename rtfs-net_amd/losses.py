@@ -23,8 +23,8 @@ def _pairwise(ests, targets, kind, zero_mean, take_log):
     B, n, L = ests.shape
     if n > 4:
         raise ValueError("MI355X PairwiseNegSDR supports n_src <= 4")
-    pw = torch.empty(B, n, n, device=ests.device, dtype=torch.float32)
-    min_loss = torch.empty(B, device=ests.device, dtype=torch.float32)
+    pw = _lib.empty(B, n, n, device=ests.device, dtype=torch.float32)
+    min_loss = _lib.empty(B, device=ests.device, dtype=torch.float32)
     perm = torch.empty(B, n, device=ests.device, dtype=torch.int32)
     _lib.check(lib.rtfs_pit_pairwise_sdr_f32(_lib.ptr(ests), _lib.ptr(targets), B, n, L, _KIND[kind], int(zero_mean), int(take_log),
                                              _lib.ptr(pw), _lib.ptr(min_loss), _lib.ptr(perm), _lib.stream_of(ests)),
@@ -50,7 +50,7 @@ class _PitLossFn(torch.autograd.Function):
         kind, zero_mean, take_log = ctx.cfg
         B, n, L = ests.shape
         dmin = dmin.contiguous().float()
-        dests = torch.empty_like(ests)
+        dests = _lib.empty_like(ests)
         _lib.check(lib.rtfs_pit_sdr_backward_f32(_lib.ptr(ests), _lib.ptr(targets), _lib.ptr(perm), _lib.ptr(dmin), _lib.ptr(dests), B, n, L,
                                                  _KIND[kind], int(zero_mean), int(take_log), _lib.stream_of(ests)), "rtfs_pit_sdr_backward_f32")
         return dests, None, None, None, None

@@ -35,7 +35,7 @@ class _EncoderTrainFn(torch.autograd.Function):
         lib = _lib.load()
         B, L = wav.shape
         T = lib.rtfs_num_frames(L)
-        a0 = torch.empty(B, 256, T, 129, device=wav.device, dtype=torch.float32)
+        a0 = _lib.empty(B, 256, T, 129, device=wav.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_stft_encoder_workspace_bytes(B, L), wav.device)
         _lib.check(lib.rtfs_stft_encoder_f32(_lib.ptr(wav), _lib.ptr(pack), _lib.ptr(a0), None, B, L, _lib.ptr(ws), ws.numel(),
                                              _lib.stream_of(wav)), "rtfs_stft_encoder_f32")
@@ -49,7 +49,7 @@ class _EncoderTrainFn(torch.autograd.Function):
         (wav,) = ctx.saved_tensors
         B, L = wav.shape
         da0 = da0.contiguous()
-        dw = torch.empty(256 * 18, device=wav.device, dtype=torch.float32)
+        dw = _lib.empty(256 * 18, device=wav.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_stft_encoder_backward_workspace_bytes(B, L), wav.device)
         _lib.check(lib.rtfs_stft_encoder_backward_f32(_lib.ptr(wav), _lib.ptr(da0), _lib.ptr(dw), B, L, _lib.ptr(ws), ws.numel(),
                                                       _lib.stream_of(wav)), "rtfs_stft_encoder_backward_f32")
@@ -63,7 +63,7 @@ class _DecoderTrainFn(torch.autograd.Function):
     def forward(ctx, x, weight, pack, length):
         lib = _lib.load()
         B, _, T, _ = x.shape
-        wav = torch.empty(B, 1, length, device=x.device, dtype=torch.float32)
+        wav = _lib.empty(B, 1, length, device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_istft_decoder_workspace_bytes(B, T), x.device)
         _lib.check(lib.rtfs_istft_decoder_f32(_lib.ptr(x), _lib.ptr(pack), _lib.ptr(wav), B, T, length, _lib.ptr(ws), ws.numel(),
                                               _lib.stream_of(x)), "rtfs_istft_decoder_f32")
@@ -77,8 +77,8 @@ class _DecoderTrainFn(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         B, _, T, _ = x.shape
         dwav = dwav.contiguous().to(torch.float32)
-        dx = torch.empty_like(x)
-        dw = torch.empty(256 * 18, device=x.device, dtype=torch.float32)
+        dx = _lib.empty_like(x)
+        dw = _lib.empty(256 * 18, device=x.device, dtype=torch.float32)
         w = weight.detach().contiguous()
         ws = _lib.workspace(lib.rtfs_istft_decoder_backward_workspace_bytes(B, T), x.device)
         _lib.check(lib.rtfs_istft_decoder_backward_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(dwav), _lib.ptr(dx), _lib.ptr(dw), B, T, ctx.length,
@@ -92,7 +92,7 @@ class _S3MulFn(torch.autograd.Function):
     @staticmethod
     def _cmul(a, b, conj):
         lib = _lib.load()
-        out = torch.empty_like(a)
+        out = _lib.empty_like(a)
         B, P = a.shape[0], a.shape[2] * a.shape[3]
         _lib.check(lib.rtfs_s3_cmul_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(out), B, P, conj, _lib.stream_of(a)), "rtfs_s3_cmul_f32")
         return out
@@ -149,8 +149,8 @@ class STFTEncoder(PackedModule):
         x = x.contiguous()
         B, L = x.shape
         T = lib.rtfs_num_frames(L)
-        a0 = torch.empty(B, 256, T, 129, device=x.device, dtype=torch.float32)
-        stats = torch.empty(B, 2, device=x.device, dtype=torch.float64) if return_stats else None
+        a0 = _lib.empty(B, 256, T, 129, device=x.device, dtype=torch.float32)
+        stats = _lib.empty(B, 2, device=x.device, dtype=torch.float64) if return_stats else None
         ws = _lib.workspace(lib.rtfs_stft_encoder_workspace_bytes(B, L), x.device)
         _lib.check(lib.rtfs_stft_encoder_f32(_lib.ptr(x), _lib.ptr(self.pack()), _lib.ptr(a0), _lib.ptr(stats), B, L, _lib.ptr(ws),
                                              ws.numel(), _lib.stream_of(x)), "rtfs_stft_encoder_f32")
@@ -186,7 +186,7 @@ class STFTDecoder(PackedModule):
         self._guard(x)
         lib = _lib.load()
         x = x.contiguous().view(batch * self.n_src, self.in_chan, T, x.shape[-1])
-        wav = torch.empty(batch, self.n_src, length, device=x.device, dtype=torch.float32)
+        wav = _lib.empty(batch, self.n_src, length, device=x.device, dtype=torch.float32)
         ws = _lib.workspace(lib.rtfs_istft_decoder_workspace_bytes(batch, T), x.device)
         _lib.check(lib.rtfs_istft_decoder_f32(_lib.ptr(x), _lib.ptr(self.pack()), _lib.ptr(wav), batch, T, length, _lib.ptr(ws), ws.numel(),
                                               _lib.stream_of(x)), "rtfs_istft_decoder_f32")
@@ -211,7 +211,7 @@ class AudioBottleneck(ConvNormAct, PackedModule):
         lib = _lib.load()
         x = x.contiguous()
         B, _, T, Fq = x.shape
-        out = torch.empty_like(x)
+        out = _lib.empty_like(x)
         ws = _lib.workspace(lib.rtfs_audio_bottleneck_workspace_bytes(B), x.device)
         _lib.check(lib.rtfs_audio_bottleneck_f32(_lib.ptr(x), _lib.ptr(stats), _lib.ptr(self.pack()), _lib.ptr(out), B, T, Fq, _lib.ptr(ws),
                                                  ws.numel(), _lib.stream_of(x)), "rtfs_audio_bottleneck_f32")
@@ -274,7 +274,7 @@ class TDANetBlock(PackedModule):
         lib = _lib.load()
         x = x.contiguous()
         B, _, Tv = x.shape
-        out = torch.empty_like(x)
+        out = _lib.empty_like(x)
         pk = self.pack_vp()
         assert pk.numel() == lib.rtfs_vp_pack_floats()
         _lib.check(lib.rtfs_vp_block_f32(_lib.ptr(x), _lib.ptr(pk), _lib.ptr(out), B, Tv, _lib.stream_of(x)), "rtfs_vp_block_f32")
@@ -361,7 +361,7 @@ class TDANetBlock(PackedModule):
         x = x.contiguous()
         x_res = None if x_res is None else x_res.contiguous()
         B, _, T, Fq = x.shape
-        out = torch.empty_like(x)
+        out = _lib.empty_like(x)
         ws = _lib.workspace(lib.rtfs_block_workspace_bytes(B, T, Fq), x.device)
         _lib.check(lib.rtfs_block_f32(_lib.ptr(x), _lib.ptr(x_res), _lib.ptr(self.pack()), _lib.ptr(out), B, T, Fq, _lib.ptr(ws), ws.numel(),
                                       _lib.stream_of(x), self.rnn_kind), "rtfs_block_f32")
@@ -524,7 +524,7 @@ class MaskGenerator(PackedModule):
         lib = _lib.load()
         r, a0 = refined_features.contiguous(), audio_mixture_embedding.contiguous()
         B, _, T, Fq = r.shape
-        out = torch.empty(B, 1, 256, T, Fq, device=r.device, dtype=torch.float32)
+        out = _lib.empty(B, 1, 256, T, Fq, device=r.device, dtype=torch.float32)
         _lib.check(lib.rtfs_s3_mask_f32(_lib.ptr(r), _lib.ptr(a0), _lib.ptr(self.pack()), _lib.ptr(out), B, T, Fq, _lib.stream_of(r)), "rtfs_s3_mask_f32")
         return out
 
@@ -641,7 +641,7 @@ class AVNet(BaseAVModel):
             ready.record(side)
         vp.record_stream(main)
         Tv = vp.shape[-1]
-        out = torch.empty(B, self.n_src, L, device=wav.device, dtype=torch.float32)
+        out = _lib.empty(B, self.n_src, L, device=wav.device, dtype=torch.float32)
         # batch split of THIS model's calls (0 = the library's process-wide default, rtfs_set_batch_split / RTFS_SPLIT): a per-call argument
         # of the C ABI, so two models / threads can run different schedules
         split = int(getattr(self, "batch_split", 0) or 0)

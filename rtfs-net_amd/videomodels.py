@@ -129,7 +129,7 @@ class FRCNNVideoModel(nn.Module):
         lib = _lib.load()
         x = x.contiguous().float()
         B, _, T, _, _ = x.shape
-        out = torch.empty(B, 512, T, device=x.device, dtype=torch.float32)
+        out = _lib.empty(B, 512, T, device=x.device, dtype=torch.float32)
         pk = self.pack()
         assert pk.numel() == lib.rtfs_video_pack_floats()
         ws = _lib.workspace(lib.rtfs_video_workspace_bytes(B, T), x.device)

@@ -108,11 +108,12 @@ def test_dualpath_sru_entry_point_400():
     B, T, F = 1, 400, 16
     xn = rand((B, 64, T, F), 4242)
     x = dev(xn)
-    out = torch.empty_like(x)
+    out = R._lib.empty_like(x)
     ws = R._lib.workspace(lib.rtfs_dualpath_workspace_bytes(B, T, F), x.device)
     rc = lib.rtfs_dualpath_sru_f32(R._lib.ptr(x), R._lib.ptr(mod.pack()), R._lib.ptr(out), B, T, F, 3, R._lib.ptr(ws), ws.numel(),
                                    R._lib.stream_of(x))
     assert rc == 0, rc
+    R._lib.check(rc, "rtfs_dualpath_sru_f32")  # under RTFS_POISON_WS: verifies the guard band after the workspace
     close("rtfs_dualpath_sru_f32 T=400", host(out), O.dualpath_rnn(xn, O._sub(BLK, "globalatt.1"), 3))
 
 
@@ -154,9 +155,10 @@ def test_tf_attention_entry_point_384():
     B, T = 2, 384
     xn = rand((B, 64, T, 64), 384)
     x = dev(xn)
-    out = torch.empty_like(x)
+    out = R._lib.empty_like(x)
     ws = R._lib.workspace(lib.rtfs_tf_attention_workspace_bytes(B, T), x.device)
     rc = lib.rtfs_tf_attention_f32(R._lib.ptr(x), R._lib.ptr(mod.pack()), R._lib.ptr(out), B, T, R._lib.ptr(ws), ws.numel(),
                                    R._lib.stream_of(x))
     assert rc == 0, rc
+    R._lib.check(rc, "rtfs_tf_attention_f32")  # under RTFS_POISON_WS: verifies the guard band after the workspace
     close("rtfs_tf_attention_f32 T=384", host(out), O.mhsa2d(xn, O._sub(BLK, "globalatt.2")))

@@ -87,12 +87,13 @@ def test_vp_block_past_256_stays_per_layer():
 
 
 def test_vp_block_entry_point_205():
+    from rtfs_net_amd import _lib
     m = model()
     L = lib()
     blk = m.refinement_module.video_net.get_block(0)
     v = rand((1, 512, 205), 905)
     x = dev(v)
-    out = torch.empty_like(x)
+    out = _lib.empty_like(x)
     pk = blk.pack_vp()
     torch.cuda.synchronize()
     rc = L.rtfs_vp_block_f32(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(pk.data_ptr()), ctypes.c_void_p(out.data_ptr()), 1, 205,
@@ -134,15 +135,19 @@ def test_rtfs_block_past_512_stays_unfused():
 
 
 def _block_entry(T, rnn_kind):
+    from rtfs_net_amd import _lib
     L = lib()
     blk = model().refinement_module.audio_net.get_block(0)
     x = torch.zeros(1, 256, T, 129, device="cuda")
-    out = torch.empty_like(x)
-    ws = torch.empty(int(L.rtfs_block_workspace_bytes(1, T, 129)), dtype=torch.uint8, device="cuda")
+    out = _lib.empty_like(x)
+    ws = _lib.workspace(L.rtfs_block_workspace_bytes(1, T, 129), x.device)
     pk = blk.pack()
     rc = L.rtfs_block_f32(ctypes.c_void_p(x.data_ptr()), None, ctypes.c_void_p(pk.data_ptr()), ctypes.c_void_p(out.data_ptr()), 1, T, 129,
                           ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), rnn_kind)
     torch.cuda.synchronize()
+    if rc == 0:
+        _lib.check(rc, "rtfs_block_f32")  # under RTFS_POISON_WS: verifies the guard band after the workspace
+        assert bool(torch.isfinite(out).all()), f"T={T}: non-finite block output"
     return rc
 
 

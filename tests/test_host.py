@@ -498,3 +498,122 @@ def test_training_segment_past_the_backward_limit_refused_up_front():
         with torch.set_grad_enabled(grad), pytest.raises(Exception) as err:
             m.forward_train(torch.zeros(1, L), torch.zeros(1, 512, 103))
         assert "TRAIN_MAX_SWEEP" not in str(err.value)
+
+
+# ---------------------------------------------------------------- poisoned memory (RTFS_POISON_WS, tests/test_hip_poisoned.py)
+def test_poison_mode_parsing():
+    from rtfs_net_amd import _lib
+    for off in (None, "", "0", " 0 "):
+        assert _lib.poison_byte(off) is None
+    assert _lib.poison_byte("1") == _lib.poison_byte("nan") == _lib.poison_byte("NaN") == 0xFF
+    assert _lib.poison_byte("big") == 0x7F
+    with pytest.raises(ValueError):
+        _lib.poison_byte("yes")
+
+
+def test_poisoned_empty_on_cpu(monkeypatch):
+    import struct
+    from rtfs_net_amd import _lib
+    monkeypatch.setattr(_lib, "_POISON", 0xFF)
+    t = _lib.empty(3, 5, device="cpu")
+    assert t.shape == (3, 5) and t.dtype == torch.float32 and bool(torch.isnan(t).all())
+    assert bool(torch.isnan(_lib.empty((2, 2), device="cpu", dtype=torch.float64)).all())
+    cl = torch.zeros(2, 3, 4, 5).to(memory_format=torch.channels_last)
+    p = _lib.empty_like(cl)
+    assert p.stride() == cl.stride() and bool(torch.isnan(p).all())
+    monkeypatch.setattr(_lib, "_POISON", 0x7F)
+    big = struct.unpack("<f", b"\x7f" * 4)[0]
+    t = _lib.empty((4, 7), device="cpu")
+    assert bool(torch.isfinite(t).all()) and bool((t == big).all()) and abs(big - 3.3961514e38) < 1e31
+    assert bool((t.view(torch.int32) == 0x7F7F7F7F).all())
+    d = _lib.empty(3, device="cpu", dtype=torch.float64)
+    assert bool((d == struct.unpack("<d", b"\x7f" * 8)[0]).all())
+    monkeypatch.setattr(torch, "empty_like", torch.zeros_like)  # (so that an unfilled tensor reads 0)
+    for dt in (torch.int32, torch.int64, torch.uint8, torch.bool):  # integer (index) outputs are never filled
+        assert bool((_lib.empty_like(torch.ones(64, dtype=dt)) == 0).all())
+
+
+def test_unpoisoned_helpers_are_torch_empty(monkeypatch):
+    """Off, empty / empty_like / workspace are torch.empty / torch.empty_like and launch nothing else."""
+    from rtfs_net_amd import _lib
+    monkeypatch.setattr(_lib, "_POISON", None)
+    calls = []
+    monkeypatch.setattr(torch.Tensor, "fill_", lambda *a: calls.append("fill_"))
+    monkeypatch.setattr(torch.UntypedStorage, "fill_", lambda *a: calls.append("storage.fill_"))
+    assert _lib.empty(4, 4, device="cpu").shape == (4, 4)
+    assert _lib.empty_like(torch.zeros(3)).shape == (3,)
+    ws = _lib.workspace(1000, "cpu")
+    assert ws.numel() == 1000 and ws.untyped_storage().nbytes() == 1000
+    assert _lib.workspace(3, "cpu").numel() == 256
+    assert calls == [] and _lib._guards() == []
+
+
+def test_workspace_guard_band_detects_overrun(monkeypatch):
+    from rtfs_net_amd import _lib
+    for byte in (0xFF, 0x7F):
+        monkeypatch.setattr(_lib, "_POISON", byte)
+        ws = _lib.workspace(1000, "cpu")
+        assert ws.numel() == 1000 and bool((ws == byte).all())
+        assert ws.untyped_storage().nbytes() >= 1000 + 64 * 1024
+        ws.fill_(3)  # the whole promised size may be written
+        _lib.check(0, "rtfs_ok_f32")
+        assert _lib._guards() == []
+        ws = _lib.workspace(1000, "cpu")
+        torch.as_strided(ws, (1,), (1,), ws.storage_offset() + 1000 + 4321).fill_(0)  # one byte past the end
+        with pytest.raises(RuntimeError, match="rtfs_overrun_f32"):
+            _lib.check(0, "rtfs_overrun_f32")
+        assert _lib._guards() == []  # verified once, then forgotten
+        _lib.check(0, "rtfs_next_f32")
+        ws = _lib.workspace(64, "cpu")  # a failing call reports its own error and drops the pending guards
+        with pytest.raises(RuntimeError, match="bad shape"):
+            _lib.check(-1, "rtfs_bad_f32")
+        assert _lib._guards() == []
+
+
+def test_workspace_guards_are_per_thread(monkeypatch):
+    import threading
+    from rtfs_net_amd import _lib
+    monkeypatch.setattr(_lib, "_POISON", 0xFF)
+    ws = _lib.workspace(512, "cpu")
+    torch.as_strided(ws, (1,), (1,), ws.storage_offset() + 512).fill_(0)
+    seen = []
+    th = threading.Thread(target=lambda: (_lib.check(0, "rtfs_other_thread_f32"), seen.append(len(_lib._guards()))))
+    th.start()
+    th.join()
+    assert seen == [0]  # the other thread neither saw nor cleared this thread's guard
+    with pytest.raises(RuntimeError, match="rtfs_this_thread_f32"):
+        _lib.check(0, "rtfs_this_thread_f32")
+
+
+# Allocations in the package that stay bare torch.empty / new_empty (everything a C call fills goes through _lib.empty /
+# _lib.empty_like / _lib.workspace, so that RTFS_POISON_WS reaches it):
+BARE_ALLOC = {
+    ("_lib.py", "t = torch.empty(*size, device=device, dtype=dtype)"): "the helper itself",
+    ("_lib.py", "e = torch.empty_like(t)"): "the helper itself",
+    ("_lib.py", "return torch.empty(n, dtype=torch.uint8"): "workspace, poisoning off",
+    ("_lib.py", "buf = torch.empty(n + GUARD_BYTES"): "workspace, poisoning on (filled right after)",
+    ("layers.py", "nn.Parameter(torch.empty(input_size"): "parameter, initialised by reset_parameters",
+    ("layers.py", "nn.Parameter(torch.empty(2 * out))"): "parameter, initialised by reset_parameters",
+    ("layers.py", "params[0].new_empty(n, dtype=torch.float32)"): "_GradBundleFn placeholder: its values are never read",
+    ("layers.py", "new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_"): "dropout mask, filled by bernoulli_",
+    ("losses.py", "perm = torch.empty(B, n, device=ests.device, dtype=torch.int32)"):
+        "integer PIT permutation, written unconditionally and compared exactly (a poisoned index would reach torch.gather)",
+    ("packing.py", "idx = torch.empty(4, 2, 2, 16, dtype=torch.long)"): "host index table filled by the loop below it",
+}
+
+
+def test_no_bare_output_allocations_in_the_package():
+    """Static guard: a new output allocated with bare torch.empty would silently escape the poisoned GPU runs."""
+    pkg = os.path.join(ROOT, "rtfs-net_amd")
+    found = set()
+    for fn in sorted(os.listdir(pkg)):
+        if not fn.endswith(".py"):
+            continue
+        for no, line in enumerate(open(os.path.join(pkg, fn)), 1):
+            code = line.split("#", 1)[0]
+            if not re.search(r"torch\.empty(_like)?\(|\.new_empty\(", code):
+                continue
+            hit = [k for k in BARE_ALLOC if k[0] == fn and k[1] in code]
+            assert hit, f"rtfs-net_amd/{fn}:{no}: bare allocation (use _lib.empty / _lib.empty_like, or list it in BARE_ALLOC): {line.strip()}"
+            found.update(hit)
+    assert found == set(BARE_ALLOC), f"stale BARE_ALLOC entries: {set(BARE_ALLOC) - found}"
