@@ -377,6 +377,17 @@ int rtfs_sweep_timing_collect(float* ms, int* seq_len, int* n_seq, int cap);
 int rtfs_pit_pairwise_sdr_f32(const float* ests, const float* targets, int B, int n_src, int L, int sdr_type, int zero_mean,
                               int take_log, float* pw_loss, float* min_loss, int* perm, void* stream);
 
+/* Evaluation metric (the reference's test-time scoring, src/metrics/allwrapper.py:57-62): classic STOI (Taal et al. 2011) as
+ * pystoi 0.4.1 computes stoi(clean, estimate, fs, extended=False): resample to 10 kHz (pystoi utils.resample_oct), remove the frames
+ * more than 40 dB below the clean signal's loudest, one-third-octave band envelopes of the 512-point STFT, mean correlation of
+ * clipped, normalised 30-frame segments.  clean, est (B, L) -> d (B) float32 and kept_frames (B) int32 = frames silence removal kept
+ * (a speech-activity count); d = 1e-5 when fewer than 30 STFT frames remain, as pystoi returns.  fs = 16000 or 10000 (no resampling),
+ * any other rate returns -4 before any launch; L needs at least one 256-sample frame at 10 kHz (L >= 410 at 16 kHz, 257 at 10 kHz).
+ * Rows are scored independently (a row's result does not depend on the batch); no atomics, capturable in a graph. */
+size_t rtfs_stoi_workspace_bytes(int B, int L, int fs);
+int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept_frames,
+                  void* stream);
+
 /* Video front-end (the step before the path): FRCNNVideoModel.forward with backbone_type "resnet",
  * relu_type "prelu", eval mode (src/models/videomodels/frcnn_videomodel.py:61-72, resnet.py:23-118).
  * lips (B, 1, T, 88, 88) grey-scale mouth crops -> out (B, 512, T), the lip embedding AVNet.forward takes.

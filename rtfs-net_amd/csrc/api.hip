@@ -1227,6 +1227,14 @@ int rtfs_pit_pairwise_sdr_f32(const float* ests, const float* targets, int B, in
     return launch_pit_pairwise(ests, targets, B, n_src, L, sdr_type, zero_mean, take_log, pw_loss, min_loss, perm, (hipStream_t)stream);
 }
 
+size_t rtfs_stoi_workspace_bytes(int B, int L, int fs) { return stoi_workspace_bytes(B, L, fs); }
+int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept_frames,
+                  void* stream) {
+    if (fs != 16000 && fs != 10000) return RTFS_ERR_ARG;
+    if (!clean || !est || !ws || !d || !kept_frames) return RTFS_ERR_ARG;
+    return launch_stoi(clean, est, B, L, fs, ws, ws_bytes, d, kept_frames, (hipStream_t)stream);
+}
+
 size_t rtfs_video_pack_floats(void) { return video_pack_floats(); }
 size_t rtfs_video_workspace_bytes(int B, int T) { return video_workspace_bytes(B, T); }
 int rtfs_video_frontend_f32(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, void* stream) {

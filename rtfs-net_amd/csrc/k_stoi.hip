@@ -1,0 +1,357 @@
+// Evaluation metric on the device: classic STOI (Taal et al. 2011) as pystoi 0.4.1 computes it -- the metric the reference's
+// src/metrics/allwrapper.py:57-62 calls as stoi(clean, estimate, 16000, extended=False).  tests/metrics_oracle.py restates pystoi in
+// float64 and names the conventions followed (frame ranges, eps, the 1e-5 short path).  Per (clean x, estimate y) row:
+//   stoi_resample_kernel  pystoi utils.resample_oct = scipy.signal.resample_poly(x, 5, 8, window = h / sum(h)) at 16 kHz: the 581 taps
+//                         (ideal sinc times Kaiser(beta = 0.1102 (60 - 8.7)), half length 290) are computed in double in each
+//                         workgroup's prologue (no host->device copy: the call stays capturable); output n = sum_j 5 h[290 + 8n - 5j] x[j],
+//                         which is resample_poly's pre-pad / pre-remove alignment written out, zero outside [0, L).  (row chunk, row, x|y)
+//   stoi_mask_kernel      remove_silent_frames: windowed (hanning(258)[1:-1]) 256-sample frames at hop 128, starts range(0, L - 256, 128)
+//                         (the last full frame excluded, as pystoi), clean energies 20 log10(|frame| + eps) in double, keep where
+//                         max - 40 - e < 0, and a ballot prefix scan that lists the kept frame indices.  One workgroup per row.
+//   stoi_bands_kernel     the STFT of the overlap-added kept frames (same window, frames, hop; rfft n = 512) restricted to bins
+//                         7 .. 218, the only bins the 15 one-third-octave bands cover, and the band values sqrt(sum |X|^2).  Reduced frame
+//                         j is built from the at most three kept frames it overlaps.  (frame group, row)
+//   stoi_corr_kernel      intermediate intelligibility per (30-frame segment, band) in double, folded to one partial sum per workgroup.
+//   stoi_final_kernel     folds a row's partials in a fixed order: d = sum / (segments * 15), or 1e-5 when fewer than 30 frames remain.
+// The DFT runs on the VALU in double, one bin per lane with the twiddle advanced by a complex rotation (no table, no LDS bank conflicts,
+// error ~256 ulp): 212 bins x 256 samples is too small and too oddly shaped (15 unequal bands) for a matrix-core tile to pay, and double
+// keeps weak bands exact next to strong ones.  No atomics: every partial has one writer and is folded in a fixed order.
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int SF = 256, SHOP = 128;       // frame length, hop
+constexpr int NBAND = 15, SEG = 30;       // bands, frames per segment
+constexpr int BIN0 = 7, NBIN = 212;       // bins 7 .. 218 (thirdoct(10000, 512, 15, 150): band 0 starts at 7, band 14 ends before 219)
+constexpr int RS_UP = 5, RS_DOWN = 8, RS_HALF = 290;  // 16 kHz -> 10 kHz; ceil((60 - 8) / (28.714 / 160)) = 290
+constexpr int RS_OUT = 4;                 // resampled outputs per lane
+constexpr int BAND_FPW = 4;               // reduced frames per bands workgroup
+// band edges [lo, hi) as bin numbers relative to BIN0 (pystoi thirdoct's argmin rule; tests/metrics_oracle.py:band_edges)
+__constant__ int kBandEdge[NBAND + 1] = {7 - BIN0, 9 - BIN0, 11 - BIN0, 14 - BIN0, 17 - BIN0, 22 - BIN0, 27 - BIN0, 34 - BIN0,
+                                         43 - BIN0, 55 - BIN0, 69 - BIN0, 87 - BIN0, 109 - BIN0, 138 - BIN0, 174 - BIN0, 219 - BIN0};
+
+__device__ __forceinline__ double block_sum_256(double v, double* red, int tid) {
+    v = wave_sum_d(v);
+    __syncthreads();
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// np.hanning(258)[1:-1][i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257)
+__device__ __forceinline__ double hann258(int i) { return 0.5 - 0.5 * cospi(2.0 * (i + 1) / 257.0); }
+
+// modified Bessel function I0 by its power series (x <= 6 here: 40 terms reach double precision)
+__device__ double bessel_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, s = 1.0;
+    for (int k = 1; k < 40; ++k) {
+        term *= q / ((double)k * k);
+        s += term;
+    }
+    return s;
+}
+
+__global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restrict__ clean, const float* __restrict__ est, int L, int L10,
+                                                            float* __restrict__ xr, float* __restrict__ yr) {
+    __shared__ double taps[2 * RS_HALF + 1];
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    // pystoi _resample_window_oct: kaiser(581, beta) * sinc(t / 8) (its constant factor 2 p fc cancels in h / sum(h))
+    const double beta = 0.1102 * (60.0 - 8.7), i0b = bessel_i0(beta);
+    double part = 0;
+    for (int i = tid; i < 2 * RS_HALF + 1; i += 256) {
+        const double r = (double)(i - RS_HALF) / RS_HALF;
+        const double t = (double)(i - RS_HALF) / RS_DOWN;  // sinc(2 fc t), fc = 1 / (2 max(p, q)) = 1 / 16
+        const double sinc = i == RS_HALF ? 1.0 : sinpi(t) / (M_PI * t);
+        const double h = bessel_i0(beta * sqrt(1.0 - r * r)) / i0b * sinc;
+        taps[i] = h;
+        part += h;
+    }
+    const double scale = RS_UP / block_sum_256(part, red, tid);  // window = h / sum(h); resample_poly multiplies it by up
+    for (int i = tid; i < 2 * RS_HALF + 1; i += 256) taps[i] *= scale;
+    __syncthreads();
+    const float* src = (blockIdx.z ? est : clean) + (size_t)b * L;
+    float* dst = (blockIdx.z ? yr : xr) + (size_t)b * L10;
+    const long long n0 = (long long)blockIdx.x * (256 * RS_OUT);
+#pragma unroll
+    for (int r = 0; r < RS_OUT; ++r) {
+        const long long n = n0 + r * 256 + tid;
+        if (n >= L10) break;
+        const long long c = n * RS_DOWN;  // output n sits at upsampled position 8n; input j at 5j
+        const long long num = c - RS_HALF;
+        long long jlo = num <= 0 ? 0 : (num + RS_UP - 1) / RS_UP;
+        long long jhi = (c + RS_HALF) / RS_UP;
+        if (jhi > L - 1) jhi = L - 1;
+        double acc = 0;
+        for (long long j = jlo; j <= jhi; ++j) acc += taps[RS_HALF + (int)(c - RS_UP * j)] * (double)src[j];
+        dst[n] = (float)acc;
+    }
+}
+
+// One workgroup per row: clean frame energies, maximum, mask, kept index list (ascending) and its length.
+__global__ __launch_bounds__(256) void stoi_mask_kernel(const float* __restrict__ xr, int L10, int K0, double* __restrict__ energy,
+                                                        int* __restrict__ kidx, int* __restrict__ kcount) {
+    __shared__ double red[4];
+    __shared__ int wcount[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
+    const float* x = xr + (size_t)b * L10;
+    double* e = energy + (size_t)b * K0;
+    double w[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w[r] = hann258(lane + 64 * r);
+    double mx = -1e300;
+    for (int f = wv; f < K0; f += 4) {  // one wave per frame
+        const float* fr = x + (size_t)f * SHOP;
+        double s = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double v = w[r] * (double)fr[lane + 64 * r];
+            s += v * v;
+        }
+        s = wave_sum_d(s);
+        const double en = 20.0 * log10(sqrt(s) + 2.220446049250313e-16);  // eps = float64 eps: an all-zero frame stays finite
+        if (lane == 0) e[f] = en;
+        mx = fmax(mx, en);
+    }
+    mx = wave_max_d(mx);
+    if (lane == 0) red[wv] = mx;
+    __syncthreads();  // also orders the energy writes above before the reads below (same workgroup)
+    mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    int* ki = kidx + (size_t)b * K0;
+    int base = 0;
+    for (int f0 = 0; f0 < K0; f0 += 256) {
+        const int f = f0 + tid;
+        const bool keep = f < K0 && (mx - 40.0 - e[f]) < 0;
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wcount[wv] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int q = 0; q < wv; ++q) off += wcount[q];
+        if (keep) ki[off + __popcll(m & ((1ull << lane) - 1ull))] = f;
+        base += wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        __syncthreads();
+    }
+    if (tid == 0) kcount[b] = base;
+}
+
+// Band values of reduced frames j = BAND_FPW * blockIdx.x + 0 .. BAND_FPW - 1 of row blockIdx.y (frames j < K - 1 exist).
+__global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict__ xr, const float* __restrict__ yr, int L10, int K0, int Fmax,
+                                                         const int* __restrict__ kidx, const int* __restrict__ kcount,
+                                                         double* __restrict__ xb, double* __restrict__ yb) {
+    __shared__ double sx[SF], sy[SF];
+    __shared__ double px[NBIN], py[NBIN];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int F = kcount[b] - 1;
+    const float* x = xr + (size_t)b * L10;
+    const float* y = yr + (size_t)b * L10;
+    const int* ki = kidx + (size_t)b * K0;
+    const double wn = hann258(tid);
+    const double wo = hann258(tid < SHOP ? tid + SHOP : tid - SHOP);  // window at the position the neighbouring frame contributes
+    double cr = 1, ci = 0, sr = 1, si = 0;
+    if (tid < NBIN) sincospi(2.0 * (BIN0 + tid) / 512.0, &si, &sr);  // rotation by -2 pi k / 512 (sign of |X| is irrelevant)
+    for (int q = 0; q < BAND_FPW; ++q) {
+        const int j = blockIdx.x * BAND_FPW + q;
+        if (j >= F) break;  // uniform over the workgroup
+        // overlap-added reduced signal over [128 j, 128 j + 256): kept frames j - 1 (first half), j, j + 1 (second half)
+        const size_t self = (size_t)ki[j] * SHOP + tid;
+        double vx = wn * (double)x[self], vy = wn * (double)y[self];
+        if (tid < SHOP) {
+            if (j >= 1) {
+                const size_t o = (size_t)ki[j - 1] * SHOP + tid + SHOP;
+                vx += wo * (double)x[o];
+                vy += wo * (double)y[o];
+            }
+        } else {
+            const size_t o = (size_t)ki[j + 1] * SHOP + tid - SHOP;
+            vx += wo * (double)x[o];
+            vy += wo * (double)y[o];
+        }
+        __syncthreads();  // the previous frame's readers of sx / sy / px / py are done
+        sx[tid] = wn * vx;  // the STFT's own window
+        sy[tid] = wn * vy;
+        __syncthreads();
+        if (tid < NBIN) {
+            double xre = 0, xim = 0, yre = 0, yim = 0;
+            cr = 1;
+            ci = 0;
+            for (int n = 0; n < SF; ++n) {
+                const double a = sx[n], c = sy[n];
+                xre = fma(a, cr, xre);
+                xim = fma(a, ci, xim);
+                yre = fma(c, cr, yre);
+                yim = fma(c, ci, yim);
+                const double t = cr * sr - ci * si;
+                ci = fma(cr, si, ci * sr);
+                cr = t;
+            }
+            px[tid] = xre * xre + xim * xim;
+            py[tid] = yre * yre + yim * yim;
+        }
+        __syncthreads();
+        if (tid < 2 * NBAND) {
+            const int band = tid % NBAND;
+            const double* p = tid < NBAND ? px : py;
+            double s = 0;
+            for (int k = kBandEdge[band]; k < kBandEdge[band + 1]; ++k) s += p[k];
+            (tid < NBAND ? xb : yb)[((size_t)b * Fmax + j) * NBAND + band] = sqrt(s);
+        }
+    }
+}
+
+// One lane per (segment s, band): frames s .. s + 29 of the row's band values; partial sums per workgroup in double.
+__global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict__ xb, const double* __restrict__ yb, int Fmax,
+                                                        const int* __restrict__ kcount, int nchunk, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const int J = kcount[b] - 1 - (SEG - 1);  // segments m = 30 .. F'
+    const int p = blockIdx.x * 256 + tid;
+    double corr = 0;
+    if (J > 0 && p < J * NBAND) {
+        const int s = p / NBAND, band = p % NBAND;
+        const double* xs = xb + ((size_t)b * Fmax + s) * NBAND + band;
+        const double* ys = yb + ((size_t)b * Fmax + s) * NBAND + band;
+        double xv[SEG], yv[SEG];
+        double nx = 0, ny = 0;
+#pragma unroll
+        for (int t = 0; t < SEG; ++t) {
+            xv[t] = xs[(size_t)t * NBAND];
+            yv[t] = ys[(size_t)t * NBAND];
+            nx += xv[t] * xv[t];
+            ny += yv[t] * yv[t];
+        }
+        const double eps = 2.220446049250313e-16;
+        const double a = sqrt(nx) / (sqrt(ny) + eps);
+        const double clip = 1.0 + 5.623413251903491;  // 1 + 10^(15 / 20)
+        double mx = 0, my = 0;
+#pragma unroll
+        for (int t = 0; t < SEG; ++t) {
+            yv[t] = fmin(yv[t] * a, xv[t] * clip);
+            mx += xv[t];
+            my += yv[t];
+        }
+        mx /= SEG;
+        my /= SEG;
+        double sxx = 0, syy = 0, sxy = 0;
+#pragma unroll
+        for (int t = 0; t < SEG; ++t) {
+            const double u = xv[t] - mx, v = yv[t] - my;
+            sxx += u * u;
+            syy += v * v;
+            sxy += u * v;
+        }
+        corr = sxy / ((sqrt(sxx) + eps) * (sqrt(syy) + eps));
+    }
+    corr = block_sum_256(corr, red, tid);
+    if (tid == 0) partial[(size_t)b * nchunk + blockIdx.x] = corr;
+}
+
+__global__ __launch_bounds__(256) void stoi_final_kernel(const double* __restrict__ partial, int nchunk, const int* __restrict__ kcount,
+                                                         float* __restrict__ d, int* __restrict__ kept) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int K = kcount[b], J = K - 1 - (SEG - 1);
+    double s = 0;
+    if (J > 0)
+        for (int c = tid; c < nchunk; c += 256) s += partial[(size_t)b * nchunk + c];
+    s = block_sum_256(s, red, tid);
+    if (tid == 0) {
+        d[b] = J > 0 ? (float)(s / ((double)J * NBAND)) : 1e-5f;  // pystoi returns 1e-5 below 30 frames
+        kept[b] = K;
+    }
+}
+
+struct StoiDims {
+    int L10, K0, Fmax, nchunk;
+    bool resample;
+};
+
+StoiDims stoi_dims(int L, int fs) {
+    StoiDims s;
+    s.resample = fs != 10000;
+    s.L10 = s.resample ? (int)(((long long)L * RS_UP + RS_DOWN - 1) / RS_DOWN) : L;  // resample_poly: ceil(L up / down)
+    s.K0 = s.L10 > SF ? cdiv(s.L10 - SF, SHOP) : 0;
+    s.Fmax = s.K0 > 0 ? s.K0 - 1 : 0;
+    const int segs = s.Fmax >= SEG ? s.Fmax - (SEG - 1) : 0;
+    s.nchunk = segs > 0 ? cdiv(segs * NBAND, 256) : 1;
+    return s;
+}
+
+struct StoiWs {
+    float *xr, *yr;
+    double *energy, *xb, *yb, *partial;
+    int *kidx, *kcount;
+};
+
+size_t stoi_carve(const StoiDims& s, int B, char* base, StoiWs* w) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        off = align_up(off, 256);
+        char* r = base ? base + off : nullptr;
+        off += bytes;
+        return r;
+    };
+    const size_t rows = s.resample ? (size_t)B * s.L10 : 0;
+    w->xr = (float*)take(rows * sizeof(float));
+    w->yr = (float*)take(rows * sizeof(float));
+    w->energy = (double*)take((size_t)B * s.K0 * sizeof(double));
+    w->kidx = (int*)take((size_t)B * s.K0 * sizeof(int));
+    w->kcount = (int*)take((size_t)B * sizeof(int));
+    w->xb = (double*)take((size_t)B * s.Fmax * NBAND * sizeof(double));
+    w->yb = (double*)take((size_t)B * s.Fmax * NBAND * sizeof(double));
+    w->partial = (double*)take((size_t)B * s.nchunk * sizeof(double));
+    return off;
+}
+
+}  // namespace
+
+int stoi_check_args(int B, int L, int fs) {
+    if (fs != 16000 && fs != 10000) return RTFS_ERR_ARG;
+    if (B < 1 || L < 1 || L > (1 << 26)) return RTFS_ERR_SHAPE;
+    if (stoi_dims(L, fs).K0 < 1) return RTFS_ERR_SHAPE;  // pystoi needs one frame (np.max of no energies raises)
+    return RTFS_OK;
+}
+
+size_t stoi_workspace_bytes(int B, int L, int fs) {
+    if (stoi_check_args(B, L, fs) != RTFS_OK) return 0;
+    StoiWs w;
+    return stoi_carve(stoi_dims(L, fs), B, nullptr, &w);
+}
+
+int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept, hipStream_t st) {
+    const int e = stoi_check_args(B, L, fs);
+    if (e != RTFS_OK) return e;
+    const StoiDims s = stoi_dims(L, fs);
+    StoiWs w;
+    if (stoi_carve(s, B, nullptr, &w) > ws_bytes) return RTFS_ERR_WORKSPACE;
+    stoi_carve(s, B, (char*)ws, &w);
+    const float *xr = clean, *yr = est;
+    if (s.resample) {
+        hipLaunchKernelGGL(stoi_resample_kernel, dim3(cdiv(s.L10, 256 * RS_OUT), B, 2), dim3(256), 0, st, clean, est, L, s.L10, w.xr, w.yr);
+        const int r = rtfs_launch_status();
+        if (r != RTFS_OK) return r;
+        xr = w.xr;
+        yr = w.yr;
+    }
+    hipLaunchKernelGGL(stoi_mask_kernel, dim3(B), dim3(256), 0, st, xr, s.L10, s.K0, w.energy, w.kidx, w.kcount);
+    int r = rtfs_launch_status();
+    if (r != RTFS_OK) return r;
+    if (s.Fmax > 0) {
+        hipLaunchKernelGGL(stoi_bands_kernel, dim3(cdiv(s.Fmax, BAND_FPW), B), dim3(256), 0, st, xr, yr, s.L10, s.K0, s.Fmax, w.kidx, w.kcount,
+                           w.xb, w.yb);
+        if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+    }
+    if (s.Fmax >= SEG) {  // otherwise every row takes the 1e-5 path and the partials are never read
+        hipLaunchKernelGGL(stoi_corr_kernel, dim3(s.nchunk, B), dim3(256), 0, st, w.xb, w.yb, s.Fmax, w.kcount, s.nchunk, w.partial);
+        if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+    }
+    hipLaunchKernelGGL(stoi_final_kernel, dim3(B), dim3(256), 0, st, w.partial, s.nchunk, w.kcount, d, kept);
+    return rtfs_launch_status();
+}

@@ -318,6 +318,10 @@ int launch_vp_block(const float* video, const float* pack, float* out, int B, in
 int launch_pit_pairwise(const float* est, const float* tgt, int B, int n, int L, int kind, int zero_mean, int take_log, float* pw,
                         float* min_loss, int* perm, hipStream_t st);
 
+// evaluation metric (k_stoi.hip): classic STOI as pystoi 0.4.1 computes it, fs 16000 (resampled to 10 kHz on the device) or 10000
+size_t stoi_workspace_bytes(int B, int L, int fs);
+int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept, hipStream_t st);
+
 // video front-end (k_video.hip): FRCNNVideoModel, ResNet-18 trunk, PReLU, eval
 size_t video_pack_floats();
 size_t video_workspace_bytes(int B, int T);
