@@ -156,6 +156,22 @@ int rtfs_separator_forward_f32(const float* wav, const float* video_vp, const fl
                                const float* pack_dec, float* out, int B, int L, int Tv, int repeats, void* ws,
                                size_t ws_bytes, void* stream, void* video_ready, int rnn_kind /* 0 SRU, 1 LSTM block pack */);
 
+/* K target speakers of each mixture in one call: the reference separates a mixture once per visible speaker (its evaluation lists every
+ * mixture once per speaker, side by side in one unshuffled batch: test.py:128-140, avspeech_dataset.py:81-84; inference on a video calls
+ * the model once per face).  Only the part of the separator before the CAF depends on the audio alone (refinement_module.py:45-62: block 0
+ * runs on the bottleneck output, the video enters after it): STFT, encoder statistics, bottleneck + block head and block 0's body run once
+ * per mixture; the CAF boundary fans out to the B * K targets, and the other blocks, the mask, the decoder and the iSTFT run per target.
+ * wav (B,L); video_vp (B*K,512,Tv) and out (B*K,1,L) per target, mixture-major: target t = b*K + k, so out reads as (B,K,L).  Target t's
+ * result is what rtfs_separator_forward_ex_f32 returns for mixture b and lips t.  Same cells, length limits and -1 rules as the fused
+ * separator; -4 for K < 1, K > 16, repeats < 2 (no CAF boundary to fan out at) or RTFS_GEMM_F32=1 (the unfused A/B sequence), all before
+ * the first launch.  split cuts the MIXTURES (each part >= 8 of them) and a part carries its mixtures' targets; the workspace query takes
+ * the same split, returns 0 for out-of-range arguments and for K = 1 asks no more than rtfs_separator_workspace_bytes_ex. */
+size_t rtfs_separator_speakers_workspace_bytes(int B, int K, int L, int Tv, int split);
+int rtfs_separator_speakers_f32(const float* wav, const float* video_vp, const float* pack_enc, const float* pack_bn,
+                                const float* pack_block, const float* pack_caf, const float* pack_s3, const float* pack_dec,
+                                float* out, int B, int K, int L, int Tv, int repeats, void* ws, size_t ws_bytes, void* stream,
+                                void* video_ready, int rnn_kind, int split);
+
 /* Operator-level seam: sru.SRU(input_size=512, hidden_size=32, num_layers=4, bidirectional=True).forward
  * (call site src/models/layers/rnn_layers.py:150; third-party asappresearch `sru`, v2 recurrence).
  * x (L,N,512) -> h (L,N,64).  pack = the DUALPATH pack (only its SRU part is read). */

@@ -50,6 +50,8 @@ SIGNATURES = {
     "rtfs_separator_workspace_bytes_ex": (_z, [_i, _i, _i, _i]),
     "rtfs_separator_forward_ex_f32": (_i, [_p] * 9 + [_i, _i, _i, _i, _p, _z, _p, _p, _i, _i]),
     "rtfs_separator_forward_f32": (_i, [_p] * 9 + [_i, _i, _i, _i, _p, _z, _p, _p, _i]),
+    "rtfs_separator_speakers_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "rtfs_separator_speakers_f32": (_i, [_p] * 9 + [_i, _i, _i, _i, _i, _p, _z, _p, _p, _i, _i]),
     "rtfs_sru_workspace_bytes": (_z, [_i, _i]),
     "rtfs_sru_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),
     "rtfs_sru_train_pack_floats": (_z, []),

@@ -587,8 +587,10 @@ int block_forward(const BlockPack& p, const float* x, const float* x_res, float*
 // res_has_a1 (in / out): whether w.residual currently holds residual + a1.  A boundary that has to read a1 anyway also adds it to the residual
 // it writes (unless it is the last one: the tail wants the plain residual), and the boundary after it then does not read a1 at all.
 int block_boundary(const BlockPack& p, const float* a1, int B, int T, int F, BlockWs& w, hipStream_t st, const CafArgs* caf, unsigned* ctr = nullptr,
-                   bool* res_has_a1 = nullptr, bool last = true, bool res_from_a1 = false) {
+                   bool* res_has_a1 = nullptr, bool last = true, bool res_from_a1 = false, int xk = 1, int a1k = 1) {
     B2bArgs a;
+    a.xk = xk;
+    a.a1k = a1k;
     a.x = w.expanded;
     a.res = w.residual;
     a.a1 = a1;
@@ -616,6 +618,7 @@ int block_boundary(const BlockPack& p, const float* a1, int B, int T, int F, Blo
         return RTFS_ERR_ARG;  // (cannot happen: the head kernel that skipped the residual qualifies on the same conditions)
     }
     const int rc = launch_pws_b2b4(a, B, ctr, st);  // padded rows: the pipelined kernel (k_b2b.hip)
+    if (rc == RTFS_ERR_ARG && (xk > 1 || a1k > 1)) return RTFS_ERR_SHAPE;  // (the first-generation kernel has no mixture index; checked up front)
     return rc == RTFS_ERR_ARG ? launch_pws_b2b(a, B, st) : rc;
 }
 
@@ -961,26 +964,29 @@ struct SepWs {
     int B_ = 0;
     int cs;
     BlockWs blk;
-    SepWs(Arena& a, int B, int T, int Tv, int cs_)
+    // K = 0: one target per mixture (rtfs_separator_forward_*).  K >= 1: K targets per mixture (rtfs_separator_speakers_f32, fused path
+    // only): what depends on the mixture alone (spec, a1, st0) is sized by B, what depends on the target (CAF tables, z, the block
+    // workspace and its statistic slots) by B * K; a0, cur and nxt exist only on the unfused path and take nothing.
+    SepWs(Arena& a, int B, int T, int Tv, int cs_, int K = 0)
         : spec(a.take<float>((size_t)B * 2 * T * NF)),
-          a0(a.take<float>((size_t)B * CA * cs_)),
+          a0(a.take<float>(K ? 0 : (size_t)B * CA * cs_)),
           a1(a.take<float>((size_t)B * CA * cs_)),
-          cur(a.take<float>((size_t)B * CA * cs_)),
-          nxt(a.take<float>((size_t)B * CA * cs_)),
-          r(a.take<float>((size_t)B * CA * Tv)),
-          att(a.take<float>((size_t)B * CA * Tv)),
-          rt(a.take<float>((size_t)B * CA * Tv)),
-          attt(a.take<float>((size_t)B * CA * Tv)),
-          z(a.take<float>((size_t)B * 18 * cs_)),
+          cur(a.take<float>(K ? 0 : (size_t)B * CA * cs_)),
+          nxt(a.take<float>(K ? 0 : (size_t)B * CA * cs_)),
+          r(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
+          att(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
+          rt(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
+          attt(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
+          z(a.take<float>((size_t)B * (K ? K : 1) * 18 * cs_)),
           encimg(a.take<float>(8192)),
           wpad(a.take<float>(73728)),
           wpad0(a.take<float>(73728)),
           st0(a.take<double>(2 * B + 32)),
           ctr(reinterpret_cast<unsigned*>(st0 ? st0 + 2 * B : nullptr)),
-          bstats(a.take<double>((size_t)STAT_APPS * BlockWs::NSTAT * B * 2)),
+          bstats(a.take<double>((size_t)STAT_APPS * BlockWs::NSTAT * B * (K ? K : 1) * 2)),
           B_(B),
           cs(cs_),
-          blk(a, B, T, NF, cs_) {}
+          blk(a, B * (K ? K : 1), T, NF, cs_) {}
 };
 }  // namespace
 
@@ -995,8 +1001,10 @@ struct SepPacks {
 };
 
 // the whole chain for mixtures [first, first + B) of the call: wav / video_vp / out already point at mixture `first`
+// K >= 1 (rtfs_separator_speakers_f32, fused path only): B mixtures with K targets each, video_vp / out per target (t = b * K + k); the
+// prefix up to block 0's body runs on the B mixtures, the first boundary fans out to the B * K targets
 int separator_part(const SepPacks& k, const float* wav, const float* video_vp, float* out, int B, int L, int T, int Tv, int repeats, SepWs& w,
-                   hipStream_t st, void* video_ready) {
+                   hipStream_t st, void* video_ready, int K = 0) {
     const EncPack& pe = k.pe;
     const BnPack& pb = k.pb;
     const BlockPack& pk = k.pk;
@@ -1004,8 +1012,9 @@ int separator_part(const SepPacks& k, const float* wav, const float* video_vp, f
     const S3Pack& ps = k.ps;
     const DecPack& pd = k.pd;
     const int P = T * NF, cs = w.cs;
+    const int KT = K ? K : 1, BK = B * KT;  // targets per mixture, targets
     // one memset per call: the bottleneck statistics, the tile counters and the statistic slots of every block application (SepWs::bstats)
-    const size_t app_stats = (size_t)BlockWs::NSTAT * B * 2;
+    const size_t app_stats = (size_t)BlockWs::NSTAT * BK * 2;
     const size_t zero_bytes = (size_t)(reinterpret_cast<char*>(w.bstats + SepWs::STAT_APPS * app_stats) - reinterpret_cast<char*>(w.st0));
     if (hipMemsetAsync(w.st0, 0, zero_bytes, st) != hipSuccess) return RTFS_ERR_LAUNCH;
     int nctr = 0;
@@ -1032,6 +1041,7 @@ int separator_part(const SepPacks& k, const float* wav, const float* video_vp, f
             head_done = true;
         }
     }
+    if (K && !head_done) return RTFS_ERR_SHAPE;  // (cannot happen: rtfs_separator_speakers_f32 checks the head kernel's conditions first)
     if (!head_done) CHECK(launch_enc_conv(w.spec, pe.w, w.a0, w.st0, B, CA, T, NF, (size_t)cs, (size_t)CA * cs, st));
     if (!head_done) CHECK(audio_bn(pb, w.a0, w.st0, w.a1, B, P, st, cs, w.ctr + nctr++));
     // refinement_module.py:45-62: block(a1); CAF; then (repeats-1) x block(audio + a1), shared weights
@@ -1062,15 +1072,16 @@ int separator_part(const SepPacks& k, const float* wav, const float* video_vp, f
         Fork cafv;
         CHECK(cafv.begin(st, 15));
         if (video_ready && hipStreamWaitEvent(cafv.side.stream, (hipEvent_t)video_ready, 0) != hipSuccess) return RTFS_ERR_LAUNCH;
-        CHECK(launch_caf_video(ca, B, cafv.side.stream));
+        CHECK(launch_caf_video(ca, BK, cafv.side.stream));
         if (!head_done) CHECK(block_head(pk, w.a1, nullptr, B, T, NF, w.blk, st, nullptr, w.ctr + nctr++));
         bool res_has_a1 = false;
         const bool own_slots = repeats <= SepWs::STAT_APPS;  // (more applications than slots: every block zeroes and reuses the first)
         for (int i = 0; i < repeats; ++i) {
             if (own_slots) w.blk.stats = w.bstats + (size_t)i * app_stats;
-            CHECK(block_body(pk, B, T, NF, w.blk, st, !own_slots));
+            CHECK(block_body(pk, i == 0 ? B : BK, T, NF, w.blk, st, !own_slots));  // block 0: the mixtures (first B samples of the workspace)
             if (i == 0) CHECK(cafv.join());
-            if (i + 1 < repeats) CHECK(block_boundary(pk, w.a1, B, T, NF, w.blk, st, i == 0 ? &ca : nullptr, nctr < 64 ? w.ctr + nctr++ : nullptr, &res_has_a1, i + 2 == repeats, head_done && i == 0));
+            // the first boundary fans out: target t reads expanded_0 and a1 of mixture t / K; every later one reads a1 of the mixture
+            if (i + 1 < repeats) CHECK(block_boundary(pk, w.a1, BK, T, NF, w.blk, st, i == 0 ? &ca : nullptr, nctr < 64 ? w.ctr + nctr++ : nullptr, &res_has_a1, i + 2 == repeats, head_done && i == 0, i == 0 ? KT : 1, KT));
             else {
                 // last application: residual conv + S3 mask + complex product + decoder taps in one kernel (k_s3f.hip); `refined` never exists
                 TailS3Args f;
@@ -1079,9 +1090,10 @@ int separator_part(const SepPacks& k, const float* wav, const float* video_vp, f
                 f.stats = w.st0; f.inv_count = 1.0 / ((double)CA * P);
                 f.P = P; f.cs = cs; f.cout_live = 18;
                 f.tile_ctr = nctr < 64 ? w.ctr + nctr++ : nullptr;
+                f.K = KT;  // spectrogram and a0 statistics of the target's mixture
                 if (head_done) {  // (the two launches qualify together: same P, same pitch)
-                    CHECK(launch_tail_s3t(f, B, st));
-                    return launch_dec_istft(w.z, out, B, T, NF, L, (size_t)cs, (size_t)18 * cs, st);
+                    CHECK(launch_tail_s3t(f, BK, st));
+                    return launch_dec_istft(w.z, out, BK, T, NF, L, (size_t)cs, (size_t)18 * cs, st);
                 }
                 CHECK(block_tail(pk, cur, B, T, NF, w.blk, st, f.tile_ctr));
             }
@@ -1138,15 +1150,12 @@ int rtfs_separator_forward_f32(const float* wav, const float* video_vp, const fl
                                          stream, video_ready, rnn_kind, 0);
 }
 
-int rtfs_separator_forward_ex_f32(const float* wav, const float* video_vp, const float* pack_enc, const float* pack_bn, const float* pack_block,
-                                  const float* pack_caf, const float* pack_s3, const float* pack_dec, float* out, int B, int L, int Tv,
-                                  int repeats, void* ws, size_t ws_bytes, void* stream, void* video_ready, int rnn_kind, int split) {
-    RTFS_RETURN_IF(split < 0 || split > 8, RTFS_ERR_ARG);
-    RTFS_RETURN_IF(!wav || !video_vp || !pack_enc || !pack_bn || !pack_block || !pack_caf || !pack_s3 || !pack_dec || !out, RTFS_ERR_ARG);
-    RTFS_RETURN_IF(B < 1 || L <= 128 || Tv < 1 || repeats < 1, RTFS_ERR_ARG);
-    const int T = rtfs_num_frames(L);
-    RTFS_RETURN_IF(!shape_ok_block(B, T, NF, rnn_kind), RTFS_ERR_SHAPE);
-    RTFS_RETURN_IF(rnn_kind != 0 && rnn_kind != 1, RTFS_ERR_ARG);
+// The batch-split driver shared by the two separator entry points (arguments checked by the caller).  K = 0: one target per mixture;
+// K >= 1: K targets per mixture, video_vp / out per target - a part carries its mixtures' K * nb targets.
+static int separator_run(const float* wav, const float* video_vp, const float* pack_enc, const float* pack_bn, const float* pack_block,
+                         const float* pack_caf, const float* pack_s3, const float* pack_dec, float* out, int B, int K, int L, int Tv, int repeats,
+                         void* ws, size_t ws_bytes, void* stream, void* video_ready, int rnn_kind, int split) {
+    const int T = rtfs_num_frames(L), KT = K ? K : 1;
     const int np = separator_parts(B, split);
     Arena ar(ws, ws_bytes);
     std::vector<SepWs> parts;
@@ -1154,12 +1163,12 @@ int rtfs_separator_forward_ex_f32(const float* wav, const float* video_vp, const
     // padded channel rows on the fused path; the unfused A/B sequence (exact-f32 GEMMs, or a single repeat) runs kernels that know only
     // contiguous tensors
     const int cstride = (gemm_f32() || repeats == 1) ? T * NF : pitch(T * NF);
-    for (int i = 0; i < np; ++i) parts.emplace_back(ar, (B * (i + 1)) / np - (B * i) / np, T, Tv, cstride);
+    for (int i = 0; i < np; ++i) parts.emplace_back(ar, (B * (i + 1)) / np - (B * i) / np, T, Tv, cstride, K);
     RTFS_RETURN_IF(!ws || !ar.ok(), RTFS_ERR_WORKSPACE);
     hipStream_t st = S(stream);
     Cursor ce(pack_enc), cb(pack_bn), ck(pack_block), cc(pack_caf), cs(pack_s3), cd(pack_dec);
     const SepPacks k{EncPack(ce), BnPack(cb), BlockPack::make(ck, rnn_kind), CafPack(cc), S3Pack(cs), DecPack(cd)};
-    if (np == 1) return separator_part(k, wav, video_vp, out, B, L, T, Tv, repeats, parts[0], st, video_ready);
+    if (np == 1) return separator_part(k, wav, video_vp, out, B, L, T, Tv, repeats, parts[0], st, video_ready, K);
     // part 0 on the caller's stream, parts 1.. on side streams forked from it and joined back into it
     std::vector<RtfsSide> side(np);
     for (int i = 1; i < np; ++i) {
@@ -1169,12 +1178,55 @@ int rtfs_separator_forward_ex_f32(const float* wav, const float* video_vp, const
     int rc = RTFS_OK;
     for (int i = 0; i < np && rc == RTFS_OK; ++i) {
         const int first = (B * i) / np, nb = (B * (i + 1)) / np - first;
-        rc = separator_part(k, wav + (size_t)first * L, video_vp + (size_t)first * 512 * Tv, out + (size_t)first * L, nb, L, T, Tv, repeats, parts[i],
-                            i == 0 ? st : side[i].stream, video_ready);
+        const size_t t0 = (size_t)first * KT;  // first target of the part
+        rc = separator_part(k, wav + (size_t)first * L, video_vp + t0 * 512 * Tv, out + t0 * L, nb, L, T, Tv, repeats, parts[i],
+                            i == 0 ? st : side[i].stream, video_ready, K);
     }
     for (int i = 1; i < np; ++i)  // join even after a failed launch: the caller's stream must not run ahead of work already queued
         if (hipEventRecord(side[i].join, side[i].stream) != hipSuccess || hipStreamWaitEvent(st, side[i].join, 0) != hipSuccess) return RTFS_ERR_LAUNCH;
     return rc;
+}
+
+int rtfs_separator_forward_ex_f32(const float* wav, const float* video_vp, const float* pack_enc, const float* pack_bn, const float* pack_block,
+                                  const float* pack_caf, const float* pack_s3, const float* pack_dec, float* out, int B, int L, int Tv,
+                                  int repeats, void* ws, size_t ws_bytes, void* stream, void* video_ready, int rnn_kind, int split) {
+    RTFS_RETURN_IF(split < 0 || split > 8, RTFS_ERR_ARG);
+    RTFS_RETURN_IF(!wav || !video_vp || !pack_enc || !pack_bn || !pack_block || !pack_caf || !pack_s3 || !pack_dec || !out, RTFS_ERR_ARG);
+    RTFS_RETURN_IF(B < 1 || L <= 128 || Tv < 1 || repeats < 1, RTFS_ERR_ARG);
+    const int T = rtfs_num_frames(L);
+    RTFS_RETURN_IF(!shape_ok_block(B, T, NF, rnn_kind), RTFS_ERR_SHAPE);
+    RTFS_RETURN_IF(rnn_kind != 0 && rnn_kind != 1, RTFS_ERR_ARG);
+    return separator_run(wav, video_vp, pack_enc, pack_bn, pack_block, pack_caf, pack_s3, pack_dec, out, B, 0, L, Tv, repeats, ws, ws_bytes, stream,
+                         video_ready, rnn_kind, split);
+}
+
+// ------------------------------------------------------------ K target speakers of one mixture
+static bool speakers_args_ok(int B, int K, int L, int Tv, int split) {
+    return B >= 1 && K >= 1 && K <= 16 && L > 128 && Tv >= 1 && split >= 0 && split <= 8;
+}
+
+size_t rtfs_separator_speakers_workspace_bytes(int B, int K, int L, int Tv, int split) {
+    if (!speakers_args_ok(B, K, L, Tv, split)) return 0;
+    Arena ar(nullptr, 0);
+    const int T = rtfs_num_frames(L), np = separator_parts(B, split);
+    for (int i = 0; i < np; ++i) SepWs w(ar, (B * (i + 1)) / np - (B * i) / np, T, Tv, pitch(T * NF), K);
+    return ar.off + 256;
+}
+
+int rtfs_separator_speakers_f32(const float* wav, const float* video_vp, const float* pack_enc, const float* pack_bn, const float* pack_block,
+                                const float* pack_caf, const float* pack_s3, const float* pack_dec, float* out, int B, int K, int L, int Tv,
+                                int repeats, void* ws, size_t ws_bytes, void* stream, void* video_ready, int rnn_kind, int split) {
+    // every refusal comes before the first launch (and before any device call)
+    RTFS_RETURN_IF(!wav || !video_vp || !pack_enc || !pack_bn || !pack_block || !pack_caf || !pack_s3 || !pack_dec || !out, RTFS_ERR_ARG);
+    RTFS_RETURN_IF(!speakers_args_ok(B, K, L, Tv, split) || repeats < 2 || (rnn_kind != 0 && rnn_kind != 1), RTFS_ERR_ARG);
+    RTFS_RETURN_IF(gemm_f32(), RTFS_ERR_ARG);  // the exact-f32 A/B switch runs the unfused sequence, which has no shared prefix
+    const int T = rtfs_num_frames(L), P = T * NF;
+    RTFS_RETURN_IF(!shape_ok_block(B, T, NF, rnn_kind), RTFS_ERR_SHAPE);
+    // the fused head, boundary and tail kernels' own conditions (launch_bn_head_qualifies, launch_pws_b2b4_qualifies, launch_tail_s3t):
+    // padded rows (pitch() always gives them), P >= 64 and one sample's 256 rows within 31-bit byte offsets
+    RTFS_RETURN_IF(P < 64 || (size_t)256 * pitch(P) * 4 >= ((size_t)1 << 31), RTFS_ERR_SHAPE);
+    return separator_run(wav, video_vp, pack_enc, pack_bn, pack_block, pack_caf, pack_s3, pack_dec, out, B, K, L, Tv, repeats, ws, ws_bytes, stream,
+                         video_ready, rnn_kind, split);
 }
 
 // ------------------------------------------------------------ stand-alone SRU operator

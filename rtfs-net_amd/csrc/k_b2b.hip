@@ -102,9 +102,11 @@ __global__ __launch_bounds__(B4_NT) void pws_b2b4_kernel(B2bArgs a, int ntiles, 
         const int b = tile / tiles_per_sample;
         const int wp0 = (tile - b * tiles_per_sample) * (B4_NT / 64 * 64) + wave * 64;  // first pixel of this wave (wave-uniform)
         if (wp0 < P) {
-            const __amdgpu_buffer_rsrc_t xs = rsrc_of(a.x + (size_t)b * 64 * CS + wp0);
+            // K targets per mixture (B2bArgs::xk / a1k): target b reads the mixture's expanded_0 / a1, writes its own residual / x_enc
+            const int bx = a.xk > 1 ? b / a.xk : b, ba = a.a1k > 1 ? b / a.a1k : b;
+            const __amdgpu_buffer_rsrc_t xs = rsrc_of(a.x + (size_t)bx * 64 * CS + wp0);
             const __amdgpu_buffer_rsrc_t ress = rsrc_of(a.res + (size_t)b * 256 * CS + wp0);
-            const __amdgpu_buffer_rsrc_t a1s = rsrc_of(a.a1 + (size_t)b * 256 * CS + wp0);
+            const __amdgpu_buffer_rsrc_t a1s = rsrc_of(a.a1 + (size_t)ba * 256 * CS + wp0);
             const __amdgpu_buffer_rsrc_t xes = rsrc_of(a.xenc + (size_t)b * 64 * CS + wp0);
             const unsigned CS4 = CS * 4u;  // row pitch in bytes
             // CAF: this lane's two video frames (legacy nearest: tv = floor(t Tv / T), t = pixel / F) in the (B, Tv, 256) tables

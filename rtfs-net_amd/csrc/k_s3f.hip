@@ -259,11 +259,12 @@ __global__ __launch_bounds__(F_NT) void tail_s3t_kernel(TailS3Args a, int ntiles
         }
         mfma_v_fence(acc1[0], acc1[1]);  // the dropped tile of "chunk 9" is still being written: nothing may move into its registers yet (tools/isa_check.py)
         // the epilogue's spectrogram taps and first encoder fragments (the residual-conv operand is dead now: their registers)
-        patch_load(spec_rsrc(a.spec + (size_t)b * 2 * P, P), wp0 + 2 * r, h, P, a.F, V);
+        const int bm = a.K > 1 ? b / a.K : b;  // the mixture of target b (TailS3Args::K)
+        patch_load(spec_rsrc(a.spec + (size_t)bm * 2 * P, P), wp0 + 2 * r, h, P, a.F, V);
         load_ea(0);
         // ---- mask, complex product with the encoder output, taps GEMM (k_pwr.hip PWR_S3T), eight encoder rows (one K step of the taps GEMM) at a time
         float esc = 1.0f, eisc = WINV;
-        if (a.stats) rms_pow2(a.stats + 2 * b, a.inv_count, esc, eisc);  // power of two nearest 1 / rms(a0) of this mixture (wave-uniform)
+        if (a.stats) rms_pow2(a.stats + 2 * bm, a.inv_count, esc, eisc);  // power of two nearest 1 / rms(a0) of this mixture (wave-uniform)
         PatchFrag pf;
         patch_build(V, wp0 + 2 * r, a.T, a.F, P, esc, pf);
         f32x16 acc2[2];

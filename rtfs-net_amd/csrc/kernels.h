@@ -82,6 +82,9 @@ struct B2bArgs {
     // bit 2 (with a CAF, i.e. the first boundary): `res` is not read - residual_0 = PReLU(gw a1 + gb) is formed from the a1 rows (the head kernel
     // then need not write it).
     int a1_mode = 1;
+    // k_b2b.hip only, separation of K targets per mixture (rtfs_separator_speakers_f32): the launch runs over targets t, and reads `x` of
+    // sample t / xk and `a1` of sample t / a1k (1 = the sample itself).  `res` and `xenc` are always the target's own.
+    int xk = 1, a1k = 1;
 };
 int launch_pws_b2b(const B2bArgs& a, int B, hipStream_t st);
 bool launch_pws_b2b4_qualifies(const B2bArgs& a);
@@ -130,6 +133,7 @@ struct TailS3Args {
     double inv_count = 0;
     int P = 0, cs = 0, cout_live = 0;
     unsigned* tile_ctr = nullptr;
+    int K = 1;  // targets per mixture: target t reads `spec` and `stats` of mixture t / K (the a0 it rebuilds is the mixture's)
 };
 int launch_tail_s3t(const TailS3Args& a, int B, hipStream_t st);
 int launch_pws_head4(const PwArgs& a, int B, hipStream_t st);  // block head on padded rows (k_b2b.hip); RTFS_ERR_ARG = use launch_pws_gateway_proj

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import os
 
+import contextlib
 import ctypes
 import sys
 
@@ -653,6 +654,81 @@ class AVNet(BaseAVModel):
                                                      ctypes.c_void_p(ready.cuda_event), rm.audio_net.get_block(0).rnn_kind, split),
                    "rtfs_separator_forward_ex_f32")
         return out
+
+    def separate_speakers(self, audio_mixture, mouth_embeddings):
+        """K target speakers of each mixture in one pass (inference only).  audio_mixture (B,L)|(L)|(B,1,L), mouth_embeddings (B,K,512,Tv)
+        -> (B,K,L), where [b, k] is what ``forward`` returns for mixture b with lips k.  The reference separates a mixture once per speaker
+        (its evaluation batch lists each mixture once per speaker: test.py:128-140, avspeech_dataset.py:81-84); only the part before the
+        CAF depends on the audio alone (refinement_module.py:45-62), so the encoder, the bottleneck and block 0 run once per mixture here.
+        Wherever ``forward`` takes the fused separator this is one C call (rtfs_separator_speakers_f32); otherwise (GRU cell, past the
+        fused length, a single repeat, ``fused = False``, RTFS_GEMM_F32=1, K > 16) the same modules composed, with block 0's output, the
+        a1 residual and the encoder output repeated K times after block 0."""
+        if audio_mixture.ndim not in (1, 2, 3) or (audio_mixture.ndim == 3 and audio_mixture.shape[1] != 1):
+            raise ValueError(f"separate_speakers: audio_mixture must be (B,L), (L) or (B,1,L); got {tuple(audio_mixture.shape)}")
+        wav = STFTEncoder.unsqueeze_to_2D(audio_mixture)
+        if mouth_embeddings.ndim != 4:
+            raise ValueError(f"separate_speakers: mouth_embeddings must be (B,K,512,Tv); got {tuple(mouth_embeddings.shape)}")
+        B, L = wav.shape
+        if mouth_embeddings.shape[0] != B or mouth_embeddings.shape[1] < 1:
+            raise ValueError(f"separate_speakers: {B} mixture(s) but mouth_embeddings {tuple(mouth_embeddings.shape)}")
+        if self.n_src != 1:
+            raise ValueError("separate_speakers: target-speaker models only (n_src 1)")
+        if self.training:
+            raise RuntimeError("AVNet.separate_speakers is inference only: call .eval()")
+        _lib.need_gpu(wav, mouth_embeddings)
+        K = int(mouth_embeddings.shape[1])
+        video = mouth_embeddings.reshape(B * K, *mouth_embeddings.shape[2:])
+        rm = self.refinement_module
+        blk = rm.audio_net.get_block(0)
+        repeats = int(self.audio_params["repeats"])
+        lib = _lib.load()
+        too_long = int(lib.rtfs_num_frames(int(L))) // 2 > layers.fused_max_block_sweep(blk.rnn_kind)
+        if not self.fused or too_long or repeats < 2 or K > 16 or os.environ.get("RTFS_GEMM_F32", "")[:1] == "1":
+            return self._separate_speakers_composed(wav, video, K, too_long)
+        wav = wav.contiguous()
+        # VP block of the B * K tracks on the side stream, as in forward
+        main = torch.cuda.current_stream(wav.device)
+        side = self._side_stream(wav.device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            vp = rm.video_net.get_block(0)(self.video_bottleneck(video)).contiguous()
+            ready = torch.cuda.Event()
+            ready.record(side)
+        vp.record_stream(main)
+        Tv = vp.shape[-1]
+        out = _lib.empty(B, K, L, device=wav.device, dtype=torch.float32)
+        split = int(getattr(self, "batch_split", 0) or 0)
+        ws = _lib.workspace(lib.rtfs_separator_speakers_workspace_bytes(B, K, L, Tv, split), wav.device)
+        packs = [self.encoder.pack(), self.audio_bottleneck.pack(), blk.pack(), rm.crossmodal_fusion.get_fusion_block(0).audio_lstm.pack(),
+                 self.mask_generator.pack(), self.decoder.pack()]
+        _lib.check(lib.rtfs_separator_speakers_f32(_lib.ptr(wav), _lib.ptr(vp), *[_lib.ptr(p) for p in packs], _lib.ptr(out), B, K, L, Tv,
+                                                   repeats, _lib.ptr(ws), ws.numel(), _lib.stream_of(wav), ctypes.c_void_p(ready.cuda_event),
+                                                   blk.rnn_kind, split),
+                   "rtfs_separator_speakers_f32")
+        return out
+
+    def _separate_speakers_composed(self, wav, video, K, train_kernels):
+        """separate_speakers from the modules: the prefix on the B mixtures, then K copies of block 0's output, the a1 residual and the
+        encoder output.  ``train_kernels``: the routes ``forward`` takes with the unfused kernels (forward_train under force_train_kernels);
+        otherwise the per-module inference entry points of forward_modular."""
+        rm = self.refinement_module
+        blk = rm.audio_net.get_block(0)
+        B, L = wav.shape
+        with torch.no_grad(), (layers.force_train_kernels() if train_kernels else contextlib.nullcontext()):
+            video = rm.video_net.get_block(0)(self.video_bottleneck(video))
+            if train_kernels:
+                emb = self.encoder(wav)
+                a_res = self.audio_bottleneck(emb)
+            else:
+                emb, stats = self.encoder(wav, return_stats=True)
+                a_res = self.audio_bottleneck(emb, stats)
+            audio = blk(a_res)
+            audio, a_res, emb = (t.repeat_interleave(K, 0) for t in (audio, a_res, emb))
+            audio, _ = rm.crossmodal_fusion.get_fusion_block(0)(audio, video)
+            for _ in range(rm.audio_repeats):
+                audio = blk(audio, a_res)
+            sep = self.mask_generator(audio, emb)
+            return self.decoder(sep, (B * K, L)).view(B, K, L)
 
     def _side_stream(self, device):
         streams = self.__dict__.setdefault("_side_streams", {})

@@ -36,6 +36,39 @@ class System(nn.Module):
             mouth_emb = self.video_model(mouth.type_as(wav))
         return self.audio_model(wav, mouth_emb)
 
+    def separate_speakers(self, wav, mouths):
+        """Every target speaker of each mixture with one audio pass (inference): wav (B,L), mouths (B,K,1,Tv,88,88) -> (B,K,L).  The video
+        front-end runs on the B*K mouth tracks (no_grad, as in ``forward``), then ``AVNet.separate_speakers``.  Without a video model the
+        mouth slot holds lip embeddings (B,K,512,Tv)."""
+        if mouths.ndim < 3:
+            raise ValueError(f"System.separate_speakers: mouths must be (B,K,...); got {tuple(mouths.shape)}")
+        B, K = int(mouths.shape[0]), int(mouths.shape[1])
+        if self.video_model is None:
+            return self.audio_model.separate_speakers(wav, mouths)
+        with torch.no_grad():
+            emb = self.video_model(mouths.reshape(B * K, *mouths.shape[2:]).type_as(wav))
+        return self.audio_model.separate_speakers(wav, emb.reshape(B, K, *emb.shape[1:]))
+
+    def forward_grouped(self, wav, mouth=None):
+        """``forward`` for a batch that may list each mixture once per target speaker, as the reference's test batches do (test.py:128-140,
+        avspeech_dataset.py:81-84: n_src 1, no shuffling, the entries of one mixture side by side).  wav (N,L) or (N,1,L) -> (N,1,L) in
+        input order.  Runs of bit-identical consecutive mixture rows are found with one device reduction and one host read; if every run has
+        the same length K > 1, the batch goes through ``separate_speakers`` (the audio prefix once per mixture), otherwise through
+        ``forward``.  Not capturable in a HIP graph: the routing reads the batch's contents back to the host."""
+        if mouth is None or wav.ndim not in (2, 3) or wav.shape[0] < 2 or wav.dtype != torch.float32:
+            return self(wav, mouth)
+        N = int(wav.shape[0])
+        bits = wav.reshape(N, -1).contiguous().view(torch.int32)
+        same = (bits[1:] == bits[:-1]).all(dim=1).tolist()  # row i + 1 repeats row i
+        starts = [0] + [i + 1 for i, s in enumerate(same) if not s] + [N]
+        runs = {b - a for a, b in zip(starts[:-1], starts[1:])}
+        if len(runs) != 1 or min(runs) < 2:
+            return self(wav, mouth)
+        K = runs.pop()
+        L = bits.shape[1]
+        out = self.separate_speakers(wav.reshape(N, L)[::K].contiguous(), mouth.reshape(N // K, K, *mouth.shape[1:]))
+        return out.reshape(N, 1, L)
+
     def common_step(self, batch, batch_nb, is_train=True):
         """core.py:94-118."""
         if self.video_model is None and len(batch) == 4:  # extension: pre-computed lip embeddings in the mouth slot
