@@ -32,6 +32,8 @@
  *     The reference has no length limit (rnn_layers.py:136-162, attention.py:149-189; infer_any_video.py:86 feeds whole files): longer
  *     inputs go through the UNFUSED entry points below (rtfs_*_forward_train_f32 and friends: GEMM + scan + GEMM sweeps, batched-GEMM
  *     attention, per-layer video block), which take any length; rtfs-net_amd/{models,layers}.py route by length (FUSED_MAX_*).
+ *     Recordings past the fused limit are also served ON the fused path by the long-form entry points (rtfs_longform_*: overlapping
+ *     windows of a length the fused separator takes, run as a batch and cross-faded back together; AVNet.separate_long).
  * F must satisfy F/2 == 64 wherever a block / attention is involved (the reference's n_freqs: 64 ties
  * LayerNormalization4D's parameters to 64 compressed frequency bins, config/lrs2_RTFSNet_4_layer.yaml:68).
  */
@@ -403,6 +405,23 @@ int rtfs_pit_pairwise_sdr_f32(const float* ests, const float* targets, int B, in
 size_t rtfs_stoi_workspace_bytes(int B, int L, int fs);
 int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept_frames,
                   void* stream);
+
+/* Long recordings in overlapping windows on the fused separator (AVNet.separate_long; no reference counterpart: infer_any_video.py:63-86
+ * hands a whole track to one forward).  SPF = 640 samples per video frame (16 kHz, 25 fps).  A recording of L samples is cut into N
+ * windows of `window` samples every `hop` samples; window n covers samples [n hop, n hop + window) (zeros past L) and video frames
+ * [n hop / SPF, (n hop + window) / SPF) (an index past Tv - 1 reads frame Tv - 1).
+ * rtfs_longform_plan (host only, no device call): checks L >= 1, Tv >= 1, window % SPF == 0, hop % SPF == 0, 0 < hop <= window (-4
+ *   otherwise) and writes N = 1 if L <= window, else 1 + ceil((L - window) / hop).  N may be NULL.
+ * rtfs_longform_frame_f32 (one launch): wav (B,L), video (B,512,Tv) -> wav_win (B*N, window), video_win (B*N, 512, window / SPF), row b*N + n.
+ * rtfs_longform_overlap_add_f32 (one launch): y (B*N, n_src, window) -> out (B, n_src, L),
+ *   out[b,s,t] = sum_n w[t - n hop] y[b*N + n, s, t - n hop] / sum_n w[t - n hop] over the windows that contain t, in ascending n, with
+ *   w[i] = 1 if window == hop, else min(1, (i + 0.5) / V, (window - i - 0.5) / V), V = window - hop.  Gather form: every output element is
+ *   written exactly once, no atomics, no scratch; deterministic.
+ * Both take the caller's stream, allocate nothing and read nothing back; wav_win, video_win, y and out must be 16-byte aligned (-4). */
+int rtfs_longform_plan(int L, int Tv, int window, int hop, int* N);
+int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
+                            void* stream);
+int rtfs_longform_overlap_add_f32(const float* y, float* out, int B, int n_src, int L, int window, int hop, void* stream);
 
 /* Video front-end (the step before the path): FRCNNVideoModel.forward with backbone_type "resnet",
  * relu_type "prelu", eval mode (src/models/videomodels/frcnn_videomodel.py:61-72, resnet.py:23-118).

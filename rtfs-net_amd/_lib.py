@@ -129,6 +129,9 @@ SIGNATURES = {
     "rtfs_pit_pairwise_sdr_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "rtfs_stoi_workspace_bytes": (_z, [_i, _i, _i]),
     "rtfs_stoi_f32": (_i, [_p, _p, _i, _i, _i, _p, _z, _p, _p, _p]),
+    "rtfs_longform_plan": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "rtfs_longform_frame_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "rtfs_longform_overlap_add_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "rtfs_video_pack_floats": (_z, []),
     "rtfs_video_workspace_bytes": (_z, [_i, _i]),
     "rtfs_video_frontend_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),

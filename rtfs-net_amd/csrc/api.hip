@@ -1287,6 +1287,17 @@ int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, vo
     return launch_stoi(clean, est, B, L, fs, ws, ws_bytes, d, kept_frames, (hipStream_t)stream);
 }
 
+int rtfs_longform_plan(int L, int Tv, int window, int hop, int* N) { return longform_plan(L, Tv, window, hop, N); }
+int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
+                            void* stream) {
+    if (!wav || !video || !wav_win || !video_win) return RTFS_ERR_ARG;
+    return launch_longform_frame(wav, video, wav_win, video_win, B, L, Tv, window, hop, (hipStream_t)stream);
+}
+int rtfs_longform_overlap_add_f32(const float* y, float* out, int B, int n_src, int L, int window, int hop, void* stream) {
+    if (!y || !out) return RTFS_ERR_ARG;
+    return launch_longform_overlap_add(y, out, B, n_src, L, window, hop, (hipStream_t)stream);
+}
+
 size_t rtfs_video_pack_floats(void) { return video_pack_floats(); }
 size_t rtfs_video_workspace_bytes(int B, int T) { return video_workspace_bytes(B, T); }
 int rtfs_video_frontend_f32(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, void* stream) {

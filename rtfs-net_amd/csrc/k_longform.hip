@@ -1,0 +1,167 @@
+// Long recordings in overlapping windows (AVNet.separate_long; DESIGN.md "Long recordings"): the two streaming passes around the fused
+// separator.  A recording of L samples is cut into N windows of `window` samples every `hop` samples (both multiples of SPF = 640, one
+// video frame at 25 fps and 16 kHz), the B * N windows go through the ordinary fused forward as a batch, and the results are cross-faded
+// back into (B, n_src, L).  tests/longform_oracle.py restates plan, framing, weights and overlap-add in float64.
+//   longform_plan          host only: argument checks and N = 1 (L <= window), else 1 + ceil((L - window) / hop)
+//   longform_frame_kernel  ONE launch for both gathers: window n of recording b = samples [n hop, n hop + window) with zeros past L, and
+//                          video frames [n hop / SPF, (n hop + window) / SPF) with an index past Tv - 1 reading frame Tv - 1
+//   longform_ola_kernel    gather form: an output sample sums its <= ceil(window / hop) windows in ascending n, each times
+//                          w[i] = min(1, (i + 0.5) / V, (window - i - 0.5) / V), V = window - hop (w = 1 when V = 0), and divides by the sum
+//                          of those weights, all recomputed in registers from the index: no atomics, no accumulator to clear, no weight
+//                          buffer; every output element has exactly one writer, so the result is deterministic
+// Stores follow the rules measured in round 3: a lane writes 16 bytes, a wave 1024 contiguous bytes = whole 128-byte lines.
+// A window row is window * 4 bytes and a video row group 512 * (window / SPF) * 4 bytes, both multiples of 128; the (B * N, 512, window / SPF)
+// gather and the (B, n_src, L) output are addressed as flat arrays, so the 200-byte video rows and an L that is not a multiple of 4
+// never start a store inside a line: the last quad of the whole output is the only partial one.  Loads are 16 bytes where the source is
+// aligned (always when L % 4 == 0 or B * n_src == 1) and coalesced dwords otherwise.
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int SPF = 640;    // samples per video frame: 16 kHz / 25 fps
+constexpr int VCH = 512;    // lip-embedding channels
+
+__global__ __launch_bounds__(256) void longform_frame_kernel(const float* __restrict__ wav, const float* __restrict__ video,
+                                                             float* __restrict__ wav_win, float* __restrict__ video_win, int N, int L, int Tv,
+                                                             int window, int hop, int qa_pad) {
+    const int row = blockIdx.x, b = row / N, n = row - b * N;
+    const int Wv = window / SPF;
+    int q = blockIdx.y * 256 + threadIdx.x;
+    if (q < qa_pad) {  // audio quads; the segment is padded to whole waves so no wave serves both gathers
+        if (q >= window / 4) return;
+        const int i = 4 * q;
+        const long long p = (long long)n * hop + i;  // position in the recording
+        const float* src = wav + (size_t)b * L;
+        f32x4 v;
+        if (p + 3 < L && (((uintptr_t)(src + p)) & 15) == 0) {
+            v = *(const f32x4*)(src + p);
+        } else {
+            v.x = p < L ? src[p] : 0.f;
+            v.y = p + 1 < L ? src[p + 1] : 0.f;
+            v.z = p + 2 < L ? src[p + 2] : 0.f;
+            v.w = p + 3 < L ? src[p + 3] : 0.f;
+        }
+        *(f32x4*)(wav_win + (size_t)row * window + i) = v;
+        return;
+    }
+    q -= qa_pad;
+    if (q >= VCH * Wv / 4) return;
+    const float* src = video + (size_t)b * VCH * Tv;
+    const int f0 = (int)((long long)n * hop / SPF);
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = 4 * q + k, c = j / Wv, f = j - c * Wv;
+        const long long fr = (long long)f0 + f;
+        v[k] = src[(size_t)c * Tv + (fr < Tv ? (int)fr : Tv - 1)];
+    }
+    *(f32x4*)(video_win + (size_t)row * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
+}
+
+__device__ __forceinline__ float ola_weight(int i, int window, float V) {
+    return fminf(1.f, fminf(((float)i + 0.5f) / V, ((float)(window - i) - 0.5f) / V));
+}
+
+// one output element: windows n_lo .. n_hi contain sample t
+__device__ __forceinline__ void ola_range(int t, int N, int window, int hop, int* n_lo, int* n_hi) {
+    const int hi = t / hop;
+    *n_hi = hi < N - 1 ? hi : N - 1;
+    const int d = t - window + 1;  // n * hop >= d
+    *n_lo = d <= 0 ? 0 : (d + hop - 1) / hop;
+}
+
+__global__ __launch_bounds__(256) void longform_ola_kernel(const float* __restrict__ y, float* __restrict__ out, size_t total, int n_src, int N,
+                                                           int L, int window, int hop) {
+    const size_t g = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;  // flat index into (B, n_src, L)
+    if (g >= total) return;
+    const int V = window - hop;
+    const float Vf = (float)V;
+    const size_t r0 = g / (size_t)L;
+    const int t0 = (int)(g - r0 * (size_t)L);
+    float res[4];
+    if (t0 + 3 < L && (t0 & 3) == 0) {
+        // the quad lies in one row at a multiple of 4: its four samples share their windows (hop and window are multiples of 4) and
+        // sit at a multiple of 4 inside each, so every window contributes one aligned 16-byte load
+        const int b = (int)(r0 / n_src), s = (int)(r0 - (size_t)b * n_src);
+        int n_lo, n_hi;
+        ola_range(t0, N, window, hop, &n_lo, &n_hi);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f}, ws[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int n = n_lo; n <= n_hi; ++n) {
+            const int i = t0 - n * hop;
+            const f32x4 v = *(const f32x4*)(y + (((size_t)b * N + n) * n_src + s) * window + i);
+            const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float w = V == 0 ? 1.f : ola_weight(i + k, window, Vf);
+                acc[k] += w * vv[k];
+                ws[k] += w;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) res[k] = acc[k] / ws[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            res[k] = 0.f;
+            if (g + k >= total) continue;
+            size_t r = r0;
+            int t = t0 + k;
+            if (t >= L) {  // L >= 1 and k <= 3: the quad may run over several rows when L < 4
+                r += (size_t)(t / L);
+                t = t % L;
+            }
+            const int b = (int)(r / n_src), s = (int)(r - (size_t)b * n_src);
+            int n_lo, n_hi;
+            ola_range(t, N, window, hop, &n_lo, &n_hi);
+            float acc = 0.f, ws = 0.f;
+            for (int n = n_lo; n <= n_hi; ++n) {
+                const int i = t - n * hop;
+                const float w = V == 0 ? 1.f : ola_weight(i, window, Vf);
+                acc += w * y[(((size_t)b * N + n) * n_src + s) * window + i];
+                ws += w;
+            }
+            res[k] = acc / ws;
+        }
+    }
+    if (g + 3 < total) {
+        *(f32x4*)(out + g) = f32x4{res[0], res[1], res[2], res[3]};
+    } else {  // the tail of the whole output: the only partial line
+        for (int k = 0; k < 4 && g + k < total; ++k) out[g + k] = res[k];
+    }
+}
+
+}  // namespace
+
+int longform_plan(int L, int Tv, int window, int hop, int* N) {
+    if (L < 1 || Tv < 1 || window < SPF || hop < SPF || hop > window || window % SPF || hop % SPF) return RTFS_ERR_ARG;
+    const long long n = L <= window ? 1 : 1 + ((long long)L - window + hop - 1) / hop;
+    if (n > 0x7fffffffLL) return RTFS_ERR_ARG;
+    if (N) *N = (int)n;
+    return RTFS_OK;
+}
+
+int launch_longform_frame(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
+                          hipStream_t st) {
+    int N = 0;
+    const int e = longform_plan(L, Tv, window, hop, &N);
+    if (e != RTFS_OK) return e;
+    if (B < 1 || (long long)B * N > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)wav_win) | ((uintptr_t)video_win)) & 15) return RTFS_ERR_ARG;
+    const int qa_pad = cdiv(window / 4, 64) * 64, qv = VCH * (window / SPF) / 4;
+    hipLaunchKernelGGL(longform_frame_kernel, dim3(B * N, cdiv(qa_pad + qv, 256)), dim3(256), 0, st, wav, video, wav_win, video_win, N, L, Tv,
+                       window, hop, qa_pad);
+    return rtfs_launch_status();
+}
+
+int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, int L, int window, int hop, hipStream_t st) {
+    int N = 0;
+    const int e = longform_plan(L, 1, window, hop, &N);
+    if (e != RTFS_OK) return e;
+    if (B < 1 || n_src < 1 || (long long)B * N > 0x7fffffffLL || (long long)B * n_src > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)y) | ((uintptr_t)out)) & 15) return RTFS_ERR_ARG;
+    const size_t total = (size_t)B * n_src * L, blocks = (total + 1023) / 1024;
+    if (blocks > 0x7fffffffULL) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(longform_ola_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, out, total, n_src, N, L, window, hop);
+    return rtfs_launch_status();
+}

@@ -326,6 +326,12 @@ int launch_pit_pairwise(const float* est, const float* tgt, int B, int n, int L,
 size_t stoi_workspace_bytes(int B, int L, int fs);
 int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept, hipStream_t st);
 
+// long recordings in overlapping windows (k_longform.hip): window plan (host), framing of audio + video in one launch, cross-faded overlap-add
+int longform_plan(int L, int Tv, int window, int hop, int* N);
+int launch_longform_frame(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
+                          hipStream_t st);
+int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, int L, int window, int hop, hipStream_t st);
+
 // video front-end (k_video.hip): FRCNNVideoModel, ResNet-18 trunk, PReLU, eval
 size_t video_pack_floats();
 size_t video_workspace_bytes(int B, int T);

@@ -544,6 +544,34 @@ def _lookup(table, identifier):
     raise ValueError("Could not interpret normalization identifier: " + str(identifier))
 
 
+# ----------------------------------------------------------------------------- long recordings: the two gathers restated in torch
+LONGFORM_SPF = 640  # samples per video frame: 16 kHz audio, 25 fps video
+
+
+def _longform_frame_torch(wav, video, N, window, hop):
+    """rtfs_longform_frame_f32 in torch ops (AVNet.separate_long off the fused path): (B,L), (B,512,Tv) -> (B*N,window), (B*N,512,window/640)."""
+    B, L = wav.shape
+    Tv, Wv = video.shape[-1], window // LONGFORM_SPF
+    xw = F.pad(wav, (0, (N - 1) * hop + window - L)).unfold(-1, window, hop)[:, :N]
+    idx = (torch.arange(N, device=video.device)[:, None] * (hop // LONGFORM_SPF) + torch.arange(Wv, device=video.device)).clamp_(max=Tv - 1)
+    vw = video[:, :, idx].permute(0, 2, 1, 3)  # (B, N, 512, Wv)
+    return xw.reshape(B * N, window).contiguous(), vw.reshape(B * N, video.shape[1], Wv).contiguous()
+
+
+def _longform_overlap_add_torch(y, B, N, L, window, hop):
+    """rtfs_longform_overlap_add_f32 in torch ops: (B*N,n_src,window) -> (B,n_src,L), windows summed in ascending n."""
+    V = window - hop
+    i = torch.arange(window, device=y.device, dtype=y.dtype)
+    w = torch.ones_like(i) if V == 0 else torch.minimum(torch.ones_like(i), torch.minimum((i + 0.5) / V, (window - i - 0.5) / V))
+    y = y.view(B, N, -1, window)
+    num = y.new_zeros(B, y.shape[2], (N - 1) * hop + window)
+    den = y.new_zeros((N - 1) * hop + window)
+    for n in range(N):
+        num[:, :, n * hop:n * hop + window] += w * y[:, n]
+        den[n * hop:n * hop + window] += w
+    return (num[:, :, :L] / den[:L]).contiguous()
+
+
 # ----------------------------------------------------------------------------- top-level model
 class BaseAVModel(nn.Module):
     """reference TDAVNet/base_av_model.py."""
@@ -729,6 +757,77 @@ class AVNet(BaseAVModel):
                 audio = blk(audio, a_res)
             sep = self.mask_generator(audio, emb)
             return self.decoder(sep, (B * K, L)).view(B, K, L)
+
+    def separate_long(self, audio_mixture, mouth_embedding, window=32000, hop=None, max_batch=32):
+        """A recording of any length in overlapping windows on the fused separator (inference only; DESIGN.md "Long recordings").
+        audio_mixture (L)|(B,L)|(B,1,L), mouth_embedding (B,512,Tv) at 25 fps (LONGFORM_SPF = 640 samples per frame) -> (B,n_src,L).
+
+        The recording is cut into N = 1 (L <= window) or 1 + ceil((L - window) / hop) windows; window n covers samples [n hop, n hop +
+        window) (zeros past L) and video frames [n hop / 640, (n hop + window) / 640) (an index past Tv - 1 reads frame Tv - 1), so every
+        window keeps the 2 s : 50 frames ratio of training.  The B * N windows go through ``forward`` in chunks of at most ``max_batch``
+        windows, without per-window renormalisation, and are cross-faded with w[i] = min(1, (i + 0.5) / V, (window - i - 0.5) / V),
+        V = window - hop (w = 1 when hop == window): out[b,s,t] = sum_n w[t - n hop] y_n[b,s,t - n hop] / sum_n w[t - n hop] over the
+        windows that contain t.  L <= window is ``forward`` on the zero-padded mixture cut to L; hop == window is concatenation.
+
+        ValueError unless window % 640 == 0, hop % 640 == 0, 0 < hop <= window (hop defaults to window // 2) and the window fits the fused
+        path of the model's cell (layers.fused_max_block_sweep: 8.2 s with the SRU cell, 4 s with the LSTM cell).
+
+        Framing and overlap-add are one HIP launch each (rtfs_longform_frame_f32, rtfs_longform_overlap_add_f32) on the current stream; at
+        fixed shapes the whole call can be captured in a HIP graph, like ``forward``.  Peak memory on top of the input and the (B,n_src,L)
+        output: the framed windows in and out, B*N*window*(1 + n_src) floats, their video, B*N*512*(window/640) floats, and ONE chunk's
+        ``forward`` (its workspace, rtfs_separator_workspace_bytes_ex(min(max_batch, B*N), window, window/640), and its
+        (chunk,n_src,window) result, both handed back to the allocator and reused by the next chunk): nothing grows with L faster than
+        linearly, and the separator's share does not grow with L at all.
+
+        With ``fused = False``, or on CPU tensors, the same plan runs with ``forward_modular`` per chunk and the two gathers restated in
+        torch."""
+        if audio_mixture.ndim not in (1, 2, 3) or (audio_mixture.ndim == 3 and audio_mixture.shape[1] != 1):
+            raise ValueError(f"separate_long: audio_mixture must be (L), (B,L) or (B,1,L); got {tuple(audio_mixture.shape)}")
+        wav = STFTEncoder.unsqueeze_to_2D(audio_mixture)
+        B, L = int(wav.shape[0]), int(wav.shape[1])
+        if mouth_embedding is None or mouth_embedding.ndim != 3 or mouth_embedding.shape[0] != B or mouth_embedding.shape[1] != 512:
+            raise ValueError(f"separate_long: {B} recording(s) but mouth_embedding "
+                             f"{None if mouth_embedding is None else tuple(mouth_embedding.shape)} (expected (B,512,Tv))")
+        Tv = int(mouth_embedding.shape[-1])
+        window = int(window)
+        hop = window // 2 if hop is None else int(hop)
+        max_batch = int(max_batch)
+        if max_batch < 1:
+            raise ValueError(f"separate_long: max_batch = {max_batch}")
+        lib = _lib.load()
+        n_win = ctypes.c_int(0)
+        if lib.rtfs_longform_plan(L, Tv, window, hop, ctypes.byref(n_win)) != 0:
+            raise ValueError(f"separate_long: window = {window}, hop = {hop} must be multiples of {LONGFORM_SPF} with 0 < hop <= window "
+                             f"(L = {L}, Tv = {Tv} at least 1)")
+        rnn_kind = self.refinement_module.audio_net.get_block(0).rnn_kind
+        if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
+            raise ValueError(f"separate_long: a window of {window} samples does not fit the fused separator of this model's cell "
+                             f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
+        if self.training:
+            raise RuntimeError("AVNet.separate_long is inference only: call .eval()")
+        N, Wv = int(n_win.value), window // LONGFORM_SPF
+        on_hip = self.fused and wav.is_cuda and mouth_embedding.is_cuda
+        with torch.no_grad():
+            if on_hip:
+                _lib.need_gpu(wav, mouth_embedding)
+                wav, video = wav.contiguous(), mouth_embedding.contiguous()
+                xw = _lib.empty(B * N, window, device=wav.device, dtype=torch.float32)
+                vw = _lib.empty(B * N, 512, Wv, device=wav.device, dtype=torch.float32)
+                _lib.check(lib.rtfs_longform_frame_f32(_lib.ptr(wav), _lib.ptr(video), _lib.ptr(xw), _lib.ptr(vw), B, L, Tv, window, hop,
+                                                       _lib.stream_of(wav)), "rtfs_longform_frame_f32")
+            else:
+                xw, vw = _longform_frame_torch(wav, mouth_embedding, N, window, hop)
+            y = _lib.empty(B * N, self.n_src, window, device=wav.device, dtype=torch.float32)
+            run = self.forward if on_hip else self.forward_modular
+            for c0 in range(0, B * N, max_batch):
+                c1 = min(B * N, c0 + max_batch)
+                y[c0:c1].copy_(run(xw[c0:c1], vw[c0:c1]))
+            if not on_hip:
+                return _longform_overlap_add_torch(y, B, N, L, window, hop)
+            out = _lib.empty(B, self.n_src, L, device=wav.device, dtype=torch.float32)
+            _lib.check(lib.rtfs_longform_overlap_add_f32(_lib.ptr(y), _lib.ptr(out), B, self.n_src, L, window, hop, _lib.stream_of(wav)),
+                       "rtfs_longform_overlap_add_f32")
+            return out
 
     def _side_stream(self, device):
         streams = self.__dict__.setdefault("_side_streams", {})

@@ -49,6 +49,18 @@ class System(nn.Module):
             emb = self.video_model(mouths.reshape(B * K, *mouths.shape[2:]).type_as(wav))
         return self.audio_model.separate_speakers(wav, emb.reshape(B, K, *emb.shape[1:]))
 
+    def separate_long(self, wav, mouth, **kw):
+        """A recording of any length in overlapping windows on the fused separator (inference): wav (L)|(B,L)|(B,1,L), mouth
+        (B,1,Tv,88,88) at 25 fps -> (B,n_src,L).  The video front-end runs ONCE on the whole mouth track (no_grad, as in ``forward``), so
+        its temporal context stays continuous across window boundaries; the embedding and ``**kw`` (window, hop, max_batch) go to
+        ``AVNet.separate_long``.  Without a video model the mouth slot holds lip embeddings (B,512,Tv).  This is what the reference's
+        ``infer_any_video.py:63-86`` call (whole track, one ``forward``) maps onto for recordings past the fused length."""
+        if self.video_model is None:
+            return self.audio_model.separate_long(wav, mouth, **kw)
+        with torch.no_grad():
+            emb = self.video_model(mouth.type_as(wav))
+        return self.audio_model.separate_long(wav, emb, **kw)
+
     def forward_grouped(self, wav, mouth=None):
         """``forward`` for a batch that may list each mixture once per target speaker, as the reference's test batches do (test.py:128-140,
         avspeech_dataset.py:81-84: n_src 1, no shuffling, the entries of one mixture side by side).  wav (N,L) or (N,1,L) -> (N,1,L) in
