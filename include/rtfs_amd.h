@@ -431,6 +431,38 @@ size_t rtfs_video_pack_floats(void);
 size_t rtfs_video_workspace_bytes(int B, int T);
 int rtfs_video_frontend_f32(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, void* stream);
 
+/* Optimizer step on the device (rtfs-net_amd/optimizers.py AdamW; the reference builds torch.optim.AdamW through
+ * src/system/optimizers.py:58-108 and Lightning clips at gradient_clip_val 5.0, train.py:142): gather of the per-tensor gradients into
+ * one flat buffer, global-norm clip and AdamW in a number of launches that does not depend on the number of tensors.
+ * Layout: tensor t owns floats [flat_off[t], flat_off[t] + numel[t]) of every flat buffer (flat_g, exp_avg, exp_avg_sq), flat_off
+ * rounded up to 4 floats, and is cut into chunks of RTFS_OPTIM_CHUNK floats, one workgroup and one float64 partial each.
+ * rtfs_optim_plan (host only): numel (n_tensors, host) -> flat_floats, n_chunks and, when `table` is not NULL, the
+ *   2 * n_tensors + 2 * n_chunks int64 words [flat_off | numel | chunk_tensor | chunk_off] the kernels read FROM DEVICE MEMORY (the caller
+ *   uploads them once).  n_tensors > RTFS_OPTIM_MAX_TENSORS -> -4 (pointer tables travel in the kernel arguments).
+ * rtfs_optim_gather_f32 (one launch): grads = HOST array of n_tensors device pointers, copied into the launch (they change every
+ *   step).  A NULL gradient is skipped (its slice of flat_g is left as it is and its partials are 0) or, with zero_missing, written as
+ *   zeros.  partials (n_chunks float64, may be NULL) = sum of squares per chunk.
+ * rtfs_optim_sumsq_f32 (one launch): the partials of flat_g alone, over every tensor (after a collective on flat_g).
+ * rtfs_optim_adamw_f32 (one launch): total = sqrt(sum partials) * grad_scale -> *total_norm (may be NULL);
+ *   coef = max_norm > 0 ? min(1, max_norm / (total + 1e-6)) : 1; per element of every tensor whose hyper_index is not 255:
+ *   g = (grad_scale * coef) * flat_g; p *= decay; m += omb1 * (g - m); v = b2 * v + omb2 * g * g;
+ *   p -= step_size * m / (sqrt(v) / bc2_sqrt + eps).  params / hyper_index (n_tensors) and hyper (n_hyper <= RTFS_OPTIM_MAX_HYPER sets of
+ *   8 floats: decay = 1 - lr * wd, omb1 = 1 - beta1, b2, omb2 = 1 - beta2, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t),
+ *   eps, 0) are HOST arrays copied into the launch.  Parameters are written where they live; 16-byte accesses where a pointer allows.
+ * No atomics: the same inputs give the same bits.  Caller's stream, no allocation, no synchronisation; flat buffers 16-byte aligned,
+ * partials and table 8-byte aligned (-4 otherwise, before any launch).  The bias corrections are host values, so a captured graph would
+ * replay one step count: not graph-replayable. */
+#define RTFS_OPTIM_CHUNK 4096
+#define RTFS_OPTIM_MAX_TENSORS 320
+#define RTFS_OPTIM_MAX_HYPER 16
+int rtfs_optim_plan(const long long* numel, int n_tensors, long long* table, long long* flat_floats, int* n_chunks);
+int rtfs_optim_gather_f32(const float* const* grads, const long long* table, int n_tensors, int n_chunks, float* flat_g, double* partials,
+                          int zero_missing, void* stream);
+int rtfs_optim_sumsq_f32(const long long* table, int n_tensors, int n_chunks, const float* flat_g, double* partials, void* stream);
+int rtfs_optim_adamw_f32(float* const* params, const unsigned char* hyper_index, const float* hyper, int n_hyper, const long long* table,
+                         int n_tensors, int n_chunks, const float* flat_g, float* exp_avg, float* exp_avg_sq, const double* partials,
+                         float max_norm, float grad_scale, float* total_norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,10 @@ SIGNATURES = {
     "rtfs_video_pack_floats": (_z, []),
     "rtfs_video_workspace_bytes": (_z, [_i, _i]),
     "rtfs_video_frontend_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),
+    "rtfs_optim_plan": (_i, [_p, _i, _p, _p, _p]),
+    "rtfs_optim_gather_f32": (_i, [_p, _p, _i, _i, _p, _p, _i, _p]),
+    "rtfs_optim_sumsq_f32": (_i, [_p, _i, _i, _p, _p, _p]),
+    "rtfs_optim_adamw_f32": (_i, [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _p, C.c_float, C.c_float, _p, _p]),
 }
 
 _lib = None

@@ -160,7 +160,14 @@ class System(nn.Module):
 
     def optimization_step(self, batch, batch_nb=0, gradient_clip_val=5.0):
         """zero_grad -> training_step -> backward -> gradient all-reduce -> clip (train.py:142 gradient_clip_val 5.0) -> optimizer step.
-        The first step of a multi-rank job broadcasts rank 0's parameters and buffers first (DDP's construction-time broadcast)."""
+        The first step of a multi-rank job broadcasts rank 0's parameters and buffers first (DDP's construction-time broadcast).
+
+        With the package's own ``optimizers.AdamW`` (``make_optimizer(..., optimizer="adamw")``) everything after backward runs on the
+        device in two launches: one gathers the gradients into the optimizer's flat buffer, a multi-rank job all-reduces THAT buffer once
+        (no cat, no per-parameter copies, the 1 / world folded into the update), one clips and updates.  The total gradient norm stays on
+        the device in ``self.last_grad_norm`` (the optimizer's buffer: the next step overwrites it).  On this route ``p.grad`` is left as
+        backward wrote it - local, unscaled, unclipped - whereas the stock route below leaves the averaged, clipped gradients there; the
+        clip covers the optimizer's parameters.  Any other optimizer takes the stock route."""
         if self.optimizer is None:
             raise RuntimeError("System.optimization_step needs an optimizer")
         if not getattr(self, "_params_broadcast", False):
@@ -169,6 +176,15 @@ class System(nn.Module):
         self.optimizer.zero_grad(set_to_none=True)
         loss = self.training_step(batch, batch_nb)["loss"]
         loss.backward()
+        from .optimizers import AdamW
+        if isinstance(self.optimizer, AdamW):
+            import torch.distributed as dist
+            world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+            flat = self.optimizer.gather_grads(zero_missing=world > 1)
+            if world > 1:
+                dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+            self.last_grad_norm = self.optimizer.step(max_norm=gradient_clip_val, grad_scale=1.0 / world)
+            return loss.detach()
         self.allreduce_gradients()
         if gradient_clip_val:
             torch.nn.utils.clip_grad_norm_(self.trainable_parameters(), gradient_clip_val)

@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--optimizer", choices=["torch", "fused"], default="torch", help="fused: rtfs_net_amd.optimizers.AdamW (gather, one "
+                    "all-reduce on its flat buffer, clip + update in two launches)")
     a = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -37,7 +39,7 @@ def main():
     torch.manual_seed(0)  # identical initial weights on every rank
     model = R.AVNet(print_macs=False, **conf).cuda().train()
     loss = R.losses.PITLossWrapper(R.losses.PairwiseNegSDR("snr"), pit_from="pw_mtx")
-    opt = torch.optim.AdamW(model.parameters(), lr=a.lr, weight_decay=0.1)
+    opt = (R.optimizers.AdamW if a.optimizer == "fused" else torch.optim.AdamW)(model.parameters(), lr=a.lr, weight_decay=0.1)
     system = R.System(audio_model=model, loss_func={"train": loss, "val": loss}, optimizer=opt)
     if world > 1:
         system.convert_sync_batchnorm()  # train.py:145 sync_batchnorm=True
