@@ -463,6 +463,36 @@ int rtfs_optim_adamw_f32(float* const* params, const unsigned char* hyper_index,
                          int n_tensors, int n_chunks, const float* flat_g, float* exp_avg, float* exp_avg_sq, const double* partials,
                          float max_norm, float grad_scale, float* total_norm, void* stream);
 
+/* Preparing raw recordings (rtfs-net_amd/datas.py; csrc/k_prep.hip): what the reference does on the host in front of the model inputs.
+ * All entries take the caller's stream, allocate nothing, read nothing back and use no atomics (deterministic; graph-capturable at fixed
+ * shapes); bad arguments return the error codes above before anything is launched.
+ * rtfs_lips_prepare_u8 (src/datas/transform.py:151-167 collapsed): roi uint8 (N,Tv,H,W) on the device, H, W >= 88 -> out float32
+ *   (N,1,Tv,88,88), 16-byte aligned: out[n,0,t,y,x] = f(roi[n,t,dy+y, dx + (flip ? 87-x : x)]),
+ *   f(v) = (float)(((double(v) - 0.0) / 255.0 - mean) / std).  table = HOST array (N,3) of dy, dx, flip per track, checked here (an
+ *   offset that leaves the ROI, a flip other than 0 / 1: -4) and copied into the launch: one launch per
+ *   RTFS_LIPS_MAX_TRACKS_PER_LAUNCH tracks.
+ * rtfs_wav_normalize_f32 (avspeech_dataset.py:18-22, 145-148): mix (B,L), src (B,K,L) or NULL with K = 0 -> the same shapes;
+ *   mix_out = (mix - mean(mix)) / (s + eps), src_out[b,k] = (src[b,k] - mean(src[b,k])) / (s[b] + eps) with s[b] the unbiased standard
+ *   deviation of mixture row b, or std_in[b] (B floats on the device) when std_in is not NULL.  Means and deviations are accumulated in
+ *   float64; L = 1 gives NaN as torch.std does.  Two launches; ws >= rtfs_wav_normalize_workspace_bytes, 8-byte aligned.
+ * rtfs_resample_plan (host only): o, n = orig / gcd, new / gcd (either > RTFS_RESAMPLE_MAX_RATIO: -4), base = min(o, n) * 0.99,
+ *   width = ceil(6 o / base), taps = 2 width + o and, when bank is not NULL, the n * taps float32 kernel bank of torchaudio's Resample
+ *   defaults computed in float64: t = clip((-p / n + (k - width) / o) * base, -6, 6), bank[p,k] = sinc(pi t) cos^2(pi t / 12) base / o.
+ * rtfs_resample_out_len (host only): ceil(n L / o), or -1 for a ratio the plan refuses.
+ * rtfs_resample_f32 (one launch): x (B,L), bank (n,taps) on the device -> y (B, ceil(n L / o)),
+ *   y[j n + p] = sum_k bank[p,k] xpad[j o + k], xpad = x with width zeros in front and width + o behind (predicates, no padded copy).
+ *   Taps outside [floor(o p / n), floor(o p / n) + 2 width] are exact zeros of the bank (the plan verifies it) and are skipped. */
+#define RTFS_LIPS_MAX_TRACKS_PER_LAUNCH 512
+#define RTFS_RESAMPLE_MAX_RATIO 640
+int rtfs_lips_prepare_u8(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double std,
+                         void* stream);
+size_t rtfs_wav_normalize_workspace_bytes(int B, int K, int L);
+int rtfs_wav_normalize_f32(const float* mix, const float* src, const float* std_in, float* mix_out, float* src_out, int B, int K, int L,
+                           double eps, void* ws, size_t ws_bytes, void* stream);
+int rtfs_resample_plan(int orig_freq, int new_freq, int* o, int* n, int* width, int* taps, float* bank);
+long long rtfs_resample_out_len(int orig_freq, int new_freq, long long L);
+int rtfs_resample_f32(const float* x, const float* bank, float* y, int B, int L, int orig_freq, int new_freq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

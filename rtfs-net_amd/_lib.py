@@ -139,6 +139,12 @@ SIGNATURES = {
     "rtfs_optim_gather_f32": (_i, [_p, _p, _i, _i, _p, _p, _i, _p]),
     "rtfs_optim_sumsq_f32": (_i, [_p, _i, _i, _p, _p, _p]),
     "rtfs_optim_adamw_f32": (_i, [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _p, C.c_float, C.c_float, _p, _p]),
+    "rtfs_lips_prepare_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, C.c_double, _p]),
+    "rtfs_wav_normalize_workspace_bytes": (_z, [_i, _i, _i]),
+    "rtfs_wav_normalize_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, C.c_double, _p, _z, _p]),
+    "rtfs_resample_plan": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _p]),
+    "rtfs_resample_out_len": (C.c_longlong, [_i, _i, C.c_longlong]),
+    "rtfs_resample_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

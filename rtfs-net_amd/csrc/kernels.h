@@ -332,6 +332,16 @@ int launch_longform_frame(const float* wav, const float* video, float* wav_win, 
                           hipStream_t st);
 int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, int L, int window, int hop, hipStream_t st);
 
+// preparing raw recordings (k_prep.hip): uint8 mouth ROIs -> normalised lips, waveform normalisation, polyphase resampling
+int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,
+                        hipStream_t st);
+size_t wav_normalize_workspace_bytes(int B, int K, int L);
+int launch_wav_normalize(const float* mix, const float* src, const float* std_in, float* mix_out, float* src_out, int B, int K, int L,
+                         double eps, void* ws, size_t ws_bytes, hipStream_t st);
+int resample_plan(int orig, int neu, int* o, int* n, int* width, int* taps, float* bank);
+long long resample_out_len(int orig, int neu, long long L);
+int launch_resample(const float* x, const float* bank, float* y, int B, int L, int orig, int neu, hipStream_t st);
+
 // video front-end (k_video.hip): FRCNNVideoModel, ResNet-18 trunk, PReLU, eval
 size_t video_pack_floats();
 size_t video_workspace_bytes(int B, int T);

@@ -1,0 +1,241 @@
+"""Preparing raw recordings on the device: what the reference does on the host in front of the model inputs, with its names.
+
+* ``resample``                       ``torchaudio.transforms.Resample(fs, 16000)`` of ``infer_any_video.py:66-68`` (its default kernel bank)
+* ``normalize_tensor_wav`` / ``normalize_mixture``   ``src/datas/avspeech_dataset.py:18-22`` and its joint use at ``:145-148, 206-209``
+* ``Compose``, ``Normalize``, ``CenterCrop``, ``RandomCrop``, ``HorizontalFlip``, ``get_preprocessing_pipelines``
+                                     ``src/datas/transform.py``: on ``uint8`` device ROIs a pipeline is ONE ``rtfs_lips_prepare_u8`` launch
+
+All arithmetic runs in ``librtfs_amd.so`` (``csrc/k_prep.hip``); there is no host fallback.  ``tests/prep_oracle.py`` restates the three
+in float64 numpy."""
+from __future__ import annotations
+
+import ctypes as C
+import random
+
+import torch
+
+from . import _lib
+
+__all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
+           "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank"]
+
+CROP = 88
+MAX_RATIO = 640
+
+
+# ---------------------------------------------------------------- resampling
+def resample_plan(orig_freq, new_freq):
+    """-> (o, n, width, taps) of ``rtfs_resample_plan``; ValueError for a reduced ratio past 640."""
+    o, n, w, t = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    if int(orig_freq) < 1 or int(new_freq) < 1 or \
+            _lib.load().rtfs_resample_plan(int(orig_freq), int(new_freq), C.byref(o), C.byref(n), C.byref(w), C.byref(t), None) != 0:
+        raise ValueError(f"resample {orig_freq} -> {new_freq}: positive rates with a reduced ratio of at most {MAX_RATIO}:{MAX_RATIO} only")
+    return o.value, n.value, w.value, t.value
+
+
+def _host_bank(orig_freq, new_freq):
+    o, n, width, taps = resample_plan(orig_freq, new_freq)
+    bank = _lib.empty(n, taps, device="cpu")
+    _lib.check(_lib.load().rtfs_resample_plan(int(orig_freq), int(new_freq), None, None, None, None, C.c_void_p(bank.data_ptr())),
+               "rtfs_resample_plan")
+    return bank
+
+
+_BANKS = {}
+
+
+def resample_bank(orig_freq, new_freq, device="cpu"):
+    """The (n, taps) float32 kernel bank of torchaudio's Resample defaults, built on the host in float64 once per (ratio, device)."""
+    o, n, _, _ = resample_plan(orig_freq, new_freq)
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (o, n, str(device))
+    if key not in _BANKS:
+        _BANKS[key] = _host_bank(o, n).to(device)
+    return _BANKS[key]
+
+
+def resample(wav, orig_freq, new_freq=16000):
+    """wav (L) | (B,L) float32 on the device -> (..., ceil(n L / o)).  Equal rates return the input tensor itself, as torchaudio does."""
+    if int(orig_freq) == int(new_freq):
+        return wav
+    o, n, _, _ = resample_plan(orig_freq, new_freq)
+    _lib.need_gpu(wav)
+    if wav.ndim not in (1, 2) or wav.shape[-1] < 1:
+        raise ValueError(f"resample: wav must be (L) or (B,L) with L >= 1; got {tuple(wav.shape)}")
+    x = wav.reshape(-1, wav.shape[-1]).contiguous()
+    B, L = int(x.shape[0]), int(x.shape[1])
+    bank = resample_bank(o, n, x.device)
+    Lout = int(_lib.load().rtfs_resample_out_len(o, n, L))
+    y = _lib.empty(B, Lout, device=x.device)
+    _lib.check(_lib.load().rtfs_resample_f32(_lib.ptr(x), _lib.ptr(bank), _lib.ptr(y), B, L, o, n, _lib.stream_of(x)), "rtfs_resample_f32")
+    return y[0] if wav.ndim == 1 else y
+
+
+# ---------------------------------------------------------------- waveform normalisation
+def _normalize(mix, src, std, eps):
+    lib = _lib.load()
+    B, L = int(mix.shape[0]), int(mix.shape[1])
+    K = 0 if src is None else int(src.shape[1])
+    mo = _lib.empty(B, L, device=mix.device)
+    so = None if src is None else _lib.empty(B, K, L, device=mix.device)
+    nbytes = lib.rtfs_wav_normalize_workspace_bytes(B, K, L)
+    ws = _lib.workspace(nbytes, mix.device)
+    _lib.check(lib.rtfs_wav_normalize_f32(_lib.ptr(mix), _lib.ptr(src), _lib.ptr(std), _lib.ptr(mo), _lib.ptr(so), B, K, L, float(eps),
+                                          _lib.ptr(ws), nbytes, _lib.stream_of(mix)), "rtfs_wav_normalize_f32")
+    return mo, so
+
+
+def normalize_mixture(mixture, sources=None, eps=1e-8):
+    """The dataset's joint form: mixture (L) | (B,L), sources (K,L) | (B,K,L) or None.  Every row gets zero mean and is divided by the
+    MIXTURE's unbiased standard deviation + eps.  Returns ``mixture`` alone, or ``(mixture, sources)``."""
+    _lib.need_gpu(mixture, sources)
+    single = mixture.ndim == 1
+    if mixture.ndim not in (1, 2) or mixture.shape[-1] < 1:
+        raise ValueError(f"normalize_mixture: mixture must be (L) or (B,L); got {tuple(mixture.shape)}")
+    mix = mixture.reshape(-1, mixture.shape[-1]).contiguous()
+    src = None
+    if sources is not None:
+        if sources.ndim != mixture.ndim + 1 or sources.shape[-1] != mix.shape[1] or (not single and sources.shape[0] != mix.shape[0]):
+            raise ValueError(f"normalize_mixture: sources {tuple(sources.shape)} do not go with mixture {tuple(mixture.shape)}")
+        src = sources.reshape(mix.shape[0], -1, mix.shape[1]).contiguous()
+    mo, so = _normalize(mix, src, None, eps)
+    mo = mo[0] if single else mo
+    if sources is None:
+        return mo
+    return mo, so.reshape(sources.shape)
+
+
+def normalize_tensor_wav(wav_tensor, eps=1e-8, std=None):
+    """avspeech_dataset.py:18-22: (wav - mean) / (std + eps) over the last axis, ``std`` the row's own unbiased deviation unless one that
+    broadcasts against ``wav_tensor.std(-1, keepdim=True)`` is given."""
+    _lib.need_gpu(wav_tensor)
+    if wav_tensor.ndim < 1 or wav_tensor.shape[-1] < 1:
+        raise ValueError(f"normalize_tensor_wav: got shape {tuple(wav_tensor.shape)}")
+    L = wav_tensor.shape[-1]
+    rows = wav_tensor.reshape(-1, L).contiguous()
+    s = None
+    if std is not None:
+        s = torch.as_tensor(std, dtype=torch.float32, device=rows.device)
+        s = s.expand(*wav_tensor.shape[:-1], 1).reshape(-1).contiguous()
+    out, _ = _normalize(rows, None, s, eps)
+    return out.reshape(wav_tensor.shape)
+
+
+# ---------------------------------------------------------------- mouth-ROI transforms (src/datas/transform.py)
+class Normalize:
+    """Normalize(mean, std): (frames - mean) / std."""
+
+    def __init__(self, mean, std):
+        self.mean, self.std = mean, std
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(mean={self.mean}, std={self.std})"
+
+
+class CenterCrop:
+    def __init__(self, size):
+        self.size = size
+
+    def offsets(self, H, W, rng=None):
+        th, tw = self.size
+        return int(round((H - th)) / 2.0), int(round((W - tw)) / 2.0)  # the reference's rounding: an odd difference truncates
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(size={self.size})"
+
+
+class RandomCrop:
+    def __init__(self, size):
+        self.size = size
+
+    def offsets(self, H, W, rng=None):
+        r = random if rng is None else rng
+        th, tw = self.size
+        dx = r.randint(0, W - tw)  # the reference draws the width offset first
+        dy = r.randint(0, H - th)
+        return dy, dx
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(size={self.size})"
+
+
+class HorizontalFlip:
+    def __init__(self, flip_ratio):
+        self.flip_ratio = flip_ratio
+
+    def draw(self, rng=None):
+        return 1 if (random if rng is None else rng).random() < self.flip_ratio else 0
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}(flip_ratio={self.flip_ratio})"
+
+
+class Compose:
+    """Compose(preprocess): the reference's two chains, [Normalize(0, 255), crop, (HorizontalFlip,) Normalize(mean, std)] with an 88 x 88
+    crop, collapse into one offset table and two constants and run as ONE ``rtfs_lips_prepare_u8`` launch; any other chain raises."""
+
+    def __init__(self, preprocess):
+        self.preprocess = preprocess
+
+    def __repr__(self):
+        return self.__class__.__name__ + "(" + "".join(f"\n    {t}" for t in self.preprocess) + "\n)"
+
+    def collapse(self):
+        """-> (crop, flip or None, mean, std); ValueError for a chain the kernel does not express."""
+        ts = list(self.preprocess)
+        ok = len(ts) in (3, 4) and isinstance(ts[0], Normalize) and isinstance(ts[-1], Normalize) and \
+            isinstance(ts[1], (CenterCrop, RandomCrop)) and (len(ts) == 3 or isinstance(ts[2], HorizontalFlip))
+        if ok:
+            ok = float(ts[0].mean) == 0.0 and float(ts[0].std) == 255.0 and tuple(ts[1].size) == (CROP, CROP) and float(ts[-1].std) != 0.0
+        if not ok:
+            raise ValueError("Compose: the device path runs the reference's chains only: Normalize(0, 255), CenterCrop | RandomCrop((88, 88)), "
+                             f"[HorizontalFlip(r)], Normalize(mean, std); got {self!r}")
+        return ts[1], (ts[2] if len(ts) == 4 else None), float(ts[-1].mean), float(ts[-1].std)
+
+    def table(self, N, H, W, rng=None):
+        """The (dy, dx, flip) rows of N tracks, drawn per track in the reference's order: dx, dy, flip."""
+        crop, flip, _, _ = self.collapse()
+        rows = []
+        for _ in range(N):
+            dy, dx = crop.offsets(H, W, rng)
+            rows.append((dy, dx, flip.draw(rng) if flip is not None else 0))
+        return rows
+
+    def __call__(self, sample, rng=None, table=None):
+        """sample uint8 (Tv,H,W) | (N,Tv,H,W) on the device -> float32 (N,1,Tv,88,88).  ``rng``: a ``random.Random`` for the draws (default:
+        the ``random`` module); ``table``: explicit (dy, dx, flip) rows instead of the chain's own."""
+        _, _, mean, std = self.collapse()
+        if not isinstance(sample, torch.Tensor) or not sample.is_cuda:
+            raise RuntimeError("rtfs_net_amd.datas pipelines run on the MI355X only: got a host array (there is no CPU fallback)")
+        if sample.dtype != torch.uint8:
+            raise RuntimeError(f"rtfs_net_amd.datas pipelines take uint8 mouth ROIs; got {sample.dtype}")
+        if sample.ndim == 3:
+            sample = sample.unsqueeze(0)
+        if sample.ndim != 4 or sample.shape[-2] < CROP or sample.shape[-1] < CROP or sample.shape[0] < 1 or sample.shape[1] < 1:
+            raise ValueError(f"mouth ROIs must be (Tv,H,W) or (N,Tv,H,W) with H, W >= {CROP}; got {tuple(sample.shape)}")
+        roi = sample.contiguous()
+        N, Tv, H, W = (int(v) for v in roi.shape)
+        rows = self.table(N, H, W, rng) if table is None else [tuple(int(v) for v in r) for r in table]
+        if len(rows) != N or any(len(r) != 3 for r in rows):
+            raise ValueError(f"offset table must hold {N} rows of (dy, dx, flip)")
+        tab = (C.c_int * (3 * N))(*[v for r in rows for v in r])
+        out = _lib.empty(N, 1, Tv, CROP, CROP, device=roi.device)
+        code = _lib.load().rtfs_lips_prepare_u8(C.c_void_p(roi.data_ptr()), tab, _lib.ptr(out), N, Tv, H, W, mean, std, _lib.stream_of(roi))
+        if code == -4:
+            raise ValueError(f"rtfs_lips_prepare_u8: an offset of {rows} leaves the {H} x {W} ROI")
+        _lib.check(code, "rtfs_lips_prepare_u8")
+        return out
+
+
+def get_preprocessing_pipelines():
+    """transform.py:151-167: {"train", "val", "test"}, LRW statistics."""
+    crop_size = (CROP, CROP)
+    mean, std = 0.421, 0.165
+    preprocessing = {
+        "train": Compose([Normalize(0.0, 255.0), RandomCrop(crop_size), HorizontalFlip(0.5), Normalize(mean, std)]),
+        "val": Compose([Normalize(0.0, 255.0), CenterCrop(crop_size), Normalize(mean, std)]),
+    }
+    preprocessing["test"] = preprocessing["val"]
+    return preprocessing

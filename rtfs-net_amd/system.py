@@ -61,6 +61,45 @@ class System(nn.Module):
             emb = self.video_model(mouth.type_as(wav))
         return self.audio_model.separate_long(wav, emb, **kw)
 
+    def separate_recording(self, wav, sample_rate, mouth_rois, normalize_audio=False, **kw):
+        """A raw recording end to end on the device (inference), the whole of ``infer_any_video.py:63-86``: wav (L) | (B,L) at
+        ``sample_rate`` Hz, mouth_rois uint8 (Tv,H,W) | (B,Tv,H,W) at 25 fps -> (B, n_src, L at 16 kHz).  ``datas.resample`` to 16 kHz, the
+        ``"val"`` pipeline on the ROIs (one launch), the video model once on the whole track, then ``separate_long(**kw)``.  Without a
+        video model the mouth slot holds lip embeddings (B,512,Tv), as in ``separate_long``; a floating mouth slot is taken as prepared
+        lips.  ``normalize_audio`` (``datas.normalize_mixture`` on the resampled mixture) is off by default: the reference's script computes
+        the mixture's deviation and never applies it."""
+        from . import datas
+        wav = datas.resample(wav, sample_rate, 16000)
+        if normalize_audio:
+            wav = datas.normalize_mixture(wav)
+        if self.video_model is not None and mouth_rois.dtype == torch.uint8:
+            mouth_rois = datas.get_preprocessing_pipelines()["val"](mouth_rois)
+        return self.separate_long(wav, mouth_rois, **kw)
+
+    def prepare_batch(self, batch, train=True, normalize_audio=False, rng=None):
+        """A reference-shaped batch (inputs, targets, target_mouths, ...) whose mouth slot may hold uint8 ROIs, (B,Tv,H,W) or (B,K,Tv,H,W):
+        returns the batch with that slot replaced by float lips, (B,1,Tv,88,88) or (B,K,1,Tv,88,88) (the layout ``separate_speakers``
+        takes), prepared by the ``"train"`` (random crop and flip per track, drawn from ``rng`` or ``random``) or ``"val"`` pipeline in one
+        launch.  A slot that is not uint8 is handed back as the same object.  ``normalize_audio`` also replaces inputs and targets by
+        ``datas.normalize_mixture`` of the two (``avspeech_dataset.py:145-148``).  ``common_step`` and ``forward`` take the result as is."""
+        from . import datas
+        out = list(batch)
+        if len(out) >= 3 and isinstance(out[2], torch.Tensor) and out[2].dtype == torch.uint8:
+            m = out[2]
+            if m.ndim not in (4, 5):
+                raise ValueError(f"System.prepare_batch: uint8 mouth ROIs must be (B,Tv,H,W) or (B,K,Tv,H,W); got {tuple(m.shape)}")
+            lips = datas.get_preprocessing_pipelines()["train" if train else "val"](m.reshape(-1, *m.shape[-3:]), rng=rng)
+            out[2] = lips.reshape(*m.shape[:-3], 1, *lips.shape[2:])
+        if normalize_audio:
+            inputs, targets = out[0], out[1]
+            if targets is None:
+                out[0] = datas.normalize_mixture(inputs)
+            else:
+                t = targets.unsqueeze(-2) if targets.ndim == inputs.ndim else targets
+                out[0], t = datas.normalize_mixture(inputs, t)
+                out[1] = t.reshape(targets.shape)
+        return type(batch)(out) if isinstance(batch, (list, tuple)) else out
+
     def forward_grouped(self, wav, mouth=None):
         """``forward`` for a batch that may list each mixture once per target speaker, as the reference's test batches do (test.py:128-140,
         avspeech_dataset.py:81-84: n_src 1, no shuffling, the entries of one mixture side by side).  wav (N,L) or (N,1,L) -> (N,1,L) in
