@@ -443,7 +443,9 @@ int launch_ln_rows(const float* x, const float* gamma, const float* beta, float*
 int launch_mha_core(const float* qkv, const float* pmask, float* o, const float* dout, float* dqkv, int B, int T, int nh, int hd, bool bwd,
                     hipStream_t st) {
     if (T < 1 || T > 256 || hd < 1 || hd > 16 || nh < 1) return RTFS_ERR_SHAPE;
-    const size_t lds = ((size_t)4 * T * hd + 3 * T) * sizeof(float);
+    const size_t lds = ((size_t)4 * T * hd + 3 * T) * sizeof(float);  // up to 68,608 bytes (T 256, hd 16): above the default limit
+    int rc = set_lds(mha_core_kernel, lds);
+    if (rc) return rc;
     hipLaunchKernelGGL(mha_core_kernel, dim3(B * nh), dim3(256), lds, st, qkv, pmask, o, dout, dqkv, T, nh, hd, bwd ? 1 : 0);
     return rtfs_launch_status();
 }

@@ -154,6 +154,12 @@ def test_conv_norm_act_training_forward_backward(name):
 def test_mhsa2d_training_forward_backward(shape, seed):
     """MultiHeadSelfAttention2D used from a training step: forward + every gradient (12 Q/K/V ConvActNorms, softmax attention,
     concat projection, residual) against the autograd oracle."""
+    mhsa2d_training_case(shape, seed)
+
+
+def mhsa2d_training_case(shape, seed):
+    """Body of test_mhsa2d_training_forward_backward (also run by tests/test_hip_training_edges.py at T next to the multiples of 64
+    the kernels pad to)."""
     import rtfs_net_amd as R
     from oracle import grad_oracle as G
     p = {k: v.copy() for k, v in O._sub(BLK, "globalatt.2").items()}
