@@ -423,6 +423,33 @@ int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win
                             void* stream);
 int rtfs_longform_overlap_add_f32(const float* y, float* out, int B, int n_src, int L, int window, int hop, void* stream);
 
+/* Many recordings of different lengths in one pooled pass (AVNet.separate_many): R recordings, each planned on its own with
+ * rtfs_longform_plan (N_r windows); the sum(N_r) windows are laid out in recording order, then window order, so `forward` runs on
+ * chunks that straddle recordings.  Per recording, framing, weights and the division are exactly those of the three entries above.
+ * rtfs_longform_many_plan (host only, the single place with the arithmetic): L, Tv (R each, host) -> total_windows = sum(N_r), out_floats =
+ *   the size of ONE flat output and, when `table` is not NULL, the 5 * R int64 words [row0 | N | L | Tv | out_off] the kernels read FROM
+ *   DEVICE MEMORY (the caller uploads them): row0[r] = sum of N before r, out_off[r] = where recording r's (n_src, L_r) block starts in the
+ *   flat output, in floats.  Padding rule: every block is rounded up to a multiple of RTFS_LONGFORM_MANY_ALIGN = 32 floats, so out_off[r]
+ *   = sum over q < r of 32 * ceil(n_src * L_q / 32), every block starts on a 128-byte line of a 128-byte aligned buffer, and out_floats
+ *   (the sum over all r) is a whole number of lines; the floats between the end of a block and the next line are never written.
+ *   Call it first with table NULL for the sizes.  R < 1, n_src < 1, an L_r or Tv_r outside [1, 2^31 - 1], a window / hop that
+ *   rtfs_longform_plan refuses: -4; sum(N_r) > 2^31 - 1: -1.  total_windows and out_floats may be NULL.
+ * rtfs_longform_frame_many_f32 (one launch for both gathers): wavs, videos = DEVICE arrays of R device pointers, recording r's (L_r) samples
+ *   and its contiguous (512, Tv_r) video - separate allocations, no packing copy - -> wav_win (total_windows, window), video_win
+ *   (total_windows, 512, window / SPF), row row0[r] + n.  A recording whose pointer is not 16-byte aligned is read with dword loads.
+ * rtfs_longform_overlap_add_many_f32 (one launch): y (total_windows, n_src, window) -> out (out_floats), recording r at out + out_off[r]
+ *   as (n_src, L_r).  Gather form: every element of every block is written exactly once, weights recomputed in registers, no atomics, no
+ *   accumulator, no scratch; deterministic.
+ * Both take the caller's stream, allocate nothing and read nothing back; wav_win, video_win, y and out must be 16-byte aligned and the
+ * tables 8-byte aligned (-4).  The kernels trust the device tables: pass what rtfs_longform_many_plan wrote. */
+#define RTFS_LONGFORM_MANY_ALIGN 32
+int rtfs_longform_many_plan(const long long* L, const long long* Tv, int R, int window, int hop, int n_src, long long* table,
+                            long long* total_windows, long long* out_floats);
+int rtfs_longform_frame_many_f32(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win, float* video_win,
+                                 int R, int total_windows, int window, int hop, void* stream);
+int rtfs_longform_overlap_add_many_f32(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
+                                       int n_src, int window, int hop, void* stream);
+
 /* Video front-end (the step before the path): FRCNNVideoModel.forward with backbone_type "resnet",
  * relu_type "prelu", eval mode (src/models/videomodels/frcnn_videomodel.py:61-72, resnet.py:23-118).
  * lips (B, 1, T, 88, 88) grey-scale mouth crops -> out (B, 512, T), the lip embedding AVNet.forward takes.

@@ -1297,6 +1297,20 @@ int rtfs_longform_overlap_add_f32(const float* y, float* out, int B, int n_src, 
     if (!y || !out) return RTFS_ERR_ARG;
     return launch_longform_overlap_add(y, out, B, n_src, L, window, hop, (hipStream_t)stream);
 }
+int rtfs_longform_many_plan(const long long* L, const long long* Tv, int R, int window, int hop, int n_src, long long* table,
+                            long long* total_windows, long long* out_floats) {
+    return longform_many_plan(L, Tv, R, window, hop, n_src, table, total_windows, out_floats);
+}
+int rtfs_longform_frame_many_f32(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win, float* video_win,
+                                 int R, int total_windows, int window, int hop, void* stream) {
+    if (!wavs || !videos || !table || !wav_win || !video_win) return RTFS_ERR_ARG;
+    return launch_longform_frame_many(wavs, videos, table, wav_win, video_win, R, total_windows, window, hop, (hipStream_t)stream);
+}
+int rtfs_longform_overlap_add_many_f32(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
+                                       int n_src, int window, int hop, void* stream) {
+    if (!y || !out || !table) return RTFS_ERR_ARG;
+    return launch_longform_overlap_add_many(y, out, table, R, total_windows, out_floats, n_src, window, hop, (hipStream_t)stream);
+}
 
 size_t rtfs_video_pack_floats(void) { return video_pack_floats(); }
 size_t rtfs_video_workspace_bytes(int B, int T) { return video_workspace_bytes(B, T); }

@@ -165,3 +165,182 @@ int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, in
     hipLaunchKernelGGL(longform_ola_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, out, total, n_src, N, L, window, hop);
     return rtfs_launch_status();
 }
+
+// ----------------------------------------------------------------------------- many recordings of different lengths in one pooled pass
+// AVNet.separate_many (DESIGN.md "Many recordings"): R recordings, each planned on its own with longform_plan, their sum(N_r) windows
+// laid out in recording order, then window order, so the fused forward runs on full chunks that straddle recordings.  The recordings
+// stay where they are (R separate allocations): the kernels read them through a device table of per-recording pointers and the plan
+// table of longform_many_plan, 5 * R int64 words [row0 | N | L | Tv | out_off].  Recording r's (n_src, L_r) result starts out_off[r]
+// floats into ONE flat output; out_off is a multiple of MANY_ALIGN = 32 floats (a 128-byte line), so no 16-byte store and no line is
+// shared by two recordings, and the floats between two blocks are never written.  Per recording the arithmetic is that of the two
+// kernels above, term by term and in the same order.
+namespace {
+
+constexpr int MANY_ALIGN = 32;  // floats: every recording's block of the flat output starts on a 128-byte line
+
+// largest r in [0, R) with key[r] <= x; key ascending, key[0] = 0 <= x
+__device__ __forceinline__ int many_find(const long long* __restrict__ key, int R, long long x) {
+    int lo = 0, hi = R - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (key[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void longform_frame_many_kernel(const float* const* __restrict__ wavs, const float* const* __restrict__ videos,
+                                                                  const long long* __restrict__ table, float* __restrict__ wav_win,
+                                                                  float* __restrict__ video_win, int R, int window, int hop, int qa_pad) {
+    const int row = blockIdx.x;
+    const int r = many_find(table, R, row);  // block-uniform: scalar loads
+    const int n = row - (int)table[r];
+    if (n >= (int)table[R + r]) return;  // a table that does not cover this row: write nothing
+    const int L = (int)table[2 * R + r], Tv = (int)table[3 * R + r];
+    const int Wv = window / SPF;
+    int q = blockIdx.y * 256 + threadIdx.x;
+    if (q < qa_pad) {  // audio quads; the segment is padded to whole waves so no wave serves both gathers
+        if (q >= window / 4) return;
+        const int i = 4 * q;
+        const long long p = (long long)n * hop + i;  // position in the recording
+        const float* src = wavs[r];
+        f32x4 v;
+        if (p + 3 < L && (((uintptr_t)(src + p)) & 15) == 0) {
+            v = *(const f32x4*)(src + p);
+        } else {
+            v.x = p < L ? src[p] : 0.f;
+            v.y = p + 1 < L ? src[p + 1] : 0.f;
+            v.z = p + 2 < L ? src[p + 2] : 0.f;
+            v.w = p + 3 < L ? src[p + 3] : 0.f;
+        }
+        *(f32x4*)(wav_win + (size_t)row * window + i) = v;
+        return;
+    }
+    q -= qa_pad;
+    if (q >= VCH * Wv / 4) return;
+    const float* src = videos[r];
+    const int f0 = (int)((long long)n * hop / SPF);
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = 4 * q + k, c = j / Wv, f = j - c * Wv;
+        const long long fr = (long long)f0 + f;
+        v[k] = src[(size_t)c * Tv + (fr < Tv ? (int)fr : Tv - 1)];
+    }
+    *(f32x4*)(video_win + (size_t)row * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
+}
+
+__global__ __launch_bounds__(256) void longform_ola_many_kernel(const float* __restrict__ y, float* __restrict__ out,
+                                                                const long long* __restrict__ table, long long out_floats, int R, int n_src,
+                                                                int window, int hop) {
+    const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;  // flat index into the padded output
+    if (g >= out_floats) return;
+    const int r = many_find(table + 4 * (size_t)R, R, g);
+    const long long row0 = table[r];
+    const int N = (int)table[R + r], L = (int)table[2 * R + r];
+    const long long total = (long long)n_src * L, e = g - table[4 * (size_t)R + r];  // this recording's (n_src, L) block, and the index into it
+    if (e >= total) return;  // padding up to the next recording's line: never written
+    const int V = window - hop;
+    const float Vf = (float)V;
+    const int s0 = (int)(e / L), t0 = (int)(e - (long long)s0 * L);
+    float res[4];
+    if (t0 + 3 < L && (t0 & 3) == 0) {
+        // the quad lies in one row at a multiple of 4: one aligned 16-byte load per window, as in longform_ola_kernel
+        int n_lo, n_hi;
+        ola_range(t0, N, window, hop, &n_lo, &n_hi);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f}, ws[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int n = n_lo; n <= n_hi; ++n) {
+            const int i = t0 - n * hop;
+            const f32x4 v = *(const f32x4*)(y + (((size_t)row0 + n) * n_src + s0) * window + i);
+            const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float w = V == 0 ? 1.f : ola_weight(i + k, window, Vf);
+                acc[k] += w * vv[k];
+                ws[k] += w;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) res[k] = acc[k] / ws[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            res[k] = 0.f;
+            if (e + k >= total) continue;
+            int s = s0, t = t0 + k;
+            if (t >= L) {  // L >= 1 and k <= 3: the quad may run over several sources when L < 4
+                s += t / L;
+                t = t % L;
+            }
+            int n_lo, n_hi;
+            ola_range(t, N, window, hop, &n_lo, &n_hi);
+            float acc = 0.f, ws = 0.f;
+            for (int n = n_lo; n <= n_hi; ++n) {
+                const int i = t - n * hop;
+                const float w = V == 0 ? 1.f : ola_weight(i, window, Vf);
+                acc += w * y[(((size_t)row0 + n) * n_src + s) * window + i];
+                ws += w;
+            }
+            res[k] = acc / ws;
+        }
+    }
+    if (e + 3 < total) {
+        *(f32x4*)(out + g) = f32x4{res[0], res[1], res[2], res[3]};
+    } else {  // the tail of a recording: the only partial quad of its block
+        for (int k = 0; k < 4 && e + k < total; ++k) out[g + k] = res[k];
+    }
+}
+
+}  // namespace
+
+int longform_many_plan(const long long* L, const long long* Tv, int R, int window, int hop, int n_src, long long* table, long long* total_windows,
+                       long long* out_floats) {
+    if (!L || !Tv || R < 1 || n_src < 1) return RTFS_ERR_ARG;
+    long long rows = 0, off = 0;
+    for (int r = 0; r < R; ++r) {
+        if (L[r] < 1 || Tv[r] < 1 || L[r] > 0x7fffffffLL || Tv[r] > 0x7fffffffLL) return RTFS_ERR_ARG;
+        int N = 0;
+        const int e = longform_plan((int)L[r], (int)Tv[r], window, hop, &N);
+        if (e != RTFS_OK) return e;
+        if (table) {
+            table[r] = rows;
+            table[(size_t)R + r] = N;
+            table[2 * (size_t)R + r] = L[r];
+            table[3 * (size_t)R + r] = Tv[r];
+            table[4 * (size_t)R + r] = off;
+        }
+        rows += N;
+        if (rows > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+        const long long block = ((long long)n_src * L[r] + MANY_ALIGN - 1) / MANY_ALIGN * MANY_ALIGN;  // n_src, L < 2^31: below 2^62
+        if (off > (1LL << 62) - block) return RTFS_ERR_SHAPE;
+        off += block;
+    }
+    if (total_windows) *total_windows = rows;
+    if (out_floats) *out_floats = off;
+    return RTFS_OK;
+}
+
+int launch_longform_frame_many(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win, float* video_win,
+                               int R, int total_windows, int window, int hop, hipStream_t st) {
+    const int e = longform_plan(1, 1, window, hop, nullptr);
+    if (e != RTFS_OK) return e;
+    if (R < 1 || total_windows < R) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)wav_win) | ((uintptr_t)video_win)) & 15) return RTFS_ERR_ARG;
+    if ((((uintptr_t)wavs) | ((uintptr_t)videos) | ((uintptr_t)table)) & 7) return RTFS_ERR_ARG;
+    const int qa_pad = cdiv(window / 4, 64) * 64, qv = VCH * (window / SPF) / 4;
+    hipLaunchKernelGGL(longform_frame_many_kernel, dim3(total_windows, cdiv(qa_pad + qv, 256)), dim3(256), 0, st, wavs, videos, table, wav_win,
+                       video_win, R, window, hop, qa_pad);
+    return rtfs_launch_status();
+}
+
+int launch_longform_overlap_add_many(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
+                                     int n_src, int window, int hop, hipStream_t st) {
+    const int e = longform_plan(1, 1, window, hop, nullptr);
+    if (e != RTFS_OK) return e;
+    if (R < 1 || total_windows < R || n_src < 1 || out_floats < MANY_ALIGN || out_floats % MANY_ALIGN) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)y) | ((uintptr_t)out)) & 15) return RTFS_ERR_ARG;
+    if (((uintptr_t)table) & 7) return RTFS_ERR_ARG;
+    const long long blocks = (out_floats + 1023) / 1024;
+    if (blocks > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(longform_ola_many_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, out, table, out_floats, R, n_src, window, hop);
+    return rtfs_launch_status();
+}

@@ -331,6 +331,14 @@ int longform_plan(int L, int Tv, int window, int hop, int* N);
 int launch_longform_frame(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
                           hipStream_t st);
 int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, int L, int window, int hop, hipStream_t st);
+// many recordings of different lengths, their windows pooled (k_longform.hip): per-recording table (host), then the same two passes reading
+// the recordings through device tables of pointers
+int longform_many_plan(const long long* L, const long long* Tv, int R, int window, int hop, int n_src, long long* table, long long* total_windows,
+                       long long* out_floats);
+int launch_longform_frame_many(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win, float* video_win,
+                               int R, int total_windows, int window, int hop, hipStream_t st);
+int launch_longform_overlap_add_many(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
+                                     int n_src, int window, int hop, hipStream_t st);
 
 // preparing raw recordings (k_prep.hip): uint8 mouth ROIs -> normalised lips, waveform normalisation, polyphase resampling
 int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,

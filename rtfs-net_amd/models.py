@@ -829,6 +829,103 @@ class AVNet(BaseAVModel):
                        "rtfs_longform_overlap_add_f32")
             return out
 
+    def separate_many(self, mixtures, mouth_embeddings, window=32000, hop=None, max_batch=32):
+        """R recordings of different lengths in one pooled pass on the fused separator (inference only; DESIGN.md "Many recordings").
+        mixtures: a sequence of R >= 1 float32 tensors (L_r)|(1,L_r); mouth_embeddings: R tensors (512,Tv_r) at 25 fps -> a list of R
+        tensors (n_src,L_r).
+
+        Result r is what ``separate_long(mixtures[r], mouth_embeddings[r][None], window, hop)[0]`` defines: every recording is planned on
+        its own (N_r windows), with the framing, edge-frame replication, weights and division by the weight sum of ``separate_long``.  The
+        only new rule is the pooling: the sum(N_r) windows are laid out in recording order, then window order, and go through ``forward``
+        in chunks of ``max_batch`` consecutive rows (the last chunk smaller), so chunks straddle recordings and short clips ride in full
+        batches.  No renormalisation per window or per recording.
+
+        ValueError, before the first launch, for what ``separate_long`` refuses about window / hop and for: an empty list, lists of
+        different lengths, L_r < 1 or Tv_r < 1, a wrong rank or channel count, tensors on different devices (or CPU and GPU mixed), a
+        dtype other than float32, max_batch < 1, sum(N_r) past int32.  RuntimeError in ``.train()`` mode.
+
+        One host call builds the per-recording table (rtfs_longform_many_plan), ONE small host-to-device copy uploads it with the 2 R
+        source pointers (7 R int64 words), then one launch frames every recording where it lies (rtfs_longform_frame_many_f32: no packing
+        copy of the inputs), the chunks run through ``forward``, and one launch cross-fades into ONE flat output
+        (rtfs_longform_overlap_add_many_f32) of which the results are views; recording r's block starts on a 128-byte line.  Because of the
+        table upload a call is NOT capturable in a HIP graph.  Peak memory on top of the inputs is that of ``separate_long`` with
+        S = sum(N_r) in place of B*N: the framed windows in and out, S*window*(1 + n_src) floats, their video, S*512*(window/640) floats,
+        the flat output, sum_r 32*ceil(n_src*L_r/32) floats, the 56 R bytes of tables, and ONE chunk's ``forward``
+        (rtfs_separator_workspace_bytes_ex(min(max_batch, S), window, window/640) and its (chunk,n_src,window) result).
+
+        With ``fused = False``, or on CPU tensors, the same plan runs with ``forward_modular`` per chunk and the gathers of
+        ``separate_long`` restated in torch, recording by recording."""
+        try:
+            mixtures, mouth_embeddings = list(mixtures), list(mouth_embeddings)
+        except TypeError:
+            raise ValueError("separate_many: mixtures and mouth_embeddings must be sequences of tensors") from None
+        R = len(mixtures)
+        if R < 1 or len(mouth_embeddings) != R:
+            raise ValueError(f"separate_many: {R} mixture(s) and {len(mouth_embeddings)} mouth embedding(s); need the same number, at least 1")
+        wavs, videos = [], []
+        for r, (w, v) in enumerate(zip(mixtures, mouth_embeddings)):
+            if not isinstance(w, torch.Tensor) or not isinstance(v, torch.Tensor):
+                raise ValueError(f"separate_many: recording {r} is not a pair of tensors")
+            if w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1) or w.shape[-1] < 1:
+                raise ValueError(f"separate_many: mixture {r} must be (L) or (1,L) with L >= 1; got {tuple(w.shape)}")
+            if v.ndim != 2 or v.shape[0] != 512 or v.shape[1] < 1:
+                raise ValueError(f"separate_many: mouth embedding {r} must be (512,Tv) with Tv >= 1; got {tuple(v.shape)}")
+            if w.dtype != torch.float32 or v.dtype != torch.float32:
+                raise ValueError(f"separate_many: recording {r} is {w.dtype} / {v.dtype}; the kernels are float32")
+            if w.device != mixtures[0].device or v.device != mixtures[0].device:
+                raise ValueError(f"separate_many: recording {r} lies on {w.device} / {v.device}, recording 0 on {mixtures[0].device}")
+            wavs.append(w.reshape(-1))
+            videos.append(v)
+        window = int(window)
+        hop = window // 2 if hop is None else int(hop)
+        max_batch = int(max_batch)
+        if max_batch < 1:
+            raise ValueError(f"separate_many: max_batch = {max_batch}")
+        lib = _lib.load()
+        if lib.rtfs_longform_plan(1, 1, window, hop, None) != 0:
+            raise ValueError(f"separate_many: window = {window}, hop = {hop} must be multiples of {LONGFORM_SPF} with 0 < hop <= window")
+        rnn_kind = self.refinement_module.audio_net.get_block(0).rnn_kind
+        if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
+            raise ValueError(f"separate_many: a window of {window} samples does not fit the fused separator of this model's cell "
+                             f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
+        Ls = (ctypes.c_longlong * R)(*[int(w.shape[0]) for w in wavs])
+        Tvs = (ctypes.c_longlong * R)(*[int(v.shape[1]) for v in videos])
+        table = (ctypes.c_longlong * (5 * R))()
+        rows, floats = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        if lib.rtfs_longform_many_plan(Ls, Tvs, R, window, hop, self.n_src, table, ctypes.byref(rows), ctypes.byref(floats)) != 0:
+            raise ValueError(f"separate_many: {R} recordings with window = {window}, hop = {hop} need more than 2^31 - 1 windows "
+                             f"(or a length is past int32)")
+        if self.training:
+            raise RuntimeError("AVNet.separate_many is inference only: call .eval()")
+        S, Wv, n_src, device = int(rows.value), window // LONGFORM_SPF, self.n_src, wavs[0].device
+        row0, Ns, offs = table[0:R], table[R:2 * R], table[4 * R:5 * R]
+        on_hip = self.fused and device.type == "cuda"
+        with torch.no_grad():
+            if on_hip:
+                wavs, videos = [w.contiguous() for w in wavs], [v.contiguous() for v in videos]
+                words = list(table) + [w.data_ptr() for w in wavs] + [v.data_ptr() for v in videos]
+                tab = torch.tensor(words, dtype=torch.int64).to(device)  # the one host-to-device copy
+                t_wav, t_vid = tab[5 * R:6 * R], tab[6 * R:7 * R]
+                xw = _lib.empty(S, window, device=device, dtype=torch.float32)
+                vw = _lib.empty(S, 512, Wv, device=device, dtype=torch.float32)
+                _lib.check(lib.rtfs_longform_frame_many_f32(_lib.ptr(t_wav), _lib.ptr(t_vid), _lib.ptr(tab), _lib.ptr(xw), _lib.ptr(vw), R, S,
+                                                            window, hop, _lib.stream_of(xw)), "rtfs_longform_frame_many_f32")
+            else:
+                framed = [_longform_frame_torch(w[None], v[None], int(N), window, hop) for w, v, N in zip(wavs, videos, Ns)]
+                xw, vw = (torch.cat(t) for t in zip(*framed))
+            y = _lib.empty(S, n_src, window, device=device, dtype=torch.float32)
+            run = self.forward if on_hip else self.forward_modular
+            for c0 in range(0, S, max_batch):
+                c1 = min(S, c0 + max_batch)
+                y[c0:c1].copy_(run(xw[c0:c1], vw[c0:c1]))
+            if not on_hip:
+                return [_longform_overlap_add_torch(y[int(a):int(a) + int(N)], 1, int(N), int(w.shape[0]), window, hop)[0]
+                        for a, N, w in zip(row0, Ns, wavs)]
+            out = _lib.empty(int(floats.value), device=device, dtype=torch.float32)
+            _lib.check(lib.rtfs_longform_overlap_add_many_f32(_lib.ptr(y), _lib.ptr(out), _lib.ptr(tab), R, S, int(floats.value), n_src,
+                                                              window, hop, _lib.stream_of(xw)), "rtfs_longform_overlap_add_many_f32")
+            return [out[int(o):int(o) + n_src * int(w.shape[0])].view(n_src, int(w.shape[0])) for o, w in zip(offs, wavs)]
+
     def _side_stream(self, device):
         streams = self.__dict__.setdefault("_side_streams", {})
         key = (device.type, device.index)

@@ -76,6 +76,54 @@ class System(nn.Module):
             mouth_rois = datas.get_preprocessing_pipelines()["val"](mouth_rois)
         return self.separate_long(wav, mouth_rois, **kw)
 
+    def separate_many(self, wavs, mouths, **kw):
+        """Many recordings of different lengths in one pooled pass (inference): wavs = R tensors (L_r)|(1,L_r), mouths = R lip tracks
+        (1,Tv_r,88,88) at 25 fps -> a list of R tensors (n_src,L_r).  The video front-end runs under no_grad ONCE PER GROUP of tracks with
+        equal Tv_r, the tracks of a group stacked as a batch; a track is never joined to another along time, because the stem's temporal
+        padding belongs to each track.  The embeddings and ``**kw`` (window, hop, max_batch) go to ``AVNet.separate_many``.  Without a
+        video model the mouth slot holds lip embeddings (512,Tv_r)."""
+        wavs, mouths = list(wavs), list(mouths)
+        if self.video_model is None:
+            return self.audio_model.separate_many(wavs, mouths, **kw)
+        if len(wavs) < 1 or len(mouths) != len(wavs):
+            raise ValueError(f"System.separate_many: {len(wavs)} recording(s) and {len(mouths)} lip track(s); need the same number, at least 1")
+        groups = {}
+        for r, m in enumerate(mouths):
+            if not isinstance(m, torch.Tensor) or m.ndim != 4 or m.shape[0] != 1 or m.shape[1] < 1:
+                raise ValueError(f"System.separate_many: lip track {r} must be (1,Tv,88,88) with Tv >= 1; "
+                                 f"got {tuple(m.shape) if isinstance(m, torch.Tensor) else type(m).__name__}")
+            groups.setdefault(int(m.shape[1]), []).append(r)
+        embs = [None] * len(mouths)
+        with torch.no_grad():
+            for rs in groups.values():
+                emb = self.video_model(torch.stack([mouths[r] for r in rs]).type_as(wavs[rs[0]]))  # (G,1,Tv,88,88) -> (G,512,Tv)
+                for g, r in enumerate(rs):
+                    embs[r] = emb[g]
+        return self.audio_model.separate_many(wavs, embs, **kw)
+
+    def separate_recordings(self, wavs, sample_rates, mouth_rois, normalize_audio=False, **kw):
+        """The list form of ``separate_recording``: wavs = R raw recordings (L_r) at ``sample_rates[r]`` Hz, mouth_rois = R uint8
+        tracks (Tv_r,H,W) at 25 fps -> a list of R tensors (n_src, L_r at 16 kHz).  Per recording ``datas.resample`` to 16 kHz and the ``"val"`` pipeline on the ROIs, then ``separate_many(**kw)``.  Without a video model the mouth
+        slot holds lip embeddings (512,Tv_r); a floating mouth slot is taken as prepared lips (1,Tv_r,88,88)."""
+        from . import datas
+        wavs, mouth_rois = list(wavs), list(mouth_rois)
+        rates = list(sample_rates)
+        if len(wavs) < 1 or len(rates) != len(wavs) or len(mouth_rois) != len(wavs):
+            raise ValueError(f"System.separate_recordings: {len(wavs)} recording(s), {len(rates)} sample rate(s), {len(mouth_rois)} mouth track(s)")
+        val = datas.get_preprocessing_pipelines()["val"]
+        prepared, mouths = [], []
+        for w, fs, roi in zip(wavs, rates, mouth_rois):
+            if not isinstance(w, torch.Tensor) or w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
+                raise ValueError("System.separate_recordings: every recording must be a tensor (L) or (1,L)")
+            w = datas.resample(w.reshape(-1), fs, 16000)
+            prepared.append(datas.normalize_mixture(w) if normalize_audio else w)
+            if self.video_model is not None and roi.dtype == torch.uint8:
+                if roi.ndim != 3:
+                    raise ValueError(f"System.separate_recordings: uint8 mouth ROIs must be (Tv,H,W) per recording; got {tuple(roi.shape)}")
+                roi = val(roi)[0]  # (1,Tv,88,88)
+            mouths.append(roi)
+        return self.separate_many(prepared, mouths, **kw)
+
     def prepare_batch(self, batch, train=True, normalize_audio=False, rng=None):
         """A reference-shaped batch (inputs, targets, target_mouths, ...) whose mouth slot may hold uint8 ROIs, (B,Tv,H,W) or (B,K,Tv,H,W):
         returns the batch with that slot replaced by float lips, (B,1,Tv,88,88) or (B,K,1,Tv,88,88) (the layout ``separate_speakers``
