@@ -450,6 +450,60 @@ int rtfs_longform_frame_many_f32(const float* const* wavs, const float* const* v
 int rtfs_longform_overlap_add_many_f32(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
                                        int n_src, int window, int hop, void* stream);
 
+/* Live streams chunk by chunk (AVNet.open_streams / StreamPool; DESIGN.md "Live streams"): the stateful form of the long-form plan.  Window
+ * n of a stream is run as soon as a >= n hop + window samples AND f >= n hop / SPF + window / SPF frames have arrived; after window n the
+ * samples [n hop, (n + 1) hop) are final.  The concatenated outputs of any chunking equal rtfs_longform_* on the whole recording.
+ * State (caller-allocated, 16-byte aligned, C = window + max_chunk): aring (slots, C), vring (slots, 512, C / SPF), acc (slots, n_src, C);
+ * sample p lives in cell p % C, frame q in column q % (C / SPF).  The caller keeps four counters per slot [a samples received | f frames
+ * received | e windows emitted | o samples output]; nothing is ever read back from the device.
+ * rtfs_live_plan (host only, no device call, the single place with the arithmetic): for the R slots named in slot_ids, counters (R x 4,
+ *   row-major) and the chunk sizes n_audio, n_video of this push (ignored when flush != 0) -> new_counters (R x 4), sizes[5] = [rows =
+ *   ready windows of the tick | out_floats of ONE flat output | max_span = most samples one slot changes | largest n_audio | largest
+ *   n_video] and the tick table, RTFS_LIVE_PLAN_WORDS = 13 int64 words per named slot, column-major:
+ *   [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]: cnt ready windows e .. e + cnt - 1 in rows row0 ..; the
+ *   slot's (n_src, end - o) result starts out_off floats into the flat output, out_off a multiple of RTFS_LIVE_ALIGN = 32 floats (a
+ *   128-byte line); apos = a % C and fpos = f % (C / SPF) are the ring positions the chunks are written at.  A push emits every ready
+ *   window and makes [o, (e + cnt) hop) final.  A flush (L = a, Tv = f) emits the windows rtfs_longform_plan(L) still owes - zeros past
+ *   L, a frame index past Tv - 1 reads frame Tv - 1 -, makes [o, L) final and returns zero counters.
+ *   Refusals return -4, write nothing else, and name themselves in refused[2] = [index into slot_ids or -1 | RTFS_LIVE_* reason]:
+ *   a window / hop rtfs_longform_plan refuses, max_chunk not a positive multiple of SPF, C > RTFS_LIVE_MAX_CAPACITY, R < 1,
+ *   n_src < 1; a slot id outside [0, slots) or named twice; a chunk outside [0, max_chunk] samples / [0, max_chunk / SPF] frames; a push after which a + na - e hop > C or
+ *   f + nf - e hop / SPF > C / SPF (it would overwrite a cell that window e still needs: one side ran too far ahead of the other); a
+ *   flush of a slot with samples and no frame; counters this planner cannot have produced.  new_counters, table, sizes, refused may
+ *   be NULL.
+ * rtfs_live_ingest_frame_f32 (one launch): table = the plan's 13 R words followed by two more columns [aptr | vptr], the DEVICE addresses
+ *   of each slot's audio chunk (na floats, any 4-byte alignment) and contiguous (512, nf) video chunk - separate allocations, read where
+ *   they lie -, uploaded by the caller.  Appends the chunks to the rings and writes the ready windows wav_win (rows, window), video_win
+ *   (rows, 512, window / SPF); a framed sample comes from the ring if it arrived in an earlier push and from the chunk otherwise.  No
+ *   block reads a ring cell another block writes: the capacity rule makes the two sets disjoint (k_live.hip).
+ * rtfs_live_overlap_add_f32 (one launch): y (rows, n_src, window) -> final samples (acc + this tick's weighted windows in ascending n) /
+ *   weight sum into out (out_floats), weights and order those of rtfs_longform_overlap_add_f32; samples a later window still reaches go
+ *   back to acc.  Gather form: one thread per four samples of a source, every cell has one thread, no atomics; deterministic.
+ * rtfs_live_reset_f32 (one launch): zeroes the state of the R slots in ids (DEVICE array; NULL = slots 0 .. R - 1).
+ * The launches take the caller's stream, allocate nothing and read nothing back, and trust the device table: pass what rtfs_live_plan
+ * wrote.  State, wav_win, video_win, y, out must be 16-byte aligned and the tables 8-byte aligned (-4).  RTFS_LIVE_MAX_CAPACITY bounds C
+ * (2^24 samples, 17 minutes of history per slot) so that every launch grid of an accepted size fits; a grid that would not is -1. */
+#define RTFS_LIVE_ALIGN 32
+#define RTFS_LIVE_MAX_CAPACITY (1 << 24)
+#define RTFS_LIVE_PLAN_WORDS 13
+#define RTFS_LIVE_BAD_ARGUMENT 1
+#define RTFS_LIVE_UNKNOWN_SLOT 2
+#define RTFS_LIVE_REPEATED_SLOT 3
+#define RTFS_LIVE_CHUNK_SIZE 4
+#define RTFS_LIVE_AUDIO_CAPACITY 5
+#define RTFS_LIVE_VIDEO_CAPACITY 6
+#define RTFS_LIVE_NO_FRAMES 7
+#define RTFS_LIVE_BAD_COUNTERS 8
+int rtfs_live_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R, int slots,
+                   int flush, int window, int hop, int max_chunk, int n_src, long long* new_counters, long long* table, long long* sizes,
+                   int* refused);
+int rtfs_live_ingest_frame_f32(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
+                               int max_na, int max_nf, int window, int hop, int max_chunk, void* stream);
+int rtfs_live_overlap_add_f32(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int n_src,
+                              int window, int hop, int max_chunk, int flush, void* stream);
+int rtfs_live_reset_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk,
+                        void* stream);
+
 /* Video front-end (the step before the path): FRCNNVideoModel.forward with backbone_type "resnet",
  * relu_type "prelu", eval mode (src/models/videomodels/frcnn_videomodel.py:61-72, resnet.py:23-118).
  * lips (B, 1, T, 88, 88) grey-scale mouth crops -> out (B, 512, T), the lip embedding AVNet.forward takes.

@@ -135,6 +135,10 @@ SIGNATURES = {
     "rtfs_longform_many_plan": (_i, [_p, _p, _i, _i, _i, _i, _p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "rtfs_longform_frame_many_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "rtfs_longform_overlap_add_many_f32": (_i, [_p, _p, _p, _i, _i, C.c_longlong, _i, _i, _i, _p]),
+    "rtfs_live_plan": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "rtfs_live_ingest_frame_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "rtfs_live_overlap_add_f32": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _i, _i, _i, _i, _i, _p]),
+    "rtfs_live_reset_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "rtfs_video_pack_floats": (_z, []),
     "rtfs_video_workspace_bytes": (_z, [_i, _i]),
     "rtfs_video_frontend_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),

@@ -1,0 +1,341 @@
+// Live streams chunk by chunk (AVNet.open_streams / StreamPool; DESIGN.md "Live streams"): the stateful form of the long-form plan of
+// k_longform.hip.  A stream delivers audio and lip frames a chunk at a time; window n = samples [n hop, n hop + window) is run as soon as
+// its samples AND its frames have arrived, and after window n the samples [n hop, (n + 1) hop) can be touched by no later window, so
+// they leave at once.  The concatenated outputs are separate_long's of the whole recording.  tests/live_oracle.py restates counters,
+// readiness, ring positions and the streaming overlap-add in float64.
+//
+// State per slot, device resident, allocated once (C = window + max_chunk samples, C / SPF frames):
+//   audio ring  (slots, C)            sample p of the stream lives in cell p % C
+//   video ring  (slots, 512, C / SPF) frame q lives in column q % (C / SPF); channel-major like the lip embedding, so the framing gather
+//                                     reads runs of a window's frames as k_longform.hip does
+//   accumulator (slots, n_src, C)     the weighted sum so far of a sample that later windows still reach, in cell t % C
+// Host counters per slot (kept by the caller, nothing is read back): a samples received, f frames received, e windows emitted,
+// o samples output.
+//
+//   live_plan                 host only, the single place with the arithmetic: counters + the sizes of this push / flush -> new counters
+//                             and the tick table, 13 int64 words per named slot, column-major
+//                             [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]; the caller appends the two
+//                             columns of chunk pointers [aptr | vptr] and uploads the 15 R words with one copy
+//   live_ingest_frame_kernel  ONE launch: blocks x >= rows append the chunks to the rings; blocks x < rows write the ready windows
+//   live_ola_kernel           gather form, one thread per 4 samples of one source: final samples are divided and written to the flat
+//                             output, samples a later window still reaches go back to the accumulator
+//   live_reset_kernel         gives a slot's state defined contents (zeros)
+//
+// WHY THE INGEST BLOCKS AND THE FRAMING BLOCKS OF ONE LAUNCH NEVER TOUCH THE SAME RING CELL.  A framing block reads sample p of window
+// n >= e from the ring only if p < a (it arrived in an earlier push), so it reads stream positions in [e hop, a); an ingest block writes
+// the stream positions [a, a + na).  live_plan refuses a push unless a + na - e hop <= C, so all positions of [e hop, a + na) have
+// different residues mod C: the cells read and the cells written are disjoint, whatever order the blocks run in.  The same holds for
+// frames with f + nf - e hop / SPF <= C / SPF.  Two named slots never share state, and live_plan refuses a slot named twice.  The cells
+// read are intact for the same reason: every accepted push kept a - e hop <= C, and e only grows.  A flush writes no ring cell.
+//
+// WHY THE ACCUMULATOR IS C FLOATS LONG.  A tick reads the sums of [e hop, (e - 1) hop + window) and writes those of [e' hop, (e' - 1) hop +
+// window) with e' = e + cnt.  A ready window has a' >= (e' - 1) hop + window, so both ranges lie in [e hop, e hop + C): distinct residues
+// mod C, every cell has at most one thread, which reads before it writes.  (A ring of `window` floats would alias t and t + window as
+// soon as one tick emits window / hop + 1 windows.)  Which cells hold a sum is known from the counters (t < (e - 1) hop + window), so
+// no kernel depends on the value of a cell that holds none.
+//
+// Stores follow k_longform.hip: a lane writes 16 bytes, a wave 1024 contiguous bytes, wherever the layout is aligned - the framed
+// windows always, the rings when the write position is a multiple of 4 (always when chunks are multiples of 4 samples), the output when
+// its block length is a multiple of 4 (always but at a flush).  Chunks may start at any 4-byte boundary: an unaligned chunk is read
+// with dword loads.
+#include "common.h"
+#include "kernels.h"
+#include "longform_common.h"  // SPF, VCH, ola_weight, many_find
+#include "../../include/rtfs_amd.h"  // RTFS_LIVE_*
+
+namespace {
+
+constexpr int LIVE_ALIGN = RTFS_LIVE_ALIGN;  // floats: every slot's block of the flat output starts on a 128-byte line
+// columns of the tick table
+enum { T_SLOT, T_A, T_NA, T_F, T_NF, T_E, T_CNT, T_ROW0, T_O, T_END, T_OFF, T_APOS, T_FPOS, T_APTR, T_VPTR };
+
+__device__ __forceinline__ f32x4 load4(const float* p) {  // 16 bytes when aligned, else four dwords
+    if ((((uintptr_t)p) & 15) == 0) return *(const f32x4*)p;
+    return f32x4{p[0], p[1], p[2], p[3]};
+}
+
+__global__ __launch_bounds__(256) void live_ingest_frame_kernel(const long long* __restrict__ table, float* aring, float* vring,
+                                                                float* __restrict__ wav_win, float* __restrict__ video_win, int R, int rows,
+                                                                int window, int hop, int C, int qa_pad, int qin_pad) {
+    const int Cv = C / SPF, Wv = window / SPF;
+    int q = blockIdx.y * 256 + threadIdx.x;
+    if ((int)blockIdx.x >= rows) {
+        // ---- ingest: chunk r -> rings of its slot
+        const int r = blockIdx.x - rows;
+        const long long slot = table[(size_t)T_SLOT * R + r];
+        const int na = (int)table[(size_t)T_NA * R + r], nf = (int)table[(size_t)T_NF * R + r];
+        if (q < qin_pad) {  // audio quads; padded to whole waves so no wave serves both copies
+            const int j = 4 * q;
+            if (j >= na) return;
+            const float* src = (const float*)(uintptr_t)table[(size_t)T_APTR * R + r] + j;
+            float* dst = aring + (size_t)slot * C;
+            int cell = (int)table[(size_t)T_APOS * R + r] + j;  // apos < C, j < max_chunk < C: one wrap at most
+            if (cell >= C) cell -= C;
+            if (j + 3 < na && cell + 3 < C && (cell & 3) == 0) {
+                *(f32x4*)(dst + cell) = load4(src);
+            } else {
+                for (int k = 0; k < 4 && j + k < na; ++k) dst[cell + k < C ? cell + k : cell + k - C] = src[k];
+            }
+            return;
+        }
+        q -= qin_pad;
+        const float* src = (const float*)(uintptr_t)table[(size_t)T_VPTR * R + r];  // (512, nf)
+        float* dst = vring + (size_t)slot * VCH * Cv;
+        const int fpos = (int)table[(size_t)T_FPOS * R + r];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int idx = 4 * q + k;
+            if (idx >= VCH * nf) return;
+            const int c = idx / nf, j = idx - c * nf;
+            int cell = fpos + j;
+            if (cell >= Cv) cell -= Cv;
+            dst[(size_t)c * Cv + cell] = src[idx];
+        }
+        return;
+    }
+    // ---- framing: row -> (slot, window n)
+    const int row = blockIdx.x;
+    const int r = many_find(table + (size_t)T_ROW0 * R, R, row);  // block-uniform: scalar loads
+    const int nl = row - (int)table[(size_t)T_ROW0 * R + r];
+    if (nl >= (int)table[(size_t)T_CNT * R + r]) return;  // a table that does not cover this row: write nothing
+    const long long slot = table[(size_t)T_SLOT * R + r], n = table[(size_t)T_E * R + r] + nl;
+    const long long a0 = table[(size_t)T_A * R + r], lim_a = a0 + table[(size_t)T_NA * R + r];  // at a flush na = 0: lim_a = L
+    if (q < qa_pad) {  // audio quads
+        if (q >= window / 4) return;
+        const int i = 4 * q;
+        const long long p = n * hop + i;  // position in the stream: a multiple of 4
+        int cell = (int)((n * hop) % C) + i;  // i < window <= C; C % 4 == 0, so a quad never wraps
+        if (cell >= C) cell -= C;
+        const float* ring = aring + (size_t)slot * C;
+        const float* chunk = (const float*)(uintptr_t)table[(size_t)T_APTR * R + r];
+        f32x4 v;
+        if (p + 3 < a0) {
+            v = *(const f32x4*)(ring + cell);
+        } else if (p >= a0 && p + 3 < lim_a) {
+            v = load4(chunk + (p - a0));
+        } else {  // the quad straddles ring | chunk | zeros past L
+            float e[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e[k] = p + k >= lim_a ? 0.f : p + k >= a0 ? chunk[p + k - a0] : ring[cell + k];
+            v = f32x4{e[0], e[1], e[2], e[3]};
+        }
+        *(f32x4*)(wav_win + (size_t)row * window + i) = v;
+        return;
+    }
+    q -= qa_pad;
+    if (q >= VCH * Wv / 4) return;
+    const long long f0 = table[(size_t)T_F * R + r];
+    const int nf = (int)table[(size_t)T_NF * R + r];
+    const long long last = f0 + nf - 1, fbase = n * (hop / SPF);  // at a flush nf = 0: last = Tv - 1
+    const int cell0 = (int)(fbase % Cv), cell_last = (int)(last % Cv);
+    const float* ring = vring + (size_t)slot * VCH * Cv;
+    const float* chunk = (const float*)(uintptr_t)table[(size_t)T_VPTR * R + r];
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = 4 * q + k, c = j / Wv, f = j - c * Wv;
+        long long fr = fbase + f;
+        int cell = cell0 + f;  // f < Wv <= Cv
+        if (cell >= Cv) cell -= Cv;
+        if (fr > last) {
+            fr = last;
+            cell = cell_last;
+        }
+        v[k] = fr >= f0 ? chunk[(size_t)c * nf + (fr - f0)] : ring[(size_t)c * Cv + cell];
+    }
+    *(f32x4*)(video_win + (size_t)row * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
+}
+
+__global__ __launch_bounds__(256) void live_ola_kernel(const long long* __restrict__ table, const float* __restrict__ y, float* __restrict__ out,
+                                                       float* acc, int R, int n_src, int window, int hop, int C, int flush) {
+    const int r = blockIdx.x, s = blockIdx.z;
+    const long long e0 = table[(size_t)T_E * R + r], e1 = e0 + table[(size_t)T_CNT * R + r];
+    const long long o = table[(size_t)T_O * R + r], end = table[(size_t)T_END * R + r];
+    const long long hi = flush ? end : (e1 > e0 ? (e1 - 1) * hop + window : o);  // samples [o, hi) change in this tick
+    const long long t = o + 4 * ((long long)blockIdx.y * 256 + threadIdx.x);      // o is a multiple of hop: the quad sits at a multiple of 4
+    if (t >= hi) return;
+    // the quad's four samples share their windows (hop and window are multiples of 4): n_lo .. n_hi of the windows emitted so far
+    const long long th = t / hop, d = t - window + 1;
+    const long long n_hi = th < e1 - 1 ? th : e1 - 1, n_lo = d <= 0 ? 0 : (d + hop - 1) / hop;
+    const int V = window - hop;
+    const float Vf = (float)V;
+    float* cell = acc + ((size_t)table[(size_t)T_SLOT * R + r] * n_src + s) * C + (size_t)(t % C);
+    float a[4] = {0.f, 0.f, 0.f, 0.f}, ws[4] = {0.f, 0.f, 0.f, 0.f};
+    if (e0 >= 1 && t < (e0 - 1) * hop + window) {  // an earlier tick's windows reached these samples
+        const f32x4 v = *(const f32x4*)cell;
+        a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+    }
+    const size_t row0 = (size_t)table[(size_t)T_ROW0 * R + r];
+    for (long long n = n_lo; n <= n_hi; ++n) {  // ascending n: the order of longform_ola_kernel
+        const int i = (int)(t - n * hop);
+        float w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w[k] = V == 0 ? 1.f : ola_weight(i + k, window, Vf);
+            ws[k] += w[k];
+        }
+        if (n < e0) continue;  // already in the accumulator
+        const f32x4 v = *(const f32x4*)(y + ((row0 + (size_t)(n - e0)) * n_src + s) * window + i);
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] += w[k] * vv[k];
+    }
+    if (t >= end) {  // a later window still reaches these samples (never at a flush)
+        *(f32x4*)cell = f32x4{a[0], a[1], a[2], a[3]};
+        return;
+    }
+    const long long idx = table[(size_t)T_OFF * R + r] + (long long)s * (end - o) + (t - o);  // block (n_src, end - o) of the flat output
+    if (t + 3 < end && (idx & 3) == 0) {
+        *(f32x4*)(out + idx) = f32x4{a[0] / ws[0], a[1] / ws[1], a[2] / ws[2], a[3] / ws[3]};
+    } else {  // a flush whose length is not a multiple of 4: its tail, and the rows of further sources
+        for (int k = 0; k < 4 && t + k < end; ++k) out[idx + k] = a[k] / ws[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void live_reset_kernel(const long long* __restrict__ ids, float* __restrict__ aring, float* __restrict__ vring,
+                                                         float* __restrict__ acc, int n_src, int C) {
+    const size_t slot = ids ? (size_t)ids[blockIdx.x] : blockIdx.x;
+    const int qa = C / 4, qv = VCH * (C / SPF) / 4, qc = n_src * (C / 4);  // C % 640 == 0: whole quads
+    int q = blockIdx.y * 256 + threadIdx.x;
+    const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (q < qa) {
+        *(f32x4*)(aring + slot * C + 4 * (size_t)q) = z;
+        return;
+    }
+    q -= qa;
+    if (q < qv) {
+        *(f32x4*)(vring + slot * VCH * (C / SPF) + 4 * (size_t)q) = z;
+        return;
+    }
+    q -= qv;
+    if (q < qc) *(f32x4*)(acc + slot * n_src * C + 4 * (size_t)q) = z;
+}
+
+// window / hop as longform_plan takes them, max_chunk a positive multiple of SPF, and a ring of at most RTFS_LIVE_MAX_CAPACITY samples:
+// with it the y dimension of the ingest / framing grid (< 0.45 C / 256 blocks) and of the overlap-add grid (C / 1024) stay far below
+// 65535, so a pool that open_streams accepted cannot fail at a launch (the launchers check their grids all the same)
+int live_sizes_ok(int window, int hop, int max_chunk) {
+    if (longform_plan(1, 1, window, hop, nullptr) != RTFS_OK) return 0;
+    return max_chunk >= SPF && max_chunk % SPF == 0 && (long long)window + max_chunk <= RTFS_LIVE_MAX_CAPACITY;
+}
+
+}  // namespace
+
+int live_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R, int slots,
+              int flush, int window, int hop, int max_chunk, int n_src, long long* new_counters, long long* table, long long* sizes,
+              int* refused) {
+    auto refuse = [&](int r, int reason) {
+        if (refused) {
+            refused[0] = r;
+            refused[1] = reason;
+        }
+        return RTFS_ERR_ARG;
+    };
+    if (!live_sizes_ok(window, hop, max_chunk) || !slot_ids || !counters || R < 1 || slots < 1 || n_src < 1 || (!flush && (!n_audio || !n_video)))
+        return refuse(-1, RTFS_LIVE_BAD_ARGUMENT);
+    const long long W = window, H = hop, Hv = hop / SPF, Wv = window / SPF, C = W + max_chunk, Cv = C / SPF, LIMIT = 1LL << 60;
+    for (int r = 0; r < R; ++r) {
+        if (slot_ids[r] < 0 || slot_ids[r] >= slots) return refuse(r, RTFS_LIVE_UNKNOWN_SLOT);
+        for (int q = 0; q < r; ++q)
+            if (slot_ids[q] == slot_ids[r]) return refuse(r, RTFS_LIVE_REPEATED_SLOT);
+    }
+    long long rows = 0, off = 0, max_span = 0, max_na = 0, max_nf = 0;
+    // two passes, so that a refusal at any slot leaves every output unwritten: pass 0 only checks, pass 1 only writes
+    for (int pass = 0; pass < 2; ++pass) {
+        rows = off = max_span = max_na = max_nf = 0;
+        for (int r = 0; r < R; ++r) {
+            const long long a = counters[4 * r], f = counters[4 * r + 1], e = counters[4 * r + 2], o = counters[4 * r + 3];
+            // what this planner itself maintains: o = e hop, windows 0 .. e - 1 were ready, the rings still hold what window e needs
+            if (a < 0 || f < 0 || e < 0 || a > LIMIT || f > LIMIT || o != e * H || (e > 0 && (a < (e - 1) * H + W || f < (e - 1) * Hv + Wv)) ||
+                a - e * H > C || f - e * Hv > Cv)
+                return refuse(r, RTFS_LIVE_BAD_COUNTERS);
+            long long na = 0, nf = 0, e1, end, span;
+            if (!flush) {
+                na = n_audio[r];
+                nf = n_video[r];
+                if (na < 0 || na > max_chunk || nf < 0 || nf > max_chunk / SPF) return refuse(r, RTFS_LIVE_CHUNK_SIZE);
+                if (a + na - e * H > C) return refuse(r, RTFS_LIVE_AUDIO_CAPACITY);
+                if (f + nf - e * Hv > Cv) return refuse(r, RTFS_LIVE_VIDEO_CAPACITY);
+                const long long ka = a + na >= W ? (a + na - W) / H + 1 : 0, kf = f + nf >= Wv ? (f + nf - Wv) / Hv + 1 : 0;  // windows that fit
+                const long long k = ka < kf ? ka : kf;
+                e1 = k > e ? k : e;
+                end = e1 * H;
+                span = e1 > e ? (e1 - 1) * H + W - o : 0;
+            } else {
+                if (a > 0 && f < 1) return refuse(r, RTFS_LIVE_NO_FRAMES);
+                e1 = a == 0 ? 0 : a <= W ? 1 : 1 + (a - W + H - 1) / H;  // longform_plan's N for L = a
+                end = a;
+                span = a - o;
+            }
+            if (pass && table) {
+                const long long col[13] = {slot_ids[r], a, na, f, nf, e, e1 - e, rows, o, end, off, a % C, f % Cv};
+                for (int k = 0; k < 13; ++k) table[(size_t)k * R + r] = col[k];
+            }
+            if (pass && new_counters) {
+                new_counters[4 * r] = flush ? 0 : a + na;
+                new_counters[4 * r + 1] = flush ? 0 : f + nf;
+                new_counters[4 * r + 2] = flush ? 0 : e1;
+                new_counters[4 * r + 3] = flush ? 0 : end;
+            }
+            rows += e1 - e;
+            off += ((long long)n_src * (end - o) + LIVE_ALIGN - 1) / LIVE_ALIGN * LIVE_ALIGN;
+            if (rows > 0x7fffffffLL || off > LIMIT) return refuse(r, RTFS_LIVE_BAD_ARGUMENT);
+            max_span = span > max_span ? span : max_span;
+            max_na = na > max_na ? na : max_na;
+            max_nf = nf > max_nf ? nf : max_nf;
+        }
+    }
+    if (sizes) {
+        sizes[0] = rows;
+        sizes[1] = off;
+        sizes[2] = max_span;
+        sizes[3] = max_na;
+        sizes[4] = max_nf;
+    }
+    if (refused) refused[0] = -1, refused[1] = 0;
+    return RTFS_OK;
+}
+
+int launch_live_ingest_frame(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows, int max_na,
+                             int max_nf, int window, int hop, int max_chunk, hipStream_t st) {
+    if (!live_sizes_ok(window, hop, max_chunk)) return RTFS_ERR_ARG;
+    if (R < 1 || rows < 0 || max_na < 0 || max_na > max_chunk || max_nf < 0 || max_nf > max_chunk / SPF) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)aring) | ((uintptr_t)vring) | ((uintptr_t)wav_win) | ((uintptr_t)video_win)) & 15) return RTFS_ERR_ARG;
+    if (((uintptr_t)table) & 7) return RTFS_ERR_ARG;
+    if (rows == 0 && max_na == 0 && max_nf == 0) return RTFS_OK;  // nothing arrived, nothing is ready
+    const int qa_pad = cdiv(window / 4, 64) * 64, qv = VCH * (window / SPF) / 4;
+    const int qin_pad = cdiv(cdiv(max_na, 4), 64) * 64, qiv = VCH * max_nf / 4;
+    const int frame_q = rows > 0 ? qa_pad + qv : 0, ingest_q = qin_pad + qiv;
+    const bool ingest = max_na > 0 || max_nf > 0;
+    const int gy = cdiv(frame_q > ingest_q ? frame_q : ingest_q, 256);
+    if (gy > 65535) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(live_ingest_frame_kernel, dim3(rows + (ingest ? R : 0), gy), dim3(256), 0, st,
+                       table, aring, vring, wav_win, video_win, R, rows, window, hop, window + max_chunk, qa_pad, qin_pad);
+    return rtfs_launch_status();
+}
+
+int launch_live_overlap_add(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int n_src, int window,
+                            int hop, int max_chunk, int flush, hipStream_t st) {
+    if (!live_sizes_ok(window, hop, max_chunk)) return RTFS_ERR_ARG;
+    const long long C = (long long)window + max_chunk;
+    if (R < 1 || n_src < 1 || n_src > 65535 || max_span < 0 || max_span > C) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)y) | ((uintptr_t)out) | ((uintptr_t)acc)) & 15) return RTFS_ERR_ARG;
+    if (((uintptr_t)table) & 7) return RTFS_ERR_ARG;
+    if (max_span == 0) return RTFS_OK;
+    if ((max_span + 1023) / 1024 > 65535) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(live_ola_kernel, dim3(R, (unsigned)((max_span + 1023) / 1024), n_src), dim3(256), 0, st, table, y, out, acc, R, n_src,
+                       window, hop, (int)C, flush ? 1 : 0);
+    return rtfs_launch_status();
+}
+
+int launch_live_reset(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk, hipStream_t st) {
+    if (!live_sizes_ok(window, window, max_chunk)) return RTFS_ERR_ARG;
+    if (R < 1 || n_src < 1) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)aring) | ((uintptr_t)vring) | ((uintptr_t)acc)) & 15) return RTFS_ERR_ARG;
+    if (((uintptr_t)ids) & 7) return RTFS_ERR_ARG;
+    const int C = window + max_chunk;
+    const long long quads = (long long)C / 4 * (1 + n_src) + (long long)VCH * (C / SPF) / 4;
+    if ((quads + 255) / 256 > 65535) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(live_reset_kernel, dim3(R, (unsigned)((quads + 255) / 256)), dim3(256), 0, st, ids, aring, vring, acc, n_src, C);
+    return rtfs_launch_status();
+}

@@ -16,11 +16,9 @@
 // aligned (always when L % 4 == 0 or B * n_src == 1) and coalesced dwords otherwise.
 #include "common.h"
 #include "kernels.h"
+#include "longform_common.h"  // SPF, VCH, ola_weight, many_find
 
 namespace {
-
-constexpr int SPF = 640;    // samples per video frame: 16 kHz / 25 fps
-constexpr int VCH = 512;    // lip-embedding channels
 
 __global__ __launch_bounds__(256) void longform_frame_kernel(const float* __restrict__ wav, const float* __restrict__ video,
                                                              float* __restrict__ wav_win, float* __restrict__ video_win, int N, int L, int Tv,
@@ -57,10 +55,6 @@ __global__ __launch_bounds__(256) void longform_frame_kernel(const float* __rest
         v[k] = src[(size_t)c * Tv + (fr < Tv ? (int)fr : Tv - 1)];
     }
     *(f32x4*)(video_win + (size_t)row * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
-}
-
-__device__ __forceinline__ float ola_weight(int i, int window, float V) {
-    return fminf(1.f, fminf(((float)i + 0.5f) / V, ((float)(window - i) - 0.5f) / V));
 }
 
 // one output element: windows n_lo .. n_hi contain sample t
@@ -177,16 +171,6 @@ int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, in
 namespace {
 
 constexpr int MANY_ALIGN = 32;  // floats: every recording's block of the flat output starts on a 128-byte line
-
-// largest r in [0, R) with key[r] <= x; key ascending, key[0] = 0 <= x
-__device__ __forceinline__ int many_find(const long long* __restrict__ key, int R, long long x) {
-    int lo = 0, hi = R - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (key[mid] <= x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void longform_frame_many_kernel(const float* const* __restrict__ wavs, const float* const* __restrict__ videos,
                                                                   const long long* __restrict__ table, float* __restrict__ wav_win,

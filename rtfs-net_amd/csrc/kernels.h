@@ -340,6 +340,16 @@ int launch_longform_frame_many(const float* const* wavs, const float* const* vid
 int launch_longform_overlap_add_many(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
                                      int n_src, int window, int hop, hipStream_t st);
 
+// live streams chunk by chunk (k_live.hip): tick plan (host), chunk ingest + framing in one launch, overlap-add with a carried accumulator
+int live_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R, int slots,
+              int flush, int window, int hop, int max_chunk, int n_src, long long* new_counters, long long* table, long long* sizes,
+              int* refused);
+int launch_live_ingest_frame(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows, int max_na,
+                             int max_nf, int window, int hop, int max_chunk, hipStream_t st);
+int launch_live_overlap_add(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int n_src, int window,
+                            int hop, int max_chunk, int flush, hipStream_t st);
+int launch_live_reset(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk, hipStream_t st);
+
 // preparing raw recordings (k_prep.hip): uint8 mouth ROIs -> normalised lips, waveform normalisation, polyphase resampling
 int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,
                         hipStream_t st);

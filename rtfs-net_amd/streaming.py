@@ -1,0 +1,268 @@
+"""Live streams chunk by chunk: ``AVNet.open_streams`` -> ``StreamPool`` (DESIGN.md "Live streams").
+
+The stateful form of ``AVNet.separate_long``: audio and lip embeddings arrive a chunk at a time, every window of the long-form plan runs
+as soon as its samples and its frames are there, and the samples no later window can touch leave at once.  For any way of cutting a
+recording into chunks the concatenated outputs equal ``separate_long`` on the whole recording with the same ``window`` / ``hop``.
+
+All arithmetic of a tick (counters, ready windows, ring positions, output ranges) is ``rtfs_live_plan`` (host only); Python keeps four
+integers per slot and never reads anything back from the device."""
+from __future__ import annotations
+
+import ctypes
+import operator
+
+import torch
+
+from . import _lib, layers
+
+SPF = 640  # samples per video frame: 16 kHz audio, 25 fps video
+MAX_CAPACITY = 1 << 24  # RTFS_LIVE_MAX_CAPACITY: window + max_chunk at most, so that every launch grid fits
+PLAN_WORDS = 13  # RTFS_LIVE_PLAN_WORDS: [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]
+_REASONS = {1: "bad argument", 2: "unknown slot id", 3: "slot named twice", 4: "chunk larger than max_chunk",
+            5: "audio ran too far ahead of video: the push would overwrite samples a not-yet-emitted window needs",
+            6: "video ran too far ahead of audio: the push would overwrite frames a not-yet-emitted window needs",
+            7: "flush of a stream with samples but no video frame", 8: "inconsistent counters"}
+
+
+def _weights(window, hop, device):
+    """The cross-fade weights of ``separate_long`` (models._longform_overlap_add_torch), float32."""
+    V = window - hop
+    i = torch.arange(window, device=device, dtype=torch.float32)
+    return torch.ones_like(i) if V == 0 else torch.minimum(torch.ones_like(i), torch.minimum((i + 0.5) / V, (window - i - 0.5) / V))
+
+
+class StreamPool:
+    """``slots`` concurrent live streams on one model (inference only).  Built by ``AVNet.open_streams``.
+
+    Per slot the pool holds, on the model's device and allocated once: a history ring of C = window + max_chunk samples, one of C / 640
+    lip-embedding frames (512 channels), and an overlap accumulator of C floats per source: 4 C (1 + n_src) + 2048 C / 640 bytes,
+    717 KB at the defaults with n_src 1.  Next to them one tick's framed windows in and out for the most windows a tick can hold,
+    slots * (1 + ceil(max_chunk / hop)) rows.  A push allocates only its flat output, the tick table and one chunk's ``forward``.
+
+    Host state is four integers per slot: a samples received, f frames received, e windows emitted, o samples output.  Window n is
+    ready when a >= n hop + window and f >= n hop / 640 + window / 640.
+
+    Because each tick uploads a small table (one host-to-device copy), ``push`` / ``flush`` are NOT capturable in a HIP graph."""
+
+    def __init__(self, model, slots, window, hop, max_chunk, max_batch):
+        self.model, self.slots, self.window, self.hop, self.max_chunk, self.max_batch = model, slots, window, hop, max_chunk, max_batch
+        self.n_src = int(model.n_src)
+        self.capacity = window + max_chunk
+        self.device = next(model.parameters()).device
+        self.on_hip = bool(model.fused) and self.device.type == "cuda"
+        self._counters = [[0, 0, 0, 0] for _ in range(slots)]
+        C, Wv, dev = self.capacity, window // SPF, self.device
+        rows_cap = slots * (1 + -(-max_chunk // hop))
+        self._aring = _lib.empty(slots, C, device=dev)
+        self._vring = _lib.empty(slots, 512, C // SPF, device=dev)
+        self._acc = _lib.empty(slots, self.n_src, C, device=dev)
+        self._xw = _lib.empty(rows_cap, window, device=dev)
+        self._vw = _lib.empty(rows_cap, 512, Wv, device=dev)
+        self._y = _lib.empty(rows_cap, self.n_src, window, device=dev)
+        self._reset_state(None, slots)
+
+    # -- public
+    def counters(self, slot):
+        """(a, f, e, o) of a slot: samples received, frames received, windows emitted, samples output."""
+        return tuple(self._counters[int(slot)])
+
+    def push(self, slot_ids, audio_chunks, video_chunks):
+        """One chunk of audio and one of lip embeddings for each slot named.  audio chunk (n)|(1,n) float32 with 0 <= n <= max_chunk, video
+        chunk (512,m) float32 with 0 <= m <= max_chunk // 640, separate allocations on the pool's device; the two sides need not arrive in
+        step and either may be empty.  Returns, per named slot, the (n_src, k) newly final samples (k may be 0): views of one flat output
+        whose per-slot blocks start on 128-byte lines.
+
+        Every ready window of every named slot runs in this call, laid out in the order the slots are named, then by window index, through
+        ``forward`` in chunks of ``max_batch`` rows.  ValueError - before any launch, all state unchanged - for an unknown or repeated slot
+        id, a bad shape / dtype / device, an oversize chunk, or a push that would overwrite history a not-yet-emitted window still needs
+        (one side more than ``max_chunk`` ahead of the other).  Not capturable in a HIP graph (the tick table is uploaded per call)."""
+        ids, na, nf, wavs, vids = self._check_chunks(slot_ids, audio_chunks, video_chunks)
+        return self._tick(ids, na, nf, wavs, vids, flush=False)
+
+    def flush(self, slot_ids):
+        """End the named streams: run the windows ``separate_long``'s plan still owes for L = samples received and Tv = frames received
+        (zeros past L, a frame index past Tv - 1 reads frame Tv - 1), return the remaining samples up to L per slot, and reset the slots.
+        A slot that received nothing returns (n_src, 0); one with samples but no frame raises ValueError (state unchanged)."""
+        ids = self._check_ids(slot_ids)
+        return self._tick(ids, None, None, None, None, flush=True)
+
+    def reset(self, slot_ids):
+        """Drop the named streams without output."""
+        ids = self._check_ids(slot_ids)
+        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
+            raise ValueError(f"StreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
+        if not ids:
+            return
+        self._reset_state(torch.tensor(ids, dtype=torch.int64).to(self.device), len(ids))
+        for s in ids:
+            self._counters[s] = [0, 0, 0, 0]
+
+    # -- checks (no launch, no state change)
+    @staticmethod
+    def _check_ids(slot_ids):
+        try:
+            ids = list(slot_ids)
+        except TypeError:
+            raise ValueError("StreamPool: slot_ids must be a sequence of integers") from None
+        try:  # anything that indexes (int, numpy integers, 0-dim integer tensors), but no bool of python, numpy or torch
+            if any(isinstance(s, bool) or str(getattr(s, "dtype", "")) in ("bool", "torch.bool") for s in ids):
+                raise TypeError
+            return [operator.index(s) for s in ids]
+        except TypeError:
+            raise ValueError(f"StreamPool: slot ids must be integers; got {ids}") from None
+
+    def _check_chunks(self, slot_ids, audio_chunks, video_chunks):
+        ids = self._check_ids(slot_ids)
+        try:
+            audio_chunks, video_chunks = list(audio_chunks), list(video_chunks)
+        except TypeError:
+            raise ValueError("StreamPool.push: audio_chunks and video_chunks must be sequences of tensors") from None
+        if not len(ids) == len(audio_chunks) == len(video_chunks):
+            raise ValueError(f"StreamPool.push: {len(ids)} slot id(s), {len(audio_chunks)} audio and {len(video_chunks)} video chunk(s)")
+        wavs, vids = [], []
+        for r, (w, v) in enumerate(zip(audio_chunks, video_chunks)):
+            if not isinstance(w, torch.Tensor) or not isinstance(v, torch.Tensor):
+                raise ValueError(f"StreamPool.push: chunk {r} is not a pair of tensors")
+            if w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
+                raise ValueError(f"StreamPool.push: audio chunk {r} must be (n) or (1,n); got {tuple(w.shape)}")
+            if v.ndim != 2 or v.shape[0] != 512:
+                raise ValueError(f"StreamPool.push: video chunk {r} must be (512,m); got {tuple(v.shape)}")
+            if w.dtype != torch.float32 or v.dtype != torch.float32:
+                raise ValueError(f"StreamPool.push: chunk {r} is {w.dtype} / {v.dtype}; the kernels are float32")
+            if w.device != self.device or v.device != self.device:
+                raise ValueError(f"StreamPool.push: chunk {r} lies on {w.device} / {v.device}, the pool on {self.device}")
+            wavs.append(w.reshape(-1).contiguous())
+            vids.append(v.contiguous())
+        return ids, [int(w.shape[0]) for w in wavs], [int(v.shape[1]) for v in vids], wavs, vids
+
+    def _plan(self, ids, na, nf, flush):
+        R = len(ids)
+        LL = ctypes.c_longlong
+        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0, 0, 0, 0))]
+        new, table, sizes, refused = (LL * (4 * R))(), (LL * (PLAN_WORDS * R))(), (LL * 5)(), (ctypes.c_int * 2)()
+        rc = _lib.load().rtfs_live_plan((LL * R)(*ids), (LL * (4 * R))(*cnt), None if flush else (LL * R)(*na), None if flush else (LL * R)(*nf),
+                                        R, self.slots, int(flush), self.window, self.hop, self.max_chunk, self.n_src, new, table, sizes, refused)
+        if rc != 0:
+            r, why = refused[0], _REASONS.get(refused[1], refused[1])
+            what = "flush" if flush else "push"
+            raise ValueError(f"StreamPool.{what}: refused ({why})" + (f" at slot {ids[r]}, counters (a, f, e, o) = {tuple(cnt[4 * r:4 * r + 4])}"
+                                                                     if 0 <= r < R else "") + "; no slot was changed")
+        return list(new), list(table), [int(v) for v in sizes]
+
+    # -- one tick
+    def _tick(self, ids, na, nf, wavs, vids, flush):
+        if self.model.training:
+            raise RuntimeError("StreamPool is inference only: call .eval() on the model")
+        R = len(ids)
+        if R == 0:
+            return []
+        new, table, (rows, floats, max_span, max_na, max_nf) = self._plan(ids, na, nf, flush)
+        col = lambda k: table[k * R:(k + 1) * R]  # noqa: E731
+        n_src = self.n_src
+        with torch.no_grad():
+            if self.on_hip:
+                out = self._tick_hip(R, table, rows, floats, max_span, max_na, max_nf, wavs, vids, flush)
+            else:
+                out = self._tick_torch(R, table, rows, floats, wavs, vids, flush)
+        for r, s in enumerate(ids):
+            self._counters[s] = new[4 * r:4 * r + 4]
+        res = []
+        for o, end, off in zip(col(8), col(9), col(10)):
+            k = end - o
+            res.append(out[off:off + n_src * k].view(n_src, k))
+        return res
+
+    def _forward_rows(self, rows):
+        run = self.model.forward if self.on_hip else self.model.forward_modular
+        for c0 in range(0, rows, self.max_batch):
+            c1 = min(rows, c0 + self.max_batch)
+            self._y[c0:c1].copy_(run(self._xw[c0:c1], self._vw[c0:c1]))
+
+    def _tick_hip(self, R, table, rows, floats, max_span, max_na, max_nf, wavs, vids, flush):
+        lib, dev = _lib.load(), self.device
+        ptrs = [0] * (2 * R) if flush else [w.data_ptr() for w in wavs] + [v.data_ptr() for v in vids]
+        tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
+        st = _lib.stream_of(self._xw)
+        _lib.check(lib.rtfs_live_ingest_frame_f32(_lib.ptr(tab), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._xw), _lib.ptr(self._vw),
+                                                  R, rows, max_na, max_nf, self.window, self.hop, self.max_chunk, st), "rtfs_live_ingest_frame_f32")
+        self._forward_rows(rows)
+        out = _lib.empty(floats, device=dev)
+        if max_span > 0:
+            _lib.check(lib.rtfs_live_overlap_add_f32(_lib.ptr(tab), _lib.ptr(self._y), _lib.ptr(out), _lib.ptr(self._acc), R, max_span, self.n_src,
+                                                     self.window, self.hop, self.max_chunk, int(flush), st), "rtfs_live_overlap_add_f32")
+        if flush:
+            self._reset_state(tab[:R], R)
+        return out
+
+    def _reset_state(self, ids, R):
+        """Give the state of R slots (a device tensor of ids; None = the first R) defined contents.  No kernel reads a cell it was not
+        told by the counters to hold data, so nothing depends on these zeros; they keep one stream's samples out of the next one's
+        buffers and make every later read one of written memory."""
+        if not self.on_hip:
+            sel = slice(0, R) if ids is None else ids
+            for t in (self._aring, self._vring, self._acc):
+                t[sel] = 0
+            return
+        _lib.check(_lib.load().rtfs_live_reset_f32(_lib.ptr(ids), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._acc), R, self.n_src,
+                                                   self.window, self.max_chunk, _lib.stream_of(self._aring)), "rtfs_live_reset_f32")
+
+    # -- the same tick in torch ops (fused = False, CPU tensors): ingest, gather from the rings, accumulate window by window
+    def _tick_torch(self, R, table, rows, floats, wavs, vids, flush):
+        W, H, C, n_src, dev = self.window, self.hop, self.capacity, self.n_src, self.device
+        Cv, Wv, Hv = C // SPF, W // SPF, H // SPF
+        slot, a0, na, f0, nf, e0, cnt, row0, o0, end, off, apos, fpos = (table[k * R:(k + 1) * R] for k in range(PLAN_WORDS))
+        iw, ifr = torch.arange(W, device=dev), torch.arange(Wv, device=dev)
+        for r in range(R):
+            if not flush:  # sequential here, so the windows can be gathered from the rings after the chunks went in
+                self._aring[slot[r], (apos[r] + torch.arange(na[r], device=dev)) % C] = wavs[r]
+                self._vring[slot[r]][:, (fpos[r] + torch.arange(nf[r], device=dev)) % Cv] = vids[r]
+            lim_a, lim_f = a0[r] + na[r], f0[r] + nf[r]
+            for n in range(e0[r], e0[r] + cnt[r]):
+                row, p = row0[r] + n - e0[r], n * H + iw
+                self._xw[row] = torch.where(p < lim_a, self._aring[slot[r], p % C], torch.zeros((), device=dev))
+                self._vw[row] = self._vring[slot[r]][:, (n * Hv + ifr).clamp(max=lim_f - 1) % Cv]
+        self._forward_rows(rows)
+        out = _lib.empty(floats, device=dev)
+        w, V = _weights(W, H, dev), W - H
+        for r in range(R):
+            acc = self._acc[slot[r]]
+            for n in range(e0[r], e0[r] + cnt[r]):  # ascending n; a cell no earlier window reached starts from this window's term
+                wy, idx = w * self._y[row0[r] + n - e0[r]], (n * H + iw) % C
+                first = V if n > 0 else 0
+                acc[:, idx[:first]] += wy[:, :first]
+                acc[:, idx[first:]] = wy[:, first:]
+            k = end[r] - o0[r]
+            if k == 0:
+                continue
+            den = torch.zeros(k, device=dev)
+            for n in range(max(0, -(-(o0[r] - W + 1) // H)), e0[r] + cnt[r]):  # the windows emitted so far that reach [o, end)
+                lo, hi = max(o0[r], n * H), min(end[r], n * H + W)
+                if lo < hi:
+                    den[lo - o0[r]:hi - o0[r]] += w[lo - n * H:hi - n * H]
+            t = torch.arange(o0[r], end[r], device=dev)
+            out[off[r]:off[r] + n_src * k] = (acc[:, t % C] / den).reshape(-1)
+        if flush:
+            self._reset_state(torch.tensor(slot, dtype=torch.int64, device=dev), R)
+        return out
+
+
+def open_streams(model, slots, window=32000, hop=None, max_chunk=None, max_batch=32):
+    """``AVNet.open_streams``: check the arguments as ``separate_long`` does, then allocate the pool."""
+    slots, window = int(slots), int(window)
+    hop = window // 2 if hop is None else int(hop)
+    max_chunk = window if max_chunk is None else int(max_chunk)
+    max_batch = int(max_batch)
+    if slots < 1 or max_batch < 1:
+        raise ValueError(f"open_streams: slots = {slots}, max_batch = {max_batch}; both at least 1")
+    lib = _lib.load()
+    if lib.rtfs_longform_plan(1, 1, window, hop, None) != 0:
+        raise ValueError(f"open_streams: window = {window}, hop = {hop} must be multiples of {SPF} with 0 < hop <= window")
+    if max_chunk < SPF or max_chunk % SPF or window + max_chunk > MAX_CAPACITY:
+        raise ValueError(f"open_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF} with window + max_chunk <= {MAX_CAPACITY}")
+    rnn_kind = model.refinement_module.audio_net.get_block(0).rnn_kind
+    if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
+        raise ValueError(f"open_streams: a window of {window} samples does not fit the fused separator of this model's cell "
+                         f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
+    if model.training:
+        raise RuntimeError("AVNet.open_streams is inference only: call .eval()")
+    return StreamPool(model, slots, window, hop, max_chunk, max_batch)

@@ -101,6 +101,12 @@ class System(nn.Module):
                     embs[r] = emb[g]
         return self.audio_model.separate_many(wavs, embs, **kw)
 
+    def open_streams(self, **kw):
+        """Live streams chunk by chunk (inference): ``AVNet.open_streams(**kw)`` of the audio model.  The caller pushes lip EMBEDDINGS
+        (512,m): the video stem is a 3-D convolution with temporal context, so frames embedded chunk by chunk are not the whole-track
+        embedding without look-ahead state; embedding incrementally is out of scope (DESIGN.md "Live streams")."""
+        return self.audio_model.open_streams(**kw)
+
     def separate_recordings(self, wavs, sample_rates, mouth_rois, normalize_audio=False, **kw):
         """The list form of ``separate_recording``: wavs = R raw recordings (L_r) at ``sample_rates[r]`` Hz, mouth_rois = R uint8
         tracks (Tv_r,H,W) at 25 fps -> a list of R tensors (n_src, L_r at 16 kHz).  Per recording ``datas.resample`` to 16 kHz and the ``"val"`` pipeline on the ROIs, then ``separate_many(**kw)``.  Without a video model the mouth
