@@ -512,6 +512,49 @@ size_t rtfs_video_pack_floats(void);
 size_t rtfs_video_workspace_bytes(int B, int T);
 int rtfs_video_frontend_f32(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, void* stream);
 
+/* Live streams from camera frames (FRCNNVideoModel.open_streams / LipStreamPool; DESIGN.md "Live streams from camera frames"): the lip
+ * embedding chunk by chunk.  Only the stem is temporal (kernel 5, padding 2), so embedding q needs prepared lips frames q - 2 .. q + 2 and
+ * nothing else.  The caller keeps three integers per slot [g frames received | v embeddings emitted | side]; a push of m frames gives
+ * g' = g + m, v' = max(v, g' - 2) and emits v .. v' - 1; a flush emits v .. g - 1 with zero planes for indices >= g and returns zero
+ * counters.  Frames with index < 0 are zero planes as well: the stem's own padding, 0.0f in the PREPARED domain.  The concatenated
+ * outputs of any chunking equal rtfs_video_frontend_f32 on the whole track.
+ * State (caller-allocated, 16-byte aligned): hist (slots, 2, 4, 88, 88), two history buffers per slot; buffer `side` holds the prepared
+ *   frames max(0, g - 4) .. g - 1, frame p in plane p % 4.  A launch reads buffer `side` and writes buffer 1 - side; a push with m > 0
+ *   flips the side, so no block reads a cell another block of the same launch writes.  Which planes hold a frame follows from g.
+ * rtfs_live_video_plan (host only, no device call, the single place with the arithmetic): for the R slots named in slot_ids, counters
+ *   (R x 3, row-major) and n_frames (R; ignored when flush != 0) -> new_counters (R x 3), sizes[3] = [rows = sum of k | out_floats of ONE
+ *   flat output | largest m] and the tick table, RTFS_LIVE_VIDEO_PLAN_WORDS = 8 int64 words per named slot, column-major:
+ *   [slot | g | m | v | k | row0 | out_off | side]: the slot emits k embeddings v .. v + k - 1 in rows row0 .. of the tick's output frames
+ *   (rows lie in the order the slots are named, then by frame index); its contiguous (512, k) block starts out_off floats into the flat
+ *   output, out_off a multiple of RTFS_LIVE_ALIGN floats; side is the buffer that is read.
+ *   Refusals return -4, write nothing else, and name themselves in refused[2] = [index into slot_ids or -1 | RTFS_LIVE_* reason]:
+ *   R < 1, slots < 1, max_frames < 1 or a missing array (BAD_ARGUMENT); a slot id outside [0, slots) or named twice; m outside
+ *   [0, max_frames] (CHUNK_SIZE); counters this planner cannot have produced (negative, v > g, v < max(0, g - 2), side not 0 / 1:
+ *   BAD_COUNTERS).  new_counters, table, sizes, refused may be NULL.
+ * rtfs_live_video_ingest_u8 / _f32 (one launch each): table = the plan's 8 R words followed by one more column, the DEVICE address of each
+ *   slot's chunk - separate allocations, read where they lie: uint8 (m, H, W) at any byte alignment, or float32 prepared lips
+ *   (m, 88, 88) at 4-byte alignment.  Writes the tick's stem input windows (rows, 5, 94, 94): for output frame n its own zero-bordered
+ *   5-frame window, the stem's layout at T = 1, and leaves buffer 1 - side of every slot with m > 0 holding frames g' - 4 .. g' - 1.
+ *   uint8 pixels go through f(v) = (float)(((double(v) - 0.0) / 255.0 - mean) / std) at crop offset (dy, dx), exactly as
+ *   rtfs_lips_prepare_u8 without flip.  flush != 0: frames >= g are zero planes and no history is written.
+ * rtfs_video_frontend_windows_f32: stem, max-pool, trunk and average pool of rtfs_video_frontend_f32 on rows [row_begin, row_begin + n)
+ *   of a window volume (windows points at row 0), then frame row's 512 values go to column row - row0 of its slot's (512, k) block of out
+ *   through the table.  ws: rtfs_video_windows_workspace_bytes(n).
+ * rtfs_live_video_reset (one launch): zeroes both history buffers of the R slots in ids (DEVICE array; NULL = slots 0 .. R - 1).  No
+ *   kernel depends on those contents.
+ * The launches take the caller's stream, allocate nothing, read nothing back, use no atomics and trust the device table: pass what
+ * rtfs_live_video_plan wrote.  hist, windows, out 16-byte aligned, tables 8-byte aligned (-4); a grid that would not fit: -1. */
+#define RTFS_LIVE_VIDEO_PLAN_WORDS 8
+int rtfs_live_video_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                         int max_frames, long long* new_counters, long long* table, long long* sizes, int* refused);
+int rtfs_live_video_ingest_u8(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, int H, int W,
+                              int dy, int dx, double mean, double std, void* stream);
+int rtfs_live_video_ingest_f32(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, void* stream);
+size_t rtfs_video_windows_workspace_bytes(int rows);
+int rtfs_video_frontend_windows_f32(const float* windows, const float* pack, const long long* table, float* out, int R, int row_begin,
+                                    int n, void* ws, size_t ws_bytes, void* stream);
+int rtfs_live_video_reset(const long long* ids, float* hist, int R, void* stream);
+
 /* Optimizer step on the device (rtfs-net_amd/optimizers.py AdamW; the reference builds torch.optim.AdamW through
  * src/system/optimizers.py:58-108 and Lightning clips at gradient_clip_val 5.0, train.py:142): gather of the per-tensor gradients into
  * one flat buffer, global-norm clip and AdamW in a number of launches that does not depend on the number of tensors.

@@ -142,6 +142,12 @@ SIGNATURES = {
     "rtfs_video_pack_floats": (_z, []),
     "rtfs_video_workspace_bytes": (_z, [_i, _i]),
     "rtfs_video_frontend_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),
+    "rtfs_live_video_plan": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "rtfs_live_video_ingest_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _p]),
+    "rtfs_live_video_ingest_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "rtfs_video_windows_workspace_bytes": (_z, [_i]),
+    "rtfs_video_frontend_windows_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _z, _p]),
+    "rtfs_live_video_reset": (_i, [_p, _p, _i, _p]),
     "rtfs_optim_plan": (_i, [_p, _i, _p, _p, _p]),
     "rtfs_optim_gather_f32": (_i, [_p, _p, _i, _i, _p, _p, _i, _p]),
     "rtfs_optim_sumsq_f32": (_i, [_p, _i, _i, _p, _p, _p]),

@@ -1,0 +1,260 @@
+// Live streams from camera frames (FRCNNVideoModel.open_streams / LipStreamPool; DESIGN.md "Live streams from camera frames"): the lip
+// embedding chunk by chunk.  Only the stem of the front-end is temporal (Conv3d kernel 5, padding 2; k_video.hip), so embedding q needs
+// the prepared lips frames q - 2 .. q + 2 and nothing else: the state of a stream is its last four prepared frames, the look-ahead two
+// frames.  tests/live_video_oracle.py restates counters, emitted ranges and the windows in numpy.
+//
+// Host counters per slot (kept by the caller, nothing is read back): g frames received, v embeddings emitted, side.
+//   push of m frames:  g' = g + m, v' = max(v, g' - 2), emits v .. v' - 1;  side' = 1 - side when m > 0
+//   flush:             emits v .. g - 1 with zero planes for frame indices >= g;  counters return to zero
+// Frames with index < 0 are zero planes too.  Zero means 0.0f in the PREPARED domain, what vid_pad_kernel writes, not f(0).
+//
+// State per slot, device resident: hist (slots, 2, 4, 88, 88), two history buffers.  Buffer `side` holds the frames max(0, g - 4) .. g - 1,
+// frame p in plane p % 4.
+//
+//   live_video_plan            host only, the single place with the arithmetic: counters + chunk sizes -> new counters and the tick
+//                              table, 8 int64 words per named slot, column-major [slot | g | m | v | k | row0 | out_off | side]; the
+//                              caller appends one column of chunk pointers and uploads the 9 R words with one copy
+//   live_video_ingest_kernel   ONE launch: block x < 5 rows writes plane j = x % 5 of output frame x / 5's zero-bordered window
+//                              (rows, 5, 94, 94), the stem's layout at T = 1; blocks x >= 5 rows write the new history planes
+//   live_video_scatter_kernel  (n, 512) embeddings of the tick's rows -> column row - row0 of each slot's (512, k) block
+//   live_video_reset_kernel    gives a slot's history defined contents (zeros)
+//
+// WHY NO BLOCK READS A HISTORY CELL THAT ANOTHER BLOCK OF THE SAME LAUNCH WRITES.  Every read of the launch - a window plane of a frame
+// p < g, or a frame p < g that stays in the history because m < 4 - goes to buffer `side` of its slot; every write goes to buffer
+// 1 - side of its slot, plane p % 4 for the frames p in [max(0, g' - 4), g'), which are four different residues: one writer per cell.
+// Two named slots never share state, and live_video_plan refuses a slot named twice.  A push with m = 0 and a flush write no history
+// (the side stays).  (One ring indexed p % 4 would have the block that writes frame g + 1 race the block that still reads frame g - 3
+// when m < 4, and a ring of 8 does the same with m > 4: the read and written index ranges are m - 3 .. m + 3 apart.)
+// A plane of buffer `side` is read only for a frame index in [max(0, g - 4), g): it was written by the push that made it current or
+// carried over by it, so no kernel depends on what reset wrote.
+#include "common.h"
+#include "kernels.h"
+#include "longform_common.h"  // VCH, many_find
+#include "../../include/rtfs_amd.h"  // RTFS_LIVE_*
+
+namespace {
+
+constexpr int LV_CROP = 88, LV_PAD = 94, LV_PLANE = LV_PAD * LV_PAD, LV_IMG = LV_CROP * LV_CROP, LV_HIST = 4, LV_WIN = 5;
+constexpr int LV_ALIGN = RTFS_LIVE_ALIGN;
+// columns of the tick table
+enum { V_SLOT, V_G, V_M, V_V, V_K, V_ROW0, V_OFF, V_SIDE, V_PTR };
+
+// where frame p of the slot of table row r comes from in this launch: nowhere (a zero plane), buffer `side`, or the chunk
+template <bool U8>
+struct FrameSrc {
+    const float* f;          // prepared plane (88, 88), or null
+    const unsigned char* b;  // uint8 plane (H, W) at the crop offset, or null
+};
+
+template <bool U8>
+__device__ __forceinline__ FrameSrc<U8> frame_src(const long long* __restrict__ table, const float* hist, int R, int r, long long p, int H,
+                                                  int W, int dy, int dx) {
+    const long long g = table[(size_t)V_G * R + r], lim = g + table[(size_t)V_M * R + r];  // at a flush m = 0: frames >= g are zeros
+    FrameSrc<U8> s{nullptr, nullptr};
+    if (p < 0 || p >= lim) return s;
+    if (p < g) {
+        const size_t slot = (size_t)table[(size_t)V_SLOT * R + r], side = (size_t)table[(size_t)V_SIDE * R + r];
+        s.f = hist + ((slot * 2 + side) * LV_HIST + (size_t)(p & 3)) * LV_IMG;
+    } else if (U8) {
+        s.b = (const unsigned char*)(uintptr_t)table[(size_t)V_PTR * R + r] + ((size_t)(p - g) * H + dy) * W + dx;
+    } else {
+        s.f = (const float*)(uintptr_t)table[(size_t)V_PTR * R + r] + (size_t)(p - g) * LV_IMG;
+    }
+    return s;
+}
+
+template <bool U8>
+__global__ __launch_bounds__(256) void live_video_ingest_kernel(const long long* __restrict__ table, float* hist, float* __restrict__ win, int R,
+                                                                int rows, int H, int W, int dy, int dx, double mean, double stdv) {
+    __shared__ float lut[256];
+    const int tid = threadIdx.x;
+    if (U8) {  // the 256 possible values through the reference's float64 arithmetic, as lips_prepare_kernel (k_prep.hip)
+        lut[tid] = (float)((((double)tid - 0.0) / 255.0 - mean) / stdv);
+        __syncthreads();
+    }
+    if ((int)blockIdx.x < rows * LV_WIN) {
+        // ---- stem input: plane j of output frame `row`
+        const int row = blockIdx.x / LV_WIN, j = blockIdx.x - row * LV_WIN;
+        const int r = many_find(table + (size_t)V_ROW0 * R, R, row);  // block-uniform
+        const int nl = row - (int)table[(size_t)V_ROW0 * R + r];
+        if (nl >= (int)table[(size_t)V_K * R + r]) return;  // a table that does not cover this row: write nothing
+        const long long p = table[(size_t)V_V * R + r] + nl - 2 + j;
+        const FrameSrc<U8> s = frame_src<U8>(table, hist, R, r, p, H, W, dy, dx);
+        float* dst = win + (size_t)blockIdx.x * LV_PLANE;
+        for (int i = tid; i < LV_PLANE; i += 256) {
+            const int yy = i / LV_PAD, y = yy - 3, x = i - yy * LV_PAD - 3;
+            float v = 0.f;
+            if (y >= 0 && y < LV_CROP && x >= 0 && x < LV_CROP) {
+                if (s.f) v = s.f[y * LV_CROP + x];
+                else if (U8 && s.b) v = lut[s.b[(size_t)y * W + x]];
+            }
+            dst[i] = v;
+        }
+        return;
+    }
+    // ---- history: plane c of buffer 1 - side of the slot of table row r
+    const int hb = blockIdx.x - rows * LV_WIN, r = hb / LV_HIST, c = hb - r * LV_HIST;
+    const long long m = table[(size_t)V_M * R + r];
+    if (m <= 0) return;  // nothing arrived: the side stays
+    const long long g1 = table[(size_t)V_G * R + r] + m;
+    const long long p = g1 - LV_HIST + ((c - (g1 - LV_HIST)) & 3);  // the frame of [g' - 4, g') that lives in plane c
+    if (p < 0) return;
+    const FrameSrc<U8> s = frame_src<U8>(table, hist, R, r, p, H, W, dy, dx);
+    const size_t slot = (size_t)table[(size_t)V_SLOT * R + r], other = 1 - (size_t)table[(size_t)V_SIDE * R + r];
+    float* dst = hist + ((slot * 2 + other) * LV_HIST + c) * LV_IMG;
+    for (int i = tid; i < LV_IMG; i += 256) {
+        const int y = i / LV_CROP, x = i - y * LV_CROP;
+        float v = 0.f;
+        if (s.f) v = s.f[i];
+        else if (U8 && s.b) v = lut[s.b[(size_t)y * W + x]];
+        dst[i] = v;
+    }
+}
+
+// emb (n, 512): frame i = row row_begin + i of the tick -> out[out_off + c k + (row - row0)]
+__global__ __launch_bounds__(256) void live_video_scatter_kernel(const float* __restrict__ emb, const long long* __restrict__ table,
+                                                                 float* __restrict__ out, int R, int row_begin) {
+    const int row = row_begin + blockIdx.x;
+    const int r = many_find(table + (size_t)V_ROW0 * R, R, row);
+    const long long col = row - table[(size_t)V_ROW0 * R + r], k = table[(size_t)V_K * R + r];
+    if (col >= k) return;
+    float* dst = out + table[(size_t)V_OFF * R + r] + col;
+    for (int c = threadIdx.x; c < VCH; c += 256) dst[(size_t)c * k] = emb[(size_t)blockIdx.x * VCH + c];
+}
+
+__global__ __launch_bounds__(256) void live_video_reset_kernel(const long long* __restrict__ ids, float* __restrict__ hist) {
+    const size_t slot = ids ? (size_t)ids[blockIdx.x] : blockIdx.x;
+    const int q = blockIdx.y * 256 + threadIdx.x;
+    if (q < 2 * LV_HIST * LV_IMG / 4) *(f32x4*)(hist + slot * 2 * LV_HIST * LV_IMG + 4 * (size_t)q) = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+}  // namespace
+
+int live_video_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                    int max_frames, long long* new_counters, long long* table, long long* sizes, int* refused) {
+    auto refuse = [&](int r, int reason) {
+        if (refused) {
+            refused[0] = r;
+            refused[1] = reason;
+        }
+        return RTFS_ERR_ARG;
+    };
+    if (!slot_ids || !counters || R < 1 || slots < 1 || max_frames < 1 || (!flush && !n_frames)) return refuse(-1, RTFS_LIVE_BAD_ARGUMENT);
+    const long long LIMIT = 1LL << 60;
+    for (int r = 0; r < R; ++r) {
+        if (slot_ids[r] < 0 || slot_ids[r] >= slots) return refuse(r, RTFS_LIVE_UNKNOWN_SLOT);
+        for (int q = 0; q < r; ++q)
+            if (slot_ids[q] == slot_ids[r]) return refuse(r, RTFS_LIVE_REPEATED_SLOT);
+    }
+    long long rows = 0, off = 0, max_m = 0;
+    // two passes, so that a refusal at any slot leaves every output unwritten: pass 0 only checks, pass 1 only writes
+    for (int pass = 0; pass < 2; ++pass) {
+        rows = off = max_m = 0;
+        for (int r = 0; r < R; ++r) {
+            const long long g = counters[3 * r], v = counters[3 * r + 1], side = counters[3 * r + 2];
+            if (g < 0 || v < 0 || g > LIMIT || v > g || v < (g > 2 ? g - 2 : 0) || (side != 0 && side != 1))
+                return refuse(r, RTFS_LIVE_BAD_COUNTERS);
+            long long m = 0, v1;
+            if (!flush) {
+                m = n_frames[r];
+                if (m < 0 || m > max_frames) return refuse(r, RTFS_LIVE_CHUNK_SIZE);
+                v1 = g + m - 2 > v ? g + m - 2 : v;
+            } else {
+                v1 = g;
+            }
+            const long long k = v1 - v;
+            if (pass && table) {
+                const long long col[RTFS_LIVE_VIDEO_PLAN_WORDS] = {slot_ids[r], g, m, v, k, rows, off, side};
+                for (int w = 0; w < RTFS_LIVE_VIDEO_PLAN_WORDS; ++w) table[(size_t)w * R + r] = col[w];
+            }
+            if (pass && new_counters) {
+                new_counters[3 * r] = flush ? 0 : g + m;
+                new_counters[3 * r + 1] = flush ? 0 : v1;
+                new_counters[3 * r + 2] = flush ? 0 : (m > 0 ? 1 - side : side);
+            }
+            rows += k;
+            off += ((long long)VCH * k + LV_ALIGN - 1) / LV_ALIGN * LV_ALIGN;
+            if (rows > 0x7fffffffLL / LV_WIN || off > LIMIT) return refuse(r, RTFS_LIVE_BAD_ARGUMENT);
+            max_m = m > max_m ? m : max_m;
+        }
+    }
+    if (sizes) {
+        sizes[0] = rows;
+        sizes[1] = off;
+        sizes[2] = max_m;
+    }
+    if (refused) refused[0] = -1, refused[1] = 0;
+    return RTFS_OK;
+}
+
+int launch_live_video_ingest(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, bool u8, int H, int W,
+                             int dy, int dx, double mean, double stdv, hipStream_t st) {
+    if (R < 1 || rows < 0 || max_m < 0 || (flush && max_m != 0)) return RTFS_ERR_SHAPE;
+    if (u8) {
+        if (H < LV_CROP || W < LV_CROP || H > 0x7fff || W > 0x7fff) return RTFS_ERR_SHAPE;
+        if (dy < 0 || dx < 0 || dy + LV_CROP > H || dx + LV_CROP > W || !(stdv != 0.0)) return RTFS_ERR_ARG;
+    }
+    if (((((uintptr_t)hist) | ((uintptr_t)windows)) & 15) || (((uintptr_t)table) & 7)) return RTFS_ERR_ARG;
+    if (rows == 0 && max_m == 0) return RTFS_OK;  // nothing arrived, nothing is ready
+    const long long blocks = (long long)rows * LV_WIN + (max_m > 0 ? (long long)R * LV_HIST : 0);
+    if (blocks > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    if (u8)
+        hipLaunchKernelGGL(live_video_ingest_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, table, hist, windows, R, rows, H, W, dy, dx,
+                           mean, stdv);
+    else
+        hipLaunchKernelGGL(live_video_ingest_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, table, hist, windows, R, rows, LV_CROP,
+                           LV_CROP, 0, 0, 0.0, 1.0);
+    return rtfs_launch_status();
+}
+
+int launch_live_video_scatter(const float* emb, const long long* table, float* out, int R, int row_begin, int n, hipStream_t st) {
+    if (R < 1 || row_begin < 0 || n < 1 || (long long)row_begin + n > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    if (((((uintptr_t)emb) | ((uintptr_t)out)) & 15) || (((uintptr_t)table) & 7)) return RTFS_ERR_ARG;
+    hipLaunchKernelGGL(live_video_scatter_kernel, dim3(n), dim3(256), 0, st, emb, table, out, R, row_begin);
+    return rtfs_launch_status();
+}
+
+int launch_live_video_reset(const long long* ids, float* hist, int R, hipStream_t st) {
+    if (R < 1) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)hist) & 15) || (((uintptr_t)ids) & 7)) return RTFS_ERR_ARG;
+    hipLaunchKernelGGL(live_video_reset_kernel, dim3(R, cdiv(2 * LV_HIST * LV_IMG / 4, 256)), dim3(256), 0, st, ids, hist);
+    return rtfs_launch_status();
+}
+
+extern "C" {
+
+int rtfs_live_video_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                         int max_frames, long long* new_counters, long long* table, long long* sizes, int* refused) {
+    return live_video_plan(slot_ids, counters, n_frames, R, slots, flush, max_frames, new_counters, table, sizes, refused);
+}
+
+int rtfs_live_video_ingest_u8(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, int H, int W,
+                              int dy, int dx, double mean, double std, void* stream) {
+    if (!table || !hist || (!windows && rows > 0)) return RTFS_ERR_ARG;
+    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, true, H, W, dy, dx, mean, std, (hipStream_t)stream);
+}
+
+int rtfs_live_video_ingest_f32(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, void* stream) {
+    if (!table || !hist || (!windows && rows > 0)) return RTFS_ERR_ARG;
+    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, false, 0, 0, 0, 0, 0.0, 1.0, (hipStream_t)stream);
+}
+
+size_t rtfs_video_windows_workspace_bytes(int rows) { return video_windows_workspace_bytes(rows); }
+
+int rtfs_video_frontend_windows_f32(const float* windows, const float* pack, const long long* table, float* out, int R, int row_begin,
+                                    int n, void* ws, size_t ws_bytes, void* stream) {
+    if (!windows || !pack || !table || !out || !ws) return RTFS_ERR_ARG;
+    if (R < 1 || row_begin < 0 || n < 1 || (long long)row_begin + n > 0x7fffffffLL / LV_WIN) return RTFS_ERR_SHAPE;
+    if (ws_bytes < video_windows_workspace_bytes(n)) return RTFS_ERR_WORKSPACE;
+    if (((((uintptr_t)windows) | ((uintptr_t)out) | ((uintptr_t)ws)) & 15) || (((uintptr_t)table) & 7)) return RTFS_ERR_ARG;
+    float* emb = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + video_windows_workspace_bytes(n)) - (size_t)n * VCH;
+    if (int rc = video_frontend_windows(windows + (size_t)row_begin * LV_WIN * LV_PLANE, pack, emb, n, ws, ws_bytes, (hipStream_t)stream)) return rc;
+    return launch_live_video_scatter(emb, table, out, R, row_begin, n, (hipStream_t)stream);
+}
+
+int rtfs_live_video_reset(const long long* ids, float* hist, int R, void* stream) {
+    if (!hist) return RTFS_ERR_ARG;
+    return launch_live_video_reset(ids, hist, R, (hipStream_t)stream);
+}
+
+}  // extern "C"

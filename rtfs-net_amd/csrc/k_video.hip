@@ -458,41 +458,49 @@ size_t video_workspace_bytes(int B, int T) {
     return n * sizeof(float);
 }
 
-int video_frontend(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (B < 1 || T < 1) return RTFS_ERR_SHAPE;
-    if (ws_bytes < video_workspace_bytes(B, T)) return RTFS_ERR_WORKSPACE;
-    const int N = B * T;
-    float* w = reinterpret_cast<float*>(ws);
-    float* xp = w;
-    w += (size_t)B * (T + 4) * 94 * 94;
-    float* y44 = w;
-    w += (size_t)N * 64 * 44 * 44;
-    const int planes[4] = {64, 128, 256, 512}, hw[4] = {24, 13, 8, 5};
+namespace {
+
+// the activation buffers of one call, laid out in the workspace behind the padded volume
+struct VidBufs {
+    float* y44;
     float* buf[4][3];
-    float* act0 = w;
+};
+
+constexpr int VID_PLANES[4] = {64, 128, 256, 512}, VID_HW[4] = {24, 13, 8, 5};
+
+float* vid_layout(float* w, int N, VidBufs& v) {
+    v.y44 = w;
+    w += (size_t)N * 64 * 44 * 44;
     for (int li = 0; li < 4; ++li)
         for (int k = 0; k < 3; ++k) {
-            buf[li][k] = w;
-            w += (size_t)N * planes[li] * hw[li] * hw[li];
+            v.buf[li][k] = w;
+            w += (size_t)N * VID_PLANES[li] * VID_HW[li] * VID_HW[li];
         }
-    (void)act0;
+    return w;
+}
+
+int vid_borders(const VidBufs& v, int N, hipStream_t st) {
     for (int li = 0; li < 4; ++li)  // zero borders (interiors are always written before they are read)
         for (int k = 0; k < 3; ++k) {
-            const size_t cnt = (size_t)N * 4 * (hw[li] - 1) * (planes[li] / 4);
-            hipLaunchKernelGGL(vid_border_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, buf[li][k], N, hw[li] - 2, planes[li]);
+            const size_t cnt = (size_t)N * 4 * (VID_HW[li] - 1) * (VID_PLANES[li] / 4);
+            hipLaunchKernelGGL(vid_border_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, v.buf[li][k], N, VID_HW[li] - 2, VID_PLANES[li]);
         }
-    if (rtfs_launch_status()) return RTFS_ERR_LAUNCH;
+    return rtfs_launch_status() ? RTFS_ERR_LAUNCH : RTFS_OK;
+}
+
+// stem, max pool, trunk and average pool from the zero-padded volume xp (B, T+4, 94, 94) -> out (B, 512, T)
+int vid_from_padded(const float* xp, const float* pack, float* out, int B, int T, const VidBufs& v, hipStream_t st) {
+    const int N = B * T;
+    const int* planes = VID_PLANES;
+    const int* hw = VID_HW;
+    float* y44 = v.y44;
+    float* const (&buf)[4][3] = v.buf;
     size_t off = 0;
     auto take = [&](size_t n) {
         const float* r = pack + off;
         off += (n + 63) / 64 * 64;
         return r;
     };
-    {
-        const size_t total = (size_t)B * (T + 4) * 94 * 94;
-        hipLaunchKernelGGL(vid_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, lips, xp, B, T);
-        if (rtfs_launch_status()) return RTFS_ERR_LAUNCH;
-    }
     {  // stem conv + BN + PReLU -> (N,64,44,44); max pool -> buf[0][0] (N,64,24,24 padded)
         VidConvArgs a{};
         a.x = xp; a.w16 = reinterpret_cast<const half8*>(take(64 * 256)); a.bias = take(64); a.slope = take(64);
@@ -542,4 +550,38 @@ int video_frontend(const float* lips, const float* pack, float* out, int B, int 
     }
     hipLaunchKernelGGL(vid_avgpool_kernel, dim3(cdiv(N * 512, 256)), dim3(256), 0, st, x, out, B, T, 512, 3);
     return rtfs_launch_status();
+}
+
+}  // namespace
+
+int video_frontend(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (B < 1 || T < 1) return RTFS_ERR_SHAPE;
+    if (ws_bytes < video_workspace_bytes(B, T)) return RTFS_ERR_WORKSPACE;
+    float* xp = reinterpret_cast<float*>(ws);
+    VidBufs v;
+    vid_layout(xp + (size_t)B * (T + 4) * 94 * 94, B * T, v);
+    if (int rc = vid_borders(v, B * T, st)) return rc;
+    {
+        const size_t total = (size_t)B * (T + 4) * 94 * 94;
+        hipLaunchKernelGGL(vid_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, lips, xp, B, T);
+        if (rtfs_launch_status()) return RTFS_ERR_LAUNCH;
+    }
+    return vid_from_padded(xp, pack, out, B, T, v, st);
+}
+
+// The same trunk on a caller's window volume (rows, 5, 94, 94): the stem's layout at T = 1, every row its own zero-padded clip of one
+// frame.  Workspace: the activation buffers of video_frontend(rows, 1) without its padded volume, then emb (rows, 512).
+size_t video_windows_workspace_bytes(int rows) {
+    if (rows < 1) return 0;
+    return video_workspace_bytes(rows, 1) - (size_t)rows * 5 * 94 * 94 * sizeof(float) + (size_t)rows * 512 * sizeof(float);
+}
+
+int video_frontend_windows(const float* windows, const float* pack, float* emb, int n, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (n < 1) return RTFS_ERR_SHAPE;
+    if (ws_bytes < video_windows_workspace_bytes(n)) return RTFS_ERR_WORKSPACE;
+    VidBufs v;
+    float* end = vid_layout(reinterpret_cast<float*>(ws), n, v);
+    if (emb != end) return RTFS_ERR_ARG;  // the embeddings lie behind the activations
+    if (int rc = vid_borders(v, n, st)) return rc;
+    return vid_from_padded(windows, pack, emb, n, 1, v, st);  // (n, 512, 1) = (n, 512)
 }

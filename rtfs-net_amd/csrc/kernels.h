@@ -364,6 +364,17 @@ int launch_resample(const float* x, const float* bank, float* y, int B, int L, i
 size_t video_pack_floats();
 size_t video_workspace_bytes(int B, int T);
 int video_frontend(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
+// the same from a caller's padded window volume (rows, 5, 94, 94), T = 1 per row: -> emb (n, 512) at the end of the workspace
+size_t video_windows_workspace_bytes(int rows);
+int video_frontend_windows(const float* windows, const float* pack, float* emb, int n, void* ws, size_t ws_bytes, hipStream_t st);
+
+// live streams from camera frames (k_live_video.hip): tick plan (host), chunk ingest + stem windows in one launch, embedding scatter
+int live_video_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                    int max_frames, long long* new_counters, long long* table, long long* sizes, int* refused);
+int launch_live_video_ingest(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, bool u8, int H, int W,
+                             int dy, int dx, double mean, double stdv, hipStream_t st);
+int launch_live_video_scatter(const float* emb, const long long* table, float* out, int R, int row_begin, int n, hipStream_t st);
+int launch_live_video_reset(const long long* ids, float* hist, int R, hipStream_t st);
 
 // training-side GEMMs and SRU scans (k_train_gemm.hip, k_train_rnn.hip)
 struct GemmArgs {

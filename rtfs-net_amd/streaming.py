@@ -266,3 +266,287 @@ def open_streams(model, slots, window=32000, hop=None, max_chunk=None, max_batch
     if model.training:
         raise RuntimeError("AVNet.open_streams is inference only: call .eval()")
     return StreamPool(model, slots, window, hop, max_chunk, max_batch)
+
+
+# ================================================================ live streams from camera frames (DESIGN.md "Live streams from camera frames")
+VIDEO_PLAN_WORDS = 8  # RTFS_LIVE_VIDEO_PLAN_WORDS: [slot | g | m | v | k | row0 | out_off | side]
+LOOKAHEAD = 2  # frames: the stem's temporal kernel is 5 with padding 2, so embedding q needs the prepared frames q - 2 .. q + 2
+CROP = 88
+
+
+class LipStreamPool:
+    """``slots`` concurrent lip tracks embedded chunk by chunk (inference only).  Built by ``FRCNNVideoModel.open_streams``.
+
+    For any way of cutting a track into chunks, the concatenation of what ``push`` and the final ``flush`` return equals
+    ``video_model(lips_whole)`` of that track.  Only the stem is temporal, so the state of a slot is its last four prepared frames (two
+    buffers of 4 x 88 x 88 floats, read one and write the other: 248 KB per slot) and embeddings lag the frames received by two frames,
+    80 ms at 25 fps.  Next to the state the pool holds one tick's stem input, slots * max_frames windows of (5, 94, 94).
+
+    Host state per slot: g frames received, v embeddings emitted (and the side of the history that is current).  All arithmetic of a
+    tick is ``rtfs_live_video_plan`` (host only); nothing is read back from the device.  Not capturable in a HIP graph (the tick table
+    is uploaded per call)."""
+
+    def __init__(self, model, slots, max_frames, roi_hw, max_batch_frames):
+        self.model, self.slots, self.max_frames, self.roi_hw, self.max_batch_frames = model, slots, max_frames, roi_hw, max_batch_frames
+        self.device = next(model.parameters()).device
+        self.on_hip = self.device.type == "cuda"
+        self._counters = [[0, 0, 0] for _ in range(slots)]
+        self._hist = _lib.empty(slots, 2, 4, CROP, CROP, device=self.device)
+        self._win = _lib.empty(slots * max(max_frames, LOOKAHEAD), 5, 94, 94, device=self.device)
+        self._reset_state(None, slots)
+
+    # -- public
+    def counters(self, slot):
+        """(g, v) of a slot: frames received, embeddings emitted."""
+        return tuple(self._counters[int(slot)][:2])
+
+    def push(self, slot_ids, chunks):
+        """One chunk of mouth frames for each slot named: uint8 ROIs (m,H,W) with (H,W) == roi_hw, which go through the ``"val"`` pipeline
+        (centre crop, scale, normalise) inside the ingest launch, or float32 prepared lips (m,88,88), taken as they are; one kind per
+        call, 0 <= m <= max_frames, separate allocations on the pool's device.  Returns, per named slot, the (512, k) embeddings that
+        became final (k may be 0): views of one flat output.  Embedding q is emitted once frame q + 2 has arrived.
+
+        ValueError - before any launch, all state unchanged - for an unknown or repeated slot id, a bad shape / dtype / device or an
+        oversize chunk."""
+        ids, ms, chunks, u8 = self._check_chunks(slot_ids, chunks)
+        return self._tick(ids, ms, chunks, u8, flush=False)
+
+    def flush(self, slot_ids):
+        """End the named tracks: the embeddings still owed, v .. g - 1, with the stem's end padding behind frame g - 1, then reset the slots.
+        A slot that received nothing returns (512, 0)."""
+        return self._tick(self._check_ids(slot_ids), None, None, False, flush=True)
+
+    def reset(self, slot_ids):
+        """Drop the named tracks without output."""
+        ids = self._check_ids(slot_ids)
+        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
+            raise ValueError(f"LipStreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
+        if not ids:
+            return
+        self._reset_state(torch.tensor(ids, dtype=torch.int64).to(self.device), len(ids))
+        for s in ids:
+            self._counters[s] = [0, 0, 0]
+
+    # -- checks (no launch, no state change)
+    _check_ids = staticmethod(StreamPool._check_ids)
+
+    def _check_chunks(self, slot_ids, chunks):
+        ids = self._check_ids(slot_ids)
+        try:
+            chunks = list(chunks)
+        except TypeError:
+            raise ValueError("LipStreamPool.push: chunks must be a sequence of tensors") from None
+        if len(ids) != len(chunks):
+            raise ValueError(f"LipStreamPool.push: {len(ids)} slot id(s) and {len(chunks)} chunk(s)")
+        if any(not isinstance(c, torch.Tensor) for c in chunks):
+            raise ValueError("LipStreamPool.push: every chunk must be a tensor")
+        kinds = {c.dtype for c in chunks}
+        if len(kinds) > 1 or (kinds and not kinds <= {torch.uint8, torch.float32}):
+            raise ValueError(f"LipStreamPool.push: chunks must be all uint8 ROIs or all float32 prepared lips; got {sorted(map(str, kinds))}")
+        u8 = kinds == {torch.uint8}
+        hw = self.roi_hw
+        for r, c in enumerate(chunks):
+            if c.ndim != 3:
+                raise ValueError(f"LipStreamPool.push: chunk {r} must be (m,H,W); got {tuple(c.shape)}")
+            if c.device != self.device:
+                raise ValueError(f"LipStreamPool.push: chunk {r} lies on {c.device}, the pool on {self.device}")
+            if u8:
+                if hw is None:
+                    hw = (int(c.shape[1]), int(c.shape[2]))
+                if tuple(c.shape[1:]) != hw or min(hw) < CROP or max(hw) > 0x7fff:
+                    raise ValueError(f"LipStreamPool.push: uint8 chunk {r} must be (m,{hw[0]},{hw[1]}) with H, W >= {CROP}; got {tuple(c.shape)}")
+            elif tuple(c.shape[1:]) != (CROP, CROP):
+                raise ValueError(f"LipStreamPool.push: float32 chunk {r} must be prepared lips (m,{CROP},{CROP}); got {tuple(c.shape)}")
+            if c.shape[0] > self.max_frames:
+                raise ValueError(f"LipStreamPool.push: chunk {r} holds {c.shape[0]} frames; max_frames = {self.max_frames}")
+        self._plan(ids, [int(c.shape[0]) for c in chunks], False)  # unknown / repeated ids
+        if u8 and self.roi_hw is None:
+            self.roi_hw = hw  # fixed by the first ROIs the pool sees
+        return ids, [int(c.shape[0]) for c in chunks], [c.contiguous() for c in chunks], u8
+
+    def _plan(self, ids, ms, flush):
+        R = len(ids)
+        if R == 0:
+            return [], [], [0, 0, 0]
+        LL = ctypes.c_longlong
+        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0, 0, 0))]
+        new, table, sizes, refused = (LL * (3 * R))(), (LL * (VIDEO_PLAN_WORDS * R))(), (LL * 3)(), (ctypes.c_int * 2)()
+        rc = _lib.load().rtfs_live_video_plan((LL * R)(*ids), (LL * (3 * R))(*cnt), None if flush else (LL * R)(*ms), R, self.slots, int(flush),
+                                              self.max_frames, new, table, sizes, refused)
+        if rc != 0:
+            r, why = refused[0], _REASONS.get(refused[1], refused[1])
+            raise ValueError(f"LipStreamPool.{'flush' if flush else 'push'}: refused ({why})" +
+                             (f" at slot {ids[r]}, counters (g, v) = {tuple(cnt[3 * r:3 * r + 2])}" if 0 <= r < R else "") + "; no slot was changed")
+        return list(new), list(table), [int(v) for v in sizes]
+
+    # -- one tick
+    def _tick(self, ids, ms, chunks, u8, flush):
+        if self.model.training:
+            raise RuntimeError("LipStreamPool is inference only: call .eval() on the model")
+        R = len(ids)
+        if R == 0:
+            return []
+        new, table, (rows, floats, max_m) = self._plan(ids, ms, flush)
+        if not self.on_hip:
+            raise RuntimeError("rtfs_net_amd kernels run on the MI355X only: the pool lies on a CPU device (there is no CPU fallback)")
+        lib, dev = _lib.load(), self.device
+        ptrs = [0] * R if flush else [c.data_ptr() for c in chunks]
+        with torch.no_grad():
+            tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
+            st = _lib.stream_of(self._win)
+            if u8:
+                from . import datas
+                H, W = self.roi_hw
+                crop, _, mean, std = datas.get_preprocessing_pipelines()["val"].collapse()
+                dy, dx = crop.offsets(H, W)
+                _lib.check(lib.rtfs_live_video_ingest_u8(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush), H, W,
+                                                         dy, dx, mean, std, st), "rtfs_live_video_ingest_u8")
+            else:
+                _lib.check(lib.rtfs_live_video_ingest_f32(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush), st),
+                           "rtfs_live_video_ingest_f32")
+            out = _lib.empty(floats, device=dev)
+            pk = self.model.pack()
+            for c0 in range(0, rows, self.max_batch_frames):  # the trunk in pieces: the workspace is ~1.7 MB per frame
+                n = min(rows - c0, self.max_batch_frames)
+                ws = _lib.workspace(lib.rtfs_video_windows_workspace_bytes(n), dev)
+                _lib.check(lib.rtfs_video_frontend_windows_f32(_lib.ptr(self._win), _lib.ptr(pk), _lib.ptr(tab), _lib.ptr(out), R, c0, n,
+                                                               _lib.ptr(ws), ws.numel(), st), "rtfs_video_frontend_windows_f32")
+            if flush:
+                self._reset_state(tab[:R], R)
+        for r, s in enumerate(ids):
+            self._counters[s] = new[3 * r:3 * r + 3]
+        ks, offs = table[4 * R:5 * R], table[6 * R:7 * R]
+        return [out[off:off + 512 * k].view(512, k) for k, off in zip(ks, offs)]
+
+    def _reset_state(self, ids, R):
+        """Give both history buffers of R slots (a device tensor of ids; None = the first R) defined contents.  Which planes hold a frame
+        follows from g, so nothing depends on these zeros."""
+        if not self.on_hip:
+            self._hist[slice(0, R) if ids is None else ids] = 0
+            return
+        _lib.check(_lib.load().rtfs_live_video_reset(_lib.ptr(ids), _lib.ptr(self._hist), R, _lib.stream_of(self._hist)), "rtfs_live_video_reset")
+
+
+def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=1600):
+    """``FRCNNVideoModel.open_streams``: check the arguments, then allocate the pool."""
+    try:
+        slots, max_frames, max_batch_frames = operator.index(slots), operator.index(max_frames), operator.index(max_batch_frames)
+        roi_hw = None if roi_hw is None else (operator.index(roi_hw[0]), operator.index(roi_hw[1]))
+        if roi_hw is not None and len(roi_hw) != 2:
+            raise TypeError
+    except (TypeError, IndexError):
+        raise ValueError("open_streams: slots, max_frames, max_batch_frames must be integers and roi_hw None or (H, W)") from None
+    if slots < 1 or max_frames < 1 or max_batch_frames < 1 or slots * max(max_frames, LOOKAHEAD) > 0x7fffffff // 5:
+        raise ValueError(f"open_streams: slots = {slots}, max_frames = {max_frames}, max_batch_frames = {max_batch_frames}; all at least 1")
+    if roi_hw is not None and (min(roi_hw) < CROP or max(roi_hw) > 0x7fff):
+        raise ValueError(f"open_streams: roi_hw = {roi_hw}; mouth ROIs must be at least {CROP} x {CROP}")
+    if model.training:
+        raise RuntimeError("FRCNNVideoModel.open_streams is inference only: call .eval()")
+    return LipStreamPool(model, slots, max_frames, roi_hw, max_batch_frames)
+
+
+class CameraStreamPool:
+    """``slots`` live streams from microphone samples and camera frames (inference only).  Built by ``System.open_camera_streams``.
+
+    A ``LipStreamPool`` embeds each tick's mouth frames and its embeddings go straight on, as the video chunks, into the audio
+    ``StreamPool``; the concatenated outputs equal ``System.separate_recording`` of the whole recording (16 kHz audio) with the same
+    ``window`` / ``hop``.  Embeddings lag the frames received by two frames, so audio window n waits for frame n hop / 640 + window / 640 + 1
+    (80 ms more than with ready embeddings), and the inner audio pool is opened with ``max_chunk + 1280``: audio in step with the camera
+    stands up to 1280 samples further ahead of the EMBEDDED video than window + max_chunk allows for."""
+
+    def __init__(self, lips, audio, max_chunk):
+        self.lips, self.audio, self.max_chunk = lips, audio, max_chunk
+        self.slots, self.device, self.n_src = audio.slots, audio.device, audio.n_src
+
+    def counters(self, slot):
+        """((a, f, e, o) of the audio pool, (g, v) of the lip pool); f == v between calls."""
+        return self.audio.counters(slot), self.lips.counters(slot)
+
+    def _check_audio(self, ids, audio_chunks):
+        try:
+            audio_chunks = list(audio_chunks)
+        except TypeError:
+            raise ValueError("CameraStreamPool.push: audio_chunks must be a sequence of tensors") from None
+        if len(audio_chunks) != len(ids):
+            raise ValueError(f"CameraStreamPool.push: {len(ids)} slot id(s) and {len(audio_chunks)} audio chunk(s)")
+        for r, w in enumerate(audio_chunks):
+            if not isinstance(w, torch.Tensor) or w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
+                raise ValueError(f"CameraStreamPool.push: audio chunk {r} must be a tensor (n) or (1,n)")
+            if w.dtype != torch.float32 or w.device != self.device:
+                raise ValueError(f"CameraStreamPool.push: audio chunk {r} is {w.dtype} on {w.device}; the pool is float32 on {self.device}")
+            if w.numel() > self.max_chunk:
+                raise ValueError(f"CameraStreamPool.push: audio chunk {r} holds {w.numel()} samples; max_chunk = {self.max_chunk}")
+        return audio_chunks
+
+    def push(self, slot_ids, audio_chunks, roi_chunks):
+        """One chunk of 16 kHz audio ((n)|(1,n) float32, 0 <= n <= max_chunk) and one of mouth frames (as ``LipStreamPool.push`` takes them,
+        at most max_chunk // 640) for each slot named; either may be empty.  Returns, per named slot, the (n_src, k) newly final samples,
+        as ``StreamPool.push`` does.  ValueError - before any launch, all state unchanged - for what either pool refuses."""
+        ids, ms, rois, u8 = self.lips._check_chunks(slot_ids, roi_chunks)
+        wavs = self._check_audio(ids, audio_chunks)
+        if not ids:
+            return []
+        _, vtab, _ = self.lips._plan(ids, ms, False)
+        ks = vtab[4 * len(ids):5 * len(ids)]
+        # frames may run (window + max_chunk) / 640 + 2 ahead of the first window not yet emitted: the two embeddings a flush still owes
+        # then always fit the inner pool's ring
+        room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
+        for s, m in zip(ids, ms):
+            if self.lips._counters[s][0] + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
+                raise ValueError(f"CameraStreamPool.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
+        self.audio._plan(ids, [int(w.numel()) for w in wavs], ks, False)  # refused here, nothing has moved yet
+        if self.audio.model.training:
+            raise RuntimeError("CameraStreamPool is inference only: call .eval() on the model")
+        embs = self.lips._tick(ids, ms, rois, u8, flush=False)
+        return self.audio.push(ids, wavs, embs)
+
+    def flush(self, slot_ids):
+        """End the named streams: the lip pool's flush, its at most two remaining embeddings pushed with empty audio, then the audio pool's
+        flush.  Returns the remaining samples per slot (the samples the middle step made final in front of the flush's own)."""
+        ids = self.lips._check_ids(slot_ids)
+        if not ids:
+            return []
+        _, vtab, _ = self.lips._plan(ids, None, True)
+        ks = vtab[4 * len(ids):5 * len(ids)]
+        new, _, _ = self.audio._plan(ids, [0] * len(ids), ks, False)
+        saved = [self.audio._counters[s] for s in ids]
+        try:  # the inner flush is planned on the counters the middle push leaves
+            for r, s in enumerate(ids):
+                self.audio._counters[s] = new[4 * r:4 * r + 4]
+            self.audio._plan(ids, None, None, True)
+        finally:
+            for s, c in zip(ids, saved):
+                self.audio._counters[s] = c
+        if self.audio.model.training:
+            raise RuntimeError("CameraStreamPool is inference only: call .eval() on the model")
+        embs = self.lips.flush(ids)
+        empty = _lib.empty(0, device=self.device)
+        mid = self.audio.push(ids, [empty] * len(ids), embs)
+        last = self.audio.flush(ids)
+        return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
+
+    def reset(self, slot_ids):
+        """Drop the named streams without output."""
+        ids = self.lips._check_ids(slot_ids)
+        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
+            raise ValueError(f"CameraStreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
+        self.lips.reset(ids)
+        self.audio.reset(ids)
+
+
+def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96)):
+    """``System.open_camera_streams``: the lip pool and the audio pool of one set of slots."""
+    if system.video_model is None:
+        raise ValueError("open_camera_streams: the system has no video model; push lip embeddings through open_streams")
+    try:
+        window = operator.index(window)
+        max_chunk = window if max_chunk is None else operator.index(max_chunk)
+    except TypeError:
+        raise ValueError("open_camera_streams: window and max_chunk must be integers") from None
+    if max_chunk < SPF or max_chunk % SPF:
+        raise ValueError(f"open_camera_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF}")
+    audio = system.audio_model.open_streams(slots, window=window, hop=hop, max_chunk=max_chunk + LOOKAHEAD * SPF, max_batch=max_batch)
+    lips = system.video_model.open_streams(slots, max_frames=max_chunk // SPF, roi_hw=roi_hw)
+    if lips.device != audio.device:
+        raise ValueError(f"open_camera_streams: the video model lies on {lips.device}, the audio model on {audio.device}")
+    return CameraStreamPool(lips, audio, max_chunk)

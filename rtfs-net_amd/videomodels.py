@@ -137,6 +137,17 @@ class FRCNNVideoModel(nn.Module):
                    "rtfs_video_frontend_f32")
         return out
 
+    def open_streams(self, slots, max_frames=50, roi_hw=None, max_batch_frames=1600):
+        """``slots`` live lip tracks embedded chunk by chunk (inference only; DESIGN.md "Live streams from camera frames") ->
+        ``streaming.LipStreamPool``.  ``pool.push(slot_ids, chunks)`` takes what the camera delivered - uint8 mouth ROIs (m,H,W) with
+        (H,W) == ``roi_hw`` (None: fixed by the first ROIs pushed), or float32 prepared lips (m,88,88), at most ``max_frames`` per chunk -
+        and returns the (512,k) embeddings that became final; ``pool.flush(slot_ids)`` ends tracks.  For any chunking the concatenated
+        outputs equal ``forward`` on the whole track: the state per slot is four prepared frames, the look-ahead two frames.  A tick's
+        frames go through the trunk in pieces of at most ``max_batch_frames``.  ValueError for sizes below 1 or ROIs under 88 x 88;
+        RuntimeError in ``.train()`` mode."""
+        from . import streaming
+        return streaming.open_lip_streams(self, slots, max_frames=max_frames, roi_hw=roi_hw, max_batch_frames=max_batch_frames)
+
     def init_from(self, path):
         """frcnn_videomodel.py:74-76 + update_frcnn_parameter (:103-115), with a non-executing loader."""
         pretrained = torch.load(path, map_location="cpu", weights_only=True)["model_state_dict"]
