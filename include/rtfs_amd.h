@@ -617,6 +617,46 @@ int rtfs_resample_plan(int orig_freq, int new_freq, int* o, int* n, int* width, 
 long long rtfs_resample_out_len(int orig_freq, int new_freq, long long L);
 int rtfs_resample_f32(const float* x, const float* bank, float* y, int B, int L, int orig_freq, int new_freq, void* stream);
 
+/* Live streams at the microphone's own rate (datas.open_resample_streams / ResampleStreamPool; DESIGN.md "Live streams at the
+ * microphone's rate"; csrc/k_live_resample.hip): rtfs_resample_f32 chunk by chunk.  In the notation of rtfs_resample_plan (o, n, width,
+ * span = 2 width + 1, c(p) = floor(o p / n)) output q = j n + p reads the inputs j o + c(p) - width .. last(q) = j o + c(p) + width, and
+ * G(A) = #{q : last(q) < A} = ceil(n max(0, A - width) / o).  The caller keeps three integers per slot [a input samples received |
+ * g output samples emitted | side]; a push of m samples gives a' = a + m, g' = G(a') and emits g .. g' - 1; a flush emits
+ * g .. ceil(n a / o) - 1 (rtfs_resample_out_len of the samples received) with exact zeros for inputs >= a and returns zero counters.
+ * Inputs with index < 0 are exact zeros as well.  Every output is formed by the fmaf chain of rtfs_resample_f32 in the same order on the
+ * same values, so the concatenated outputs of any chunking are BIT-equal to rtfs_resample_f32 on the whole recording; an output leaves
+ * width / orig_freq seconds after the last input it reads arrived.
+ * State (caller-allocated, 16-byte aligned): hist (slots, 2, 2 width), two history buffers per slot; buffer `side` holds the inputs
+ *   a - 2 width .. a - 1, input x in cell x - (a - 2 width).  A launch reads buffer `side` and writes buffer 1 - side; a push with m > 0
+ *   flips the side, so no block reads a cell another block of the same launch writes.  Which cells hold a sample follows from a.
+ * rtfs_live_resample_plan (host only, no device call, the single place with the arithmetic): for the R slots named in slot_ids, counters
+ *   (R x 3, row-major) and n_samples (R; ignored when flush != 0) -> new_counters (R x 3), sizes[3] = [out_floats of ONE flat output |
+ *   largest m | largest k] and the tick table, RTFS_LIVE_RESAMPLE_PLAN_WORDS = 7 int64 words per named slot, column-major:
+ *   [slot | a | m | g | k | out_off | side]: the slot emits the k outputs g .. g + k - 1; its block starts out_off floats into the flat
+ *   output, out_off a multiple of RTFS_LIVE_ALIGN floats; side is the buffer that is read.
+ *   Refusals return -4, write nothing else, and name themselves in refused[2] = [index into slot_ids or -1 | RTFS_LIVE_* reason]:
+ *   R < 1, slots < 1, max_chunk_in < 1, a missing array or a ratio rtfs_resample_plan refuses (BAD_ARGUMENT); a slot id outside
+ *   [0, slots) or named twice; m outside [0, max_chunk_in] (CHUNK_SIZE); counters this planner cannot have produced (negative,
+ *   g != G(a), side not 0 / 1: BAD_COUNTERS).  new_counters, table, sizes, refused may be NULL.
+ * rtfs_live_resample_f32 / _i16 (one launch each): table = the plan's 7 R words followed by one more column, the DEVICE address of each
+ *   slot's chunk - separate allocations, read where they lie: float32 at any 4-byte alignment, or int16 PCM at any 2-byte alignment,
+ *   which enters as (float)s / 32768 (exact).  bank = the (n, taps) bank of rtfs_resample_plan on the device.  Writes each slot's k
+ *   outputs and leaves buffer 1 - side of every slot with m > 0 holding the inputs a' - 2 width .. a' - 1.  max_m, max_k = sizes[1],
+ *   sizes[2]; flush != 0 requires max_m == 0 and writes no history.
+ * rtfs_live_resample_reset (one launch): zeroes both history buffers of the R slots in ids (DEVICE array; NULL = slots 0 .. R - 1).  No
+ *   kernel depends on those contents.
+ * The launches take the caller's stream, allocate nothing, read nothing back, use no atomics and trust the device table: pass what
+ * rtfs_live_resample_plan wrote.  hist, out 16-byte aligned, tables 8-byte aligned (-4); a grid that would not fit: -1. */
+#define RTFS_LIVE_RESAMPLE_PLAN_WORDS 7
+int rtfs_live_resample_plan(const long long* slot_ids, const long long* counters, const long long* n_samples, int R, int slots, int flush,
+                            int orig_freq, int new_freq, long long max_chunk_in, long long* new_counters, long long* table, long long* sizes,
+                            int* refused);
+int rtfs_live_resample_f32(const long long* table, const float* bank, float* hist, float* out, int R, long long max_m, long long max_k,
+                           int flush, int orig_freq, int new_freq, void* stream);
+int rtfs_live_resample_i16(const long long* table, const float* bank, float* hist, float* out, int R, long long max_m, long long max_k,
+                           int flush, int orig_freq, int new_freq, void* stream);
+int rtfs_live_resample_reset(const long long* ids, float* hist, int R, int orig_freq, int new_freq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -376,6 +376,13 @@ int launch_live_video_ingest(const long long* table, float* hist, float* windows
 int launch_live_video_scatter(const float* emb, const long long* table, float* out, int R, int row_begin, int n, hipStream_t st);
 int launch_live_video_reset(const long long* ids, float* hist, int R, hipStream_t st);
 
+// live streams at the microphone's rate (k_live_resample.hip): tick plan (host), the polyphase resampler chunk by chunk in one launch
+int live_resample_plan(const long long* slot_ids, const long long* counters, const long long* n_samples, int R, int slots, int flush,
+                       int orig, int neu, long long max_chunk_in, long long* new_counters, long long* table, long long* sizes, int* refused);
+int launch_live_resample(const long long* table, const float* bank, float* hist, float* out, int R, long long max_m, long long max_k,
+                         int flush, bool i16, int orig, int neu, hipStream_t st);
+int launch_live_resample_reset(const long long* ids, float* hist, int R, int orig, int neu, hipStream_t st);
+
 // training-side GEMMs and SRU scans (k_train_gemm.hip, k_train_rnn.hip)
 struct GemmArgs {
     const float *A = nullptr, *B = nullptr;

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 
 __all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
-           "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank"]
+           "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams"]
 
 CROP = 88
 MAX_RATIO = 640
@@ -71,6 +71,16 @@ def resample(wav, orig_freq, new_freq=16000):
     y = _lib.empty(B, Lout, device=x.device)
     _lib.check(_lib.load().rtfs_resample_f32(_lib.ptr(x), _lib.ptr(bank), _lib.ptr(y), B, L, o, n, _lib.stream_of(x)), "rtfs_resample_f32")
     return y[0] if wav.ndim == 1 else y
+
+
+def open_resample_streams(slots, orig_freq, new_freq=16000, max_chunk=None, device=None):
+    """``slots`` live streams resampled chunk by chunk (DESIGN.md "Live streams at the microphone's rate") ->
+    ``streaming.ResampleStreamPool``.  ``pool.push(slot_ids, chunks)`` takes float32 or int16 PCM chunks of at most ``max_chunk`` input
+    samples (default one second) and returns the (k,) outputs that became final; ``pool.flush(slot_ids)`` ends streams.  For any
+    chunking the concatenated outputs are bit-equal to ``resample`` of the whole recording, which ``resample`` per chunk is not: it pads
+    every chunk edge with zeros and rounds every chunk's length up.  ValueError for equal rates and for what ``resample_plan`` refuses."""
+    from . import streaming
+    return streaming.open_resample_streams(slots, orig_freq, new_freq, max_chunk=max_chunk, device=device)
 
 
 # ---------------------------------------------------------------- waveform normalisation

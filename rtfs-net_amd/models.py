@@ -926,7 +926,7 @@ class AVNet(BaseAVModel):
                                                               window, hop, _lib.stream_of(xw)), "rtfs_longform_overlap_add_many_f32")
             return [out[int(o):int(o) + n_src * int(w.shape[0])].view(n_src, int(w.shape[0])) for o, w in zip(offs, wavs)]
 
-    def open_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32):
+    def open_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
         """``slots`` live streams separated chunk by chunk (inference only; DESIGN.md "Live streams") -> ``streaming.StreamPool``.  The
         stateful form of ``separate_long``: ``pool.push(slot_ids, audio_chunks, video_chunks)`` takes what arrived (audio chunks of at most
         ``max_chunk`` samples, default ``window``; lip embeddings (512,m) at 25 fps) and returns the samples no later window can touch;
@@ -934,9 +934,14 @@ class AVNet(BaseAVModel):
         with the same ``window`` / ``hop``.  All device state is allocated here, once.
 
         ValueError for what ``separate_long`` refuses about window / hop / the cell's fused limit, for slots < 1, max_batch < 1 and a
-        ``max_chunk`` that is not a positive multiple of 640; RuntimeError in ``.train()`` mode."""
+        ``max_chunk`` that is not a positive multiple of 640; RuntimeError in ``.train()`` mode.
+
+        ``sample_rate`` other than 16000 (DESIGN.md "Live streams at the microphone's rate") -> ``streaming.RateStreamPool``, the same
+        surface with audio chunks at that rate, float32 or int16 PCM, of at most floor(max_chunk o / n) samples, resampled on the device
+        chunk by chunk; the outputs equal ``separate_long(datas.resample(wav, sample_rate), ...)``.  ``window``, ``hop`` and
+        ``max_chunk`` stay in 16 kHz samples."""
         from . import streaming
-        return streaming.open_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch)
+        return streaming.open_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, sample_rate=sample_rate)
 
     def _side_stream(self, device):
         streams = self.__dict__.setdefault("_side_streams", {})

@@ -8,6 +8,7 @@ All arithmetic of a tick (counters, ready windows, ring positions, output ranges
 integers per slot and never reads anything back from the device."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import operator
 
@@ -16,6 +17,7 @@ import torch
 from . import _lib, layers
 
 SPF = 640  # samples per video frame: 16 kHz audio, 25 fps video
+FS = 16000  # the model's sample rate
 MAX_CAPACITY = 1 << 24  # RTFS_LIVE_MAX_CAPACITY: window + max_chunk at most, so that every launch grid fits
 PLAN_WORDS = 13  # RTFS_LIVE_PLAN_WORDS: [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]
 _REASONS = {1: "bad argument", 2: "unknown slot id", 3: "slot named twice", 4: "chunk larger than max_chunk",
@@ -246,12 +248,14 @@ class StreamPool:
         return out
 
 
-def open_streams(model, slots, window=32000, hop=None, max_chunk=None, max_batch=32):
+def open_streams(model, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
     """``AVNet.open_streams``: check the arguments as ``separate_long`` does, then allocate the pool."""
     slots, window = int(slots), int(window)
     hop = window // 2 if hop is None else int(hop)
     max_chunk = window if max_chunk is None else int(max_chunk)
     max_batch = int(max_batch)
+    if _rate(sample_rate) != FS:
+        return _open_at_rate(lambda room: open_streams(model, slots, window, hop, max_chunk + room, max_batch), sample_rate, max_chunk)
     if slots < 1 or max_batch < 1:
         raise ValueError(f"open_streams: slots = {slots}, max_batch = {max_batch}; both at least 1")
     lib = _lib.load()
@@ -445,6 +449,20 @@ def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=
     return LipStreamPool(model, slots, max_frames, roi_hw, max_batch_frames)
 
 
+@contextlib.contextmanager
+def _counters_as(pool, ids, new, words):
+    """Plan a later step of a composite call: inside the block the named slots of ``pool`` carry the counters ``new`` (R x words, as a
+    planner returned them); the pool's own are back afterwards, whatever happened."""
+    saved = [pool._counters[s] for s in ids]
+    try:
+        for r, s in enumerate(ids):
+            pool._counters[s] = list(new[words * r:words * r + words])
+        yield
+    finally:
+        for s, c in zip(ids, saved):
+            pool._counters[s] = c
+
+
 class CameraStreamPool:
     """``slots`` live streams from microphone samples and camera frames (inference only).  Built by ``System.open_camera_streams``.
 
@@ -486,6 +504,14 @@ class CameraStreamPool:
         wavs = self._check_audio(ids, audio_chunks)
         if not ids:
             return []
+        self._plan_push(ids, [int(w.numel()) for w in wavs], ms)  # refused here, nothing has moved yet
+        if self.audio.model.training:
+            raise RuntimeError("CameraStreamPool is inference only: call .eval() on the model")
+        embs = self.lips._tick(ids, ms, rois, u8, flush=False)
+        return self.audio.push(ids, wavs, embs)
+
+    def _plan_push(self, ids, na, ms):
+        """The dry run of a push of na samples and ms frames per named slot on both planners: ValueError for what either refuses."""
         _, vtab, _ = self.lips._plan(ids, ms, False)
         ks = vtab[4 * len(ids):5 * len(ids)]
         # frames may run (window + max_chunk) / 640 + 2 ahead of the first window not yet emitted: the two embeddings a flush still owes
@@ -494,11 +520,7 @@ class CameraStreamPool:
         for s, m in zip(ids, ms):
             if self.lips._counters[s][0] + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
                 raise ValueError(f"CameraStreamPool.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
-        self.audio._plan(ids, [int(w.numel()) for w in wavs], ks, False)  # refused here, nothing has moved yet
-        if self.audio.model.training:
-            raise RuntimeError("CameraStreamPool is inference only: call .eval() on the model")
-        embs = self.lips._tick(ids, ms, rois, u8, flush=False)
-        return self.audio.push(ids, wavs, embs)
+        return self.audio._plan(ids, na, ks, False)
 
     def flush(self, slot_ids):
         """End the named streams: the lip pool's flush, its at most two remaining embeddings pushed with empty audio, then the audio pool's
@@ -506,17 +528,7 @@ class CameraStreamPool:
         ids = self.lips._check_ids(slot_ids)
         if not ids:
             return []
-        _, vtab, _ = self.lips._plan(ids, None, True)
-        ks = vtab[4 * len(ids):5 * len(ids)]
-        new, _, _ = self.audio._plan(ids, [0] * len(ids), ks, False)
-        saved = [self.audio._counters[s] for s in ids]
-        try:  # the inner flush is planned on the counters the middle push leaves
-            for r, s in enumerate(ids):
-                self.audio._counters[s] = new[4 * r:4 * r + 4]
-            self.audio._plan(ids, None, None, True)
-        finally:
-            for s, c in zip(ids, saved):
-                self.audio._counters[s] = c
+        self._plan_flush(ids)
         if self.audio.model.training:
             raise RuntimeError("CameraStreamPool is inference only: call .eval() on the model")
         embs = self.lips.flush(ids)
@@ -524,6 +536,14 @@ class CameraStreamPool:
         mid = self.audio.push(ids, [empty] * len(ids), embs)
         last = self.audio.flush(ids)
         return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
+
+    def _plan_flush(self, ids):
+        """The dry run of a flush on both planners: ValueError for what either refuses."""
+        _, vtab, _ = self.lips._plan(ids, None, True)
+        ks = vtab[4 * len(ids):5 * len(ids)]
+        new, _, _ = self.audio._plan(ids, [0] * len(ids), ks, False)
+        with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the middle push leaves
+            self.audio._plan(ids, None, None, True)
 
     def reset(self, slot_ids):
         """Drop the named streams without output."""
@@ -534,8 +554,11 @@ class CameraStreamPool:
         self.audio.reset(ids)
 
 
-def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96)):
+def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000):
     """``System.open_camera_streams``: the lip pool and the audio pool of one set of slots."""
+    if _rate(sample_rate) != FS:
+        mc = (window if max_chunk is None else max_chunk)
+        return _open_at_rate(lambda room: open_camera_streams(system, slots, window, hop, mc + room, max_batch, roi_hw), sample_rate, mc)
     if system.video_model is None:
         raise ValueError("open_camera_streams: the system has no video model; push lip embeddings through open_streams")
     try:
@@ -550,3 +573,279 @@ def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, m
     if lips.device != audio.device:
         raise ValueError(f"open_camera_streams: the video model lies on {lips.device}, the audio model on {audio.device}")
     return CameraStreamPool(lips, audio, max_chunk)
+
+
+# ================================================================ live streams at the microphone's rate (DESIGN.md "Live streams at the microphone's rate")
+RESAMPLE_PLAN_WORDS = 7  # RTFS_LIVE_RESAMPLE_PLAN_WORDS: [slot | a | m | g | k | out_off | side]
+
+
+class ResampleStreamPool:
+    """``slots`` concurrent streams resampled chunk by chunk.  Built by ``datas.open_resample_streams``.
+
+    For any way of cutting a recording into chunks, the concatenation of what ``push`` and the final ``flush`` return is BIT-equal to
+    ``datas.resample`` of the whole recording: every output is formed by the same chain of fused multiply-adds on the same values.  In
+    the notation of ``datas.resample_plan`` output q = j n + p reads the inputs up to last(q) = j o + floor(o p / n) + width, and after
+    a samples the outputs emitted are G(a) = ceil(n max(0, a - width) / o): an output leaves width / orig_freq seconds after the last
+    sample it reads arrived (0.4 ms at 48 kHz).  The state of a slot is its last 2 width samples in two buffers, read one and write the
+    other (304 bytes per slot at 48 kHz).
+
+    Host state per slot: a samples received, g samples emitted (and the side of the history that is current).  All arithmetic of a tick
+    is ``rtfs_live_resample_plan`` (host only); per tick one plan, one table upload, one launch, nothing read back.  Not capturable in
+    a HIP graph (the tick table is uploaded per call)."""
+
+    def __init__(self, slots, orig_freq, new_freq, max_chunk, device):
+        from . import datas
+        self.slots, self.orig_freq, self.new_freq, self.max_chunk = slots, orig_freq, new_freq, max_chunk
+        self.o, self.n, self.width, _ = datas.resample_plan(orig_freq, new_freq)
+        self.device = device
+        self.on_hip = device.type == "cuda"
+        self._counters = [[0, 0, 0] for _ in range(slots)]
+        self._hist = _lib.empty(slots, 2, 2 * self.width, device=device)
+        self._bank = datas.resample_bank(self.o, self.n, device) if self.on_hip else None
+        self._reset_state(None, slots)
+
+    # -- public
+    def counters(self, slot):
+        """(a, g) of a slot: input samples received, output samples emitted."""
+        return tuple(self._counters[int(slot)][:2])
+
+    def push(self, slot_ids, chunks):
+        """One chunk for each slot named: (m)|(1,m) float32, or int16 PCM (a sample s enters as s / 32768, what reading a 16-bit file as
+        float32 gives); one kind per call, 0 <= m <= max_chunk, separate allocations on the pool's device, read where they lie.  Returns,
+        per named slot, the (k,) float32 outputs that became final (k may be 0): views of one flat output whose per-slot blocks start on
+        128-byte lines.
+
+        ValueError - before any launch, all state unchanged - for an unknown or repeated slot id, a bad shape / dtype / device or an
+        oversize chunk."""
+        ids, ms, chunks, i16, plan = self._check_chunks(slot_ids, chunks)
+        return self._tick(ids, ms, chunks, i16, flush=False, plan=plan)
+
+    def flush(self, slot_ids):
+        """End the named streams: the outputs still owed up to ceil(n a / o), the length ``datas.resample`` gives the samples received,
+        with zeros behind the last sample, then reset the slots.  A slot that received nothing returns (0,)."""
+        return self._tick(self._check_ids(slot_ids), None, None, False, flush=True)
+
+    def reset(self, slot_ids):
+        """Drop the named streams without output."""
+        ids = self._check_ids(slot_ids)
+        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
+            raise ValueError(f"ResampleStreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
+        if not ids:
+            return
+        self._reset_state(torch.tensor(ids, dtype=torch.int64).to(self.device), len(ids))
+        for s in ids:
+            self._counters[s] = [0, 0, 0]
+
+    # -- checks (no launch, no state change)
+    _check_ids = staticmethod(StreamPool._check_ids)
+
+    def _check_chunks(self, slot_ids, chunks):
+        ids = self._check_ids(slot_ids)
+        try:
+            chunks = list(chunks)
+        except TypeError:
+            raise ValueError("ResampleStreamPool.push: chunks must be a sequence of tensors") from None
+        if len(ids) != len(chunks):
+            raise ValueError(f"ResampleStreamPool.push: {len(ids)} slot id(s) and {len(chunks)} chunk(s)")
+        if any(not isinstance(c, torch.Tensor) for c in chunks):
+            raise ValueError("ResampleStreamPool.push: every chunk must be a tensor")
+        kinds = {c.dtype for c in chunks}
+        if len(kinds) > 1 or (kinds and not kinds <= {torch.int16, torch.float32}):
+            raise ValueError(f"ResampleStreamPool.push: chunks must be all float32 or all int16 PCM; got {sorted(map(str, kinds))}")
+        for r, c in enumerate(chunks):
+            if c.ndim not in (1, 2) or (c.ndim == 2 and c.shape[0] != 1):
+                raise ValueError(f"ResampleStreamPool.push: chunk {r} must be (m) or (1,m); got {tuple(c.shape)}")
+            if c.device != self.device:
+                raise ValueError(f"ResampleStreamPool.push: chunk {r} lies on {c.device}, the pool on {self.device}")
+            if c.numel() > self.max_chunk:
+                raise ValueError(f"ResampleStreamPool.push: chunk {r} holds {c.numel()} samples; max_chunk = {self.max_chunk}")
+        ms = [int(c.numel()) for c in chunks]
+        plan = self._plan(ids, ms, False)  # unknown / repeated ids; the tick that follows takes this plan
+        return ids, ms, [c.reshape(-1).contiguous() for c in chunks], kinds == {torch.int16}, plan
+
+    def _plan(self, ids, ms, flush):
+        R = len(ids)
+        if R == 0:
+            return [], [], [0, 0, 0]
+        LL = ctypes.c_longlong
+        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0, 0, 0))]
+        new, table, sizes, refused = (LL * (3 * R))(), (LL * (RESAMPLE_PLAN_WORDS * R))(), (LL * 3)(), (ctypes.c_int * 2)()
+        rc = _lib.load().rtfs_live_resample_plan((LL * R)(*ids), (LL * (3 * R))(*cnt), None if flush else (LL * R)(*ms), R, self.slots,
+                                                 int(flush), self.o, self.n, self.max_chunk, new, table, sizes, refused)
+        if rc != 0:
+            r, why = refused[0], _REASONS.get(refused[1], refused[1])
+            raise ValueError(f"ResampleStreamPool.{'flush' if flush else 'push'}: refused ({why})" +
+                             (f" at slot {ids[r]}, counters (a, g) = {tuple(cnt[3 * r:3 * r + 2])}" if 0 <= r < R else "") + "; no slot was changed")
+        return list(new), list(table), [int(v) for v in sizes]
+
+    # -- one tick
+    def _tick(self, ids, ms, chunks, i16, flush, plan=None):
+        R = len(ids)
+        if R == 0:
+            return []
+        new, table, (floats, max_m, max_k) = plan or self._plan(ids, ms, flush)
+        if not self.on_hip:
+            raise RuntimeError("rtfs_net_amd kernels run on the MI355X only: the pool lies on a CPU device (there is no CPU fallback)")
+        lib, dev = _lib.load(), self.device
+        ptrs = [0] * R if flush else [c.data_ptr() for c in chunks]
+        with torch.no_grad():
+            tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
+            out = _lib.empty(floats, device=dev)
+            run = lib.rtfs_live_resample_i16 if i16 else lib.rtfs_live_resample_f32
+            _lib.check(run(_lib.ptr(tab), _lib.ptr(self._bank), _lib.ptr(self._hist), _lib.ptr(out), R, max_m, max_k, int(flush), self.o, self.n,
+                           _lib.stream_of(self._hist)), "rtfs_live_resample_i16" if i16 else "rtfs_live_resample_f32")
+            if flush:
+                self._reset_state(tab[:R], R)
+        for r, s in enumerate(ids):
+            self._counters[s] = new[3 * r:3 * r + 3]
+        ks, offs = table[4 * R:5 * R], table[5 * R:6 * R]
+        return [out[off:off + k] for k, off in zip(ks, offs)]
+
+    def _reset_state(self, ids, R):
+        """Give both history buffers of R slots (a device tensor of ids; None = the first R) defined contents.  Which cells hold a sample
+        follows from a, so nothing depends on these zeros."""
+        if not self.on_hip:
+            self._hist[slice(0, R) if ids is None else ids] = 0
+            return
+        _lib.check(_lib.load().rtfs_live_resample_reset(_lib.ptr(ids), _lib.ptr(self._hist), R, self.o, self.n, _lib.stream_of(self._hist)),
+                   "rtfs_live_resample_reset")
+
+
+def _rate(sample_rate):
+    try:
+        return operator.index(sample_rate)
+    except TypeError:
+        raise ValueError(f"sample_rate must be an integer number of Hz; got {sample_rate!r}") from None
+
+
+def open_resample_streams(slots, orig_freq, new_freq=FS, max_chunk=None, device=None):
+    """``datas.open_resample_streams``: check the arguments, then allocate the pool.  ``max_chunk`` (input samples per push and slot)
+    defaults to one second."""
+    from . import datas
+    try:
+        slots, orig_freq, new_freq = operator.index(slots), operator.index(orig_freq), operator.index(new_freq)
+        max_chunk = orig_freq if max_chunk is None else operator.index(max_chunk)
+    except TypeError:
+        raise ValueError("open_resample_streams: slots, orig_freq, new_freq and max_chunk must be integers") from None
+    if slots < 1 or slots > 65535 or max_chunk < 1 or max_chunk > MAX_CAPACITY * datas.MAX_RATIO:
+        raise ValueError(f"open_resample_streams: slots = {slots} (1 .. 65535), max_chunk = {max_chunk} (at least 1)")
+    if orig_freq == new_freq:
+        raise ValueError(f"open_resample_streams: {orig_freq} -> {new_freq} is no resampling (datas.resample hands such input back as it is)")
+    datas.resample_plan(orig_freq, new_freq)  # ValueError for a ratio the kernel does not take
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return ResampleStreamPool(slots, orig_freq, new_freq, max_chunk, device)
+
+
+class RateStreamPool:
+    """A ``StreamPool`` or ``CameraStreamPool`` whose audio arrives at the microphone's rate.  Built by ``open_streams`` /
+    ``open_camera_streams`` with ``sample_rate`` other than 16000; same ``push`` / ``flush`` / ``reset`` / ``counters`` surface.
+
+    A ``ResampleStreamPool`` brings each tick's audio chunks (float32 or int16 PCM at ``sample_rate``, at most ``max_chunk_in`` =
+    floor(max_chunk o / n) samples) to 16 kHz and its output blocks go straight on, without a copy, as the inner pool's audio chunks;
+    the concatenated outputs equal ``separate_long(datas.resample(wav, sample_rate), ...)`` / ``System.separate_recording(wav,
+    sample_rate, rois)`` of the whole recording.  ``window``, ``hop`` and ``max_chunk`` stay in 16 kHz samples.  A chunk of m samples
+    gives at most floor(m n / o) + 1 outputs, so the inner pool is opened with ``max_chunk + 640``, and a push is refused unless the
+    resampler's flush tail (at most ceil(n width / o) + 1 samples) still fits the inner ring behind it: the tail of a ``flush`` is
+    then never refused.  ``datas.normalize_mixture`` is NOT applied and cannot be: it needs the deviation of the whole recording, which
+    a stream does not have (``separate_recording``'s ``normalize_audio`` is off by default as well)."""
+
+    def __init__(self, resampler, inner, max_chunk):
+        self.resampler, self.inner, self.max_chunk = resampler, inner, max_chunk
+        self.camera = isinstance(inner, CameraStreamPool)
+        self.audio = inner.audio if self.camera else inner
+        self.slots, self.device, self.n_src = inner.slots, inner.device, inner.n_src
+        self.sample_rate, self.max_chunk_in = resampler.orig_freq, resampler.max_chunk
+        self.tail = -(-resampler.n * resampler.width // resampler.o) + 1
+
+    def counters(self, slot):
+        """((a, g) of the resampler, the inner pool's counters)."""
+        return self.resampler.counters(slot), self.inner.counters(slot)
+
+    def _no_video(self, R):
+        if not self.camera:
+            return [_lib.empty(512, 0, device=self.device)] * R
+        hw = self.inner.lips.roi_hw
+        return [_lib.empty(0, CROP, CROP, device=self.device) if hw is None else _lib.empty(0, *hw, device=self.device, dtype=torch.uint8)] * R
+
+    def _plan_inner(self, ids, ks, nf):
+        """The inner pool's dry run of a push of ks 16 kHz samples and nf frames; refuses a push behind which the flush tail would not
+        fit.  -> the inner audio pool's new counters."""
+        new = (self.inner._plan_push(ids, ks, nf) if self.camera else self.audio._plan(ids, ks, nf, False))[0]
+        for r, s in enumerate(ids):
+            a, _, e, _ = new[4 * r:4 * r + 4]
+            if a + self.tail - e * self.audio.hop > self.audio.capacity:
+                raise ValueError(f"RateStreamPool.push: refused ({_REASONS[5]}) at slot {s}; no slot was changed")
+        return new
+
+    def push(self, slot_ids, audio_chunks, video_chunks):
+        """As the inner pool's ``push``, with audio chunks at ``sample_rate``: (m)|(1,m) float32 or int16 PCM, 0 <= m <= max_chunk_in.
+        All pools plan first - the resampler's plan gives the 16 kHz sizes the inner plan takes - so a ValueError from any of them comes
+        before any launch with all state unchanged."""
+        ids, ms, wavs, i16, rplan = self.resampler._check_chunks(slot_ids, audio_chunks)
+        if self.camera:
+            _, nf, rois, u8 = self.inner.lips._check_chunks(ids, video_chunks)
+            if any(f > self.max_chunk // SPF for f in nf):
+                raise ValueError(f"RateStreamPool.push: a chunk of {max(nf)} frames; at most max_chunk // {SPF} = {self.max_chunk // SPF}")
+        else:
+            _, _, nf, _, _ = self.audio._check_chunks(ids, [_lib.empty(0, device=self.device)] * len(ids), video_chunks)
+        if not ids:
+            return []
+        self._plan_inner(ids, rplan[1][4 * len(ids):5 * len(ids)], nf)
+        if self.audio.model.training:
+            raise RuntimeError("RateStreamPool is inference only: call .eval() on the model")
+        blocks = self.resampler._tick(ids, ms, wavs, i16, flush=False, plan=rplan)
+        if self.camera:  # CameraStreamPool.push behind its checks, which have all been made
+            video_chunks = self.inner.lips._tick(ids, nf, rois, u8, flush=False)
+        return self.audio.push(ids, blocks, video_chunks)
+
+    def flush(self, slot_ids):
+        """End the named streams: the resampler's flush, its tail pushed with empty video, then the inner flush.  Returns the remaining
+        samples per slot (those the middle step made final in front of the flush's own)."""
+        ids = self.resampler._check_ids(slot_ids)
+        if not ids:
+            return []
+        R = len(ids)
+        _, rtab, _ = self.resampler._plan(ids, None, True)
+        if self.camera:
+            new = self.inner._plan_push(ids, rtab[4 * R:5 * R], [0] * R)[0]
+        else:
+            new = self.audio._plan(ids, rtab[4 * R:5 * R], [0] * R, False)[0]
+        with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the tail leaves
+            if self.camera:
+                self.inner._plan_flush(ids)
+            else:
+                self.audio._plan(ids, None, None, True)
+        if self.audio.model.training:
+            raise RuntimeError("RateStreamPool is inference only: call .eval() on the model")
+        mid = self.inner.push(ids, self.resampler.flush(ids), self._no_video(R))
+        last = self.inner.flush(ids)
+        return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
+
+    def reset(self, slot_ids):
+        """Drop the named streams without output."""
+        ids = self.resampler._check_ids(slot_ids)
+        self.resampler.reset(ids)
+        self.inner.reset(ids)
+
+
+def _open_at_rate(open_inner, sample_rate, max_chunk):
+    """The pool ``open_inner(640)`` returns (one more frame of room: a chunk may resample to max_chunk + 1 samples) behind a resampler
+    from ``sample_rate``."""
+    from . import datas
+    try:
+        max_chunk = operator.index(max_chunk)
+    except TypeError:
+        raise ValueError("open_streams: max_chunk must be an integer") from None
+    o, n, width, _ = datas.resample_plan(sample_rate, FS)
+    if max_chunk < SPF or max_chunk % SPF:
+        raise ValueError(f"open_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF}")
+    tail = -(-n * width // o) + 1
+    if tail > max_chunk:
+        raise ValueError(f"open_streams: at {sample_rate} Hz a flush leaves up to {tail} samples, more than max_chunk = {max_chunk}")
+    inner = open_inner(SPF)
+    return RateStreamPool(open_resample_streams(inner.slots, sample_rate, FS, max_chunk=max(1, max_chunk * o // n), device=inner.device),
+                          inner, max_chunk)

@@ -101,22 +101,28 @@ class System(nn.Module):
                     embs[r] = emb[g]
         return self.audio_model.separate_many(wavs, embs, **kw)
 
-    def open_streams(self, **kw):
+    def open_streams(self, sample_rate=16000, **kw):
         """Live streams chunk by chunk (inference): ``AVNet.open_streams(**kw)`` of the audio model.  The caller pushes lip EMBEDDINGS
         (512,m): the video stem is a 3-D convolution with temporal context, so frames embedded chunk by chunk are not the whole-track
-        embedding without look-ahead state.  ``open_camera_streams`` is the entry that takes the camera's frames and keeps that state."""
-        return self.audio_model.open_streams(**kw)
+        embedding without look-ahead state.  ``open_camera_streams`` is the entry that takes the camera's frames and keeps that state.
+        ``sample_rate``: the rate of the audio chunks, as ``AVNet.open_streams`` takes it."""
+        return self.audio_model.open_streams(sample_rate=sample_rate, **kw)
 
-    def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96)):
+    def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000):
         """Live streams from microphone samples and camera frames (inference; DESIGN.md "Live streams from camera frames") ->
         ``streaming.CameraStreamPool``.  ``pool.push(slot_ids, audio_chunks, roi_chunks)`` takes 16 kHz audio chunks of at most
         ``max_chunk`` samples (default ``window``) and uint8 mouth ROIs (m,H,W) with (H,W) == ``roi_hw`` at 25 fps (or float32 prepared lips
         (m,88,88)), and returns the (n_src,k) newly final samples; ``pool.flush`` / ``pool.reset`` end streams.  The frames are embedded
         chunk by chunk with two frames (80 ms) of look-ahead and pushed straight on into the audio ``StreamPool``; for any chunking the
-        concatenated outputs equal ``separate_recording(wav, 16000, rois, window=..., hop=...)``.  Audio must arrive at 16 kHz: a
-        streaming resampler is out of scope (resample each chunk's source upstream, or use ``separate_recording`` offline)."""
+        concatenated outputs equal ``separate_recording(wav, sample_rate, rois, window=..., hop=...)``.
+
+        ``sample_rate`` other than 16000 (DESIGN.md "Live streams at the microphone's rate") -> ``streaming.RateStreamPool``: the audio
+        chunks are at that rate, float32 or int16 PCM, at most floor(max_chunk o / n) samples, and are resampled on the device chunk by
+        chunk, bit-equal to ``datas.resample`` of the whole recording; ``window``, ``hop`` and ``max_chunk`` stay in 16 kHz samples.
+        ``normalize_audio`` has no streamed form: it needs the whole recording's deviation."""
         from . import streaming
-        return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw)
+        return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
+                                             sample_rate=sample_rate)
 
     def separate_recordings(self, wavs, sample_rates, mouth_rois, normalize_audio=False, **kw):
         """The list form of ``separate_recording``: wavs = R raw recordings (L_r) at ``sample_rates[r]`` Hz, mouth_rois = R uint8
