@@ -423,6 +423,17 @@ int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win
                             void* stream);
 int rtfs_longform_overlap_add_f32(const float* y, float* out, int B, int n_src, int L, int window, int hop, void* stream);
 
+/* Every face of a recording (AVNet.separate_long_speakers): K lip tracks per recording, 1 <= K <= RTFS_MAX_SPEAKERS (the limit of
+ * rtfs_separator_speakers_f32), one audio track.  Plan, zeros past L and edge-frame replication are those of rtfs_longform_frame_f32.
+ * rtfs_longform_frame_speakers_f32 (one launch): wav (B,L), video (B,K,512,Tv) -> wav_win (B*N, window), written ONCE per window, and
+ *   video_win (B*N*K, 512, window / SPF), target row (b*N + n)*K + k: the (rows, K, 512, window / SPF) layout rtfs_separator_speakers_f32
+ *   takes without a copy.  Its result y (B*N, K, window) is the (B*N, n_src, window) layout of rtfs_longform_overlap_add_f32 with
+ *   n_src = K, which serves as it stands.  K outside [1, RTFS_MAX_SPEAKERS]: -4; B*N*K > 2^31 - 1 or a grid that does not fit: -1.
+ * Takes the caller's stream, allocates nothing, reads nothing back; wav_win and video_win must be 16-byte aligned (-4). */
+#define RTFS_MAX_SPEAKERS 16
+int rtfs_longform_frame_speakers_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int K, int L, int Tv,
+                                     int window, int hop, void* stream);
+
 /* Many recordings of different lengths in one pooled pass (AVNet.separate_many): R recordings, each planned on its own with
  * rtfs_longform_plan (N_r windows); the sum(N_r) windows are laid out in recording order, then window order, so `forward` runs on
  * chunks that straddle recordings.  Per recording, framing, weights and the division are exactly those of the three entries above.
@@ -503,6 +514,25 @@ int rtfs_live_overlap_add_f32(const long long* table, const float* y, float* out
                               int window, int hop, int max_chunk, int flush, void* stream);
 int rtfs_live_reset_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk,
                         void* stream);
+
+/* Every face of a stream (AVNet.open_streams(speakers = K) / SpeakerStreamPool; DESIGN.md "Every face of a stream"): a slot has one audio
+ * track and K lip tracks, 1 <= K <= RTFS_MAX_SPEAKERS.  State: aring (slots, C) as above, vring (slots, K, 512, C / SPF), acc (slots, K, C);
+ * the four counters per slot are shared by the K tracks, which are pushed together with one n_video.  rtfs_live_plan and
+ * rtfs_live_overlap_add_f32 serve as they stand with n_src = K: y (rows, K, window), a slot's result is (K, end - o).
+ * rtfs_live_speakers_sizes_ok (host only): 1 when window / hop / max_chunk are what rtfs_live_plan takes, 1 <= K <= RTFS_MAX_SPEAKERS and
+ *   K * (window + max_chunk) <= RTFS_LIVE_MAX_CAPACITY - the video share of the launch grids grows K-fold -, else 0.  A pool of sizes this
+ *   accepts cannot fail at a launch.
+ * rtfs_live_ingest_frame_speakers_f32 (one launch): table = the plan's 13 R words followed by 1 + K columns [aptr | vptr_0 | .. |
+ *   vptr_{K-1}], vptr_k[r] = the DEVICE address of speaker k's contiguous (512, nf) chunk of slot r - K separate allocations, read where
+ *   they lie, nothing packed first.  Appends the chunks to the rings and writes wav_win (rows, window), once per window, and video_win
+ *   (rows * K, 512, window / SPF), target row r*K + k.  No block reads a ring cell another block writes (k_live.hip, per track).
+ * rtfs_live_reset_speakers_f32 (one launch): rtfs_live_reset_f32 for the K-track state.
+ * Streams, alignment and trust in the device table as above; sizes rtfs_live_speakers_sizes_ok refuses: -4. */
+int rtfs_live_speakers_sizes_ok(int window, int hop, int max_chunk, int K);
+int rtfs_live_ingest_frame_speakers_f32(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
+                                        int K, int max_na, int max_nf, int window, int hop, int max_chunk, void* stream);
+int rtfs_live_reset_speakers_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int window, int max_chunk,
+                                 void* stream);
 
 /* Video front-end (the step before the path): FRCNNVideoModel.forward with backbone_type "resnet",
  * relu_type "prelu", eval mode (src/models/videomodels/frcnn_videomodel.py:61-72, resnet.py:23-118).

@@ -131,6 +131,7 @@ SIGNATURES = {
     "rtfs_stoi_f32": (_i, [_p, _p, _i, _i, _i, _p, _z, _p, _p, _p]),
     "rtfs_longform_plan": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "rtfs_longform_frame_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "rtfs_longform_frame_speakers_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rtfs_longform_overlap_add_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "rtfs_longform_many_plan": (_i, [_p, _p, _i, _i, _i, _i, _p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "rtfs_longform_frame_many_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
@@ -139,6 +140,9 @@ SIGNATURES = {
     "rtfs_live_ingest_frame_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rtfs_live_overlap_add_f32": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _i, _i, _i, _i, _i, _p]),
     "rtfs_live_reset_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "rtfs_live_speakers_sizes_ok": (_i, [_i, _i, _i, _i]),
+    "rtfs_live_ingest_frame_speakers_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "rtfs_live_reset_speakers_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "rtfs_video_pack_floats": (_z, []),
     "rtfs_video_workspace_bytes": (_z, [_i, _i]),
     "rtfs_video_frontend_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),

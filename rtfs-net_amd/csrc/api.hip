@@ -1293,6 +1293,11 @@ int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win
     if (!wav || !video || !wav_win || !video_win) return RTFS_ERR_ARG;
     return launch_longform_frame(wav, video, wav_win, video_win, B, L, Tv, window, hop, (hipStream_t)stream);
 }
+int rtfs_longform_frame_speakers_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int K, int L, int Tv,
+                                     int window, int hop, void* stream) {
+    if (!wav || !video || !wav_win || !video_win) return RTFS_ERR_ARG;
+    return launch_longform_frame_speakers(wav, video, wav_win, video_win, B, K, L, Tv, window, hop, (hipStream_t)stream);
+}
 int rtfs_longform_overlap_add_f32(const float* y, float* out, int B, int n_src, int L, int window, int hop, void* stream) {
     if (!y || !out) return RTFS_ERR_ARG;
     return launch_longform_overlap_add(y, out, B, n_src, L, window, hop, (hipStream_t)stream);
@@ -1331,6 +1336,19 @@ int rtfs_live_reset_f32(const long long* ids, float* aring, float* vring, float*
                         void* stream) {
     if (!aring || !vring || !acc) return RTFS_ERR_ARG;
     return launch_live_reset(ids, aring, vring, acc, R, n_src, window, max_chunk, (hipStream_t)stream);
+}
+
+int rtfs_live_speakers_sizes_ok(int window, int hop, int max_chunk, int K) { return live_speakers_sizes_ok(window, hop, max_chunk, K); }
+int rtfs_live_ingest_frame_speakers_f32(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
+                                        int K, int max_na, int max_nf, int window, int hop, int max_chunk, void* stream) {
+    if (!table || !aring || !vring || !wav_win || !video_win) return RTFS_ERR_ARG;
+    return launch_live_ingest_frame_speakers(table, aring, vring, wav_win, video_win, R, rows, K, max_na, max_nf, window, hop, max_chunk,
+                                             (hipStream_t)stream);
+}
+int rtfs_live_reset_speakers_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int window, int max_chunk,
+                                 void* stream) {
+    if (!aring || !vring || !acc) return RTFS_ERR_ARG;
+    return launch_live_reset_speakers(ids, aring, vring, acc, R, K, window, max_chunk, (hipStream_t)stream);
 }
 
 size_t rtfs_video_pack_floats(void) { return video_pack_floats(); }

@@ -546,6 +546,7 @@ def _lookup(table, identifier):
 
 # ----------------------------------------------------------------------------- long recordings: the two gathers restated in torch
 LONGFORM_SPF = 640  # samples per video frame: 16 kHz audio, 25 fps video
+MAX_SPEAKERS = 16  # RTFS_MAX_SPEAKERS: the most targets per mixture rtfs_separator_speakers_f32 fans out to
 
 
 def _longform_frame_torch(wav, video, N, window, hop):
@@ -829,6 +830,76 @@ class AVNet(BaseAVModel):
                        "rtfs_longform_overlap_add_f32")
             return out
 
+    def separate_long_speakers(self, audio_mixture, mouth_embeddings, window=32000, hop=None, max_batch=32):
+        """Every face of a long recording with one audio pass per window (inference only; DESIGN.md "Every face of a stream").
+        audio_mixture (L)|(B,L)|(B,1,L), mouth_embeddings (B,K,512,Tv) at 25 fps, 1 <= K <= 16, n_src 1 -> (B,K,L), where [b, k] is what
+        ``separate_long(audio_mixture, mouth_embeddings[:, k])`` gives for recording b: windows, edge-frame replication, cross-fade
+        weights and the division by the weight sum are exactly those of ``separate_long``.
+
+        The audio is framed once per window (rtfs_longform_frame_speakers_f32: one launch, the K video windows of a row behind each other)
+        and the B * N windows go through ``separate_speakers`` in chunks of max(1, max_batch // K) windows, so a call never carries more
+        than ``max_batch`` targets when K <= max_batch; y (B*N, K, window) is the overlap-add's (B*N, n_src, window) layout with n_src = K
+        (rtfs_longform_overlap_add_f32, one launch).  Capturable in a HIP graph at fixed shapes, like ``separate_long``.
+
+        ValueError for what ``separate_long`` refuses and for what ``separate_speakers`` refuses (rank, n_src != 1), and for K outside
+        1 .. 16; RuntimeError in ``.train()`` mode.  With ``fused = False``, or on CPU tensors, the same plan runs with ``forward_modular``
+        on the windows repeated K times and the two gathers restated in torch."""
+        if audio_mixture.ndim not in (1, 2, 3) or (audio_mixture.ndim == 3 and audio_mixture.shape[1] != 1):
+            raise ValueError(f"separate_long_speakers: audio_mixture must be (L), (B,L) or (B,1,L); got {tuple(audio_mixture.shape)}")
+        wav = STFTEncoder.unsqueeze_to_2D(audio_mixture)
+        B, L = int(wav.shape[0]), int(wav.shape[1])
+        if mouth_embeddings is None or mouth_embeddings.ndim != 4 or mouth_embeddings.shape[0] != B or mouth_embeddings.shape[2] != 512:
+            raise ValueError(f"separate_long_speakers: {B} recording(s) but mouth_embeddings "
+                             f"{None if mouth_embeddings is None else tuple(mouth_embeddings.shape)} (expected (B,K,512,Tv))")
+        K, Tv = int(mouth_embeddings.shape[1]), int(mouth_embeddings.shape[-1])
+        if not 1 <= K <= MAX_SPEAKERS:
+            raise ValueError(f"separate_long_speakers: K = {K} target speakers; 1 .. {MAX_SPEAKERS}")
+        if self.n_src != 1:
+            raise ValueError("separate_long_speakers: target-speaker models only (n_src 1)")
+        window = int(window)
+        hop = window // 2 if hop is None else int(hop)
+        max_batch = int(max_batch)
+        if max_batch < 1:
+            raise ValueError(f"separate_long_speakers: max_batch = {max_batch}")
+        lib = _lib.load()
+        n_win = ctypes.c_int(0)
+        if lib.rtfs_longform_plan(L, Tv, window, hop, ctypes.byref(n_win)) != 0:
+            raise ValueError(f"separate_long_speakers: window = {window}, hop = {hop} must be multiples of {LONGFORM_SPF} with "
+                             f"0 < hop <= window (L = {L}, Tv = {Tv} at least 1)")
+        rnn_kind = self.refinement_module.audio_net.get_block(0).rnn_kind
+        if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
+            raise ValueError(f"separate_long_speakers: a window of {window} samples does not fit the fused separator of this model's cell "
+                             f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
+        if self.training:
+            raise RuntimeError("AVNet.separate_long_speakers is inference only: call .eval()")
+        N, Wv = int(n_win.value), window // LONGFORM_SPF
+        on_hip = self.fused and wav.is_cuda and mouth_embeddings.is_cuda
+        step = max(1, max_batch // K)
+        with torch.no_grad():
+            if on_hip:
+                _lib.need_gpu(wav, mouth_embeddings)
+                wav, video = wav.contiguous(), mouth_embeddings.contiguous()
+                xw = _lib.empty(B * N, window, device=wav.device, dtype=torch.float32)
+                vw = _lib.empty(B * N, K, 512, Wv, device=wav.device, dtype=torch.float32)
+                _lib.check(lib.rtfs_longform_frame_speakers_f32(_lib.ptr(wav), _lib.ptr(video), _lib.ptr(xw), _lib.ptr(vw), B, K, L, Tv, window,
+                                                                hop, _lib.stream_of(wav)), "rtfs_longform_frame_speakers_f32")
+            else:
+                xw, vw = _longform_frame_torch(wav, mouth_embeddings.reshape(B, K * 512, Tv), N, window, hop)
+                vw = vw.view(B * N, K, 512, Wv)
+            y = _lib.empty(B * N, K, window, device=wav.device, dtype=torch.float32)
+            for c0 in range(0, B * N, step):
+                c1 = min(B * N, c0 + step)
+                if on_hip:
+                    y[c0:c1].copy_(self.separate_speakers(xw[c0:c1], vw[c0:c1]))
+                else:
+                    y[c0:c1].copy_(self.forward_modular(xw[c0:c1].repeat_interleave(K, 0), vw[c0:c1].reshape(-1, 512, Wv)).view(c1 - c0, K, window))
+            if not on_hip:
+                return _longform_overlap_add_torch(y, B, N, L, window, hop)
+            out = _lib.empty(B, K, L, device=wav.device, dtype=torch.float32)
+            _lib.check(lib.rtfs_longform_overlap_add_f32(_lib.ptr(y), _lib.ptr(out), B, K, L, window, hop, _lib.stream_of(wav)),
+                       "rtfs_longform_overlap_add_f32")
+            return out
+
     def separate_many(self, mixtures, mouth_embeddings, window=32000, hop=None, max_batch=32):
         """R recordings of different lengths in one pooled pass on the fused separator (inference only; DESIGN.md "Many recordings").
         mixtures: a sequence of R >= 1 float32 tensors (L_r)|(1,L_r); mouth_embeddings: R tensors (512,Tv_r) at 25 fps -> a list of R
@@ -926,7 +997,7 @@ class AVNet(BaseAVModel):
                                                               window, hop, _lib.stream_of(xw)), "rtfs_longform_overlap_add_many_f32")
             return [out[int(o):int(o) + n_src * int(w.shape[0])].view(n_src, int(w.shape[0])) for o, w in zip(offs, wavs)]
 
-    def open_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
+    def open_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000, speakers=1):
         """``slots`` live streams separated chunk by chunk (inference only; DESIGN.md "Live streams") -> ``streaming.StreamPool``.  The
         stateful form of ``separate_long``: ``pool.push(slot_ids, audio_chunks, video_chunks)`` takes what arrived (audio chunks of at most
         ``max_chunk`` samples, default ``window``; lip embeddings (512,m) at 25 fps) and returns the samples no later window can touch;
@@ -939,9 +1010,19 @@ class AVNet(BaseAVModel):
         ``sample_rate`` other than 16000 (DESIGN.md "Live streams at the microphone's rate") -> ``streaming.RateStreamPool``, the same
         surface with audio chunks at that rate, float32 or int16 PCM, of at most floor(max_chunk o / n) samples, resampled on the device
         chunk by chunk; the outputs equal ``separate_long(datas.resample(wav, sample_rate), ...)``.  ``window``, ``hop`` and
-        ``max_chunk`` stay in 16 kHz samples."""
+        ``max_chunk`` stay in 16 kHz samples.
+
+        ``speakers`` = K > 1 (DESIGN.md "Every face of a stream"; 1 <= K <= 16, n_src 1) -> ``streaming.SpeakerStreamPool``: every slot has
+        one audio track and K lip tracks, the video chunk of a slot is a (K,512,m) tensor or a sequence of K (512,m) tensors, ``push`` /
+        ``flush`` return (K,k) per slot, and target k equals the single-track pool on the same audio with lips k.  The audio is stored,
+        framed and run through the audio-only prefix once per window (``separate_speakers`` in chunks of max(1, max_batch // K) windows).
+        ValueError for K outside 1 .. 16, n_src != 1, K * (window + max_chunk) > 2^24, and for ``speakers`` > 1 together with a
+        ``sample_rate`` other than 16000, which this pool does not take.  ``speakers`` = 1 is today's pool."""
         from . import streaming
-        return streaming.open_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, sample_rate=sample_rate)
+        if streaming.speakers_of(speakers) == 1:
+            return streaming.open_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, sample_rate=sample_rate)
+        return streaming.open_speaker_streams(self, slots, speakers, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch,
+                                              sample_rate=sample_rate)
 
     def _side_stream(self, device):
         streams = self.__dict__.setdefault("_side_streams", {})

@@ -210,7 +210,12 @@ class StreamPool:
 
     # -- the same tick in torch ops (fused = False, CPU tensors): ingest, gather from the rings, accumulate window by window
     def _tick_torch(self, R, table, rows, floats, wavs, vids, flush):
-        W, H, C, n_src, dev = self.window, self.hop, self.capacity, self.n_src, self.device
+        self._frame_torch(R, table, wavs, vids, flush)
+        self._forward_rows(rows)
+        return self._overlap_add_torch(R, table, floats, flush)
+
+    def _frame_torch(self, R, table, wavs, vids, flush):
+        W, H, C, dev = self.window, self.hop, self.capacity, self.device
         Cv, Wv, Hv = C // SPF, W // SPF, H // SPF
         slot, a0, na, f0, nf, e0, cnt, row0, o0, end, off, apos, fpos = (table[k * R:(k + 1) * R] for k in range(PLAN_WORDS))
         iw, ifr = torch.arange(W, device=dev), torch.arange(Wv, device=dev)
@@ -223,7 +228,11 @@ class StreamPool:
                 row, p = row0[r] + n - e0[r], n * H + iw
                 self._xw[row] = torch.where(p < lim_a, self._aring[slot[r], p % C], torch.zeros((), device=dev))
                 self._vw[row] = self._vring[slot[r]][:, (n * Hv + ifr).clamp(max=lim_f - 1) % Cv]
-        self._forward_rows(rows)
+
+    def _overlap_add_torch(self, R, table, floats, flush):
+        W, H, C, n_src, dev = self.window, self.hop, self.capacity, self.n_src, self.device
+        slot, a0, na, f0, nf, e0, cnt, row0, o0, end, off, apos, fpos = (table[k * R:(k + 1) * R] for k in range(PLAN_WORDS))
+        iw = torch.arange(W, device=dev)
         out = _lib.empty(floats, device=dev)
         w, V = _weights(W, H, dev), W - H
         for r in range(R):
@@ -270,6 +279,187 @@ def open_streams(model, slots, window=32000, hop=None, max_chunk=None, max_batch
     if model.training:
         raise RuntimeError("AVNet.open_streams is inference only: call .eval()")
     return StreamPool(model, slots, window, hop, max_chunk, max_batch)
+
+
+# ================================================================ every face of a stream (DESIGN.md "Every face of a stream")
+MAX_SPEAKERS = 16  # RTFS_MAX_SPEAKERS: the most targets per mixture rtfs_separator_speakers_f32 fans out to
+
+
+def speakers_of(speakers):
+    """``speakers`` as an integer in 1 .. MAX_SPEAKERS; ValueError otherwise."""
+    try:
+        if isinstance(speakers, bool):
+            raise TypeError
+        K = operator.index(speakers)
+    except TypeError:
+        raise ValueError(f"open_streams: speakers must be an integer; got {speakers!r}") from None
+    if not 1 <= K <= MAX_SPEAKERS:
+        raise ValueError(f"open_streams: speakers = {K}; 1 .. {MAX_SPEAKERS} target speakers per stream")
+    return K
+
+
+class SpeakerStreamPool(StreamPool):
+    """``slots`` live streams with ``speakers`` = K faces each on one target-speaker model (n_src 1, inference only).  Built by
+    ``AVNet.open_streams(..., speakers=K)``; the surface is ``StreamPool``'s.
+
+    A slot has ONE audio track and K lip tracks.  Target k of a slot gets what a ``StreamPool`` gives for the same audio with lips k, but
+    the audio is stored once (one ring), framed once per window and run through the audio-only prefix once per window
+    (``AVNet.separate_speakers`` on (rows, K, 512, window / 640) in chunks of max(1, max_batch // K) windows).  Device state per slot:
+    an audio ring of C = window + max_chunk samples, K lip rings (K, 512, C / 640) and K accumulators (K, C):
+    4 C (1 + K) + 2048 K C / 640 bytes, allocated once.  Host state stays four integers per slot: the K tracks are pushed together with
+    one m, so they share f.  The tick is ``rtfs_live_plan`` and ``rtfs_live_overlap_add_f32`` with n_src = K around
+    ``rtfs_live_ingest_frame_speakers_f32``, whose table carries one device address per (slot, speaker): the K chunks of a slot are
+    read where they lie, still one table upload per tick."""
+
+    def __init__(self, model, slots, speakers, window, hop, max_chunk, max_batch):
+        self.model, self.slots, self.window, self.hop, self.max_chunk, self.max_batch = model, slots, window, hop, max_chunk, max_batch
+        self.speakers = self.n_src = K = int(speakers)  # the plan, the accumulator and the results see K sources
+        self.capacity = window + max_chunk
+        self.device = next(model.parameters()).device
+        self.on_hip = bool(model.fused) and self.device.type == "cuda"
+        self._counters = [[0, 0, 0, 0] for _ in range(slots)]
+        C, Wv, dev = self.capacity, window // SPF, self.device
+        rows_cap = slots * (1 + -(-max_chunk // hop))
+        self._aring = _lib.empty(slots, C, device=dev)
+        self._vring = _lib.empty(slots, K, 512, C // SPF, device=dev)
+        self._acc = _lib.empty(slots, K, C, device=dev)
+        self._xw = _lib.empty(rows_cap, window, device=dev)
+        self._vw = _lib.empty(rows_cap * K, 512, Wv, device=dev)
+        self._y = _lib.empty(rows_cap, K, window, device=dev)
+        self._reset_state(None, slots)
+
+    def push(self, slot_ids, audio_chunks, video_chunks):
+        """As ``StreamPool.push``, with the video chunk of a slot a (K,512,m) tensor or a sequence of K (512,m) tensors - K separate
+        allocations are read where they lie - with one m, 0 <= m <= max_chunk // 640.  Returns, per named slot, the (K, k) newly final
+        samples.  ValueError - before any launch, all state unchanged - for what ``StreamPool.push`` refuses, for a wrong number of
+        tracks and for tracks that differ in m."""
+        ids, na, nf, wavs, vids = self._check_chunks(slot_ids, audio_chunks, video_chunks)
+        return self._tick(ids, na, nf, wavs, vids, flush=False)
+
+    def _check_chunks(self, slot_ids, audio_chunks, video_chunks):
+        K = self.speakers
+        ids = self._check_ids(slot_ids)
+        try:
+            audio_chunks, video_chunks = list(audio_chunks), list(video_chunks)
+        except TypeError:
+            raise ValueError("SpeakerStreamPool.push: audio_chunks and video_chunks must be sequences") from None
+        if not len(ids) == len(audio_chunks) == len(video_chunks):
+            raise ValueError(f"SpeakerStreamPool.push: {len(ids)} slot id(s), {len(audio_chunks)} audio and {len(video_chunks)} video chunk(s)")
+        wavs, vids = [], []
+        for r, (w, v) in enumerate(zip(audio_chunks, video_chunks)):
+            if isinstance(v, torch.Tensor):
+                if v.ndim != 3:
+                    raise ValueError(f"SpeakerStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m); got {tuple(v.shape)}")
+                tracks = list(v.unbind(0))
+            else:
+                try:
+                    tracks = list(v)
+                except TypeError:
+                    raise ValueError(f"SpeakerStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m)") from None
+            if len(tracks) != K:
+                raise ValueError(f"SpeakerStreamPool.push: video chunk {r} holds {len(tracks)} track(s); the pool has {K} speakers per slot")
+            if not isinstance(w, torch.Tensor) or any(not isinstance(t, torch.Tensor) for t in tracks):
+                raise ValueError(f"SpeakerStreamPool.push: chunk {r} is not made of tensors")
+            if w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
+                raise ValueError(f"SpeakerStreamPool.push: audio chunk {r} must be (n) or (1,n); got {tuple(w.shape)}")
+            for t in tracks:
+                if t.ndim != 2 or t.shape[0] != 512:
+                    raise ValueError(f"SpeakerStreamPool.push: every track of video chunk {r} must be (512,m); got {tuple(t.shape)}")
+                if t.dtype != torch.float32 or t.device != self.device:
+                    raise ValueError(f"SpeakerStreamPool.push: video chunk {r} is {t.dtype} on {t.device}; the pool is float32 on {self.device}")
+            if len({int(t.shape[1]) for t in tracks}) != 1:
+                raise ValueError(f"SpeakerStreamPool.push: the tracks of video chunk {r} hold {[int(t.shape[1]) for t in tracks]} frames; "
+                                 "all speakers of a slot are pushed with one m")
+            if w.dtype != torch.float32 or w.device != self.device:
+                raise ValueError(f"SpeakerStreamPool.push: audio chunk {r} is {w.dtype} on {w.device}; the pool is float32 on {self.device}")
+            wavs.append(w.reshape(-1).contiguous())
+            vids.append([t.contiguous() for t in tracks])
+        return ids, [int(w.shape[0]) for w in wavs], [int(v[0].shape[1]) for v in vids], wavs, vids
+
+    def _forward_rows(self, rows):
+        K, Wv = self.speakers, self.window // SPF
+        vw = self._vw.view(-1, K, 512, Wv)
+        step = max(1, self.max_batch // K)
+        for c0 in range(0, rows, step):
+            c1 = min(rows, c0 + step)
+            if self.on_hip:
+                self._y[c0:c1].copy_(self.model.separate_speakers(self._xw[c0:c1], vw[c0:c1]))
+            else:  # target k of a window = the model on that window with lips k
+                y = self.model.forward_modular(self._xw[c0:c1].repeat_interleave(K, 0), self._vw[c0 * K:c1 * K])
+                self._y[c0:c1].copy_(y.view(c1 - c0, K, self.window))
+
+    def _tick_hip(self, R, table, rows, floats, max_span, max_na, max_nf, wavs, vids, flush):
+        lib, dev, K = _lib.load(), self.device, self.speakers
+        if flush:
+            ptrs = [0] * ((1 + K) * R)
+        else:  # columns [aptr | vptr_0 | .. | vptr_{K-1}]: one device address per (slot, speaker)
+            ptrs = [w.data_ptr() for w in wavs] + [v[k].data_ptr() for k in range(K) for v in vids]
+        tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
+        st = _lib.stream_of(self._xw)
+        _lib.check(lib.rtfs_live_ingest_frame_speakers_f32(_lib.ptr(tab), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._xw),
+                                                           _lib.ptr(self._vw), R, rows, K, max_na, max_nf, self.window, self.hop, self.max_chunk,
+                                                           st), "rtfs_live_ingest_frame_speakers_f32")
+        self._forward_rows(rows)
+        out = _lib.empty(floats, device=dev)
+        if max_span > 0:
+            _lib.check(lib.rtfs_live_overlap_add_f32(_lib.ptr(tab), _lib.ptr(self._y), _lib.ptr(out), _lib.ptr(self._acc), R, max_span, K,
+                                                     self.window, self.hop, self.max_chunk, int(flush), st), "rtfs_live_overlap_add_f32")
+        if flush:
+            self._reset_state(tab[:R], R)
+        return out
+
+    def _reset_state(self, ids, R):
+        if not self.on_hip:
+            return super()._reset_state(ids, R)
+        _lib.check(_lib.load().rtfs_live_reset_speakers_f32(_lib.ptr(ids), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._acc), R,
+                                                            self.speakers, self.window, self.max_chunk, _lib.stream_of(self._aring)),
+                   "rtfs_live_reset_speakers_f32")
+
+    # -- the same ingest + framing in torch ops: the audio once, every track as StreamPool frames its one
+    def _frame_torch(self, R, table, wavs, vids, flush):
+        W, H, C, K, dev = self.window, self.hop, self.capacity, self.speakers, self.device
+        Cv, Wv, Hv = C // SPF, W // SPF, H // SPF
+        slot, a0, na, f0, nf, e0, cnt, row0, o0, end, off, apos, fpos = (table[k * R:(k + 1) * R] for k in range(PLAN_WORDS))
+        iw, ifr = torch.arange(W, device=dev), torch.arange(Wv, device=dev)
+        for r in range(R):
+            if not flush:
+                self._aring[slot[r], (apos[r] + torch.arange(na[r], device=dev)) % C] = wavs[r]
+                for k in range(K):
+                    self._vring[slot[r], k][:, (fpos[r] + torch.arange(nf[r], device=dev)) % Cv] = vids[r][k]
+            lim_a, lim_f = a0[r] + na[r], f0[r] + nf[r]
+            for n in range(e0[r], e0[r] + cnt[r]):
+                row, p = row0[r] + n - e0[r], n * H + iw
+                self._xw[row] = torch.where(p < lim_a, self._aring[slot[r], p % C], torch.zeros((), device=dev))
+                for k in range(K):
+                    self._vw[row * K + k] = self._vring[slot[r], k][:, (n * Hv + ifr).clamp(max=lim_f - 1) % Cv]
+
+
+def open_speaker_streams(model, slots, speakers, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
+    """``AVNet.open_streams(speakers=K)`` with K > 1: the checks of ``open_streams`` and those of ``separate_speakers``, then the pool."""
+    K = speakers_of(speakers)
+    slots, window = int(slots), int(window)
+    hop = window // 2 if hop is None else int(hop)
+    max_chunk = window if max_chunk is None else int(max_chunk)
+    max_batch = int(max_batch)
+    if _rate(sample_rate) != FS:
+        raise ValueError(f"open_streams: speakers = {K} with sample_rate = {sample_rate}: a pool with several speakers takes 16 kHz audio only")
+    if int(model.n_src) != 1:
+        raise ValueError("open_streams: speakers > 1 needs a target-speaker model (n_src 1)")
+    if slots < 1 or max_batch < 1:
+        raise ValueError(f"open_streams: slots = {slots}, max_batch = {max_batch}; both at least 1")
+    lib = _lib.load()
+    if lib.rtfs_longform_plan(1, 1, window, hop, None) != 0:
+        raise ValueError(f"open_streams: window = {window}, hop = {hop} must be multiples of {SPF} with 0 < hop <= window")
+    if max_chunk < SPF or max_chunk % SPF or not lib.rtfs_live_speakers_sizes_ok(window, hop, max_chunk, K):
+        raise ValueError(f"open_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF} with speakers * (window + max_chunk) "
+                         f"<= {MAX_CAPACITY} (speakers = {K})")
+    rnn_kind = model.refinement_module.audio_net.get_block(0).rnn_kind
+    if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
+        raise ValueError(f"open_streams: a window of {window} samples does not fit the fused separator of this model's cell "
+                         f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
+    if model.training:
+        raise RuntimeError("AVNet.open_streams is inference only: call .eval()")
+    return SpeakerStreamPool(model, slots, K, window, hop, max_chunk, max_batch)
 
 
 # ================================================================ live streams from camera frames (DESIGN.md "Live streams from camera frames")
@@ -554,8 +744,107 @@ class CameraStreamPool:
         self.audio.reset(ids)
 
 
-def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000):
+class SpeakerCameraStreamPool(CameraStreamPool):
+    """``CameraStreamPool`` with ``speakers`` = K faces per slot.  Built by ``System.open_camera_streams(..., speakers=K)``.
+
+    The ``LipStreamPool`` has slots * K tracks, track s K + k for face k of slot s, and the audio pool is a ``SpeakerStreamPool``: the
+    per-track embedding blocks of a tick go straight on, as the K video chunks of slot s, through the per-speaker addresses of the
+    tick table.  The ROI chunk of a slot is (K,m,H,W) uint8 or (K,m,88,88) float32.  For any chunking output k of a slot equals
+    ``System.separate_recording(wav, 16000, rois[k])``."""
+
+    def __init__(self, lips, audio, max_chunk):
+        super().__init__(lips, audio, max_chunk)
+        self.speakers = audio.speakers
+
+    def _tracks(self, ids):
+        K = self.speakers
+        return [s * K + k for s in ids for k in range(K)]
+
+    def _group(self, embs):
+        K = self.speakers
+        return [embs[r:r + K] for r in range(0, len(embs), K)]
+
+    def _check_slots(self, slot_ids):
+        ids = self.lips._check_ids(slot_ids)
+        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
+            raise ValueError(f"SpeakerCameraStreamPool: slot ids {ids} must be distinct and in [0, {self.slots})")
+        return ids
+
+    def counters(self, slot):
+        """((a, f, e, o) of the audio pool, (g, v) of the slot's lip tracks, which move together); f == v between calls."""
+        return self.audio.counters(slot), self.lips.counters(int(slot) * self.speakers)
+
+    def push(self, slot_ids, audio_chunks, roi_chunks):
+        """As ``CameraStreamPool.push``, with the mouth frames of a slot as ONE tensor (K,m,H,W) uint8 or (K,m,88,88) float32.  Returns,
+        per named slot, the (K, k) newly final samples.  ValueError - before any launch, all state unchanged - for what either pool
+        refuses and for a chunk that does not hold K tracks."""
+        K = self.speakers
+        ids = self._check_slots(slot_ids)
+        try:
+            roi_chunks = list(roi_chunks)
+        except TypeError:
+            raise ValueError("SpeakerCameraStreamPool.push: roi_chunks must be a sequence of tensors") from None
+        if len(roi_chunks) != len(ids):
+            raise ValueError(f"SpeakerCameraStreamPool.push: {len(ids)} slot id(s) and {len(roi_chunks)} ROI chunk(s)")
+        for r, c in enumerate(roi_chunks):
+            if not isinstance(c, torch.Tensor) or c.ndim != 4 or c.shape[0] != K:
+                raise ValueError(f"SpeakerCameraStreamPool.push: ROI chunk {r} must be a tensor ({K},m,H,W)")
+        _, ms, rois, u8 = self.lips._check_chunks(self._tracks(ids), [t for c in roi_chunks for t in c.contiguous().unbind(0)])
+        wavs = self._check_audio(ids, audio_chunks)
+        if not ids:
+            return []
+        self._plan_push(ids, [int(w.numel()) for w in wavs], ms)  # refused here, nothing has moved yet
+        if self.audio.model.training:
+            raise RuntimeError("SpeakerCameraStreamPool is inference only: call .eval() on the model")
+        embs = self.lips._tick(self._tracks(ids), ms, rois, u8, flush=False)
+        return self.audio.push(ids, wavs, self._group(embs))
+
+    def _plan_push(self, ids, na, ms):
+        """The dry run of a push of na samples per named slot and ms frames per named TRACK on both planners."""
+        K, R = self.speakers, len(ids)
+        _, vtab, _ = self.lips._plan(self._tracks(ids), ms, False)
+        ks = vtab[4 * R * K:5 * R * K][::K]  # the tracks of a slot share their counters: one k per slot
+        room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
+        for s, m in zip(ids, ms[::K]):
+            if self.lips._counters[s * K][0] + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
+                raise ValueError(f"SpeakerCameraStreamPool.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
+        return self.audio._plan(ids, na, ks, False)
+
+    def flush(self, slot_ids):
+        """As ``CameraStreamPool.flush``: the lip pool's flush of the slots' tracks, their remaining embeddings pushed with empty audio,
+        then the audio pool's flush.  Returns the remaining (K, k) samples per slot."""
+        ids = self._check_slots(slot_ids)
+        if not ids:
+            return []
+        self._plan_flush(ids)
+        if self.audio.model.training:
+            raise RuntimeError("SpeakerCameraStreamPool is inference only: call .eval() on the model")
+        embs = self.lips.flush(self._tracks(ids))
+        empty = _lib.empty(0, device=self.device)
+        mid = self.audio.push(ids, [empty] * len(ids), self._group(embs))
+        last = self.audio.flush(ids)
+        return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
+
+    def _plan_flush(self, ids):
+        K, R = self.speakers, len(ids)
+        _, vtab, _ = self.lips._plan(self._tracks(ids), None, True)
+        ks = vtab[4 * R * K:5 * R * K][::K]
+        new, _, _ = self.audio._plan(ids, [0] * R, ks, False)
+        with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the middle push leaves
+            self.audio._plan(ids, None, None, True)
+
+    def reset(self, slot_ids):
+        """Drop the named streams without output."""
+        ids = self._check_slots(slot_ids)
+        self.lips.reset(self._tracks(ids))
+        self.audio.reset(ids)
+
+
+def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1):
     """``System.open_camera_streams``: the lip pool and the audio pool of one set of slots."""
+    K = speakers_of(speakers)
+    if K > 1 and _rate(sample_rate) != FS:
+        raise ValueError(f"open_camera_streams: speakers = {K} with sample_rate = {sample_rate}: several speakers take 16 kHz audio only")
     if _rate(sample_rate) != FS:
         mc = (window if max_chunk is None else max_chunk)
         return _open_at_rate(lambda room: open_camera_streams(system, slots, window, hop, mc + room, max_batch, roi_hw), sample_rate, mc)
@@ -568,11 +857,12 @@ def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, m
         raise ValueError("open_camera_streams: window and max_chunk must be integers") from None
     if max_chunk < SPF or max_chunk % SPF:
         raise ValueError(f"open_camera_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF}")
-    audio = system.audio_model.open_streams(slots, window=window, hop=hop, max_chunk=max_chunk + LOOKAHEAD * SPF, max_batch=max_batch)
-    lips = system.video_model.open_streams(slots, max_frames=max_chunk // SPF, roi_hw=roi_hw)
+    audio = system.audio_model.open_streams(slots, window=window, hop=hop, max_chunk=max_chunk + LOOKAHEAD * SPF, max_batch=max_batch,
+                                            speakers=K)
+    lips = system.video_model.open_streams(audio.slots * K, max_frames=max_chunk // SPF, roi_hw=roi_hw)
     if lips.device != audio.device:
         raise ValueError(f"open_camera_streams: the video model lies on {lips.device}, the audio model on {audio.device}")
-    return CameraStreamPool(lips, audio, max_chunk)
+    return (SpeakerCameraStreamPool if K > 1 else CameraStreamPool)(lips, audio, max_chunk)
 
 
 # ================================================================ live streams at the microphone's rate (DESIGN.md "Live streams at the microphone's rate")

@@ -61,6 +61,19 @@ class System(nn.Module):
             emb = self.video_model(mouth.type_as(wav))
         return self.audio_model.separate_long(wav, emb, **kw)
 
+    def separate_long_speakers(self, wav, mouths, **kw):
+        """Every face of a long recording with one audio pass per window (inference): wav (L)|(B,L)|(B,1,L), mouths (B,K,1,Tv,88,88) at
+        25 fps -> (B,K,L).  The video front-end runs ONCE on the B*K whole tracks (no_grad), then ``AVNet.separate_long_speakers(**kw)``.
+        Without a video model the mouth slot holds lip embeddings (B,K,512,Tv)."""
+        if self.video_model is None:
+            return self.audio_model.separate_long_speakers(wav, mouths, **kw)
+        if mouths.ndim != 6:
+            raise ValueError(f"System.separate_long_speakers: mouths must be (B,K,1,Tv,88,88); got {tuple(mouths.shape)}")
+        B, K = int(mouths.shape[0]), int(mouths.shape[1])
+        with torch.no_grad():
+            emb = self.video_model(mouths.reshape(B * K, *mouths.shape[2:]).type_as(wav))
+        return self.audio_model.separate_long_speakers(wav, emb.reshape(B, K, *emb.shape[1:]), **kw)
+
     def separate_recording(self, wav, sample_rate, mouth_rois, normalize_audio=False, **kw):
         """A raw recording end to end on the device (inference), the whole of ``infer_any_video.py:63-86``: wav (L) | (B,L) at
         ``sample_rate`` Hz, mouth_rois uint8 (Tv,H,W) | (B,Tv,H,W) at 25 fps -> (B, n_src, L at 16 kHz).  ``datas.resample`` to 16 kHz, the
@@ -105,10 +118,11 @@ class System(nn.Module):
         """Live streams chunk by chunk (inference): ``AVNet.open_streams(**kw)`` of the audio model.  The caller pushes lip EMBEDDINGS
         (512,m): the video stem is a 3-D convolution with temporal context, so frames embedded chunk by chunk are not the whole-track
         embedding without look-ahead state.  ``open_camera_streams`` is the entry that takes the camera's frames and keeps that state.
-        ``sample_rate``: the rate of the audio chunks, as ``AVNet.open_streams`` takes it."""
+        ``sample_rate``: the rate of the audio chunks, as ``AVNet.open_streams`` takes it.  ``speakers=K`` (in ``**kw``): K lip tracks per
+        slot -> ``streaming.SpeakerStreamPool``, as ``AVNet.open_streams`` describes."""
         return self.audio_model.open_streams(sample_rate=sample_rate, **kw)
 
-    def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000):
+    def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1):
         """Live streams from microphone samples and camera frames (inference; DESIGN.md "Live streams from camera frames") ->
         ``streaming.CameraStreamPool``.  ``pool.push(slot_ids, audio_chunks, roi_chunks)`` takes 16 kHz audio chunks of at most
         ``max_chunk`` samples (default ``window``) and uint8 mouth ROIs (m,H,W) with (H,W) == ``roi_hw`` at 25 fps (or float32 prepared lips
@@ -119,10 +133,14 @@ class System(nn.Module):
         ``sample_rate`` other than 16000 (DESIGN.md "Live streams at the microphone's rate") -> ``streaming.RateStreamPool``: the audio
         chunks are at that rate, float32 or int16 PCM, at most floor(max_chunk o / n) samples, and are resampled on the device chunk by
         chunk, bit-equal to ``datas.resample`` of the whole recording; ``window``, ``hop`` and ``max_chunk`` stay in 16 kHz samples.
-        ``normalize_audio`` has no streamed form: it needs the whole recording's deviation."""
+        ``normalize_audio`` has no streamed form: it needs the whole recording's deviation.
+
+        ``speakers`` = K > 1 (DESIGN.md "Every face of a stream") -> ``streaming.SpeakerCameraStreamPool``: the ROI chunk of a slot is
+        (K,m,H,W) uint8 or (K,m,88,88) float32, the results are (K,k), and output k of a slot equals ``separate_recording(wav, 16000,
+        rois[k])``; 16 kHz audio only (ValueError with another ``sample_rate``)."""
         from . import streaming
         return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
-                                             sample_rate=sample_rate)
+                                             sample_rate=sample_rate, speakers=speakers)
 
     def separate_recordings(self, wavs, sample_rates, mouth_rois, normalize_audio=False, **kw):
         """The list form of ``separate_recording``: wavs = R raw recordings (L_r) at ``sample_rates[r]`` Hz, mouth_rois = R uint8
