@@ -412,7 +412,7 @@ int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, vo
  * [n hop / SPF, (n hop + window) / SPF) (an index past Tv - 1 reads frame Tv - 1).
  * rtfs_longform_plan (host only, no device call): checks L >= 1, Tv >= 1, window % SPF == 0, hop % SPF == 0, 0 < hop <= window (-4
  *   otherwise) and writes N = 1 if L <= window, else 1 + ceil((L - window) / hop).  N may be NULL.
- * rtfs_longform_frame_f32 (one launch): wav (B,L), video (B,512,Tv) -> wav_win (B*N, window), video_win (B*N, 512, window / SPF), row b*N + n.
+ * rtfs_longform_frame_f32: rtfs_longform_frame_speakers_f32 (below) with K = 1: video (B,512,Tv) -> video_win (B*N, 512, window / SPF), row b*N + n.
  * rtfs_longform_overlap_add_f32 (one launch): y (B*N, n_src, window) -> out (B, n_src, L),
  *   out[b,s,t] = sum_n w[t - n hop] y[b*N + n, s, t - n hop] / sum_n w[t - n hop] over the windows that contain t, in ascending n, with
  *   w[i] = 1 if window == hop, else min(1, (i + 0.5) / V, (window - i - 0.5) / V), V = window - hop.  Gather form: every output element is
@@ -424,7 +424,7 @@ int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win
 int rtfs_longform_overlap_add_f32(const float* y, float* out, int B, int n_src, int L, int window, int hop, void* stream);
 
 /* Every face of a recording (AVNet.separate_long_speakers): K lip tracks per recording, 1 <= K <= RTFS_MAX_SPEAKERS (the limit of
- * rtfs_separator_speakers_f32), one audio track.  Plan, zeros past L and edge-frame replication are those of rtfs_longform_frame_f32.
+ * rtfs_separator_speakers_f32), one audio track.  Plan, zeros past L and edge-frame replication are those described above.
  * rtfs_longform_frame_speakers_f32 (one launch): wav (B,L), video (B,K,512,Tv) -> wav_win (B*N, window), written ONCE per window, and
  *   video_win (B*N*K, 512, window / SPF), target row (b*N + n)*K + k: the (rows, K, 512, window / SPF) layout rtfs_separator_speakers_f32
  *   takes without a copy.  Its result y (B*N, K, window) is the (B*N, n_src, window) layout of rtfs_longform_overlap_add_f32 with
@@ -464,9 +464,13 @@ int rtfs_longform_overlap_add_many_f32(const float* y, float* out, const long lo
 /* Live streams chunk by chunk (AVNet.open_streams / StreamPool; DESIGN.md "Live streams"): the stateful form of the long-form plan.  Window
  * n of a stream is run as soon as a >= n hop + window samples AND f >= n hop / SPF + window / SPF frames have arrived; after window n the
  * samples [n hop, (n + 1) hop) are final.  The concatenated outputs of any chunking equal rtfs_longform_* on the whole recording.
- * State (caller-allocated, 16-byte aligned, C = window + max_chunk): aring (slots, C), vring (slots, 512, C / SPF), acc (slots, n_src, C);
- * sample p lives in cell p % C, frame q in column q % (C / SPF).  The caller keeps four counters per slot [a samples received | f frames
- * received | e windows emitted | o samples output]; nothing is ever read back from the device.
+ * A slot has one audio track and K lip tracks, 1 <= K <= RTFS_MAX_SPEAKERS, pushed together with one n_video; the entry points without
+ * "speakers" in their name are K = 1 of those with it (below).
+ * State (caller-allocated, 16-byte aligned, C = window + max_chunk): aring (slots, C), vring (slots, K, 512, C / SPF), acc (slots, n_src, C);
+ * sample p lives in cell p % C, frame q of track k in column q % (C / SPF) of plane (slot, k).  n_src counts the rows of a window's
+ * result y: the model's sources at K = 1, the K targets of rtfs_separator_speakers_f32 otherwise.  The caller keeps four counters per
+ * slot [a samples received | f frames received | e windows emitted | o samples output], shared by the K tracks; nothing is ever read
+ * back from the device.
  * rtfs_live_plan (host only, no device call, the single place with the arithmetic): for the R slots named in slot_ids, counters (R x 4,
  *   row-major) and the chunk sizes n_audio, n_video of this push (ignored when flush != 0) -> new_counters (R x 4), sizes[5] = [rows =
  *   ready windows of the tick | out_floats of ONE flat output | max_span = most samples one slot changes | largest n_audio | largest
@@ -482,15 +486,22 @@ int rtfs_longform_overlap_add_many_f32(const float* y, float* out, const long lo
  *   f + nf - e hop / SPF > C / SPF (it would overwrite a cell that window e still needs: one side ran too far ahead of the other); a
  *   flush of a slot with samples and no frame; counters this planner cannot have produced.  new_counters, table, sizes, refused may
  *   be NULL.
- * rtfs_live_ingest_frame_f32 (one launch): table = the plan's 13 R words followed by two more columns [aptr | vptr], the DEVICE addresses
- *   of each slot's audio chunk (na floats, any 4-byte alignment) and contiguous (512, nf) video chunk - separate allocations, read where
- *   they lie -, uploaded by the caller.  Appends the chunks to the rings and writes the ready windows wav_win (rows, window), video_win
- *   (rows, 512, window / SPF); a framed sample comes from the ring if it arrived in an earlier push and from the chunk otherwise.  No
- *   block reads a ring cell another block writes: the capacity rule makes the two sets disjoint (k_live.hip).
+ * rtfs_live_ingest_frame_speakers_f32 (one launch): table = the plan's 13 R words followed by 1 + K columns [aptr | vptr_0 | .. |
+ *   vptr_{K-1}], the DEVICE addresses of each slot's audio chunk (na floats, any 4-byte alignment) and of its K contiguous (512, nf)
+ *   video chunks - separate allocations, read where they lie, nothing packed first -, uploaded by the caller.  Appends the chunks to the
+ *   rings and writes the ready windows wav_win (rows, window), once per window, and video_win (rows * K, 512, window / SPF), target row
+ *   r*K + k; a framed sample comes from the ring if it arrived in an earlier push and from the chunk otherwise.  No block reads a ring
+ *   cell another block writes: the capacity rule makes the two sets disjoint in every plane (k_live.hip).  Sizes
+ *   rtfs_live_speakers_sizes_ok refuses: -4.
+ * rtfs_live_ingest_frame_f32: the same with K = 1, table columns [aptr | vptr].
  * rtfs_live_overlap_add_f32 (one launch): y (rows, n_src, window) -> final samples (acc + this tick's weighted windows in ascending n) /
  *   weight sum into out (out_floats), weights and order those of rtfs_longform_overlap_add_f32; samples a later window still reaches go
  *   back to acc.  Gather form: one thread per four samples of a source, every cell has one thread, no atomics; deterministic.
- * rtfs_live_reset_f32 (one launch): zeroes the state of the R slots in ids (DEVICE array; NULL = slots 0 .. R - 1).
+ * rtfs_live_reset_f32 (one launch): zeroes the state of the R slots in ids (DEVICE array; NULL = slots 0 .. R - 1): one lip track and
+ *   n_src accumulator rows.  rtfs_live_reset_speakers_f32: K lip tracks and K accumulator rows.
+ * rtfs_live_speakers_sizes_ok (host only): 1 when window / hop / max_chunk are what rtfs_live_plan takes, 1 <= K <= RTFS_MAX_SPEAKERS and
+ *   K * (window + max_chunk) <= RTFS_LIVE_MAX_CAPACITY - the video share of the launch grids grows K-fold -, else 0.  A pool of sizes this
+ *   accepts cannot fail at a launch.
  * The launches take the caller's stream, allocate nothing and read nothing back, and trust the device table: pass what rtfs_live_plan
  * wrote.  State, wav_win, video_win, y, out must be 16-byte aligned and the tables 8-byte aligned (-4).  RTFS_LIVE_MAX_CAPACITY bounds C
  * (2^24 samples, 17 minutes of history per slot) so that every launch grid of an accepted size fits; a grid that would not is -1. */
@@ -515,19 +526,7 @@ int rtfs_live_overlap_add_f32(const long long* table, const float* y, float* out
 int rtfs_live_reset_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk,
                         void* stream);
 
-/* Every face of a stream (AVNet.open_streams(speakers = K) / SpeakerStreamPool; DESIGN.md "Every face of a stream"): a slot has one audio
- * track and K lip tracks, 1 <= K <= RTFS_MAX_SPEAKERS.  State: aring (slots, C) as above, vring (slots, K, 512, C / SPF), acc (slots, K, C);
- * the four counters per slot are shared by the K tracks, which are pushed together with one n_video.  rtfs_live_plan and
- * rtfs_live_overlap_add_f32 serve as they stand with n_src = K: y (rows, K, window), a slot's result is (K, end - o).
- * rtfs_live_speakers_sizes_ok (host only): 1 when window / hop / max_chunk are what rtfs_live_plan takes, 1 <= K <= RTFS_MAX_SPEAKERS and
- *   K * (window + max_chunk) <= RTFS_LIVE_MAX_CAPACITY - the video share of the launch grids grows K-fold -, else 0.  A pool of sizes this
- *   accepts cannot fail at a launch.
- * rtfs_live_ingest_frame_speakers_f32 (one launch): table = the plan's 13 R words followed by 1 + K columns [aptr | vptr_0 | .. |
- *   vptr_{K-1}], vptr_k[r] = the DEVICE address of speaker k's contiguous (512, nf) chunk of slot r - K separate allocations, read where
- *   they lie, nothing packed first.  Appends the chunks to the rings and writes wav_win (rows, window), once per window, and video_win
- *   (rows * K, 512, window / SPF), target row r*K + k.  No block reads a ring cell another block writes (k_live.hip, per track).
- * rtfs_live_reset_speakers_f32 (one launch): rtfs_live_reset_f32 for the K-track state.
- * Streams, alignment and trust in the device table as above; sizes rtfs_live_speakers_sizes_ok refuses: -4. */
+/* K lip tracks per slot (AVNet.open_streams(speakers = K) / SpeakerStreamPool): described above */
 int rtfs_live_speakers_sizes_ok(int window, int hop, int max_chunk, int K);
 int rtfs_live_ingest_frame_speakers_f32(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
                                         int K, int max_na, int max_nf, int window, int hop, int max_chunk, void* stream);

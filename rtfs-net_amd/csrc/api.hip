@@ -1290,8 +1290,7 @@ int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, vo
 int rtfs_longform_plan(int L, int Tv, int window, int hop, int* N) { return longform_plan(L, Tv, window, hop, N); }
 int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
                             void* stream) {
-    if (!wav || !video || !wav_win || !video_win) return RTFS_ERR_ARG;
-    return launch_longform_frame(wav, video, wav_win, video_win, B, L, Tv, window, hop, (hipStream_t)stream);
+    return rtfs_longform_frame_speakers_f32(wav, video, wav_win, video_win, B, 1, L, Tv, window, hop, stream);
 }
 int rtfs_longform_frame_speakers_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int K, int L, int Tv,
                                      int window, int hop, void* stream) {
@@ -1324,8 +1323,7 @@ int rtfs_live_plan(const long long* slot_ids, const long long* counters, const l
 }
 int rtfs_live_ingest_frame_f32(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
                                int max_na, int max_nf, int window, int hop, int max_chunk, void* stream) {
-    if (!table || !aring || !vring || !wav_win || !video_win) return RTFS_ERR_ARG;
-    return launch_live_ingest_frame(table, aring, vring, wav_win, video_win, R, rows, max_na, max_nf, window, hop, max_chunk, (hipStream_t)stream);
+    return rtfs_live_ingest_frame_speakers_f32(table, aring, vring, wav_win, video_win, R, rows, 1, max_na, max_nf, window, hop, max_chunk, stream);
 }
 int rtfs_live_overlap_add_f32(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int n_src,
                               int window, int hop, int max_chunk, int flush, void* stream) {
@@ -1335,7 +1333,7 @@ int rtfs_live_overlap_add_f32(const long long* table, const float* y, float* out
 int rtfs_live_reset_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk,
                         void* stream) {
     if (!aring || !vring || !acc) return RTFS_ERR_ARG;
-    return launch_live_reset(ids, aring, vring, acc, R, n_src, window, max_chunk, (hipStream_t)stream);
+    return launch_live_reset(ids, aring, vring, acc, R, 1, n_src, window, max_chunk, (hipStream_t)stream);
 }
 
 int rtfs_live_speakers_sizes_ok(int window, int hop, int max_chunk, int K) { return live_speakers_sizes_ok(window, hop, max_chunk, K); }
@@ -1348,7 +1346,7 @@ int rtfs_live_ingest_frame_speakers_f32(const long long* table, float* aring, fl
 int rtfs_live_reset_speakers_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int window, int max_chunk,
                                  void* stream) {
     if (!aring || !vring || !acc) return RTFS_ERR_ARG;
-    return launch_live_reset_speakers(ids, aring, vring, acc, R, K, window, max_chunk, (hipStream_t)stream);
+    return launch_live_reset(ids, aring, vring, acc, R, K, K, window, max_chunk, (hipStream_t)stream);
 }
 
 size_t rtfs_video_pack_floats(void) { return video_pack_floats(); }

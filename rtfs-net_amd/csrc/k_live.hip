@@ -1,32 +1,40 @@
-// Live streams chunk by chunk (AVNet.open_streams / StreamPool; DESIGN.md "Live streams"): the stateful form of the long-form plan of
-// k_longform.hip.  A stream delivers audio and lip frames a chunk at a time; window n = samples [n hop, n hop + window) is run as soon as
-// its samples AND its frames have arrived, and after window n the samples [n hop, (n + 1) hop) can be touched by no later window, so
-// they leave at once.  The concatenated outputs are separate_long's of the whole recording.  tests/live_oracle.py restates counters,
-// readiness, ring positions and the streaming overlap-add in float64.
+// Live streams chunk by chunk (AVNet.open_streams / StreamPool; DESIGN.md "Live streams", "Every face of a stream"): the stateful form
+// of the long-form plan of k_longform.hip.  A stream delivers audio and lip frames a chunk at a time; window n = samples [n hop, n hop +
+// window) is run as soon as its samples AND its frames have arrived, and after window n the samples [n hop, (n + 1) hop) can be touched by
+// no later window, so they leave at once.  The concatenated outputs are separate_long's of the whole recording.  tests/live_oracle.py
+// and tests/live_speakers_oracle.py restate counters, readiness, ring positions and the streaming overlap-add in float64.
 //
-// State per slot, device resident, allocated once (C = window + max_chunk samples, C / SPF frames):
-//   audio ring  (slots, C)            sample p of the stream lives in cell p % C
-//   video ring  (slots, 512, C / SPF) frame q lives in column q % (C / SPF); channel-major like the lip embedding, so the framing gather
-//                                     reads runs of a window's frames as k_longform.hip does
-//   accumulator (slots, n_src, C)     the weighted sum so far of a sample that later windows still reach, in cell t % C
+// A slot has ONE microphone track and K lip tracks, 1 <= K <= RTFS_MAX_SPEAKERS; the single-track pool is K = 1.  State per slot, device
+// resident, allocated once (C = window + max_chunk samples, C / SPF frames):
+//   audio ring  (slots, C)                sample p of the stream lives in cell p % C: stored once, framed once, whatever K
+//   video ring  (slots, K, 512, C / SPF)  frame q of track k lives in column q % (C / SPF) of plane (slot, k); channel-major like the lip
+//                                         embedding, so the framing gather reads runs of a window's frames as k_longform.hip does
+//   accumulator (slots, n_acc, C)         the weighted sum so far of a sample that later windows still reach, in cell t % C; n_acc = the
+//                                         rows of y per window: n_src of `forward` at K = 1, K of separate_speakers otherwise
 // Host counters per slot (kept by the caller, nothing is read back): a samples received, f frames received, e windows emitted,
-// o samples output.
+// o samples output.  The K tracks of a slot are pushed together with ONE m, so they share f (and a, e, o).
 //
-//   live_plan                 host only, the single place with the arithmetic: counters + the sizes of this push / flush -> new counters
-//                             and the tick table, 13 int64 words per named slot, column-major
-//                             [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]; the caller appends the two
-//                             columns of chunk pointers [aptr | vptr] and uploads the 15 R words with one copy
-//   live_ingest_frame_kernel  ONE launch: blocks x >= rows append the chunks to the rings; blocks x < rows write the ready windows
-//   live_ola_kernel           gather form, one thread per 4 samples of one source: final samples are divided and written to the flat
-//                             output, samples a later window still reaches go back to the accumulator
-//   live_reset_kernel         gives a slot's state defined contents (zeros)
+//   live_plan                          host only, the single place with the arithmetic: counters + the sizes of this push / flush -> new
+//                                      counters and the tick table, 13 int64 words per named slot, column-major
+//                                      [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]; the caller appends the
+//                                      1 + K columns of chunk pointers [aptr | vptr_0 | .. | vptr_{K-1}] - the K chunks of a slot are K
+//                                      separate allocations - and uploads the (14 + K) R words with one copy
+//   live_ingest_frame_speakers_kernel  ONE launch: blocks x >= rows append the audio chunk and the K lip chunks of their slot to the
+//                                      rings; blocks x < rows write the audio window once and the K video windows of the row behind
+//                                      each other: video_win (rows * K, 512, Wv), target row r K + k
+//   live_ola_kernel                    gather form, one thread per 4 samples of one of the n_acc rows: final samples are divided and
+//                                      written to the flat output, samples a later window still reaches go back to the accumulator
+//   live_reset_kernel                  gives a slot's state defined contents (zeros)
 //
 // WHY THE INGEST BLOCKS AND THE FRAMING BLOCKS OF ONE LAUNCH NEVER TOUCH THE SAME RING CELL.  A framing block reads sample p of window
-// n >= e from the ring only if p < a (it arrived in an earlier push), so it reads stream positions in [e hop, a); an ingest block writes
-// the stream positions [a, a + na).  live_plan refuses a push unless a + na - e hop <= C, so all positions of [e hop, a + na) have
-// different residues mod C: the cells read and the cells written are disjoint, whatever order the blocks run in.  The same holds for
-// frames with f + nf - e hop / SPF <= C / SPF.  Two named slots never share state, and live_plan refuses a slot named twice.  The cells
-// read are intact for the same reason: every accepted push kept a - e hop <= C, and e only grows.  A flush writes no ring cell.
+// n >= e from the audio ring only if p < a (it arrived in an earlier push), so it reads stream positions in [e hop, a); an ingest block
+// writes the stream positions [a, a + na).  live_plan refuses a push unless a + na - e hop <= C, so all positions of [e hop, a + na) have
+// different residues mod C: the cells read and the cells written are disjoint, whatever order the blocks run in.  Per lip track the same
+// holds in its plane (slot, k): frame q of window n >= e is read only if q < f, positions [e hop / SPF, f); an ingest block writes
+// [f, f + nf) of that plane; all tracks of a slot share f and e, and live_plan refuses a push unless f + nf - e hop / SPF <= C / SPF.
+// Two planes (another track, another slot) share no cell at all, and live_plan refuses a slot named twice.  The cells read are intact
+// for the same reason: every accepted push kept a - e hop <= C and f - e hop / SPF <= C / SPF, for all K tracks at once, and e only
+// grows.  A flush writes no ring cell.
 //
 // WHY THE ACCUMULATOR IS C FLOATS LONG.  A tick reads the sums of [e hop, (e - 1) hop + window) and writes those of [e' hop, (e' - 1) hop +
 // window) with e' = e + cnt.  A ready window has a' >= (e' - 1) hop + window, so both ranges lie in [e hop, e hop + C): distinct residues
@@ -34,28 +42,10 @@
 // soon as one tick emits window / hop + 1 windows.)  Which cells hold a sum is known from the counters (t < (e - 1) hop + window), so
 // no kernel depends on the value of a cell that holds none.
 //
-// EVERY FACE OF A STREAM (AVNet.open_streams(speakers = K) / SpeakerStreamPool; DESIGN.md "Every face of a stream").  A slot has ONE
-// microphone track and K lip tracks, 1 <= K <= RTFS_MAX_SPEAKERS.  State per slot:
-//   audio ring  (slots, C)                as above: stored once, framed once
-//   video ring  (slots, K, 512, C / SPF)  frame q of track k lives in column q % (C / SPF) of plane (slot, k)
-//   accumulator (slots, K, C)             the (slots, n_src, C) accumulator with n_src := K
-// The counters stay four per slot: the K tracks of a slot are pushed together with ONE m, so they share f (and a, e, o).  live_plan,
-// live_ola_kernel serve as they stand with n_src = K: y of separate_speakers is (rows, K, window), the (rows, n_src, window) layout.
-//   live_ingest_frame_speakers_kernel  ONE launch, the block roles of live_ingest_frame_kernel: blocks x >= rows append the audio chunk
-//                                      and the K lip chunks of their slot, blocks x < rows write the audio window once and the K video
-//                                      windows of the row behind each other: video_win (rows * K, 512, Wv), target row r K + k.  The K
-//                                      chunks of a slot are K separate allocations: the tick table carries one device address per
-//                                      (slot, speaker), columns [aptr | vptr_0 | .. | vptr_{K-1}], 14 + K words per slot, one upload.
-//   live_reset_speakers_kernel         live_reset_kernel over the K-times larger video ring
-// THE DISJOINTNESS ARGUMENT PER TRACK.  For the audio ring nothing changes.  For track k of a slot, a framing block reads frame q of
-// window n >= e from plane (slot, k) only if q < f, so it reads frame positions in [e hop / SPF, f) of THAT plane; an ingest block writes
-// the positions [f, f + nf) of that plane.  All tracks of a slot share the counters f and e, and live_plan refuses a push unless
-// f + nf - e hop / SPF <= C / SPF, so within every plane the positions of [e hop / SPF, f + nf) have different residues mod C / SPF:
-// cells read and cells written are disjoint in each plane, and two planes (another track, another slot) share no cell at all.  The
-// cells read are intact because every accepted push kept f - e hop / SPF <= C / SPF for all K tracks at once.
-// LAUNCH SIZES.  The video share of the framing grid is K times larger, so a K-track pool needs K (window + max_chunk) <=
-// RTFS_LIVE_MAX_CAPACITY (live_speakers_sizes_ok): the framing / ingest grid then has < 0.45 K C / 256 and the reset grid < 0.7 K C / 256
-// blocks in y, both below 65535.  open_streams refuses a larger pool, so a pool it accepted cannot fail at a launch.
+// LAUNCH SIZES.  window / hop as longform_plan takes them, max_chunk a positive multiple of SPF, and K (window + max_chunk) <=
+// RTFS_LIVE_MAX_CAPACITY (live_speakers_sizes_ok): the video share of the grids grows K-fold, so the framing / ingest grid has
+// < 0.45 K C / 256 and the reset grid of a K-track pool < 0.7 K C / 256 blocks in y, the overlap-add grid C / 1024, all below 65535.
+// open_streams refuses a larger pool, so a pool it accepted cannot fail at a launch (the launchers check their grids all the same).
 //
 // Stores follow k_longform.hip: a lane writes 16 bytes, a wave 1024 contiguous bytes, wherever the layout is aligned - the framed
 // windows always, the rings when the write position is a multiple of 4 (always when chunks are multiples of 4 samples), the output when
@@ -77,99 +67,7 @@ __device__ __forceinline__ f32x4 load4(const float* p) {  // 16 bytes when align
     return f32x4{p[0], p[1], p[2], p[3]};
 }
 
-__global__ __launch_bounds__(256) void live_ingest_frame_kernel(const long long* __restrict__ table, float* aring, float* vring,
-                                                                float* __restrict__ wav_win, float* __restrict__ video_win, int R, int rows,
-                                                                int window, int hop, int C, int qa_pad, int qin_pad) {
-    const int Cv = C / SPF, Wv = window / SPF;
-    int q = blockIdx.y * 256 + threadIdx.x;
-    if ((int)blockIdx.x >= rows) {
-        // ---- ingest: chunk r -> rings of its slot
-        const int r = blockIdx.x - rows;
-        const long long slot = table[(size_t)T_SLOT * R + r];
-        const int na = (int)table[(size_t)T_NA * R + r], nf = (int)table[(size_t)T_NF * R + r];
-        if (q < qin_pad) {  // audio quads; padded to whole waves so no wave serves both copies
-            const int j = 4 * q;
-            if (j >= na) return;
-            const float* src = (const float*)(uintptr_t)table[(size_t)T_APTR * R + r] + j;
-            float* dst = aring + (size_t)slot * C;
-            int cell = (int)table[(size_t)T_APOS * R + r] + j;  // apos < C, j < max_chunk < C: one wrap at most
-            if (cell >= C) cell -= C;
-            if (j + 3 < na && cell + 3 < C && (cell & 3) == 0) {
-                *(f32x4*)(dst + cell) = load4(src);
-            } else {
-                for (int k = 0; k < 4 && j + k < na; ++k) dst[cell + k < C ? cell + k : cell + k - C] = src[k];
-            }
-            return;
-        }
-        q -= qin_pad;
-        const float* src = (const float*)(uintptr_t)table[(size_t)T_VPTR * R + r];  // (512, nf)
-        float* dst = vring + (size_t)slot * VCH * Cv;
-        const int fpos = (int)table[(size_t)T_FPOS * R + r];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int idx = 4 * q + k;
-            if (idx >= VCH * nf) return;
-            const int c = idx / nf, j = idx - c * nf;
-            int cell = fpos + j;
-            if (cell >= Cv) cell -= Cv;
-            dst[(size_t)c * Cv + cell] = src[idx];
-        }
-        return;
-    }
-    // ---- framing: row -> (slot, window n)
-    const int row = blockIdx.x;
-    const int r = many_find(table + (size_t)T_ROW0 * R, R, row);  // block-uniform: scalar loads
-    const int nl = row - (int)table[(size_t)T_ROW0 * R + r];
-    if (nl >= (int)table[(size_t)T_CNT * R + r]) return;  // a table that does not cover this row: write nothing
-    const long long slot = table[(size_t)T_SLOT * R + r], n = table[(size_t)T_E * R + r] + nl;
-    const long long a0 = table[(size_t)T_A * R + r], lim_a = a0 + table[(size_t)T_NA * R + r];  // at a flush na = 0: lim_a = L
-    if (q < qa_pad) {  // audio quads
-        if (q >= window / 4) return;
-        const int i = 4 * q;
-        const long long p = n * hop + i;  // position in the stream: a multiple of 4
-        int cell = (int)((n * hop) % C) + i;  // i < window <= C; C % 4 == 0, so a quad never wraps
-        if (cell >= C) cell -= C;
-        const float* ring = aring + (size_t)slot * C;
-        const float* chunk = (const float*)(uintptr_t)table[(size_t)T_APTR * R + r];
-        f32x4 v;
-        if (p + 3 < a0) {
-            v = *(const f32x4*)(ring + cell);
-        } else if (p >= a0 && p + 3 < lim_a) {
-            v = load4(chunk + (p - a0));
-        } else {  // the quad straddles ring | chunk | zeros past L
-            float e[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) e[k] = p + k >= lim_a ? 0.f : p + k >= a0 ? chunk[p + k - a0] : ring[cell + k];
-            v = f32x4{e[0], e[1], e[2], e[3]};
-        }
-        *(f32x4*)(wav_win + (size_t)row * window + i) = v;
-        return;
-    }
-    q -= qa_pad;
-    if (q >= VCH * Wv / 4) return;
-    const long long f0 = table[(size_t)T_F * R + r];
-    const int nf = (int)table[(size_t)T_NF * R + r];
-    const long long last = f0 + nf - 1, fbase = n * (hop / SPF);  // at a flush nf = 0: last = Tv - 1
-    const int cell0 = (int)(fbase % Cv), cell_last = (int)(last % Cv);
-    const float* ring = vring + (size_t)slot * VCH * Cv;
-    const float* chunk = (const float*)(uintptr_t)table[(size_t)T_VPTR * R + r];
-    float v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int j = 4 * q + k, c = j / Wv, f = j - c * Wv;
-        long long fr = fbase + f;
-        int cell = cell0 + f;  // f < Wv <= Cv
-        if (cell >= Cv) cell -= Cv;
-        if (fr > last) {
-            fr = last;
-            cell = cell_last;
-        }
-        v[k] = fr >= f0 ? chunk[(size_t)c * nf + (fr - f0)] : ring[(size_t)c * Cv + cell];
-    }
-    *(f32x4*)(video_win + (size_t)row * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
-}
-
-// K lip tracks per slot: see "EVERY FACE OF A STREAM" at the top.  table columns T_VPTR + k hold the chunk address of speaker k.
+// table columns T_VPTR + k hold the chunk address of lip track k
 __global__ __launch_bounds__(256) void live_ingest_frame_speakers_kernel(const long long* __restrict__ table, float* aring, float* vring,
                                                                          float* __restrict__ wav_win, float* __restrict__ video_win, int R,
                                                                          int rows, int K, int window, int hop, int C, int qa_pad, int qin_pad) {
@@ -312,29 +210,11 @@ __global__ __launch_bounds__(256) void live_ola_kernel(const long long* __restri
     }
 }
 
+// K scales the video ring, n_acc the accumulator: a single-track pool has (1, n_src), a K-track pool (K, K)
 __global__ __launch_bounds__(256) void live_reset_kernel(const long long* __restrict__ ids, float* __restrict__ aring, float* __restrict__ vring,
-                                                         float* __restrict__ acc, int n_src, int C) {
+                                                         float* __restrict__ acc, int K, int n_acc, int C) {
     const size_t slot = ids ? (size_t)ids[blockIdx.x] : blockIdx.x;
-    const int qa = C / 4, qv = VCH * (C / SPF) / 4, qc = n_src * (C / 4);  // C % 640 == 0: whole quads
-    int q = blockIdx.y * 256 + threadIdx.x;
-    const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (q < qa) {
-        *(f32x4*)(aring + slot * C + 4 * (size_t)q) = z;
-        return;
-    }
-    q -= qa;
-    if (q < qv) {
-        *(f32x4*)(vring + slot * VCH * (C / SPF) + 4 * (size_t)q) = z;
-        return;
-    }
-    q -= qv;
-    if (q < qc) *(f32x4*)(acc + slot * n_src * C + 4 * (size_t)q) = z;
-}
-
-__global__ __launch_bounds__(256) void live_reset_speakers_kernel(const long long* __restrict__ ids, float* __restrict__ aring,
-                                                                  float* __restrict__ vring, float* __restrict__ acc, int K, int C) {
-    const size_t slot = ids ? (size_t)ids[blockIdx.x] : blockIdx.x;
-    const int qa = C / 4, qv = K * (VCH * (C / SPF) / 4), qc = K * (C / 4);  // K C <= 2^24: all below 2^31
+    const int qa = C / 4, qv = K * (VCH * (C / SPF) / 4), qc = n_acc * (C / 4);  // the launcher bounds their sum: all below 2^31
     int q = blockIdx.y * 256 + threadIdx.x;
     const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
     if (q < qa) {
@@ -347,20 +227,16 @@ __global__ __launch_bounds__(256) void live_reset_speakers_kernel(const long lon
         return;
     }
     q -= qv;
-    if (q < qc) *(f32x4*)(acc + slot * K * C + 4 * (size_t)q) = z;
+    if (q < qc) *(f32x4*)(acc + slot * n_acc * C + 4 * (size_t)q) = z;
 }
 
-// window / hop as longform_plan takes them, max_chunk a positive multiple of SPF, and a ring of at most RTFS_LIVE_MAX_CAPACITY samples:
-// with it the y dimension of the ingest / framing grid (< 0.45 C / 256 blocks) and of the overlap-add grid (C / 1024) stay far below
-// 65535, so a pool that open_streams accepted cannot fail at a launch (the launchers check their grids all the same)
+// what live_plan and the overlap-add need of the sizes, whatever K (LAUNCH SIZES at the top)
 int live_sizes_ok(int window, int hop, int max_chunk) {
     if (longform_plan(1, 1, window, hop, nullptr) != RTFS_OK) return 0;
     return max_chunk >= SPF && max_chunk % SPF == 0 && (long long)window + max_chunk <= RTFS_LIVE_MAX_CAPACITY;
 }
 
 }  // namespace
-
-// a K-track pool: K (window + max_chunk) <= RTFS_LIVE_MAX_CAPACITY bounds the K-fold video share of the grids (top of the file)
 
 int live_speakers_sizes_ok(int window, int hop, int max_chunk, int K) {
     if (K < 1 || K > RTFS_MAX_SPEAKERS || !live_sizes_ok(window, hop, max_chunk)) return 0;
@@ -442,24 +318,6 @@ int live_plan(const long long* slot_ids, const long long* counters, const long l
     return RTFS_OK;
 }
 
-int launch_live_ingest_frame(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows, int max_na,
-                             int max_nf, int window, int hop, int max_chunk, hipStream_t st) {
-    if (!live_sizes_ok(window, hop, max_chunk)) return RTFS_ERR_ARG;
-    if (R < 1 || rows < 0 || max_na < 0 || max_na > max_chunk || max_nf < 0 || max_nf > max_chunk / SPF) return RTFS_ERR_SHAPE;
-    if ((((uintptr_t)aring) | ((uintptr_t)vring) | ((uintptr_t)wav_win) | ((uintptr_t)video_win)) & 15) return RTFS_ERR_ARG;
-    if (((uintptr_t)table) & 7) return RTFS_ERR_ARG;
-    if (rows == 0 && max_na == 0 && max_nf == 0) return RTFS_OK;  // nothing arrived, nothing is ready
-    const int qa_pad = cdiv(window / 4, 64) * 64, qv = VCH * (window / SPF) / 4;
-    const int qin_pad = cdiv(cdiv(max_na, 4), 64) * 64, qiv = VCH * max_nf / 4;
-    const int frame_q = rows > 0 ? qa_pad + qv : 0, ingest_q = qin_pad + qiv;
-    const bool ingest = max_na > 0 || max_nf > 0;
-    const int gy = cdiv(frame_q > ingest_q ? frame_q : ingest_q, 256);
-    if (gy > 65535) return RTFS_ERR_SHAPE;
-    hipLaunchKernelGGL(live_ingest_frame_kernel, dim3(rows + (ingest ? R : 0), gy), dim3(256), 0, st,
-                       table, aring, vring, wav_win, video_win, R, rows, window, hop, window + max_chunk, qa_pad, qin_pad);
-    return rtfs_launch_status();
-}
-
 int launch_live_overlap_add(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int n_src, int window,
                             int hop, int max_chunk, int flush, hipStream_t st) {
     if (!live_sizes_ok(window, hop, max_chunk)) return RTFS_ERR_ARG;
@@ -471,18 +329,6 @@ int launch_live_overlap_add(const long long* table, const float* y, float* out, 
     if ((max_span + 1023) / 1024 > 65535) return RTFS_ERR_SHAPE;
     hipLaunchKernelGGL(live_ola_kernel, dim3(R, (unsigned)((max_span + 1023) / 1024), n_src), dim3(256), 0, st, table, y, out, acc, R, n_src,
                        window, hop, (int)C, flush ? 1 : 0);
-    return rtfs_launch_status();
-}
-
-int launch_live_reset(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk, hipStream_t st) {
-    if (!live_sizes_ok(window, window, max_chunk)) return RTFS_ERR_ARG;
-    if (R < 1 || n_src < 1) return RTFS_ERR_SHAPE;
-    if ((((uintptr_t)aring) | ((uintptr_t)vring) | ((uintptr_t)acc)) & 15) return RTFS_ERR_ARG;
-    if (((uintptr_t)ids) & 7) return RTFS_ERR_ARG;
-    const int C = window + max_chunk;
-    const long long quads = (long long)C / 4 * (1 + n_src) + (long long)VCH * (C / SPF) / 4;
-    if ((quads + 255) / 256 > 65535) return RTFS_ERR_SHAPE;
-    hipLaunchKernelGGL(live_reset_kernel, dim3(R, (unsigned)((quads + 255) / 256)), dim3(256), 0, st, ids, aring, vring, acc, n_src, C);
     return rtfs_launch_status();
 }
 
@@ -504,15 +350,15 @@ int launch_live_ingest_frame_speakers(const long long* table, float* aring, floa
     return rtfs_launch_status();
 }
 
-int launch_live_reset_speakers(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int window, int max_chunk,
-                               hipStream_t st) {
+int launch_live_reset(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int n_acc, int window, int max_chunk,
+                      hipStream_t st) {
     if (!live_speakers_sizes_ok(window, window, max_chunk, K)) return RTFS_ERR_ARG;
-    if (R < 1) return RTFS_ERR_SHAPE;
+    if (R < 1 || n_acc < 1) return RTFS_ERR_SHAPE;
     if ((((uintptr_t)aring) | ((uintptr_t)vring) | ((uintptr_t)acc)) & 15) return RTFS_ERR_ARG;
     if (((uintptr_t)ids) & 7) return RTFS_ERR_ARG;
     const int C = window + max_chunk;
-    const long long quads = (long long)C / 4 * (1 + K) + (long long)K * VCH * (C / SPF) / 4;
+    const long long quads = (long long)C / 4 * (1 + n_acc) + (long long)K * VCH * (C / SPF) / 4;
     if ((quads + 255) / 256 > 65535) return RTFS_ERR_SHAPE;
-    hipLaunchKernelGGL(live_reset_speakers_kernel, dim3(R, (unsigned)((quads + 255) / 256)), dim3(256), 0, st, ids, aring, vring, acc, K, C);
+    hipLaunchKernelGGL(live_reset_kernel, dim3(R, (unsigned)((quads + 255) / 256)), dim3(256), 0, st, ids, aring, vring, acc, K, n_acc, C);
     return rtfs_launch_status();
 }

@@ -3,9 +3,9 @@
 // video frame at 25 fps and 16 kHz), the B * N windows go through the ordinary fused forward as a batch, and the results are cross-faded
 // back into (B, n_src, L).  tests/longform_oracle.py restates plan, framing, weights and overlap-add in float64.
 //   longform_plan          host only: argument checks and N = 1 (L <= window), else 1 + ceil((L - window) / hop)
-//   longform_frame_kernel  ONE launch for both gathers: window n of recording b = samples [n hop, n hop + window) with zeros past L, and
-//                          video frames [n hop / SPF, (n hop + window) / SPF) with an index past Tv - 1 reading frame Tv - 1
-//   longform_frame_speakers_kernel  the same launch with K lip tracks per recording: the audio window once, K video windows per row
+//   longform_frame_speakers_kernel  ONE launch for both gathers, K >= 1 lip tracks per recording: window n of recording b = samples
+//                          [n hop, n hop + window) with zeros past L, written once, and per track the video frames [n hop / SPF,
+//                          (n hop + window) / SPF) with an index past Tv - 1 reading frame Tv - 1.  (B,512,Tv) is K = 1 of (B,K,512,Tv)
 //   longform_ola_kernel    gather form: an output sample sums its <= ceil(window / hop) windows in ascending n, each times
 //                          w[i] = min(1, (i + 0.5) / V, (window - i - 0.5) / V), V = window - hop (w = 1 when V = 0), and divides by the sum
 //                          of those weights, all recomputed in registers from the index: no atomics, no accumulator to clear, no weight
@@ -22,47 +22,10 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void longform_frame_kernel(const float* __restrict__ wav, const float* __restrict__ video,
-                                                             float* __restrict__ wav_win, float* __restrict__ video_win, int N, int L, int Tv,
-                                                             int window, int hop, int qa_pad) {
-    const int row = blockIdx.x, b = row / N, n = row - b * N;
-    const int Wv = window / SPF;
-    int q = blockIdx.y * 256 + threadIdx.x;
-    if (q < qa_pad) {  // audio quads; the segment is padded to whole waves so no wave serves both gathers
-        if (q >= window / 4) return;
-        const int i = 4 * q;
-        const long long p = (long long)n * hop + i;  // position in the recording
-        const float* src = wav + (size_t)b * L;
-        f32x4 v;
-        if (p + 3 < L && (((uintptr_t)(src + p)) & 15) == 0) {
-            v = *(const f32x4*)(src + p);
-        } else {
-            v.x = p < L ? src[p] : 0.f;
-            v.y = p + 1 < L ? src[p + 1] : 0.f;
-            v.z = p + 2 < L ? src[p + 2] : 0.f;
-            v.w = p + 3 < L ? src[p + 3] : 0.f;
-        }
-        *(f32x4*)(wav_win + (size_t)row * window + i) = v;
-        return;
-    }
-    q -= qa_pad;
-    if (q >= VCH * Wv / 4) return;
-    const float* src = video + (size_t)b * VCH * Tv;
-    const int f0 = (int)((long long)n * hop / SPF);
-    float v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int j = 4 * q + k, c = j / Wv, f = j - c * Wv;
-        const long long fr = (long long)f0 + f;
-        v[k] = src[(size_t)c * Tv + (fr < Tv ? (int)fr : Tv - 1)];
-    }
-    *(f32x4*)(video_win + (size_t)row * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
-}
-
-// K lip tracks per recording (AVNet.separate_long_speakers): the audio window is written ONCE per (b, n), the K video windows of the row
-// behind each other, target row (b N + n) K + k - the (rows, K, 512, Wv) layout separate_speakers takes without a copy.  Same block
-// roles as longform_frame_kernel; the video share of a row is the flat (K, 512, Wv) array, K * 512 * Wv * 4 bytes = a multiple of 128,
-// and 512 * Wv is a multiple of 4, so a quad never serves two tracks.
+// K lip tracks per recording (AVNet.separate_long: K = 1, separate_long_speakers): the audio window is written ONCE per (b, n), the K
+// video windows of the row behind each other, target row (b N + n) K + k - the (rows, K, 512, Wv) layout separate_speakers takes
+// without a copy.  The video share of a row is the flat (K, 512, Wv) array, K * 512 * Wv * 4 bytes = a multiple of 128, and 512 * Wv is
+// a multiple of 4, so a quad never serves two tracks.
 __global__ __launch_bounds__(256) void longform_frame_speakers_kernel(const float* __restrict__ wav, const float* __restrict__ video,
                                                                       float* __restrict__ wav_win, float* __restrict__ video_win, int N, int K,
                                                                       int L, int Tv, int window, int hop, int qa_pad) {
@@ -178,19 +141,6 @@ int longform_plan(int L, int Tv, int window, int hop, int* N) {
     if (n > 0x7fffffffLL) return RTFS_ERR_ARG;
     if (N) *N = (int)n;
     return RTFS_OK;
-}
-
-int launch_longform_frame(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
-                          hipStream_t st) {
-    int N = 0;
-    const int e = longform_plan(L, Tv, window, hop, &N);
-    if (e != RTFS_OK) return e;
-    if (B < 1 || (long long)B * N > 0x7fffffffLL) return RTFS_ERR_SHAPE;
-    if ((((uintptr_t)wav_win) | ((uintptr_t)video_win)) & 15) return RTFS_ERR_ARG;
-    const int qa_pad = cdiv(window / 4, 64) * 64, qv = VCH * (window / SPF) / 4;
-    hipLaunchKernelGGL(longform_frame_kernel, dim3(B * N, cdiv(qa_pad + qv, 256)), dim3(256), 0, st, wav, video, wav_win, video_win, N, L, Tv,
-                       window, hop, qa_pad);
-    return rtfs_launch_status();
 }
 
 int launch_longform_frame_speakers(const float* wav, const float* video, float* wav_win, float* video_win, int B, int K, int L, int Tv,

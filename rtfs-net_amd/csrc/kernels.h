@@ -328,12 +328,10 @@ int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void
 
 // long recordings in overlapping windows (k_longform.hip): window plan (host), framing of audio + video in one launch, cross-faded overlap-add
 int longform_plan(int L, int Tv, int window, int hop, int* N);
-int launch_longform_frame(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
-                          hipStream_t st);
-int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, int L, int window, int hop, hipStream_t st);
-// K lip tracks per recording: the audio window once, video_win (B*N*K, 512, window / SPF), target row (b*N + n)*K + k
+// K lip tracks per recording (one track: K = 1): the audio window once, video_win (B*N*K, 512, window / SPF), target row (b*N + n)*K + k
 int launch_longform_frame_speakers(const float* wav, const float* video, float* wav_win, float* video_win, int B, int K, int L, int Tv,
                                    int window, int hop, hipStream_t st);
+int launch_longform_overlap_add(const float* y, float* out, int B, int n_src, int L, int window, int hop, hipStream_t st);
 // many recordings of different lengths, their windows pooled (k_longform.hip): per-recording table (host), then the same two passes reading
 // the recordings through device tables of pointers
 int longform_many_plan(const long long* L, const long long* Tv, int R, int window, int hop, int n_src, long long* table, long long* total_windows,
@@ -347,17 +345,15 @@ int launch_longform_overlap_add_many(const float* y, float* out, const long long
 int live_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R, int slots,
               int flush, int window, int hop, int max_chunk, int n_src, long long* new_counters, long long* table, long long* sizes,
               int* refused);
-int launch_live_ingest_frame(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows, int max_na,
-                             int max_nf, int window, int hop, int max_chunk, hipStream_t st);
-int launch_live_overlap_add(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int n_src, int window,
-                            int hop, int max_chunk, int flush, hipStream_t st);
-int launch_live_reset(const long long* ids, float* aring, float* vring, float* acc, int R, int n_src, int window, int max_chunk, hipStream_t st);
-// K lip tracks per slot (k_live.hip "EVERY FACE OF A STREAM"): live_plan and launch_live_overlap_add serve with n_src = K
 int live_speakers_sizes_ok(int window, int hop, int max_chunk, int K);
+// K lip tracks per slot (one track: K = 1); the table carries 1 + K columns of chunk pointers behind the plan's 13
 int launch_live_ingest_frame_speakers(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
                                       int K, int max_na, int max_nf, int window, int hop, int max_chunk, hipStream_t st);
-int launch_live_reset_speakers(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int window, int max_chunk,
-                               hipStream_t st);
+int launch_live_overlap_add(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int n_src, int window,
+                            int hop, int max_chunk, int flush, hipStream_t st);
+// K scales the video ring, n_acc the accumulator rows
+int launch_live_reset(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int n_acc, int window, int max_chunk,
+                      hipStream_t st);
 
 // preparing raw recordings (k_prep.hip): uint8 mouth ROIs -> normalised lips, waveform normalisation, polyphase resampling
 int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,

@@ -573,6 +573,29 @@ def _longform_overlap_add_torch(y, B, N, L, window, hop):
     return (num[:, :, :L] / den[:L]).contiguous()
 
 
+def _window_args(model, who, window, hop, max_batch, L=1, Tv=1):
+    """``window`` / ``hop`` / ``max_batch`` of the windowed entry point ``who`` (its name in messages) as integers, checked the one way
+    all of them do: max_batch >= 1, rtfs_longform_plan, the fused limit of the model's cell, eval mode.  -> (window, hop, max_batch, N),
+    N the windows of a recording of L samples and Tv frames."""
+    window = int(window)
+    hop = window // 2 if hop is None else int(hop)
+    max_batch = int(max_batch)
+    if max_batch < 1:
+        raise ValueError(f"{who}: max_batch = {max_batch}; at least 1")
+    lib = _lib.load()
+    n_win = ctypes.c_int(0)
+    if lib.rtfs_longform_plan(L, Tv, window, hop, ctypes.byref(n_win)) != 0:
+        raise ValueError(f"{who}: window = {window}, hop = {hop} must be multiples of {LONGFORM_SPF} with 0 < hop <= window "
+                         f"(L = {L}, Tv = {Tv} at least 1)")
+    limit = layers.fused_max_block_sweep(model.refinement_module.audio_net.get_block(0).rnn_kind)
+    if int(lib.rtfs_num_frames(window)) // 2 > limit:
+        raise ValueError(f"{who}: a window of {window} samples does not fit the fused separator of this model's cell (T/2 <= {limit})")
+    if model.training:
+        raise RuntimeError(f"AVNet.{who} is inference only: call .eval()")
+    return window, hop, max_batch, n_win.value
+
+
+
 # ----------------------------------------------------------------------------- top-level model
 class BaseAVModel(nn.Module):
     """reference TDAVNet/base_av_model.py."""
@@ -790,43 +813,41 @@ class AVNet(BaseAVModel):
             raise ValueError(f"separate_long: {B} recording(s) but mouth_embedding "
                              f"{None if mouth_embedding is None else tuple(mouth_embedding.shape)} (expected (B,512,Tv))")
         Tv = int(mouth_embedding.shape[-1])
-        window = int(window)
-        hop = window // 2 if hop is None else int(hop)
-        max_batch = int(max_batch)
-        if max_batch < 1:
-            raise ValueError(f"separate_long: max_batch = {max_batch}")
+        window, hop, max_batch, N = _window_args(self, "separate_long", window, hop, max_batch, L, Tv)
+        return self._separate_long(wav, mouth_embedding[:, None], None, window, hop, max_batch, N)
+
+    def _separate_long(self, wav, video, K, window, hop, max_batch, N):
+        """Frame, run the chunks, overlap-add: wav (B,L), video (B,Kv,512,Tv) -> (B,n_out,L).  K None (``separate_long``, Kv = 1): the
+        chunks go through ``forward``, n_out = n_src.  K = Kv (``separate_long_speakers``): through ``separate_speakers``, n_out = K."""
+        B, L, Kv, Tv = int(wav.shape[0]), int(wav.shape[1]), int(video.shape[1]), int(video.shape[3])
+        Wv, n_out = window // LONGFORM_SPF, self.n_src if K is None else K
+        step = max_batch if K is None else max(1, max_batch // K)
+        on_hip = self.fused and wav.is_cuda and video.is_cuda
         lib = _lib.load()
-        n_win = ctypes.c_int(0)
-        if lib.rtfs_longform_plan(L, Tv, window, hop, ctypes.byref(n_win)) != 0:
-            raise ValueError(f"separate_long: window = {window}, hop = {hop} must be multiples of {LONGFORM_SPF} with 0 < hop <= window "
-                             f"(L = {L}, Tv = {Tv} at least 1)")
-        rnn_kind = self.refinement_module.audio_net.get_block(0).rnn_kind
-        if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
-            raise ValueError(f"separate_long: a window of {window} samples does not fit the fused separator of this model's cell "
-                             f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
-        if self.training:
-            raise RuntimeError("AVNet.separate_long is inference only: call .eval()")
-        N, Wv = int(n_win.value), window // LONGFORM_SPF
-        on_hip = self.fused and wav.is_cuda and mouth_embedding.is_cuda
         with torch.no_grad():
             if on_hip:
-                _lib.need_gpu(wav, mouth_embedding)
-                wav, video = wav.contiguous(), mouth_embedding.contiguous()
+                _lib.need_gpu(wav, video)
+                wav, video = wav.contiguous(), video.contiguous()
                 xw = _lib.empty(B * N, window, device=wav.device, dtype=torch.float32)
-                vw = _lib.empty(B * N, 512, Wv, device=wav.device, dtype=torch.float32)
-                _lib.check(lib.rtfs_longform_frame_f32(_lib.ptr(wav), _lib.ptr(video), _lib.ptr(xw), _lib.ptr(vw), B, L, Tv, window, hop,
-                                                       _lib.stream_of(wav)), "rtfs_longform_frame_f32")
+                vw = _lib.empty(B * N, Kv, 512, Wv, device=wav.device, dtype=torch.float32)
+                _lib.check(lib.rtfs_longform_frame_speakers_f32(_lib.ptr(wav), _lib.ptr(video), _lib.ptr(xw), _lib.ptr(vw), B, Kv, L, Tv, window,
+                                                                hop, _lib.stream_of(wav)), "rtfs_longform_frame_speakers_f32")
             else:
-                xw, vw = _longform_frame_torch(wav, mouth_embedding, N, window, hop)
-            y = _lib.empty(B * N, self.n_src, window, device=wav.device, dtype=torch.float32)
-            run = self.forward if on_hip else self.forward_modular
-            for c0 in range(0, B * N, max_batch):
-                c1 = min(B * N, c0 + max_batch)
-                y[c0:c1].copy_(run(xw[c0:c1], vw[c0:c1]))
+                xw, vw = _longform_frame_torch(wav, video.reshape(B, Kv * 512, Tv), N, window, hop)
+                vw = vw.view(B * N, Kv, 512, Wv)
+            y = _lib.empty(B * N, n_out, window, device=wav.device, dtype=torch.float32)
+            for c0 in range(0, B * N, step):
+                c1 = min(B * N, c0 + step)
+                if K is None:
+                    y[c0:c1].copy_((self.forward if on_hip else self.forward_modular)(xw[c0:c1], vw[c0:c1, 0]))
+                elif on_hip:
+                    y[c0:c1].copy_(self.separate_speakers(xw[c0:c1], vw[c0:c1]))
+                else:  # target k of a window = the model on that window with lips k
+                    y[c0:c1].copy_(self.forward_modular(xw[c0:c1].repeat_interleave(K, 0), vw[c0:c1].reshape(-1, 512, Wv)).view(c1 - c0, K, window))
             if not on_hip:
                 return _longform_overlap_add_torch(y, B, N, L, window, hop)
-            out = _lib.empty(B, self.n_src, L, device=wav.device, dtype=torch.float32)
-            _lib.check(lib.rtfs_longform_overlap_add_f32(_lib.ptr(y), _lib.ptr(out), B, self.n_src, L, window, hop, _lib.stream_of(wav)),
+            out = _lib.empty(B, n_out, L, device=wav.device, dtype=torch.float32)
+            _lib.check(lib.rtfs_longform_overlap_add_f32(_lib.ptr(y), _lib.ptr(out), B, n_out, L, window, hop, _lib.stream_of(wav)),
                        "rtfs_longform_overlap_add_f32")
             return out
 
@@ -856,49 +877,8 @@ class AVNet(BaseAVModel):
             raise ValueError(f"separate_long_speakers: K = {K} target speakers; 1 .. {MAX_SPEAKERS}")
         if self.n_src != 1:
             raise ValueError("separate_long_speakers: target-speaker models only (n_src 1)")
-        window = int(window)
-        hop = window // 2 if hop is None else int(hop)
-        max_batch = int(max_batch)
-        if max_batch < 1:
-            raise ValueError(f"separate_long_speakers: max_batch = {max_batch}")
-        lib = _lib.load()
-        n_win = ctypes.c_int(0)
-        if lib.rtfs_longform_plan(L, Tv, window, hop, ctypes.byref(n_win)) != 0:
-            raise ValueError(f"separate_long_speakers: window = {window}, hop = {hop} must be multiples of {LONGFORM_SPF} with "
-                             f"0 < hop <= window (L = {L}, Tv = {Tv} at least 1)")
-        rnn_kind = self.refinement_module.audio_net.get_block(0).rnn_kind
-        if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
-            raise ValueError(f"separate_long_speakers: a window of {window} samples does not fit the fused separator of this model's cell "
-                             f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
-        if self.training:
-            raise RuntimeError("AVNet.separate_long_speakers is inference only: call .eval()")
-        N, Wv = int(n_win.value), window // LONGFORM_SPF
-        on_hip = self.fused and wav.is_cuda and mouth_embeddings.is_cuda
-        step = max(1, max_batch // K)
-        with torch.no_grad():
-            if on_hip:
-                _lib.need_gpu(wav, mouth_embeddings)
-                wav, video = wav.contiguous(), mouth_embeddings.contiguous()
-                xw = _lib.empty(B * N, window, device=wav.device, dtype=torch.float32)
-                vw = _lib.empty(B * N, K, 512, Wv, device=wav.device, dtype=torch.float32)
-                _lib.check(lib.rtfs_longform_frame_speakers_f32(_lib.ptr(wav), _lib.ptr(video), _lib.ptr(xw), _lib.ptr(vw), B, K, L, Tv, window,
-                                                                hop, _lib.stream_of(wav)), "rtfs_longform_frame_speakers_f32")
-            else:
-                xw, vw = _longform_frame_torch(wav, mouth_embeddings.reshape(B, K * 512, Tv), N, window, hop)
-                vw = vw.view(B * N, K, 512, Wv)
-            y = _lib.empty(B * N, K, window, device=wav.device, dtype=torch.float32)
-            for c0 in range(0, B * N, step):
-                c1 = min(B * N, c0 + step)
-                if on_hip:
-                    y[c0:c1].copy_(self.separate_speakers(xw[c0:c1], vw[c0:c1]))
-                else:
-                    y[c0:c1].copy_(self.forward_modular(xw[c0:c1].repeat_interleave(K, 0), vw[c0:c1].reshape(-1, 512, Wv)).view(c1 - c0, K, window))
-            if not on_hip:
-                return _longform_overlap_add_torch(y, B, N, L, window, hop)
-            out = _lib.empty(B, K, L, device=wav.device, dtype=torch.float32)
-            _lib.check(lib.rtfs_longform_overlap_add_f32(_lib.ptr(y), _lib.ptr(out), B, K, L, window, hop, _lib.stream_of(wav)),
-                       "rtfs_longform_overlap_add_f32")
-            return out
+        window, hop, max_batch, N = _window_args(self, "separate_long_speakers", window, hop, max_batch, L, Tv)
+        return self._separate_long(wav, mouth_embeddings, K, window, hop, max_batch, N)
 
     def separate_many(self, mixtures, mouth_embeddings, window=32000, hop=None, max_batch=32):
         """R recordings of different lengths in one pooled pass on the fused separator (inference only; DESIGN.md "Many recordings").
@@ -947,18 +927,8 @@ class AVNet(BaseAVModel):
                 raise ValueError(f"separate_many: recording {r} lies on {w.device} / {v.device}, recording 0 on {mixtures[0].device}")
             wavs.append(w.reshape(-1))
             videos.append(v)
-        window = int(window)
-        hop = window // 2 if hop is None else int(hop)
-        max_batch = int(max_batch)
-        if max_batch < 1:
-            raise ValueError(f"separate_many: max_batch = {max_batch}")
+        window, hop, max_batch, _ = _window_args(self, "separate_many", window, hop, max_batch)
         lib = _lib.load()
-        if lib.rtfs_longform_plan(1, 1, window, hop, None) != 0:
-            raise ValueError(f"separate_many: window = {window}, hop = {hop} must be multiples of {LONGFORM_SPF} with 0 < hop <= window")
-        rnn_kind = self.refinement_module.audio_net.get_block(0).rnn_kind
-        if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
-            raise ValueError(f"separate_many: a window of {window} samples does not fit the fused separator of this model's cell "
-                             f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
         Ls = (ctypes.c_longlong * R)(*[int(w.shape[0]) for w in wavs])
         Tvs = (ctypes.c_longlong * R)(*[int(v.shape[1]) for v in videos])
         table = (ctypes.c_longlong * (5 * R))()
@@ -966,8 +936,6 @@ class AVNet(BaseAVModel):
         if lib.rtfs_longform_many_plan(Ls, Tvs, R, window, hop, self.n_src, table, ctypes.byref(rows), ctypes.byref(floats)) != 0:
             raise ValueError(f"separate_many: {R} recordings with window = {window}, hop = {hop} need more than 2^31 - 1 windows "
                              f"(or a length is past int32)")
-        if self.training:
-            raise RuntimeError("AVNet.separate_many is inference only: call .eval()")
         S, Wv, n_src, device = int(rows.value), window // LONGFORM_SPF, self.n_src, wavs[0].device
         row0, Ns, offs = table[0:R], table[R:2 * R], table[4 * R:5 * R]
         on_hip = self.fused and device.type == "cuda"

@@ -1,4 +1,4 @@
-"""Live streams chunk by chunk: ``AVNet.open_streams`` -> ``StreamPool`` (DESIGN.md "Live streams").
+"""Live streams chunk by chunk: ``AVNet.open_streams`` -> ``StreamPool`` (DESIGN.md "Live streams", "Every face of a stream").
 
 The stateful form of ``AVNet.separate_long``: audio and lip embeddings arrive a chunk at a time, every window of the long-form plan runs
 as soon as its samples and its frames are there, and the samples no later window can touch leave at once.  For any way of cutting a
@@ -14,11 +14,12 @@ import operator
 
 import torch
 
-from . import _lib, layers
+from . import _lib, models
 
 SPF = 640  # samples per video frame: 16 kHz audio, 25 fps video
 FS = 16000  # the model's sample rate
-MAX_CAPACITY = 1 << 24  # RTFS_LIVE_MAX_CAPACITY: window + max_chunk at most, so that every launch grid fits
+MAX_CAPACITY = 1 << 24  # RTFS_LIVE_MAX_CAPACITY: speakers * (window + max_chunk) at most, so that every launch grid fits
+MAX_SPEAKERS = 16  # RTFS_MAX_SPEAKERS: the most targets per mixture rtfs_separator_speakers_f32 fans out to
 PLAN_WORDS = 13  # RTFS_LIVE_PLAN_WORDS: [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]
 _REASONS = {1: "bad argument", 2: "unknown slot id", 3: "slot named twice", 4: "chunk larger than max_chunk",
             5: "audio ran too far ahead of video: the push would overwrite samples a not-yet-emitted window needs",
@@ -33,22 +34,83 @@ def _weights(window, hop, device):
     return torch.ones_like(i) if V == 0 else torch.minimum(torch.ones_like(i), torch.minimum((i + 0.5) / V, (window - i - 0.5) / V))
 
 
-class StreamPool:
+def _join(mid, last):
+    """The tail of a composite flush: per slot, what the middle push made final in front of the flush's own samples."""
+    return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
+
+
+class _Pool:
+    """What every pool shares: the checks of slot ids and ``reset``; for the table-driven pools (``_counters``, ``_reset_state``) also the
+    call of their host planner."""
+
+    _WORDS, _NAMES = 4, ("a", "f", "e", "o")  # host counters per slot, and those a refusal shows
+
+    @staticmethod
+    def _check_ids(slot_ids):
+        try:
+            ids = list(slot_ids)
+        except TypeError:
+            raise ValueError("slot_ids must be a sequence of integers") from None
+        try:  # anything that indexes (int, numpy integers, 0-dim integer tensors), but no bool of python, numpy or torch
+            if any(isinstance(s, bool) or str(getattr(s, "dtype", "")) in ("bool", "torch.bool") for s in ids):
+                raise TypeError
+            return [operator.index(s) for s in ids]
+        except TypeError:
+            raise ValueError(f"slot ids must be integers; got {ids}") from None
+
+    def _check_slots(self, slot_ids):
+        ids = self._check_ids(slot_ids)
+        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
+            raise ValueError(f"{type(self).__name__}: slot ids {ids} must be distinct and in [0, {self.slots})")
+        return ids
+
+    def reset(self, slot_ids):
+        """Drop the named streams without output."""
+        ids = self._check_slots(slot_ids)
+        if ids:
+            self._drop(ids)
+
+    def _drop(self, ids):
+        self._reset_state(torch.tensor(ids, dtype=torch.int64).to(self.device), len(ids))
+        for s in ids:
+            self._counters[s] = [0] * self._WORDS
+
+    def _call_planner(self, fn, ids, inputs, flush, consts, plan_words, n_sizes):
+        """One call of the host planner ``fn(slot_ids, counters, *inputs, R, slots, flush, *consts, new_counters, table, sizes, refused)``
+        for the named slots; ``inputs`` are the per-slot sizes of a push (NULL at a flush).  -> (new counters, table, sizes) as lists;
+        ValueError with the planner's reason for what it refuses.  Nothing is changed."""
+        R, W, LL = len(ids), self._WORDS, ctypes.c_longlong
+        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0,) * W)]
+        new, table, sizes, refused = (LL * (W * R))(), (LL * (plan_words * R))(), (LL * n_sizes)(), (ctypes.c_int * 2)()
+        rc = fn((LL * R)(*ids), (LL * (W * R))(*cnt), *(None if flush else (LL * R)(*v) for v in inputs), R, self.slots, int(flush), *consts,
+                new, table, sizes, refused)
+        if rc != 0:
+            r, why = refused[0], _REASONS.get(refused[1], refused[1])
+            at = f" at slot {ids[r]}, counters ({', '.join(self._NAMES)}) = {tuple(cnt[W * r:W * r + len(self._NAMES)])}" if 0 <= r < R else ""
+            raise ValueError(f"{type(self).__name__}.{'flush' if flush else 'push'}: refused ({why}){at}; no slot was changed")
+        return list(new), list(table), [int(v) for v in sizes]
+
+
+class StreamPool(_Pool):
     """``slots`` concurrent live streams on one model (inference only).  Built by ``AVNet.open_streams``.
 
-    Per slot the pool holds, on the model's device and allocated once: a history ring of C = window + max_chunk samples, one of C / 640
-    lip-embedding frames (512 channels), and an overlap accumulator of C floats per source: 4 C (1 + n_src) + 2048 C / 640 bytes,
-    717 KB at the defaults with n_src 1.  Next to them one tick's framed windows in and out for the most windows a tick can hold,
-    slots * (1 + ceil(max_chunk / hop)) rows.  A push allocates only its flat output, the tick table and one chunk's ``forward``.
+    A slot has one audio track and ``speakers`` = K lip tracks; this class is K = 1, ``SpeakerStreamPool`` any K.  Per slot the pool
+    holds, on the model's device and allocated once: a history ring of C = window + max_chunk samples, K rings of C / 640 lip-embedding
+    frames (512 channels), ``_vring`` (slots, K, 512, C / 640), and an overlap accumulator of C floats per row of a window's result
+    (``n_src`` rows: the model's sources at K = 1, the K targets otherwise): 4 C (1 + n_src) + 2048 K C / 640 bytes, 717 KB at the
+    defaults with n_src 1.  Next to them one tick's framed windows in and out for the most windows a tick can hold,
+    slots * (1 + ceil(max_chunk / hop)) rows, the K video windows of a row behind each other.  A push allocates only its flat output, the
+    tick table and one chunk's ``forward``.
 
     Host state is four integers per slot: a samples received, f frames received, e windows emitted, o samples output.  Window n is
     ready when a >= n hop + window and f >= n hop / 640 + window / 640.
 
     Because each tick uploads a small table (one host-to-device copy), ``push`` / ``flush`` are NOT capturable in a HIP graph."""
 
-    def __init__(self, model, slots, window, hop, max_chunk, max_batch):
+    def __init__(self, model, slots, window, hop, max_chunk, max_batch, speakers=1):
         self.model, self.slots, self.window, self.hop, self.max_chunk, self.max_batch = model, slots, window, hop, max_chunk, max_batch
-        self.n_src = int(model.n_src)
+        self.speakers = K = int(speakers)
+        self.n_src = int(model.n_src) if K == 1 else K  # K > 1 has a target-speaker model: the plan, the accumulator and the results see K rows
         self.capacity = window + max_chunk
         self.device = next(model.parameters()).device
         self.on_hip = bool(model.fused) and self.device.type == "cuda"
@@ -56,10 +118,10 @@ class StreamPool:
         C, Wv, dev = self.capacity, window // SPF, self.device
         rows_cap = slots * (1 + -(-max_chunk // hop))
         self._aring = _lib.empty(slots, C, device=dev)
-        self._vring = _lib.empty(slots, 512, C // SPF, device=dev)
+        self._vring = _lib.empty(slots, K, 512, C // SPF, device=dev)
         self._acc = _lib.empty(slots, self.n_src, C, device=dev)
         self._xw = _lib.empty(rows_cap, window, device=dev)
-        self._vw = _lib.empty(rows_cap, 512, Wv, device=dev)
+        self._vw = _lib.empty(rows_cap * K, 512, Wv, device=dev)
         self._y = _lib.empty(rows_cap, self.n_src, window, device=dev)
         self._reset_state(None, slots)
 
@@ -88,73 +150,56 @@ class StreamPool:
         ids = self._check_ids(slot_ids)
         return self._tick(ids, None, None, None, None, flush=True)
 
-    def reset(self, slot_ids):
-        """Drop the named streams without output."""
-        ids = self._check_ids(slot_ids)
-        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
-            raise ValueError(f"StreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
-        if not ids:
-            return
-        self._reset_state(torch.tensor(ids, dtype=torch.int64).to(self.device), len(ids))
-        for s in ids:
-            self._counters[s] = [0, 0, 0, 0]
-
     # -- checks (no launch, no state change)
-    @staticmethod
-    def _check_ids(slot_ids):
-        try:
-            ids = list(slot_ids)
-        except TypeError:
-            raise ValueError("StreamPool: slot_ids must be a sequence of integers") from None
-        try:  # anything that indexes (int, numpy integers, 0-dim integer tensors), but no bool of python, numpy or torch
-            if any(isinstance(s, bool) or str(getattr(s, "dtype", "")) in ("bool", "torch.bool") for s in ids):
-                raise TypeError
-            return [operator.index(s) for s in ids]
-        except TypeError:
-            raise ValueError(f"StreamPool: slot ids must be integers; got {ids}") from None
+    def _tracks_of(self, r, v):
+        """The lip tracks of video chunk r as a list of ``speakers`` (512,m) tensors; their shapes are checked by the caller."""
+        return [v]
 
     def _check_chunks(self, slot_ids, audio_chunks, video_chunks):
+        who = f"{type(self).__name__}.push"
         ids = self._check_ids(slot_ids)
         try:
             audio_chunks, video_chunks = list(audio_chunks), list(video_chunks)
         except TypeError:
-            raise ValueError("StreamPool.push: audio_chunks and video_chunks must be sequences of tensors") from None
+            raise ValueError(f"{who}: audio_chunks and video_chunks must be sequences of tensors") from None
         if not len(ids) == len(audio_chunks) == len(video_chunks):
-            raise ValueError(f"StreamPool.push: {len(ids)} slot id(s), {len(audio_chunks)} audio and {len(video_chunks)} video chunk(s)")
+            raise ValueError(f"{who}: {len(ids)} slot id(s), {len(audio_chunks)} audio and {len(video_chunks)} video chunk(s)")
         wavs, vids = [], []
         for r, (w, v) in enumerate(zip(audio_chunks, video_chunks)):
-            if not isinstance(w, torch.Tensor) or not isinstance(v, torch.Tensor):
-                raise ValueError(f"StreamPool.push: chunk {r} is not a pair of tensors")
+            tracks = self._tracks_of(r, v)
+            if not isinstance(w, torch.Tensor) or any(not isinstance(t, torch.Tensor) for t in tracks):
+                raise ValueError(f"{who}: chunk {r} is not made of tensors")
             if w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
-                raise ValueError(f"StreamPool.push: audio chunk {r} must be (n) or (1,n); got {tuple(w.shape)}")
-            if v.ndim != 2 or v.shape[0] != 512:
-                raise ValueError(f"StreamPool.push: video chunk {r} must be (512,m); got {tuple(v.shape)}")
-            if w.dtype != torch.float32 or v.dtype != torch.float32:
-                raise ValueError(f"StreamPool.push: chunk {r} is {w.dtype} / {v.dtype}; the kernels are float32")
-            if w.device != self.device or v.device != self.device:
-                raise ValueError(f"StreamPool.push: chunk {r} lies on {w.device} / {v.device}, the pool on {self.device}")
+                raise ValueError(f"{who}: audio chunk {r} must be (n) or (1,n); got {tuple(w.shape)}")
+            for t in tracks:
+                if t.ndim != 2 or t.shape[0] != 512:
+                    raise ValueError(f"{who}: every track of video chunk {r} must be (512,m); got {tuple(t.shape)}")
+            for t in (w, *tracks):
+                if t.dtype != torch.float32 or t.device != self.device:
+                    raise ValueError(f"{who}: chunk {r} is {t.dtype} on {t.device}; the pool is float32 on {self.device}")
+            if len({int(t.shape[1]) for t in tracks}) != 1:
+                raise ValueError(f"{who}: the tracks of video chunk {r} hold {[int(t.shape[1]) for t in tracks]} frames; "
+                                 "all speakers of a slot are pushed with one m")
             wavs.append(w.reshape(-1).contiguous())
-            vids.append(v.contiguous())
-        return ids, [int(w.shape[0]) for w in wavs], [int(v.shape[1]) for v in vids], wavs, vids
+            vids.append([t.contiguous() for t in tracks])
+        return ids, [int(w.shape[0]) for w in wavs], [int(v[0].shape[1]) for v in vids], wavs, vids
 
     def _plan(self, ids, na, nf, flush):
-        R = len(ids)
-        LL = ctypes.c_longlong
-        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0, 0, 0, 0))]
-        new, table, sizes, refused = (LL * (4 * R))(), (LL * (PLAN_WORDS * R))(), (LL * 5)(), (ctypes.c_int * 2)()
-        rc = _lib.load().rtfs_live_plan((LL * R)(*ids), (LL * (4 * R))(*cnt), None if flush else (LL * R)(*na), None if flush else (LL * R)(*nf),
-                                        R, self.slots, int(flush), self.window, self.hop, self.max_chunk, self.n_src, new, table, sizes, refused)
-        if rc != 0:
-            r, why = refused[0], _REASONS.get(refused[1], refused[1])
-            what = "flush" if flush else "push"
-            raise ValueError(f"StreamPool.{what}: refused ({why})" + (f" at slot {ids[r]}, counters (a, f, e, o) = {tuple(cnt[4 * r:4 * r + 4])}"
-                                                                     if 0 <= r < R else "") + "; no slot was changed")
-        return list(new), list(table), [int(v) for v in sizes]
+        return self._call_planner(_lib.load().rtfs_live_plan, ids, (na, nf), flush, (self.window, self.hop, self.max_chunk, self.n_src),
+                                  PLAN_WORDS, 5)
+
+    def _plan_push(self, ids, na, nf):
+        """The dry run of a push: ValueError for what the planner refuses.  (The composite pools have the same two methods.)"""
+        return self._plan(ids, na, nf, False)
+
+    def _plan_flush(self, ids):
+        """The dry run of a flush."""
+        return self._plan(ids, None, None, True)
 
     # -- one tick
     def _tick(self, ids, na, nf, wavs, vids, flush):
         if self.model.training:
-            raise RuntimeError("StreamPool is inference only: call .eval() on the model")
+            raise RuntimeError(f"{type(self).__name__} is inference only: call .eval() on the model")
         R = len(ids)
         if R == 0:
             return []
@@ -175,18 +220,34 @@ class StreamPool:
         return res
 
     def _forward_rows(self, rows):
-        run = self.model.forward if self.on_hip else self.model.forward_modular
-        for c0 in range(0, rows, self.max_batch):
-            c1 = min(rows, c0 + self.max_batch)
-            self._y[c0:c1].copy_(run(self._xw[c0:c1], self._vw[c0:c1]))
+        K, Wv = self.speakers, self.window // SPF
+        if K == 1:
+            run = self.model.forward if self.on_hip else self.model.forward_modular
+            for c0 in range(0, rows, self.max_batch):
+                c1 = min(rows, c0 + self.max_batch)
+                self._y[c0:c1].copy_(run(self._xw[c0:c1], self._vw[c0:c1]))
+            return
+        vw = self._vw.view(-1, K, 512, Wv)
+        step = max(1, self.max_batch // K)
+        for c0 in range(0, rows, step):
+            c1 = min(rows, c0 + step)
+            if self.on_hip:
+                self._y[c0:c1].copy_(self.model.separate_speakers(self._xw[c0:c1], vw[c0:c1]))
+            else:  # target k of a window = the model on that window with lips k
+                y = self.model.forward_modular(self._xw[c0:c1].repeat_interleave(K, 0), self._vw[c0 * K:c1 * K])
+                self._y[c0:c1].copy_(y.view(c1 - c0, K, self.window))
 
     def _tick_hip(self, R, table, rows, floats, max_span, max_na, max_nf, wavs, vids, flush):
-        lib, dev = _lib.load(), self.device
-        ptrs = [0] * (2 * R) if flush else [w.data_ptr() for w in wavs] + [v.data_ptr() for v in vids]
+        lib, dev, K = _lib.load(), self.device, self.speakers
+        if flush:
+            ptrs = [0] * ((1 + K) * R)
+        else:  # columns [aptr | vptr_0 | .. | vptr_{K-1}]: one device address per (slot, track)
+            ptrs = [w.data_ptr() for w in wavs] + [v[k].data_ptr() for k in range(K) for v in vids]
         tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
         st = _lib.stream_of(self._xw)
-        _lib.check(lib.rtfs_live_ingest_frame_f32(_lib.ptr(tab), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._xw), _lib.ptr(self._vw),
-                                                  R, rows, max_na, max_nf, self.window, self.hop, self.max_chunk, st), "rtfs_live_ingest_frame_f32")
+        _lib.check(lib.rtfs_live_ingest_frame_speakers_f32(_lib.ptr(tab), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._xw),
+                                                           _lib.ptr(self._vw), R, rows, K, max_na, max_nf, self.window, self.hop, self.max_chunk,
+                                                           st), "rtfs_live_ingest_frame_speakers_f32")
         self._forward_rows(rows)
         out = _lib.empty(floats, device=dev)
         if max_span > 0:
@@ -205,8 +266,10 @@ class StreamPool:
             for t in (self._aring, self._vring, self._acc):
                 t[sel] = 0
             return
-        _lib.check(_lib.load().rtfs_live_reset_f32(_lib.ptr(ids), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._acc), R, self.n_src,
-                                                   self.window, self.max_chunk, _lib.stream_of(self._aring)), "rtfs_live_reset_f32")
+        # one track and n_src accumulator rows, or K of each
+        name = "rtfs_live_reset_f32" if self.speakers == 1 else "rtfs_live_reset_speakers_f32"
+        _lib.check(getattr(_lib.load(), name)(_lib.ptr(ids), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._acc), R, self.n_src,
+                                              self.window, self.max_chunk, _lib.stream_of(self._aring)), name)
 
     # -- the same tick in torch ops (fused = False, CPU tensors): ingest, gather from the rings, accumulate window by window
     def _tick_torch(self, R, table, rows, floats, wavs, vids, flush):
@@ -215,19 +278,21 @@ class StreamPool:
         return self._overlap_add_torch(R, table, floats, flush)
 
     def _frame_torch(self, R, table, wavs, vids, flush):
-        W, H, C, dev = self.window, self.hop, self.capacity, self.device
+        W, H, C, K, dev = self.window, self.hop, self.capacity, self.speakers, self.device
         Cv, Wv, Hv = C // SPF, W // SPF, H // SPF
         slot, a0, na, f0, nf, e0, cnt, row0, o0, end, off, apos, fpos = (table[k * R:(k + 1) * R] for k in range(PLAN_WORDS))
         iw, ifr = torch.arange(W, device=dev), torch.arange(Wv, device=dev)
         for r in range(R):
             if not flush:  # sequential here, so the windows can be gathered from the rings after the chunks went in
                 self._aring[slot[r], (apos[r] + torch.arange(na[r], device=dev)) % C] = wavs[r]
-                self._vring[slot[r]][:, (fpos[r] + torch.arange(nf[r], device=dev)) % Cv] = vids[r]
+                for k in range(K):
+                    self._vring[slot[r], k][:, (fpos[r] + torch.arange(nf[r], device=dev)) % Cv] = vids[r][k]
             lim_a, lim_f = a0[r] + na[r], f0[r] + nf[r]
             for n in range(e0[r], e0[r] + cnt[r]):
                 row, p = row0[r] + n - e0[r], n * H + iw
                 self._xw[row] = torch.where(p < lim_a, self._aring[slot[r], p % C], torch.zeros((), device=dev))
-                self._vw[row] = self._vring[slot[r]][:, (n * Hv + ifr).clamp(max=lim_f - 1) % Cv]
+                for k in range(K):  # the audio once, the K video windows of the row behind each other
+                    self._vw[row * K + k] = self._vring[slot[r], k][:, (n * Hv + ifr).clamp(max=lim_f - 1) % Cv]
 
     def _overlap_add_torch(self, R, table, floats, flush):
         W, H, C, n_src, dev = self.window, self.hop, self.capacity, self.n_src, self.device
@@ -257,32 +322,37 @@ class StreamPool:
         return out
 
 
-def open_streams(model, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
-    """``AVNet.open_streams``: check the arguments as ``separate_long`` does, then allocate the pool."""
-    slots, window = int(slots), int(window)
-    hop = window // 2 if hop is None else int(hop)
-    max_chunk = window if max_chunk is None else int(max_chunk)
-    max_batch = int(max_batch)
-    if _rate(sample_rate) != FS:
-        return _open_at_rate(lambda room: open_streams(model, slots, window, hop, max_chunk + room, max_batch), sample_rate, max_chunk)
-    if slots < 1 or max_batch < 1:
-        raise ValueError(f"open_streams: slots = {slots}, max_batch = {max_batch}; both at least 1")
-    lib = _lib.load()
-    if lib.rtfs_longform_plan(1, 1, window, hop, None) != 0:
-        raise ValueError(f"open_streams: window = {window}, hop = {hop} must be multiples of {SPF} with 0 < hop <= window")
-    if max_chunk < SPF or max_chunk % SPF or window + max_chunk > MAX_CAPACITY:
-        raise ValueError(f"open_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF} with window + max_chunk <= {MAX_CAPACITY}")
-    rnn_kind = model.refinement_module.audio_net.get_block(0).rnn_kind
-    if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
-        raise ValueError(f"open_streams: a window of {window} samples does not fit the fused separator of this model's cell "
-                         f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
-    if model.training:
-        raise RuntimeError("AVNet.open_streams is inference only: call .eval()")
-    return StreamPool(model, slots, window, hop, max_chunk, max_batch)
+class SpeakerStreamPool(StreamPool):
+    """``slots`` live streams with ``speakers`` = K faces each on one target-speaker model (n_src 1, inference only).  Built by
+    ``AVNet.open_streams(..., speakers=K)``; the surface is ``StreamPool``'s, which also holds the state and runs the tick.
 
+    Target k of a slot gets what a ``StreamPool`` gives for the same audio with lips k, but the audio is stored once (one ring), framed
+    once per window and, for K > 1, run through the audio-only prefix once per window (``AVNet.separate_speakers`` on
+    (rows, K, 512, window / 640) in chunks of max(1, max_batch // K) windows).  Host state stays four integers per slot: the K tracks
+    are pushed together with one m, so they share f.  The tick table carries one device address per (slot, speaker): the K chunks of a
+    slot are read where they lie, still one table upload per tick."""
 
-# ================================================================ every face of a stream (DESIGN.md "Every face of a stream")
-MAX_SPEAKERS = 16  # RTFS_MAX_SPEAKERS: the most targets per mixture rtfs_separator_speakers_f32 fans out to
+    def push(self, slot_ids, audio_chunks, video_chunks):
+        """As ``StreamPool.push``, with the video chunk of a slot a (K,512,m) tensor or a sequence of K (512,m) tensors - K separate
+        allocations are read where they lie - with one m, 0 <= m <= max_chunk // 640.  Returns, per named slot, the (K, k) newly final
+        samples.  ValueError - before any launch, all state unchanged - for what ``StreamPool.push`` refuses, for a wrong number of
+        tracks and for tracks that differ in m."""
+        return super().push(slot_ids, audio_chunks, video_chunks)
+
+    def _tracks_of(self, r, v):
+        K = self.speakers
+        if isinstance(v, torch.Tensor):
+            if v.ndim != 3:
+                raise ValueError(f"SpeakerStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m); got {tuple(v.shape)}")
+            tracks = list(v.unbind(0))
+        else:
+            try:
+                tracks = list(v)
+            except TypeError:
+                raise ValueError(f"SpeakerStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m)") from None
+        if len(tracks) != K:
+            raise ValueError(f"SpeakerStreamPool.push: video chunk {r} holds {len(tracks)} track(s); the pool has {K} speakers per slot")
+        return tracks
 
 
 def speakers_of(speakers):
@@ -298,168 +368,35 @@ def speakers_of(speakers):
     return K
 
 
-class SpeakerStreamPool(StreamPool):
-    """``slots`` live streams with ``speakers`` = K faces each on one target-speaker model (n_src 1, inference only).  Built by
-    ``AVNet.open_streams(..., speakers=K)``; the surface is ``StreamPool``'s.
+def _open(cls, model, slots, K, window, hop, max_chunk, max_batch):
+    """Check the arguments as ``separate_long`` does, then allocate the pool."""
+    slots = int(slots)
+    if slots < 1:
+        raise ValueError(f"open_streams: slots = {slots}; at least 1")
+    window, hop, max_batch, _ = models._window_args(model, "open_streams", window, hop, max_batch)
+    max_chunk = window if max_chunk is None else int(max_chunk)
+    if not _lib.load().rtfs_live_speakers_sizes_ok(window, hop, max_chunk, K):
+        raise ValueError(f"open_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF} with speakers * (window + max_chunk) "
+                         f"<= {MAX_CAPACITY} (speakers = {K})")
+    return cls(model, slots, window, hop, max_chunk, max_batch, K)
 
-    A slot has ONE audio track and K lip tracks.  Target k of a slot gets what a ``StreamPool`` gives for the same audio with lips k, but
-    the audio is stored once (one ring), framed once per window and run through the audio-only prefix once per window
-    (``AVNet.separate_speakers`` on (rows, K, 512, window / 640) in chunks of max(1, max_batch // K) windows).  Device state per slot:
-    an audio ring of C = window + max_chunk samples, K lip rings (K, 512, C / 640) and K accumulators (K, C):
-    4 C (1 + K) + 2048 K C / 640 bytes, allocated once.  Host state stays four integers per slot: the K tracks are pushed together with
-    one m, so they share f.  The tick is ``rtfs_live_plan`` and ``rtfs_live_overlap_add_f32`` with n_src = K around
-    ``rtfs_live_ingest_frame_speakers_f32``, whose table carries one device address per (slot, speaker): the K chunks of a slot are
-    read where they lie, still one table upload per tick."""
 
-    def __init__(self, model, slots, speakers, window, hop, max_chunk, max_batch):
-        self.model, self.slots, self.window, self.hop, self.max_chunk, self.max_batch = model, slots, window, hop, max_chunk, max_batch
-        self.speakers = self.n_src = K = int(speakers)  # the plan, the accumulator and the results see K sources
-        self.capacity = window + max_chunk
-        self.device = next(model.parameters()).device
-        self.on_hip = bool(model.fused) and self.device.type == "cuda"
-        self._counters = [[0, 0, 0, 0] for _ in range(slots)]
-        C, Wv, dev = self.capacity, window // SPF, self.device
-        rows_cap = slots * (1 + -(-max_chunk // hop))
-        self._aring = _lib.empty(slots, C, device=dev)
-        self._vring = _lib.empty(slots, K, 512, C // SPF, device=dev)
-        self._acc = _lib.empty(slots, K, C, device=dev)
-        self._xw = _lib.empty(rows_cap, window, device=dev)
-        self._vw = _lib.empty(rows_cap * K, 512, Wv, device=dev)
-        self._y = _lib.empty(rows_cap, K, window, device=dev)
-        self._reset_state(None, slots)
-
-    def push(self, slot_ids, audio_chunks, video_chunks):
-        """As ``StreamPool.push``, with the video chunk of a slot a (K,512,m) tensor or a sequence of K (512,m) tensors - K separate
-        allocations are read where they lie - with one m, 0 <= m <= max_chunk // 640.  Returns, per named slot, the (K, k) newly final
-        samples.  ValueError - before any launch, all state unchanged - for what ``StreamPool.push`` refuses, for a wrong number of
-        tracks and for tracks that differ in m."""
-        ids, na, nf, wavs, vids = self._check_chunks(slot_ids, audio_chunks, video_chunks)
-        return self._tick(ids, na, nf, wavs, vids, flush=False)
-
-    def _check_chunks(self, slot_ids, audio_chunks, video_chunks):
-        K = self.speakers
-        ids = self._check_ids(slot_ids)
-        try:
-            audio_chunks, video_chunks = list(audio_chunks), list(video_chunks)
-        except TypeError:
-            raise ValueError("SpeakerStreamPool.push: audio_chunks and video_chunks must be sequences") from None
-        if not len(ids) == len(audio_chunks) == len(video_chunks):
-            raise ValueError(f"SpeakerStreamPool.push: {len(ids)} slot id(s), {len(audio_chunks)} audio and {len(video_chunks)} video chunk(s)")
-        wavs, vids = [], []
-        for r, (w, v) in enumerate(zip(audio_chunks, video_chunks)):
-            if isinstance(v, torch.Tensor):
-                if v.ndim != 3:
-                    raise ValueError(f"SpeakerStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m); got {tuple(v.shape)}")
-                tracks = list(v.unbind(0))
-            else:
-                try:
-                    tracks = list(v)
-                except TypeError:
-                    raise ValueError(f"SpeakerStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m)") from None
-            if len(tracks) != K:
-                raise ValueError(f"SpeakerStreamPool.push: video chunk {r} holds {len(tracks)} track(s); the pool has {K} speakers per slot")
-            if not isinstance(w, torch.Tensor) or any(not isinstance(t, torch.Tensor) for t in tracks):
-                raise ValueError(f"SpeakerStreamPool.push: chunk {r} is not made of tensors")
-            if w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
-                raise ValueError(f"SpeakerStreamPool.push: audio chunk {r} must be (n) or (1,n); got {tuple(w.shape)}")
-            for t in tracks:
-                if t.ndim != 2 or t.shape[0] != 512:
-                    raise ValueError(f"SpeakerStreamPool.push: every track of video chunk {r} must be (512,m); got {tuple(t.shape)}")
-                if t.dtype != torch.float32 or t.device != self.device:
-                    raise ValueError(f"SpeakerStreamPool.push: video chunk {r} is {t.dtype} on {t.device}; the pool is float32 on {self.device}")
-            if len({int(t.shape[1]) for t in tracks}) != 1:
-                raise ValueError(f"SpeakerStreamPool.push: the tracks of video chunk {r} hold {[int(t.shape[1]) for t in tracks]} frames; "
-                                 "all speakers of a slot are pushed with one m")
-            if w.dtype != torch.float32 or w.device != self.device:
-                raise ValueError(f"SpeakerStreamPool.push: audio chunk {r} is {w.dtype} on {w.device}; the pool is float32 on {self.device}")
-            wavs.append(w.reshape(-1).contiguous())
-            vids.append([t.contiguous() for t in tracks])
-        return ids, [int(w.shape[0]) for w in wavs], [int(v[0].shape[1]) for v in vids], wavs, vids
-
-    def _forward_rows(self, rows):
-        K, Wv = self.speakers, self.window // SPF
-        vw = self._vw.view(-1, K, 512, Wv)
-        step = max(1, self.max_batch // K)
-        for c0 in range(0, rows, step):
-            c1 = min(rows, c0 + step)
-            if self.on_hip:
-                self._y[c0:c1].copy_(self.model.separate_speakers(self._xw[c0:c1], vw[c0:c1]))
-            else:  # target k of a window = the model on that window with lips k
-                y = self.model.forward_modular(self._xw[c0:c1].repeat_interleave(K, 0), self._vw[c0 * K:c1 * K])
-                self._y[c0:c1].copy_(y.view(c1 - c0, K, self.window))
-
-    def _tick_hip(self, R, table, rows, floats, max_span, max_na, max_nf, wavs, vids, flush):
-        lib, dev, K = _lib.load(), self.device, self.speakers
-        if flush:
-            ptrs = [0] * ((1 + K) * R)
-        else:  # columns [aptr | vptr_0 | .. | vptr_{K-1}]: one device address per (slot, speaker)
-            ptrs = [w.data_ptr() for w in wavs] + [v[k].data_ptr() for k in range(K) for v in vids]
-        tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
-        st = _lib.stream_of(self._xw)
-        _lib.check(lib.rtfs_live_ingest_frame_speakers_f32(_lib.ptr(tab), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._xw),
-                                                           _lib.ptr(self._vw), R, rows, K, max_na, max_nf, self.window, self.hop, self.max_chunk,
-                                                           st), "rtfs_live_ingest_frame_speakers_f32")
-        self._forward_rows(rows)
-        out = _lib.empty(floats, device=dev)
-        if max_span > 0:
-            _lib.check(lib.rtfs_live_overlap_add_f32(_lib.ptr(tab), _lib.ptr(self._y), _lib.ptr(out), _lib.ptr(self._acc), R, max_span, K,
-                                                     self.window, self.hop, self.max_chunk, int(flush), st), "rtfs_live_overlap_add_f32")
-        if flush:
-            self._reset_state(tab[:R], R)
-        return out
-
-    def _reset_state(self, ids, R):
-        if not self.on_hip:
-            return super()._reset_state(ids, R)
-        _lib.check(_lib.load().rtfs_live_reset_speakers_f32(_lib.ptr(ids), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._acc), R,
-                                                            self.speakers, self.window, self.max_chunk, _lib.stream_of(self._aring)),
-                   "rtfs_live_reset_speakers_f32")
-
-    # -- the same ingest + framing in torch ops: the audio once, every track as StreamPool frames its one
-    def _frame_torch(self, R, table, wavs, vids, flush):
-        W, H, C, K, dev = self.window, self.hop, self.capacity, self.speakers, self.device
-        Cv, Wv, Hv = C // SPF, W // SPF, H // SPF
-        slot, a0, na, f0, nf, e0, cnt, row0, o0, end, off, apos, fpos = (table[k * R:(k + 1) * R] for k in range(PLAN_WORDS))
-        iw, ifr = torch.arange(W, device=dev), torch.arange(Wv, device=dev)
-        for r in range(R):
-            if not flush:
-                self._aring[slot[r], (apos[r] + torch.arange(na[r], device=dev)) % C] = wavs[r]
-                for k in range(K):
-                    self._vring[slot[r], k][:, (fpos[r] + torch.arange(nf[r], device=dev)) % Cv] = vids[r][k]
-            lim_a, lim_f = a0[r] + na[r], f0[r] + nf[r]
-            for n in range(e0[r], e0[r] + cnt[r]):
-                row, p = row0[r] + n - e0[r], n * H + iw
-                self._xw[row] = torch.where(p < lim_a, self._aring[slot[r], p % C], torch.zeros((), device=dev))
-                for k in range(K):
-                    self._vw[row * K + k] = self._vring[slot[r], k][:, (n * Hv + ifr).clamp(max=lim_f - 1) % Cv]
+def open_streams(model, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
+    """``AVNet.open_streams``: one lip track per slot."""
+    if _rate(sample_rate) != FS:
+        mc = int(window) if max_chunk is None else int(max_chunk)
+        return _open_at_rate(lambda room: open_streams(model, slots, window, hop, mc + room, max_batch), sample_rate, mc)
+    return _open(StreamPool, model, slots, 1, window, hop, max_chunk, max_batch)
 
 
 def open_speaker_streams(model, slots, speakers, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
     """``AVNet.open_streams(speakers=K)`` with K > 1: the checks of ``open_streams`` and those of ``separate_speakers``, then the pool."""
     K = speakers_of(speakers)
-    slots, window = int(slots), int(window)
-    hop = window // 2 if hop is None else int(hop)
-    max_chunk = window if max_chunk is None else int(max_chunk)
-    max_batch = int(max_batch)
     if _rate(sample_rate) != FS:
         raise ValueError(f"open_streams: speakers = {K} with sample_rate = {sample_rate}: a pool with several speakers takes 16 kHz audio only")
     if int(model.n_src) != 1:
         raise ValueError("open_streams: speakers > 1 needs a target-speaker model (n_src 1)")
-    if slots < 1 or max_batch < 1:
-        raise ValueError(f"open_streams: slots = {slots}, max_batch = {max_batch}; both at least 1")
-    lib = _lib.load()
-    if lib.rtfs_longform_plan(1, 1, window, hop, None) != 0:
-        raise ValueError(f"open_streams: window = {window}, hop = {hop} must be multiples of {SPF} with 0 < hop <= window")
-    if max_chunk < SPF or max_chunk % SPF or not lib.rtfs_live_speakers_sizes_ok(window, hop, max_chunk, K):
-        raise ValueError(f"open_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF} with speakers * (window + max_chunk) "
-                         f"<= {MAX_CAPACITY} (speakers = {K})")
-    rnn_kind = model.refinement_module.audio_net.get_block(0).rnn_kind
-    if int(lib.rtfs_num_frames(window)) // 2 > layers.fused_max_block_sweep(rnn_kind):
-        raise ValueError(f"open_streams: a window of {window} samples does not fit the fused separator of this model's cell "
-                         f"(T/2 <= {layers.fused_max_block_sweep(rnn_kind)})")
-    if model.training:
-        raise RuntimeError("AVNet.open_streams is inference only: call .eval()")
-    return SpeakerStreamPool(model, slots, K, window, hop, max_chunk, max_batch)
+    return _open(SpeakerStreamPool, model, slots, K, window, hop, max_chunk, max_batch)
 
 
 # ================================================================ live streams from camera frames (DESIGN.md "Live streams from camera frames")
@@ -468,7 +405,7 @@ LOOKAHEAD = 2  # frames: the stem's temporal kernel is 5 with padding 2, so embe
 CROP = 88
 
 
-class LipStreamPool:
+class LipStreamPool(_Pool):
     """``slots`` concurrent lip tracks embedded chunk by chunk (inference only).  Built by ``FRCNNVideoModel.open_streams``.
 
     For any way of cutting a track into chunks, the concatenation of what ``push`` and the final ``flush`` return equals
@@ -479,6 +416,8 @@ class LipStreamPool:
     Host state per slot: g frames received, v embeddings emitted (and the side of the history that is current).  All arithmetic of a
     tick is ``rtfs_live_video_plan`` (host only); nothing is read back from the device.  Not capturable in a HIP graph (the tick table
     is uploaded per call)."""
+
+    _WORDS, _NAMES = 3, ("g", "v")
 
     def __init__(self, model, slots, max_frames, roi_hw, max_batch_frames):
         self.model, self.slots, self.max_frames, self.roi_hw, self.max_batch_frames = model, slots, max_frames, roi_hw, max_batch_frames
@@ -510,20 +449,7 @@ class LipStreamPool:
         A slot that received nothing returns (512, 0)."""
         return self._tick(self._check_ids(slot_ids), None, None, False, flush=True)
 
-    def reset(self, slot_ids):
-        """Drop the named tracks without output."""
-        ids = self._check_ids(slot_ids)
-        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
-            raise ValueError(f"LipStreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
-        if not ids:
-            return
-        self._reset_state(torch.tensor(ids, dtype=torch.int64).to(self.device), len(ids))
-        for s in ids:
-            self._counters[s] = [0, 0, 0]
-
     # -- checks (no launch, no state change)
-    _check_ids = staticmethod(StreamPool._check_ids)
-
     def _check_chunks(self, slot_ids, chunks):
         ids = self._check_ids(slot_ids)
         try:
@@ -559,19 +485,9 @@ class LipStreamPool:
         return ids, [int(c.shape[0]) for c in chunks], [c.contiguous() for c in chunks], u8
 
     def _plan(self, ids, ms, flush):
-        R = len(ids)
-        if R == 0:
+        if not ids:
             return [], [], [0, 0, 0]
-        LL = ctypes.c_longlong
-        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0, 0, 0))]
-        new, table, sizes, refused = (LL * (3 * R))(), (LL * (VIDEO_PLAN_WORDS * R))(), (LL * 3)(), (ctypes.c_int * 2)()
-        rc = _lib.load().rtfs_live_video_plan((LL * R)(*ids), (LL * (3 * R))(*cnt), None if flush else (LL * R)(*ms), R, self.slots, int(flush),
-                                              self.max_frames, new, table, sizes, refused)
-        if rc != 0:
-            r, why = refused[0], _REASONS.get(refused[1], refused[1])
-            raise ValueError(f"LipStreamPool.{'flush' if flush else 'push'}: refused ({why})" +
-                             (f" at slot {ids[r]}, counters (g, v) = {tuple(cnt[3 * r:3 * r + 2])}" if 0 <= r < R else "") + "; no slot was changed")
-        return list(new), list(table), [int(v) for v in sizes]
+        return self._call_planner(_lib.load().rtfs_live_video_plan, ids, (ms,), flush, (self.max_frames,), VIDEO_PLAN_WORDS, 3)
 
     # -- one tick
     def _tick(self, ids, ms, chunks, u8, flush):
@@ -653,122 +569,118 @@ def _counters_as(pool, ids, new, words):
             pool._counters[s] = c
 
 
-class CameraStreamPool:
+class CameraStreamPool(_Pool):
     """``slots`` live streams from microphone samples and camera frames (inference only).  Built by ``System.open_camera_streams``.
 
     A ``LipStreamPool`` embeds each tick's mouth frames and its embeddings go straight on, as the video chunks, into the audio
     ``StreamPool``; the concatenated outputs equal ``System.separate_recording`` of the whole recording (16 kHz audio) with the same
     ``window`` / ``hop``.  Embeddings lag the frames received by two frames, so audio window n waits for frame n hop / 640 + window / 640 + 1
     (80 ms more than with ready embeddings), and the inner audio pool is opened with ``max_chunk + 1280``: audio in step with the camera
-    stands up to 1280 samples further ahead of the EMBEDDED video than window + max_chunk allows for."""
+    stands up to 1280 samples further ahead of the EMBEDDED video than window + max_chunk allows for.
+
+    With ``speakers`` = K faces per slot (``SpeakerCameraStreamPool``) the lip pool has slots * K tracks, track s K + k for face k of
+    slot s, which move together; here K = 1 and track s is slot s."""
 
     def __init__(self, lips, audio, max_chunk):
         self.lips, self.audio, self.max_chunk = lips, audio, max_chunk
-        self.slots, self.device, self.n_src = audio.slots, audio.device, audio.n_src
-
-    def counters(self, slot):
-        """((a, f, e, o) of the audio pool, (g, v) of the lip pool); f == v between calls."""
-        return self.audio.counters(slot), self.lips.counters(slot)
-
-    def _check_audio(self, ids, audio_chunks):
-        try:
-            audio_chunks = list(audio_chunks)
-        except TypeError:
-            raise ValueError("CameraStreamPool.push: audio_chunks must be a sequence of tensors") from None
-        if len(audio_chunks) != len(ids):
-            raise ValueError(f"CameraStreamPool.push: {len(ids)} slot id(s) and {len(audio_chunks)} audio chunk(s)")
-        for r, w in enumerate(audio_chunks):
-            if not isinstance(w, torch.Tensor) or w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
-                raise ValueError(f"CameraStreamPool.push: audio chunk {r} must be a tensor (n) or (1,n)")
-            if w.dtype != torch.float32 or w.device != self.device:
-                raise ValueError(f"CameraStreamPool.push: audio chunk {r} is {w.dtype} on {w.device}; the pool is float32 on {self.device}")
-            if w.numel() > self.max_chunk:
-                raise ValueError(f"CameraStreamPool.push: audio chunk {r} holds {w.numel()} samples; max_chunk = {self.max_chunk}")
-        return audio_chunks
-
-    def push(self, slot_ids, audio_chunks, roi_chunks):
-        """One chunk of 16 kHz audio ((n)|(1,n) float32, 0 <= n <= max_chunk) and one of mouth frames (as ``LipStreamPool.push`` takes them,
-        at most max_chunk // 640) for each slot named; either may be empty.  Returns, per named slot, the (n_src, k) newly final samples,
-        as ``StreamPool.push`` does.  ValueError - before any launch, all state unchanged - for what either pool refuses."""
-        ids, ms, rois, u8 = self.lips._check_chunks(slot_ids, roi_chunks)
-        wavs = self._check_audio(ids, audio_chunks)
-        if not ids:
-            return []
-        self._plan_push(ids, [int(w.numel()) for w in wavs], ms)  # refused here, nothing has moved yet
-        if self.audio.model.training:
-            raise RuntimeError("CameraStreamPool is inference only: call .eval() on the model")
-        embs = self.lips._tick(ids, ms, rois, u8, flush=False)
-        return self.audio.push(ids, wavs, embs)
-
-    def _plan_push(self, ids, na, ms):
-        """The dry run of a push of na samples and ms frames per named slot on both planners: ValueError for what either refuses."""
-        _, vtab, _ = self.lips._plan(ids, ms, False)
-        ks = vtab[4 * len(ids):5 * len(ids)]
-        # frames may run (window + max_chunk) / 640 + 2 ahead of the first window not yet emitted: the two embeddings a flush still owes
-        # then always fit the inner pool's ring
-        room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
-        for s, m in zip(ids, ms):
-            if self.lips._counters[s][0] + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
-                raise ValueError(f"CameraStreamPool.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
-        return self.audio._plan(ids, na, ks, False)
-
-    def flush(self, slot_ids):
-        """End the named streams: the lip pool's flush, its at most two remaining embeddings pushed with empty audio, then the audio pool's
-        flush.  Returns the remaining samples per slot (the samples the middle step made final in front of the flush's own)."""
-        ids = self.lips._check_ids(slot_ids)
-        if not ids:
-            return []
-        self._plan_flush(ids)
-        if self.audio.model.training:
-            raise RuntimeError("CameraStreamPool is inference only: call .eval() on the model")
-        embs = self.lips.flush(ids)
-        empty = _lib.empty(0, device=self.device)
-        mid = self.audio.push(ids, [empty] * len(ids), embs)
-        last = self.audio.flush(ids)
-        return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
-
-    def _plan_flush(self, ids):
-        """The dry run of a flush on both planners: ValueError for what either refuses."""
-        _, vtab, _ = self.lips._plan(ids, None, True)
-        ks = vtab[4 * len(ids):5 * len(ids)]
-        new, _, _ = self.audio._plan(ids, [0] * len(ids), ks, False)
-        with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the middle push leaves
-            self.audio._plan(ids, None, None, True)
-
-    def reset(self, slot_ids):
-        """Drop the named streams without output."""
-        ids = self.lips._check_ids(slot_ids)
-        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
-            raise ValueError(f"CameraStreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
-        self.lips.reset(ids)
-        self.audio.reset(ids)
-
-
-class SpeakerCameraStreamPool(CameraStreamPool):
-    """``CameraStreamPool`` with ``speakers`` = K faces per slot.  Built by ``System.open_camera_streams(..., speakers=K)``.
-
-    The ``LipStreamPool`` has slots * K tracks, track s K + k for face k of slot s, and the audio pool is a ``SpeakerStreamPool``: the
-    per-track embedding blocks of a tick go straight on, as the K video chunks of slot s, through the per-speaker addresses of the
-    tick table.  The ROI chunk of a slot is (K,m,H,W) uint8 or (K,m,88,88) float32.  For any chunking output k of a slot equals
-    ``System.separate_recording(wav, 16000, rois[k])``."""
-
-    def __init__(self, lips, audio, max_chunk):
-        super().__init__(lips, audio, max_chunk)
-        self.speakers = audio.speakers
+        self.slots, self.device, self.n_src, self.speakers = audio.slots, audio.device, audio.n_src, audio.speakers
 
     def _tracks(self, ids):
         K = self.speakers
         return [s * K + k for s in ids for k in range(K)]
 
     def _group(self, embs):
+        """The per-track blocks of a lip tick as the audio pool's video chunks: K per slot (at K = 1 a plain ``StreamPool``: the block)."""
         K = self.speakers
-        return [embs[r:r + K] for r in range(0, len(embs), K)]
+        return embs if K == 1 else [embs[r:r + K] for r in range(0, len(embs), K)]
 
-    def _check_slots(self, slot_ids):
-        ids = self.lips._check_ids(slot_ids)
-        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
-            raise ValueError(f"SpeakerCameraStreamPool: slot ids {ids} must be distinct and in [0, {self.slots})")
-        return ids
+    def counters(self, slot):
+        """((a, f, e, o) of the audio pool, (g, v) of the lip pool); f == v between calls."""
+        return self.audio.counters(slot), self.lips.counters(slot)
+
+    def _check_audio(self, ids, audio_chunks):
+        who = f"{type(self).__name__}.push"
+        try:
+            audio_chunks = list(audio_chunks)
+        except TypeError:
+            raise ValueError(f"{who}: audio_chunks must be a sequence of tensors") from None
+        if len(audio_chunks) != len(ids):
+            raise ValueError(f"{who}: {len(ids)} slot id(s) and {len(audio_chunks)} audio chunk(s)")
+        for r, w in enumerate(audio_chunks):
+            if not isinstance(w, torch.Tensor) or w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
+                raise ValueError(f"{who}: audio chunk {r} must be a tensor (n) or (1,n)")
+            if w.dtype != torch.float32 or w.device != self.device:
+                raise ValueError(f"{who}: audio chunk {r} is {w.dtype} on {w.device}; the pool is float32 on {self.device}")
+            if w.numel() > self.max_chunk:
+                raise ValueError(f"{who}: audio chunk {r} holds {w.numel()} samples; max_chunk = {self.max_chunk}")
+        return audio_chunks
+
+    def _check_rois(self, slot_ids, roi_chunks):
+        """-> slot ids, and frames per TRACK, chunks per track and their kind as ``LipStreamPool._check_chunks`` returns them."""
+        return self.lips._check_chunks(slot_ids, roi_chunks)
+
+    def push(self, slot_ids, audio_chunks, roi_chunks):
+        """One chunk of 16 kHz audio ((n)|(1,n) float32, 0 <= n <= max_chunk) and one of mouth frames (as ``LipStreamPool.push`` takes them,
+        at most max_chunk // 640) for each slot named; either may be empty.  Returns, per named slot, the (n_src, k) newly final samples,
+        as ``StreamPool.push`` does.  ValueError - before any launch, all state unchanged - for what either pool refuses."""
+        ids, ms, rois, u8 = self._check_rois(slot_ids, roi_chunks)
+        wavs = self._check_audio(ids, audio_chunks)
+        if not ids:
+            return []
+        self._plan_push(ids, [int(w.numel()) for w in wavs], ms)  # refused here, nothing has moved yet
+        if self.audio.model.training:
+            raise RuntimeError(f"{type(self).__name__} is inference only: call .eval() on the model")
+        embs = self.lips._tick(self._tracks(ids), ms, rois, u8, flush=False)
+        return self.audio.push(ids, wavs, self._group(embs))
+
+    def _plan_push(self, ids, na, ms):
+        """The dry run of a push of na samples per named slot and ms frames per named TRACK on both planners: ValueError for what
+        either refuses."""
+        K, R = self.speakers, len(ids)
+        _, vtab, _ = self.lips._plan(self._tracks(ids), ms, False)
+        ks = vtab[4 * R * K:5 * R * K][::K]  # the tracks of a slot share their counters: one k per slot
+        # frames may run (window + max_chunk) / 640 + 2 ahead of the first window not yet emitted: the two embeddings a flush still owes
+        # then always fit the inner pool's ring
+        room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
+        for s, m in zip(ids, ms[::K]):
+            if self.lips._counters[s * K][0] + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
+                raise ValueError(f"{type(self).__name__}.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
+        return self.audio._plan_push(ids, na, ks)
+
+    def flush(self, slot_ids):
+        """End the named streams: the lip pool's flush of the slots' tracks, its at most two remaining embeddings per track pushed with
+        empty audio, then the audio pool's flush.  Returns the remaining samples per slot (the samples the middle step made final in
+        front of the flush's own)."""
+        ids = self._check_slots(slot_ids)
+        if not ids:
+            return []
+        self._plan_flush(ids)
+        if self.audio.model.training:
+            raise RuntimeError(f"{type(self).__name__} is inference only: call .eval() on the model")
+        embs = self.lips.flush(self._tracks(ids))
+        empty = _lib.empty(0, device=self.device)
+        mid = self.audio.push(ids, [empty] * len(ids), self._group(embs))
+        return _join(mid, self.audio.flush(ids))
+
+    def _plan_flush(self, ids):
+        """The dry run of a flush on both planners: ValueError for what either refuses."""
+        K, R = self.speakers, len(ids)
+        _, vtab, _ = self.lips._plan(self._tracks(ids), None, True)
+        new, _, _ = self.audio._plan_push(ids, [0] * R, vtab[4 * R * K:5 * R * K][::K])
+        with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the middle push leaves
+            self.audio._plan_flush(ids)
+
+    def _drop(self, ids):
+        self.lips.reset(self._tracks(ids))
+        self.audio.reset(ids)
+
+
+class SpeakerCameraStreamPool(CameraStreamPool):
+    """``CameraStreamPool`` with ``speakers`` = K faces per slot.  Built by ``System.open_camera_streams(..., speakers=K)``.
+
+    The audio pool is a ``SpeakerStreamPool``: the per-track embedding blocks of a tick go straight on, as the K video chunks of slot s,
+    through the per-speaker addresses of the tick table.  The ROI chunk of a slot is (K,m,H,W) uint8 or (K,m,88,88) float32.  For any
+    chunking output k of a slot equals ``System.separate_recording(wav, 16000, rois[k])``."""
 
     def counters(self, slot):
         """((a, f, e, o) of the audio pool, (g, v) of the slot's lip tracks, which move together); f == v between calls."""
@@ -778,6 +690,9 @@ class SpeakerCameraStreamPool(CameraStreamPool):
         """As ``CameraStreamPool.push``, with the mouth frames of a slot as ONE tensor (K,m,H,W) uint8 or (K,m,88,88) float32.  Returns,
         per named slot, the (K, k) newly final samples.  ValueError - before any launch, all state unchanged - for what either pool
         refuses and for a chunk that does not hold K tracks."""
+        return super().push(slot_ids, audio_chunks, roi_chunks)
+
+    def _check_rois(self, slot_ids, roi_chunks):
         K = self.speakers
         ids = self._check_slots(slot_ids)
         try:
@@ -789,55 +704,7 @@ class SpeakerCameraStreamPool(CameraStreamPool):
         for r, c in enumerate(roi_chunks):
             if not isinstance(c, torch.Tensor) or c.ndim != 4 or c.shape[0] != K:
                 raise ValueError(f"SpeakerCameraStreamPool.push: ROI chunk {r} must be a tensor ({K},m,H,W)")
-        _, ms, rois, u8 = self.lips._check_chunks(self._tracks(ids), [t for c in roi_chunks for t in c.contiguous().unbind(0)])
-        wavs = self._check_audio(ids, audio_chunks)
-        if not ids:
-            return []
-        self._plan_push(ids, [int(w.numel()) for w in wavs], ms)  # refused here, nothing has moved yet
-        if self.audio.model.training:
-            raise RuntimeError("SpeakerCameraStreamPool is inference only: call .eval() on the model")
-        embs = self.lips._tick(self._tracks(ids), ms, rois, u8, flush=False)
-        return self.audio.push(ids, wavs, self._group(embs))
-
-    def _plan_push(self, ids, na, ms):
-        """The dry run of a push of na samples per named slot and ms frames per named TRACK on both planners."""
-        K, R = self.speakers, len(ids)
-        _, vtab, _ = self.lips._plan(self._tracks(ids), ms, False)
-        ks = vtab[4 * R * K:5 * R * K][::K]  # the tracks of a slot share their counters: one k per slot
-        room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
-        for s, m in zip(ids, ms[::K]):
-            if self.lips._counters[s * K][0] + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
-                raise ValueError(f"SpeakerCameraStreamPool.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
-        return self.audio._plan(ids, na, ks, False)
-
-    def flush(self, slot_ids):
-        """As ``CameraStreamPool.flush``: the lip pool's flush of the slots' tracks, their remaining embeddings pushed with empty audio,
-        then the audio pool's flush.  Returns the remaining (K, k) samples per slot."""
-        ids = self._check_slots(slot_ids)
-        if not ids:
-            return []
-        self._plan_flush(ids)
-        if self.audio.model.training:
-            raise RuntimeError("SpeakerCameraStreamPool is inference only: call .eval() on the model")
-        embs = self.lips.flush(self._tracks(ids))
-        empty = _lib.empty(0, device=self.device)
-        mid = self.audio.push(ids, [empty] * len(ids), self._group(embs))
-        last = self.audio.flush(ids)
-        return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
-
-    def _plan_flush(self, ids):
-        K, R = self.speakers, len(ids)
-        _, vtab, _ = self.lips._plan(self._tracks(ids), None, True)
-        ks = vtab[4 * R * K:5 * R * K][::K]
-        new, _, _ = self.audio._plan(ids, [0] * R, ks, False)
-        with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the middle push leaves
-            self.audio._plan(ids, None, None, True)
-
-    def reset(self, slot_ids):
-        """Drop the named streams without output."""
-        ids = self._check_slots(slot_ids)
-        self.lips.reset(self._tracks(ids))
-        self.audio.reset(ids)
+        return (ids, *self.lips._check_chunks(self._tracks(ids), [t for c in roi_chunks for t in c.contiguous().unbind(0)])[1:])
 
 
 def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1):
@@ -869,7 +736,7 @@ def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, m
 RESAMPLE_PLAN_WORDS = 7  # RTFS_LIVE_RESAMPLE_PLAN_WORDS: [slot | a | m | g | k | out_off | side]
 
 
-class ResampleStreamPool:
+class ResampleStreamPool(_Pool):
     """``slots`` concurrent streams resampled chunk by chunk.  Built by ``datas.open_resample_streams``.
 
     For any way of cutting a recording into chunks, the concatenation of what ``push`` and the final ``flush`` return is BIT-equal to
@@ -882,6 +749,8 @@ class ResampleStreamPool:
     Host state per slot: a samples received, g samples emitted (and the side of the history that is current).  All arithmetic of a tick
     is ``rtfs_live_resample_plan`` (host only); per tick one plan, one table upload, one launch, nothing read back.  Not capturable in
     a HIP graph (the tick table is uploaded per call)."""
+
+    _WORDS, _NAMES = 3, ("a", "g")
 
     def __init__(self, slots, orig_freq, new_freq, max_chunk, device):
         from . import datas
@@ -915,20 +784,7 @@ class ResampleStreamPool:
         with zeros behind the last sample, then reset the slots.  A slot that received nothing returns (0,)."""
         return self._tick(self._check_ids(slot_ids), None, None, False, flush=True)
 
-    def reset(self, slot_ids):
-        """Drop the named streams without output."""
-        ids = self._check_ids(slot_ids)
-        if len(set(ids)) != len(ids) or any(not 0 <= s < self.slots for s in ids):
-            raise ValueError(f"ResampleStreamPool.reset: slot ids {ids} must be distinct and in [0, {self.slots})")
-        if not ids:
-            return
-        self._reset_state(torch.tensor(ids, dtype=torch.int64).to(self.device), len(ids))
-        for s in ids:
-            self._counters[s] = [0, 0, 0]
-
     # -- checks (no launch, no state change)
-    _check_ids = staticmethod(StreamPool._check_ids)
-
     def _check_chunks(self, slot_ids, chunks):
         ids = self._check_ids(slot_ids)
         try:
@@ -954,19 +810,10 @@ class ResampleStreamPool:
         return ids, ms, [c.reshape(-1).contiguous() for c in chunks], kinds == {torch.int16}, plan
 
     def _plan(self, ids, ms, flush):
-        R = len(ids)
-        if R == 0:
+        if not ids:
             return [], [], [0, 0, 0]
-        LL = ctypes.c_longlong
-        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0, 0, 0))]
-        new, table, sizes, refused = (LL * (3 * R))(), (LL * (RESAMPLE_PLAN_WORDS * R))(), (LL * 3)(), (ctypes.c_int * 2)()
-        rc = _lib.load().rtfs_live_resample_plan((LL * R)(*ids), (LL * (3 * R))(*cnt), None if flush else (LL * R)(*ms), R, self.slots,
-                                                 int(flush), self.o, self.n, self.max_chunk, new, table, sizes, refused)
-        if rc != 0:
-            r, why = refused[0], _REASONS.get(refused[1], refused[1])
-            raise ValueError(f"ResampleStreamPool.{'flush' if flush else 'push'}: refused ({why})" +
-                             (f" at slot {ids[r]}, counters (a, g) = {tuple(cnt[3 * r:3 * r + 2])}" if 0 <= r < R else "") + "; no slot was changed")
-        return list(new), list(table), [int(v) for v in sizes]
+        return self._call_planner(_lib.load().rtfs_live_resample_plan, ids, (ms,), flush, (self.o, self.n, self.max_chunk),
+                                  RESAMPLE_PLAN_WORDS, 3)
 
     # -- one tick
     def _tick(self, ids, ms, chunks, i16, flush, plan=None):
@@ -1030,7 +877,7 @@ def open_resample_streams(slots, orig_freq, new_freq=FS, max_chunk=None, device=
     return ResampleStreamPool(slots, orig_freq, new_freq, max_chunk, device)
 
 
-class RateStreamPool:
+class RateStreamPool(_Pool):
     """A ``StreamPool`` or ``CameraStreamPool`` whose audio arrives at the microphone's rate.  Built by ``open_streams`` /
     ``open_camera_streams`` with ``sample_rate`` other than 16000; same ``push`` / ``flush`` / ``reset`` / ``counters`` surface.
 
@@ -1064,7 +911,7 @@ class RateStreamPool:
     def _plan_inner(self, ids, ks, nf):
         """The inner pool's dry run of a push of ks 16 kHz samples and nf frames; refuses a push behind which the flush tail would not
         fit.  -> the inner audio pool's new counters."""
-        new = (self.inner._plan_push(ids, ks, nf) if self.camera else self.audio._plan(ids, ks, nf, False))[0]
+        new = self.inner._plan_push(ids, ks, nf)[0]
         for r, s in enumerate(ids):
             a, _, e, _ = new[4 * r:4 * r + 4]
             if a + self.tail - e * self.audio.hop > self.audio.capacity:
@@ -1095,29 +942,20 @@ class RateStreamPool:
     def flush(self, slot_ids):
         """End the named streams: the resampler's flush, its tail pushed with empty video, then the inner flush.  Returns the remaining
         samples per slot (those the middle step made final in front of the flush's own)."""
-        ids = self.resampler._check_ids(slot_ids)
+        ids = self._check_ids(slot_ids)
         if not ids:
             return []
         R = len(ids)
         _, rtab, _ = self.resampler._plan(ids, None, True)
-        if self.camera:
-            new = self.inner._plan_push(ids, rtab[4 * R:5 * R], [0] * R)[0]
-        else:
-            new = self.audio._plan(ids, rtab[4 * R:5 * R], [0] * R, False)[0]
+        new = self.inner._plan_push(ids, rtab[4 * R:5 * R], [0] * R)[0]
         with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the tail leaves
-            if self.camera:
-                self.inner._plan_flush(ids)
-            else:
-                self.audio._plan(ids, None, None, True)
+            self.inner._plan_flush(ids)
         if self.audio.model.training:
             raise RuntimeError("RateStreamPool is inference only: call .eval() on the model")
         mid = self.inner.push(ids, self.resampler.flush(ids), self._no_video(R))
-        last = self.inner.flush(ids)
-        return [torch.cat([m, t], dim=1) if m.shape[1] else t for m, t in zip(mid, last)]
+        return _join(mid, self.inner.flush(ids))
 
-    def reset(self, slot_ids):
-        """Drop the named streams without output."""
-        ids = self.resampler._check_ids(slot_ids)
+    def _drop(self, ids):
         self.resampler.reset(ids)
         self.inner.reset(ids)
 

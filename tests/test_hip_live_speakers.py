@@ -121,7 +121,7 @@ def three_slots(window, hop, max_chunk, K, seed):
 
 
 # ---------------------------------------------------------------- 1 + 2. the launches on synthetic windows
-@pytest.mark.parametrize("K", [2, 3])
+@pytest.mark.parametrize("K", [1, 2, 3])
 @pytest.mark.parametrize("window,hop", PLANS)
 def test_ingest_framing_is_a_copy_and_overlap_add_meets_the_oracle(window, hop, K):
     xs, vs, events = three_slots(window, hop, window, K, window + hop + K)
@@ -153,6 +153,15 @@ def test_longform_framing_kernel_is_bit_exact(window, hop):
     L_.check(L_.load().rtfs_longform_frame_speakers_f32(L_.ptr(xd), L_.ptr(vd), L_.ptr(xw), L_.ptr(vw), B, K, L, Tv, window, hop,
                                                         L_.stream_of(xd)), "rtfs_longform_frame_speakers_f32")
     assert np.array_equal(host(xw), exw) and np.array_equal(host(vw), evw)
+    # one track through the single-track entry: K = 1 of the same kernel, == track 0 of the K = 3 rows
+    v0 = np.ascontiguousarray(v[:, 0])
+    xw1 = L_.empty(B * N, window, device=xd.device)
+    vw1 = L_.empty(B * N, 512, window // SPF, device=xd.device)
+    L_.check(L_.load().rtfs_longform_frame_f32(L_.ptr(xd), L_.ptr(dev(v0)), L_.ptr(xw1), L_.ptr(vw1), B, L, Tv, window, hop,
+                                               L_.stream_of(xd)), "rtfs_longform_frame_f32")
+    exw1, evw1 = SO.frame_long(x, v[:, :1], window, hop)
+    assert np.array_equal(host(xw1), exw) and np.array_equal(host(vw1), host(vw)[0::K])
+    assert np.array_equal(host(xw1), exw1) and np.array_equal(host(vw1), evw1)
     for bad in (0, 17):
         assert L_.load().rtfs_longform_frame_speakers_f32(L_.ptr(xd), L_.ptr(vd), L_.ptr(xw), L_.ptr(vw), B, bad, L, Tv, window, hop,
                                                           L_.stream_of(xd)) == -4
