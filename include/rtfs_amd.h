@@ -195,15 +195,19 @@ size_t rtfs_sru_backward_workspace_bytes(int L, int N);
 int rtfs_sru_forward_train_f32(const float* x, const float* tpack, float* h, float* saved, int L, int N, void* stream);
 int rtfs_sru_backward_f32(const float* x, const float* tpack, const float* saved, const float* dh, float* dx, float* dparams,
                           int L, int N, void* ws, size_t ws_bytes, void* stream);
-/* DualPathRNN.forward / backward for training (src/models/layers/rnn_layers.py:136-162 with rnn_type SRU).
- * x, out, dout, dx (B,64,T,F); dim as in the reference (4: sweep along F, 3: along T); dim 14 / 13: the same sweeps with x, out, dout, dx
- * as rows (B,T,F,64) (the layout the training kernels of a block hand each other; size queries take the plain 4 / 3).  `saved` (rtfs_dualpath_saved_floats)
- * is written by the forward and read by the backward; the same workspace size serves both.
- * tpack (rtfs_dualpath_train_pack_floats(), packing.py:pack_dualpath_train):
- *   LN gamma (64) | LN beta (64) | SRU training pack with layer-0 rows in k*64 + c order | ConvTranspose1d weight as
- *   (co, (7-k)*64 + ci) | as (ci, k*64 + co) | bias (64).
- * dparams (rtfs_dualpath_grad_floats(), overwritten): dgamma | dbeta | SRU gradients (rtfs_sru_backward_f32 layout, layer-0
- *   rows k*64 + c) | d ConvTranspose1d weight as ((7-k)*64 + ci, co) | d bias. */
+/* DualPathRNN.forward / backward for training (src/models/layers/rnn_layers.py:136-162), one set of six symbols per
+ * cell: rtfs_dualpath_* (rnn_type SRU), rtfs_dualpath_lstm_* (LSTM), rtfs_dualpath_gru_* (GRU).  Common to the three:
+ * x, out, dout, dx (B,64,T,F); dim as in the reference (4: sweep along F, 3: along T).  `saved` (*_saved_floats) is written by the forward
+ * and read by the backward; the same workspace size (*_train_workspace_bytes) serves both; dparams (*_grad_floats()) is overwritten.
+ * Refused: RTFS_ERR_ARG (null pointer, B < 1, dim), then RTFS_ERR_SHAPE (sweep axis < 8; backward: > 256), then RTFS_ERR_WORKSPACE.
+ * Every tpack starts with LN gamma (64) | LN beta (64) and ends with the ConvTranspose1d weight as (co, (7-k)*64 + ci) | as
+ * (ci, k*64 + co) | bias (64); every dparams starts with dgamma | dbeta and ends with d ConvTranspose1d weight as ((7-k)*64 + ci, co) | d bias.
+ *
+ * SRU cell.  dim 14 / 13 (this cell only; the others answer RTFS_ERR_ARG): the same sweeps with x, out, dout, dx as rows (B,T,F,64) (the
+ * layout the training kernels of a block hand each other; size queries take the plain 4 / 3).
+ * tpack (rtfs_dualpath_train_pack_floats(), packing.py:pack_dualpath_train), between the common parts: SRU training pack with layer-0
+ *   rows in k*64 + c order.
+ * dparams (rtfs_dualpath_grad_floats()): SRU gradients (rtfs_sru_backward_f32 layout, layer-0 rows k*64 + c). */
 size_t rtfs_dualpath_train_pack_floats(void);
 size_t rtfs_dualpath_grad_floats(void);
 size_t rtfs_dualpath_saved_floats(int B, int T, int F, int dim);
@@ -212,12 +216,11 @@ int rtfs_dualpath_forward_train_f32(const float* x, const float* tpack, float* o
                                     void* ws, size_t ws_bytes, void* stream);
 int rtfs_dualpath_backward_f32(const float* x, const float* tpack, const float* saved, const float* dout, float* dx,
                                float* dparams, int B, int T, int F, int dim, void* ws, size_t ws_bytes, void* stream);
-/* The same module with rnn_type LSTM (rnn_layers.py:116-122: nn.LSTM(512, 32, 4 layers, bidirectional)) in training.
- * tpack (rtfs_dualpath_lstm_train_pack_floats(), packing.py:pack_dualpath_lstm_train): LN gamma | beta | per layer [W_ih both directions
- *   (256, Din), rows dir*128 + gate*32 + j, layer-0 columns in k*64 + c order | its transpose | b_ih + b_hh (256) | W_hh (2,128,32)] |
- *   ConvTranspose1d weight as (co, (7-k)*64 + ci) | as (ci, k*64 + co) | bias.
- * dparams (rtfs_dualpath_lstm_grad_floats(), overwritten): dgamma | dbeta | per layer [dW_ih (256, Din) | d bias (256; the gradient of
- *   b_ih and of b_hh alike) | dW_hh (2,128,32)] | d ConvTranspose1d weight ((7-k)*64 + ci, co) | d bias. */
+/* LSTM cell (rnn_layers.py:116-122: nn.LSTM(512, 32, 4 layers, bidirectional)).
+ * tpack (rtfs_dualpath_lstm_train_pack_floats(), packing.py:pack_dualpath_lstm_train), between the common parts: per layer [W_ih both
+ *   directions (256, Din), rows dir*128 + gate*32 + j, layer-0 columns in k*64 + c order | its transpose | b_ih + b_hh (256) | W_hh (2,128,32)].
+ * dparams (rtfs_dualpath_lstm_grad_floats()): per layer [dW_ih (256, Din) | d bias (256; the gradient of b_ih and of b_hh alike) |
+ *   dW_hh (2,128,32)]. */
 size_t rtfs_dualpath_lstm_train_pack_floats(void);
 size_t rtfs_dualpath_lstm_grad_floats(void);
 size_t rtfs_dualpath_lstm_saved_floats(int B, int T, int F, int dim);
@@ -226,13 +229,12 @@ int rtfs_dualpath_lstm_forward_train_f32(const float* x, const float* tpack, flo
                                          void* ws, size_t ws_bytes, void* stream);
 int rtfs_dualpath_lstm_backward_f32(const float* x, const float* tpack, const float* saved, const float* dout, float* dx,
                                     float* dparams, int B, int T, int F, int dim, void* ws, size_t ws_bytes, void* stream);
-/* The same module with rnn_type GRU (rnn_layers.py:116-122: nn.GRU(512, 32, 4 layers, bidirectional); gates r, z, n).  There is no fused
- * inference kernel for this cell (no reference yaml uses it in a DualPathRNN): the forward below also serves inference.
- * tpack (rtfs_dualpath_gru_train_pack_floats(), packing.py:pack_dualpath_gru_train): LN gamma | beta | per layer [W_ih both directions
- *   (192, Din), rows dir*96 + gate*32 + j, layer-0 columns in k*64 + c order | its transpose | b_ih (192) | W_hh (2,96,32) | b_hh (192)] |
- *   ConvTranspose1d weight as (co, (7-k)*64 + ci) | as (ci, k*64 + co) | bias.
- * dparams (rtfs_dualpath_gru_grad_floats(), overwritten): dgamma | dbeta | per layer [dW_ih | db_ih | dW_hh | db_hh] | d ConvTranspose1d
- *   weight ((7-k)*64 + ci, co) | d bias. */
+/* GRU cell (rnn_layers.py:116-122: nn.GRU(512, 32, 4 layers, bidirectional); gates r, z, n).  There is no fused inference kernel for
+ * this cell (no reference yaml uses it in a DualPathRNN): the forward below also serves inference.
+ * tpack (rtfs_dualpath_gru_train_pack_floats(), packing.py:pack_dualpath_gru_train), between the common parts: per layer [W_ih both
+ *   directions (192, Din), rows dir*96 + gate*32 + j, layer-0 columns in k*64 + c order | its transpose | b_ih (192) | W_hh (2,96,32) |
+ *   b_hh (192)].
+ * dparams (rtfs_dualpath_gru_grad_floats()): per layer [dW_ih | db_ih | dW_hh | db_hh]. */
 size_t rtfs_dualpath_gru_train_pack_floats(void);
 size_t rtfs_dualpath_gru_grad_floats(void);
 size_t rtfs_dualpath_gru_saved_floats(int B, int T, int F, int dim);

@@ -60,24 +60,14 @@ SIGNATURES = {
     "rtfs_sru_backward_workspace_bytes": (_z, [_i, _i]),
     "rtfs_sru_forward_train_f32": (_i, [_p, _p, _p, _p, _i, _i, _p]),
     "rtfs_sru_backward_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p, _z, _p]),
-    "rtfs_dualpath_train_pack_floats": (_z, []),
-    "rtfs_dualpath_grad_floats": (_z, []),
-    "rtfs_dualpath_saved_floats": (_z, [_i, _i, _i, _i]),
-    "rtfs_dualpath_train_workspace_bytes": (_z, [_i, _i, _i, _i]),
-    "rtfs_dualpath_forward_train_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "rtfs_dualpath_backward_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "rtfs_dualpath_lstm_train_pack_floats": (_z, []),
-    "rtfs_dualpath_lstm_grad_floats": (_z, []),
-    "rtfs_dualpath_lstm_saved_floats": (_z, [_i, _i, _i, _i]),
-    "rtfs_dualpath_lstm_train_workspace_bytes": (_z, [_i, _i, _i, _i]),
-    "rtfs_dualpath_lstm_forward_train_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "rtfs_dualpath_lstm_backward_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "rtfs_dualpath_gru_train_pack_floats": (_z, []),
-    "rtfs_dualpath_gru_grad_floats": (_z, []),
-    "rtfs_dualpath_gru_saved_floats": (_z, [_i, _i, _i, _i]),
-    "rtfs_dualpath_gru_train_workspace_bytes": (_z, [_i, _i, _i, _i]),
-    "rtfs_dualpath_gru_forward_train_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p]),
-    "rtfs_dualpath_gru_backward_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p]),
+    # DualPathRNN, training side: the same six symbols for each cell (SRU, LSTM, GRU)
+    **{f"rtfs_dualpath_{infix}{name}": sig for infix in ("", "lstm_", "gru_") for name, sig in (
+        ("train_pack_floats", (_z, [])),
+        ("grad_floats", (_z, [])),
+        ("saved_floats", (_z, [_i, _i, _i, _i])),
+        ("train_workspace_bytes", (_z, [_i, _i, _i, _i])),
+        ("forward_train_f32", (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p])),
+        ("backward_f32", (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p])))},
     "rtfs_cna_param_floats": (_z, [_p]),
     "rtfs_cna_grad_floats": (_z, [_p]),
     "rtfs_cna_saved_floats": (_z, [_p, _i, _i, _i]),

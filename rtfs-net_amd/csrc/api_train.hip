@@ -74,24 +74,14 @@ int rtfs_sru_backward_f32(const float* x, const float* tpack, const float* saved
     return RTFS_OK;
 }
 
-// ------------------------------------------------------------ DualPathRNN (SRU cell), training side
+// ------------------------------------------------------------ DualPathRNN, training side: one scaffold, three cells (SRU, LSTM, GRU)
+// dp_forward_train / dp_backward hold what every cell shares: the checks, the workspace, the way into and out of the sweep layout, the
+// zero tails, LayerNorm, the ConvTranspose1d GEMMs over 8-row windows and the residual.  A cell (SruCell, GatedCell) supplies its pack and
+// gradient offsets (Layout), its view of the saved state, its extra workspace and the two loops over its four layers.
 namespace {
 constexpr size_t DT_G = 0, DT_B = 64, DT_SRU = 128, DT_WCF = DT_SRU + TP_END, DT_WCB = DT_WCF + 64 * 512, DT_BT = DT_WCB + 64 * 512,
                  DT_END = DT_BT + 64;
 constexpr size_t DG_G = 0, DG_B = 64, DG_SRU = 128, DG_WCT = DG_SRU + GP_END, DG_BT = DG_WCT + 512 * 64, DG_END = DG_BT + 64;
-struct DpSaved {  // sequence-major training layout, see k_train_rnn.hip
-    float *xn, *U[4], *c[4], *hpad[4];
-    size_t floats;
-    DpSaved(float* p, size_t rows) {
-        float* p0 = p;
-        xn = p; p += (rows + 8) * 64;
-        U[0] = p; p += rows * 256;
-        for (int l = 1; l < 4; ++l) { U[l] = p; p += rows * 192; }
-        for (int l = 0; l < 4; ++l) { c[l] = p; p += rows * 64; }
-        for (int l = 0; l < 4; ++l) { hpad[l] = p; p += (rows + 8) * 64; }
-        floats = (size_t)(p - p0);
-    }
-};
 struct DpGeom {
     int nseq, R, Ls, L;
     size_t rows, elems;
@@ -108,38 +98,205 @@ struct DpGeom {
     bool ok() const { return Ls >= 8 && rows * 512 < 0x7fffffffu; }
     bool ok_backward() const { return ok() && Ls <= 256; }
 };
-}  // namespace
+// Saved state of one forward, sequence-major training layout (k_train_rnn.hip).  U: the SRU's projections (256 columns in layer 0, 192
+// above) or a gated cell's per-step gate state (256 a row); c: SRU and LSTM; hprev (h_{t-1} of every row, the operand of the W_hh
+// gradient): LSTM and GRU.  What a cell does not have stays null.
+struct DpSaved {
+    float *xn, *U[4], *c[4] = {}, *hpad[4], *hprev[4] = {};
+    size_t floats;
+    DpSaved(float* p, size_t rows, bool sru, bool has_c) {
+        float* p0 = p;
+        xn = p; p += (rows + 8) * 64;
+        for (int l = 0; l < 4; ++l) { U[l] = p; p += rows * (sru && l ? 192 : 256); }
+        for (int l = 0; has_c && l < 4; ++l) { c[l] = p; p += rows * 64; }
+        for (int l = 0; l < 4; ++l) { hpad[l] = p; p += (rows + 8) * 64; }
+        for (int l = 0; !sru && l < 4; ++l) { hprev[l] = p; p += rows * 64; }
+        floats = (size_t)(p - p0);
+    }
+};
 
-size_t rtfs_dualpath_train_pack_floats(void) { return DT_END; }
-size_t rtfs_dualpath_grad_floats(void) { return DG_END; }
-size_t rtfs_dualpath_saved_floats(int B, int T, int F, int dim) {
-    DpGeom g(B, T, F, dim);
-    return DpSaved(nullptr, g.rows).floats;
+struct SruCell {
+    static constexpr bool kRows = true;  // dim 13 / 14: x, out, dout, dx as rows (B,T,F,64)
+    static constexpr int kDU = 256;      // floats a row of the backward's gate-gradient buffer
+    struct Layout {
+        size_t wcf = DT_WCF, wcb = DT_WCB, bt = DT_BT, end = DT_END, g_wct = DG_WCT, g_bt = DG_BT, g_end = DG_END;
+    };
+    struct Extra {
+        Extra(Arena&, size_t, bool) {}
+    };
+    static size_t extra_bytes(size_t) { return 0; }
+    static DpSaved saved(float* p, size_t rows) { return DpSaved(p, rows, true, true); }
+
+    static int forward(const Layout&, const float* tpack, const DpSaved& sv, const DpGeom& g, const Extra&, hipStream_t st) {
+        const float* sp = tpack + DT_SRU;
+        for (int l = 0; l < 4; ++l) {
+            const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
+            const int K = l == 0 ? 512 : 64, KC = l == 0 ? 256 : 192;
+            const float* Wt = l == 0 ? sp + TP_WT0 : sp + TP_WTL + (size_t)(l - 1) * 192 * 64;
+            CHECK(launch_gemm_nt(xin, 64, Wt, K, sv.U[l], KC, (int)g.rows, KC, K, 0, st));
+            SruScanArgs a;
+            a.U = sv.U[l]; a.xin = l == 0 ? nullptr : xin; a.wc = sp + TP_WC + 128 * l; a.bias = sp + TP_BIAS + 128 * l;
+            a.h = sv.hpad[l] + 7 * 64; a.c = sv.c[l]; a.L = g.L; a.N = g.nseq; a.KC = KC; a.ts = 1; a.ns = g.Ls; a.pad = 1;
+            CHECK(launch_sru_scan_fwd(a, st));
+        }
+        return RTFS_OK;
+    }
+
+    // gbuf[0] holds dL/dh of layer 3 on entry; dxn (zeroed) receives the gradient of the LayerNorm output
+    static int backward(const Layout&, const float* tpack, float* dparams, const DpSaved& sv, const DpGeom& g, float* dU, float* const* gbuf,
+                        float* dxn, const Extra&, hipStream_t st) {
+        const int M = (int)g.rows;
+        const float* gcur = gbuf[0];
+        const float* sp = tpack + DT_SRU;
+        float* gp = dparams + DG_SRU;
+        for (int l = 3; l >= 0; --l) {
+            const int K = l == 0 ? 512 : 64, KC = l == 0 ? 256 : 192;
+            const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
+            float* gnext = gcur == gbuf[0] ? gbuf[1] : gbuf[0];
+            SruScanArgs a;
+            a.U = sv.U[l]; a.xin = l == 0 ? nullptr : xin; a.wc = sp + TP_WC + 128 * l; a.bias = sp + TP_BIAS + 128 * l;
+            a.c = sv.c[l]; a.g = gcur; a.dU = dU; a.dxp = l == 0 ? nullptr : gnext; a.dwc = gp + GP_WC + 128 * l;
+            a.dbias = gp + GP_BIAS + 128 * l; a.L = g.L; a.N = g.nseq; a.KC = KC; a.ts = 1; a.ns = g.Ls; a.pad = 1;
+            CHECK(launch_sru_scan_bwd(a, st));
+            const float* Wp = l == 0 ? sp + TP_WP0 : sp + TP_WPL + (size_t)(l - 1) * 64 * 192;
+            float* dWp = l == 0 ? gp + GP_W0 : gp + GP_WL + (size_t)(l - 1) * 64 * 192;
+            if (l == 0) CHECK(launch_gemm_nt(dU, KC, Wp, KC, dxn, 64, M, 512, KC, 2, st));  // fold: adjoint of the unfold windows
+            else CHECK(launch_gemm_nt(dU, KC, Wp, KC, gnext, 64, M, 64, KC, 1, st));        // + the highway term the scan already wrote
+            CHECK(launch_gemm_tn(xin, 64, dU, KC, dWp, KC, K, KC, (long)M, st));
+            gcur = gnext;
+        }
+        return RTFS_OK;
+    }
+};
+
+// nn.LSTM / nn.GRU (512 -> 32, 4 layers, bidirectional) on the GEMM + scan kernels.  GW: gate columns of both directions (LSTM 256, GRU
+// 192); BHH: b_hh has a slot of its own (GRU: it sits inside the reset gate's product) instead of being summed into b_ih (LSTM).
+template <int GW, bool BHH>
+struct GatedCell {
+    static constexpr bool kRows = false;
+    static constexpr int kDU = BHH ? 2 * GW : GW;  // the GRU's scan writes two gate gradients a row: dU | dHR (recurrent side)
+    struct Layout {  // per-layer slots (Din = 512 for layer 0, 64 above)
+        size_t wih[4], wiht[4], bias[4], whh[4], bhh[4], wcf, wcb, bt, end;   // pack
+        size_t g_wih[4], g_bias[4], g_whh[4], g_bhh[4], g_wct, g_bt, g_end;   // gradients
+        Layout() {
+            size_t o = 128, go = 128;
+            for (int l = 0; l < 4; ++l) {
+                const size_t din = l == 0 ? 512 : 64;
+                wih[l] = o; o += GW * din;
+                wiht[l] = o; o += din * GW;
+                bias[l] = o; o += GW;
+                whh[l] = o; o += GW * 32;
+                bhh[l] = o; o += BHH ? GW : 0;
+                g_wih[l] = go; go += GW * din;
+                g_bias[l] = go; go += GW;
+                g_whh[l] = go; go += GW * 32;
+                g_bhh[l] = go; go += BHH ? GW : 0;
+            }
+            wcf = o; o += 64 * 512; wcb = o; o += 64 * 512; bt = o; o += 64; end = o;
+            g_wct = go; go += 512 * 64; g_bt = go; go += 64; g_end = go;
+        }
+    };
+    struct Extra {  // forward: the input projections of one layer; backward: the dense (GW, 64) product that holds the W_hh gradient
+        float *U = nullptr, *whh64 = nullptr;
+        Extra(Arena& ar, size_t rows, bool bwd) { (bwd ? whh64 : U) = ar.take<float>(bwd ? (size_t)GW * 64 : rows * GW); }
+    };
+    static size_t extra_bytes(size_t rows) { return (rows * kDU + GW * 64) * sizeof(float) + 4 * 256; }
+    static DpSaved saved(float* p, size_t rows) { return DpSaved(p, rows, false, !BHH); }
+
+    static int forward(const Layout& lo, const float* tpack, const DpSaved& sv, const DpGeom& g, const Extra& ex, hipStream_t st) {
+        for (int l = 0; l < 4; ++l) {
+            const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
+            const int K = l == 0 ? 512 : 64;
+            CHECK(launch_gemm_nt(xin, 64, tpack + lo.wih[l], K, ex.U, GW, (int)g.rows, GW, K, 0, st, tpack + lo.bias[l]));
+            if constexpr (BHH) {
+                GruScanArgs a;
+                a.U = ex.U; a.whh = tpack + lo.whh[l]; a.bhh = tpack + lo.bhh[l]; a.S = sv.U[l]; a.h = sv.hpad[l] + 7 * 64; a.hprev = sv.hprev[l];
+                a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
+                CHECK(launch_gru_scan(a, false, st));
+            } else {
+                LstmScanArgs a;
+                a.U = ex.U; a.whh = tpack + lo.whh[l]; a.G = sv.U[l]; a.c = sv.c[l]; a.h = sv.hpad[l] + 7 * 64; a.hprev = sv.hprev[l];
+                a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
+                CHECK(launch_lstm_scan(a, false, st));
+            }
+        }
+        return RTFS_OK;
+    }
+
+    static int backward(const Layout& lo, const float* tpack, float* dparams, const DpSaved& sv, const DpGeom& g, float* dU, float* const* gbuf,
+                        float* dxn, const Extra& ex, hipStream_t st) {
+        const int M = (int)g.rows;
+        float* dHR = BHH ? dU + g.rows * GW : dU;  // what multiplies h_{t-1}: the LSTM's gate gradient itself
+        const float* gcur = gbuf[0];
+        for (int l = 3; l >= 0; --l) {
+            const int K = l == 0 ? 512 : 64;
+            const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
+            float* gnext = gcur == gbuf[0] ? gbuf[1] : gbuf[0];
+            if constexpr (BHH) {
+                GruScanArgs a;
+                a.whh = tpack + lo.whh[l]; a.bhh = tpack + lo.bhh[l]; a.S = sv.U[l]; a.hprev = sv.hprev[l]; a.g = gcur; a.dU = dU; a.dHR = dHR;
+                a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
+                CHECK(launch_gru_scan(a, true, st));
+            } else {
+                LstmScanArgs a;
+                a.whh = tpack + lo.whh[l]; a.G = sv.U[l]; a.c = sv.c[l]; a.g = gcur; a.dU = dU;
+                a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
+                CHECK(launch_lstm_scan(a, true, st));
+            }
+            CHECK(launch_cl_colsum(dU, dparams + lo.g_bias[l], g.rows * GW, GW, st));
+            if (BHH) CHECK(launch_cl_colsum(dHR, dparams + lo.g_bhh[l], g.rows * GW, GW, st));
+            // recurrent weights: (dHR^T . h_{t-1}) is (GW, 64); its two (GW / 2, 32) diagonal blocks are the two directions
+            if (hipMemsetAsync(ex.whh64, 0, GW * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
+            CHECK(launch_gemm_tn(dHR, GW, sv.hprev[l], 64, ex.whh64, 64, GW, 64, (long)M, st));
+            for (int d = 0; d < 2; ++d)
+                if (hipMemcpy2DAsync(dparams + lo.g_whh[l] + (size_t)d * (GW / 2) * 32, 32 * sizeof(float),
+                                     ex.whh64 + (size_t)d * (GW / 2) * 64 + d * 32, 64 * sizeof(float), 32 * sizeof(float), GW / 2,
+                                     hipMemcpyDeviceToDevice, st) != hipSuccess)
+                    return RTFS_ERR_LAUNCH;
+            if (l == 0) CHECK(launch_gemm_nt(dU, GW, tpack + lo.wiht[l], GW, dxn, 64, M, 512, GW, 2, st));  // fold: adjoint of the unfold windows
+            else CHECK(launch_gemm_nt(dU, GW, tpack + lo.wiht[l], GW, gnext, 64, M, 64, GW, 0, st));
+            CHECK(launch_gemm_tn(dU, GW, xin, 64, dparams + lo.g_wih[l], K, GW, K, (long)M, st));
+            gcur = gnext;
+        }
+        return RTFS_OK;
+    }
+};
+using LstmCell = GatedCell<256, false>;
+using GruCell = GatedCell<192, true>;
+
+template <class Cell>
+size_t dp_saved_floats(int B, int T, int F, int dim) {
+    return Cell::saved(nullptr, DpGeom(B, T, F, dim).rows).floats;
 }
-size_t rtfs_dualpath_train_workspace_bytes(int B, int T, int F, int dim) {
+template <class Cell>
+size_t dp_workspace_bytes(int B, int T, int F, int dim) {
     DpGeom g(B, T, F, dim);
     // forward: xt, out_t, y; backward: xt, dout_t, dx_t, dy, dU, 2 x g, dxn  (the larger of the two, plus alignment slack)
     const size_t fwd = 2 * g.elems + g.rows * 64, bwd = 3 * g.elems + (g.rows + 8) * 64 * 2 + g.rows * (256 + 128);
-    return (fwd > bwd ? fwd : bwd) * sizeof(float) + 16 * 256;
+    return (fwd > bwd ? fwd : bwd) * sizeof(float) + 16 * 256 + Cell::extra_bytes(g.rows);
 }
 
-// dim 3 / 4: x, out (B,64,T,F) as in the reference; dim 13 / 14: the same sweeps on rows (B,T,F,64) (what the training kernels of a block
-// hand each other): the F-sweep's slots then ARE the rows, the T-sweep goes through a row permutation instead of two tiled transposes.
-int rtfs_dualpath_forward_train_f32(const float* x, const float* tpack, float* out, float* saved, int B, int T, int F, int dim, void* ws,
-                                    size_t ws_bytes, void* stream) {
+// dim 3 / 4: x, out (B,64,T,F) as in the reference; dim 13 / 14 (cells with kRows): the same sweeps on rows (B,T,F,64) (what the training
+// kernels of a block hand each other): the F-sweep's slots then ARE the rows, the T-sweep goes through a row permutation instead of two
+// tiled transposes.
+template <class Cell>
+int dp_forward_train(const float* x, const float* tpack, float* out, float* saved, int B, int T, int F, int dim, void* ws, size_t ws_bytes,
+                     void* stream) {
     const bool rows = dim >= 10;
     dim = rows ? dim - 10 : dim;
-    RTFS_RETURN_IF(!x || !tpack || !out || !saved || B < 1 || (dim != 3 && dim != 4), RTFS_ERR_ARG);
+    RTFS_RETURN_IF(!x || !tpack || !out || !saved || B < 1 || (dim != 3 && dim != 4) || (rows && !Cell::kRows), RTFS_ERR_ARG);
     DpGeom g(B, T, F, dim);
     RTFS_RETURN_IF(!g.ok(), RTFS_ERR_SHAPE);
-    RTFS_RETURN_IF(!ws || ws_bytes < rtfs_dualpath_train_workspace_bytes(B, T, F, dim), RTFS_ERR_WORKSPACE);
+    RTFS_RETURN_IF(!ws || ws_bytes < dp_workspace_bytes<Cell>(B, T, F, dim), RTFS_ERR_WORKSPACE);
     Arena ar(ws, ws_bytes);
     float* xt = ar.take<float>(g.elems);
     float* ot = ar.take<float>(g.elems);
     float* y = ar.take<float>(g.rows * 64);
-    DpSaved sv(saved, g.rows);
+    const typename Cell::Extra ex(ar, g.rows, false);
+    RTFS_RETURN_IF(!ar.ok(), RTFS_ERR_WORKSPACE);
+    const DpSaved sv = Cell::saved(saved, g.rows);
+    const typename Cell::Layout lo{};
     hipStream_t st = S(stream);
-    const int M = (int)g.rows;
     const float* src = x;
     if (dim == 3) {
         if (rows) CHECK(launch_rows_permute(x, xt, B, T, F, CH, st));
@@ -148,51 +305,48 @@ int rtfs_dualpath_forward_train_f32(const float* x, const float* tpack, float* o
     }
     // rows past the last slot are read by the last windows: keep them zero
     if (hipMemsetAsync(sv.xn + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    for (int l = 0; l < 4; ++l)
+    for (int l = 0; l < 4; ++l) {
         if (hipMemsetAsync(sv.hpad[l] + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
+        // the non-step rows of hprev feed a GEMM
+        if (sv.hprev[l] && hipMemsetAsync(sv.hprev[l], 0, g.rows * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
+    }
     if (rows) CHECK(launch_ln_rows(src, tpack + DT_G, tpack + DT_B, sv.xn, nullptr, nullptr, nullptr, nullptr, g.rows, CH, false, st));
     else CHECK(launch_dp_ln_fwd(src, tpack + DT_G, tpack + DT_B, sv.xn, g.nseq, g.R, g.Ls, st));
-    const float* sp = tpack + DT_SRU;
-    for (int l = 0; l < 4; ++l) {
-        const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
-        const int K = l == 0 ? 512 : 64, KC = l == 0 ? 256 : 192;
-        const float* Wt = l == 0 ? sp + TP_WT0 : sp + TP_WTL + (size_t)(l - 1) * 192 * 64;
-        CHECK(launch_gemm_nt(xin, 64, Wt, K, sv.U[l], KC, M, KC, K, 0, st));
-        SruScanArgs a;
-        a.U = sv.U[l]; a.xin = l == 0 ? nullptr : xin; a.wc = sp + TP_WC + 128 * l; a.bias = sp + TP_BIAS + 128 * l;
-        a.h = sv.hpad[l] + 7 * 64; a.c = sv.c[l]; a.L = g.L; a.N = g.nseq; a.KC = KC; a.ts = 1; a.ns = g.Ls; a.pad = 1;
-        CHECK(launch_sru_scan_fwd(a, st));
-    }
+    CHECK(Cell::forward(lo, tpack, sv, g, ex, st));
     // ConvTranspose1d as a GEMM over the 8-row windows of the zero-padded hidden sequence (rnn_layers.py:129,153)
-    CHECK(launch_gemm_nt(sv.hpad[3], 64, tpack + DT_WCF, 512, y, 64, M, 64, 512, 0, st));
+    CHECK(launch_gemm_nt(sv.hpad[3], 64, tpack + lo.wcf, 512, y, 64, (int)g.rows, 64, 512, 0, st));
     if (rows) {
-        CHECK(launch_rows_bias_res(y, tpack + DT_BT, src, dim == 4 ? out : ot, g.rows * 64, CH, st));
+        CHECK(launch_rows_bias_res(y, tpack + lo.bt, src, dim == 4 ? out : ot, g.rows * 64, CH, st));
         if (dim == 3) CHECK(launch_rows_permute(ot, out, B, F, T, CH, st));
         return RTFS_OK;
     }
-    CHECK(launch_dp_out(y, tpack + DT_BT, src, dim == 4 ? out : ot, g.nseq, g.R, g.Ls, st));
+    CHECK(launch_dp_out(y, tpack + lo.bt, src, dim == 4 ? out : ot, g.nseq, g.R, g.Ls, st));
     if (dim == 3) CHECK(launch_transpose(ot, out, B * CH, F, T, st));
     return RTFS_OK;
 }
 
-int rtfs_dualpath_backward_f32(const float* x, const float* tpack, const float* saved, const float* dout, float* dx, float* dparams, int B,
-                               int T, int F, int dim, void* ws, size_t ws_bytes, void* stream) {
+template <class Cell>
+int dp_backward(const float* x, const float* tpack, const float* saved, const float* dout, float* dx, float* dparams, int B, int T, int F,
+                int dim, void* ws, size_t ws_bytes, void* stream) {
     const bool rows = dim >= 10;
     dim = rows ? dim - 10 : dim;
-    RTFS_RETURN_IF(!x || !tpack || !saved || !dout || !dx || !dparams || B < 1 || (dim != 3 && dim != 4), RTFS_ERR_ARG);
+    RTFS_RETURN_IF(!x || !tpack || !saved || !dout || !dx || !dparams || B < 1 || (dim != 3 && dim != 4) || (rows && !Cell::kRows),
+                   RTFS_ERR_ARG);
     DpGeom g(B, T, F, dim);
     RTFS_RETURN_IF(!g.ok_backward(), RTFS_ERR_SHAPE);
-    RTFS_RETURN_IF(!ws || ws_bytes < rtfs_dualpath_train_workspace_bytes(B, T, F, dim), RTFS_ERR_WORKSPACE);
+    RTFS_RETURN_IF(!ws || ws_bytes < dp_workspace_bytes<Cell>(B, T, F, dim), RTFS_ERR_WORKSPACE);
     Arena ar(ws, ws_bytes);
     float* xt = ar.take<float>(g.elems);
     float* dt = ar.take<float>(g.elems);
     float* dxt = ar.take<float>(g.elems);
     float* dy = ar.take<float>((g.rows + 8) * 64);
     float* dxn = ar.take<float>((g.rows + 8) * 64);
-    float* dU = ar.take<float>(g.rows * 256);
+    float* dU = ar.take<float>(g.rows * Cell::kDU);
     float* gbuf[2] = {ar.take<float>(g.rows * 64), ar.take<float>(g.rows * 64)};
+    const typename Cell::Extra ex(ar, g.rows, true);
     RTFS_RETURN_IF(!ar.ok(), RTFS_ERR_WORKSPACE);
-    DpSaved sv(const_cast<float*>(saved), g.rows);
+    const DpSaved sv = Cell::saved(const_cast<float*>(saved), g.rows);
+    const typename Cell::Layout lo{};
     hipStream_t st = S(stream);
     const int M = (int)g.rows;
     const float *srcx = x, *srcd = dout;
@@ -207,37 +361,19 @@ int rtfs_dualpath_backward_f32(const float* x, const float* tpack, const float* 
         srcx = xt;
         srcd = dt;
     }
-    if (hipMemsetAsync(dparams, 0, DG_END * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
+    if (hipMemsetAsync(dparams, 0, lo.g_end * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
     if (hipMemsetAsync(dy + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
     if (hipMemsetAsync(dxn, 0, (g.rows + 8) * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
     if (rows) {  // the gradient already is rows: copy it next to its zero tail (the windows read 7 rows past the end), bias gradient = column sums
         if (hipMemcpyAsync(dy, srcd, g.rows * 64 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return RTFS_ERR_LAUNCH;
-        CHECK(launch_cl_colsum(srcd, dparams + DG_BT, g.rows * 64, 64, st));
+        CHECK(launch_cl_colsum(srcd, dparams + lo.g_bt, g.rows * 64, 64, st));
     } else {
-        CHECK(launch_dp_dy(srcd, dy, dparams + DG_BT, g.nseq, g.R, g.Ls, st));
+        CHECK(launch_dp_dy(srcd, dy, dparams + lo.g_bt, g.nseq, g.R, g.Ls, st));
     }
     // ConvTranspose1d: weight gradient = (windows of h)^T . dy, input gradient = windows of dy . W
-    CHECK(launch_gemm_tn(sv.hpad[3], 64, dy, 64, dparams + DG_WCT, 64, 512, 64, (long)M, st));
-    CHECK(launch_gemm_nt(dy, 64, tpack + DT_WCB, 512, gbuf[0], 64, M, 64, 512, 0, st));
-    const float* gcur = gbuf[0];
-    const float* sp = tpack + DT_SRU;
-    float* gp = dparams + DG_SRU;
-    for (int l = 3; l >= 0; --l) {
-        const int K = l == 0 ? 512 : 64, KC = l == 0 ? 256 : 192;
-        const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
-        float* gnext = gcur == gbuf[0] ? gbuf[1] : gbuf[0];
-        SruScanArgs a;
-        a.U = sv.U[l]; a.xin = l == 0 ? nullptr : xin; a.wc = sp + TP_WC + 128 * l; a.bias = sp + TP_BIAS + 128 * l;
-        a.c = sv.c[l]; a.g = gcur; a.dU = dU; a.dxp = l == 0 ? nullptr : gnext; a.dwc = gp + GP_WC + 128 * l;
-        a.dbias = gp + GP_BIAS + 128 * l; a.L = g.L; a.N = g.nseq; a.KC = KC; a.ts = 1; a.ns = g.Ls; a.pad = 1;
-        CHECK(launch_sru_scan_bwd(a, st));
-        const float* Wp = l == 0 ? sp + TP_WP0 : sp + TP_WPL + (size_t)(l - 1) * 64 * 192;
-        float* dWp = l == 0 ? gp + GP_W0 : gp + GP_WL + (size_t)(l - 1) * 64 * 192;
-        if (l == 0) CHECK(launch_gemm_nt(dU, KC, Wp, KC, dxn, 64, M, 512, KC, 2, st));  // fold: adjoint of the unfold windows
-        else CHECK(launch_gemm_nt(dU, KC, Wp, KC, gnext, 64, M, 64, KC, 1, st));
-        CHECK(launch_gemm_tn(xin, 64, dU, KC, dWp, KC, K, KC, (long)M, st));
-        gcur = gnext;
-    }
+    CHECK(launch_gemm_tn(sv.hpad[3], 64, dy, 64, dparams + lo.g_wct, 64, 512, 64, (long)M, st));
+    CHECK(launch_gemm_nt(dy, 64, tpack + lo.wcb, 512, gbuf[0], 64, M, 64, 512, 0, st));
+    CHECK(Cell::backward(lo, tpack, dparams, sv, g, dU, gbuf, dxn, ex, st));
     if (rows) {
         CHECK(launch_ln_rows(srcx, tpack + DT_G, nullptr, nullptr, dxn, dim == 4 ? dx : dxt, dparams + DG_G, dparams + DG_B, g.rows, CH, true, st, srcd));
         if (dim == 3) CHECK(launch_rows_permute(dxt, dx, B, F, T, CH, st));
@@ -247,313 +383,44 @@ int rtfs_dualpath_backward_f32(const float* x, const float* tpack, const float* 
     if (dim == 3) CHECK(launch_transpose(dxt, dx, B * CH, F, T, st));
     return RTFS_OK;
 }
-
-// ------------------------------------------------------------ DualPathRNN with the LSTM cell, training side
-namespace {
-// per-layer slots of the LSTM training pack / gradient buffer (Din = 512 for layer 0, 64 above)
-struct LstmLayout {
-    size_t wih[4], wiht[4], bias[4], whh[4], wcf, wcb, bt, end;   // pack
-    size_t g_wih[4], g_bias[4], g_whh[4], g_wct, g_bt, g_end;     // gradients
-    LstmLayout() {
-        size_t o = 128;
-        for (int l = 0; l < 4; ++l) {
-            const size_t din = l == 0 ? 512 : 64;
-            wih[l] = o; o += 256 * din;
-            wiht[l] = o; o += din * 256;
-            bias[l] = o; o += 256;
-            whh[l] = o; o += 2 * 128 * 32;
-        }
-        wcf = o; o += 64 * 512; wcb = o; o += 64 * 512; bt = o; o += 64; end = o;
-        o = 128;
-        for (int l = 0; l < 4; ++l) {
-            const size_t din = l == 0 ? 512 : 64;
-            g_wih[l] = o; o += 256 * din;
-            g_bias[l] = o; o += 256;
-            g_whh[l] = o; o += 2 * 128 * 32;
-        }
-        g_wct = o; o += 512 * 64; g_bt = o; o += 64; g_end = o;
-    }
-};
-struct LstmSaved {
-    float *xn, *G[4], *c[4], *hpad[4], *hprev[4];
-    size_t floats;
-    LstmSaved(float* p, size_t rows) {
-        float* p0 = p;
-        xn = p; p += (rows + 8) * 64;
-        for (int l = 0; l < 4; ++l) { G[l] = p; p += rows * 256; }
-        for (int l = 0; l < 4; ++l) { c[l] = p; p += rows * 64; }
-        for (int l = 0; l < 4; ++l) { hpad[l] = p; p += (rows + 8) * 64; }
-        for (int l = 0; l < 4; ++l) { hprev[l] = p; p += rows * 64; }
-        floats = (size_t)(p - p0);
-    }
-};
 }  // namespace
 
-size_t rtfs_dualpath_lstm_train_pack_floats(void) { return LstmLayout().end; }
-size_t rtfs_dualpath_lstm_grad_floats(void) { return LstmLayout().g_end; }
-size_t rtfs_dualpath_lstm_saved_floats(int B, int T, int F, int dim) {
-    DpGeom g(B, T, F, dim);
-    return LstmSaved(nullptr, g.rows).floats;
+// the exported symbols (include/rtfs_amd.h): six per cell
+size_t rtfs_dualpath_train_pack_floats(void) { return SruCell::Layout().end; }
+size_t rtfs_dualpath_grad_floats(void) { return SruCell::Layout().g_end; }
+size_t rtfs_dualpath_saved_floats(int B, int T, int F, int dim) { return dp_saved_floats<SruCell>(B, T, F, dim); }
+size_t rtfs_dualpath_train_workspace_bytes(int B, int T, int F, int dim) { return dp_workspace_bytes<SruCell>(B, T, F, dim); }
+int rtfs_dualpath_forward_train_f32(const float* x, const float* tpack, float* out, float* saved, int B, int T, int F, int dim,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    return dp_forward_train<SruCell>(x, tpack, out, saved, B, T, F, dim, ws, ws_bytes, stream);
 }
-size_t rtfs_dualpath_lstm_train_workspace_bytes(int B, int T, int F, int dim) {
-    DpGeom g(B, T, F, dim);
-    return rtfs_dualpath_train_workspace_bytes(B, T, F, dim) + (g.rows * 256 + 256 * 64) * sizeof(float) + 4 * 256;
+int rtfs_dualpath_backward_f32(const float* x, const float* tpack, const float* saved, const float* dout, float* dx, float* dparams,
+                               int B, int T, int F, int dim, void* ws, size_t ws_bytes, void* stream) {
+    return dp_backward<SruCell>(x, tpack, saved, dout, dx, dparams, B, T, F, dim, ws, ws_bytes, stream);
 }
-
-int rtfs_dualpath_lstm_forward_train_f32(const float* x, const float* tpack, float* out, float* saved, int B, int T, int F, int dim, void* ws,
-                                         size_t ws_bytes, void* stream) {
-    RTFS_RETURN_IF(!x || !tpack || !out || !saved || B < 1 || (dim != 3 && dim != 4), RTFS_ERR_ARG);
-    DpGeom g(B, T, F, dim);
-    RTFS_RETURN_IF(!g.ok(), RTFS_ERR_SHAPE);
-    RTFS_RETURN_IF(!ws || ws_bytes < rtfs_dualpath_lstm_train_workspace_bytes(B, T, F, dim), RTFS_ERR_WORKSPACE);
-    Arena ar(ws, ws_bytes);
-    float* xt = ar.take<float>(g.elems);
-    float* ot = ar.take<float>(g.elems);
-    float* y = ar.take<float>(g.rows * 64);
-    float* U = ar.take<float>(g.rows * 256);
-    RTFS_RETURN_IF(!ar.ok(), RTFS_ERR_WORKSPACE);
-    LstmSaved sv(saved, g.rows);
-    LstmLayout lo;
-    hipStream_t st = S(stream);
-    const int M = (int)g.rows;
-    const float* src = x;
-    if (dim == 3) {
-        CHECK(launch_transpose(x, xt, B * CH, T, F, st));
-        src = xt;
-    }
-    if (hipMemsetAsync(sv.xn + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    for (int l = 0; l < 4; ++l) {
-        if (hipMemsetAsync(sv.hpad[l] + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-        if (hipMemsetAsync(sv.hprev[l], 0, g.rows * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;  // non-step rows feed a GEMM
-    }
-    CHECK(launch_dp_ln_fwd(src, tpack + DT_G, tpack + DT_B, sv.xn, g.nseq, g.R, g.Ls, st));
-    for (int l = 0; l < 4; ++l) {
-        const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
-        const int K = l == 0 ? 512 : 64;
-        CHECK(launch_gemm_nt(xin, 64, tpack + lo.wih[l], K, U, 256, M, 256, K, 0, st, tpack + lo.bias[l]));
-        LstmScanArgs a;
-        a.U = U; a.whh = tpack + lo.whh[l]; a.G = sv.G[l]; a.c = sv.c[l]; a.h = sv.hpad[l] + 7 * 64; a.hprev = sv.hprev[l];
-        a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
-        CHECK(launch_lstm_scan(a, false, st));
-    }
-    CHECK(launch_gemm_nt(sv.hpad[3], 64, tpack + lo.wcf, 512, y, 64, M, 64, 512, 0, st));
-    CHECK(launch_dp_out(y, tpack + lo.bt, src, dim == 4 ? out : ot, g.nseq, g.R, g.Ls, st));
-    if (dim == 3) CHECK(launch_transpose(ot, out, B * CH, F, T, st));
-    return RTFS_OK;
+size_t rtfs_dualpath_lstm_train_pack_floats(void) { return LstmCell::Layout().end; }
+size_t rtfs_dualpath_lstm_grad_floats(void) { return LstmCell::Layout().g_end; }
+size_t rtfs_dualpath_lstm_saved_floats(int B, int T, int F, int dim) { return dp_saved_floats<LstmCell>(B, T, F, dim); }
+size_t rtfs_dualpath_lstm_train_workspace_bytes(int B, int T, int F, int dim) { return dp_workspace_bytes<LstmCell>(B, T, F, dim); }
+int rtfs_dualpath_lstm_forward_train_f32(const float* x, const float* tpack, float* out, float* saved, int B, int T, int F, int dim,
+                                         void* ws, size_t ws_bytes, void* stream) {
+    return dp_forward_train<LstmCell>(x, tpack, out, saved, B, T, F, dim, ws, ws_bytes, stream);
 }
-
 int rtfs_dualpath_lstm_backward_f32(const float* x, const float* tpack, const float* saved, const float* dout, float* dx, float* dparams,
                                     int B, int T, int F, int dim, void* ws, size_t ws_bytes, void* stream) {
-    RTFS_RETURN_IF(!x || !tpack || !saved || !dout || !dx || !dparams || B < 1 || (dim != 3 && dim != 4), RTFS_ERR_ARG);
-    DpGeom g(B, T, F, dim);
-    RTFS_RETURN_IF(!g.ok_backward(), RTFS_ERR_SHAPE);
-    RTFS_RETURN_IF(!ws || ws_bytes < rtfs_dualpath_lstm_train_workspace_bytes(B, T, F, dim), RTFS_ERR_WORKSPACE);
-    Arena ar(ws, ws_bytes);
-    float* xt = ar.take<float>(g.elems);
-    float* dt = ar.take<float>(g.elems);
-    float* dxt = ar.take<float>(g.elems);
-    float* dy = ar.take<float>((g.rows + 8) * 64);
-    float* dxn = ar.take<float>((g.rows + 8) * 64);
-    float* dU = ar.take<float>(g.rows * 256);
-    float* gbuf[2] = {ar.take<float>(g.rows * 64), ar.take<float>(g.rows * 64)};
-    float* whh64 = ar.take<float>(256 * 64);
-    RTFS_RETURN_IF(!ar.ok(), RTFS_ERR_WORKSPACE);
-    LstmSaved sv(const_cast<float*>(saved), g.rows);
-    LstmLayout lo;
-    hipStream_t st = S(stream);
-    const int M = (int)g.rows;
-    const float *srcx = x, *srcd = dout;
-    if (dim == 3) {
-        CHECK(launch_transpose(x, xt, B * CH, T, F, st));
-        CHECK(launch_transpose(dout, dt, B * CH, T, F, st));
-        srcx = xt;
-        srcd = dt;
-    }
-    if (hipMemsetAsync(dparams, 0, lo.g_end * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    if (hipMemsetAsync(dy + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    if (hipMemsetAsync(dxn, 0, (g.rows + 8) * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    CHECK(launch_dp_dy(srcd, dy, dparams + lo.g_bt, g.nseq, g.R, g.Ls, st));
-    CHECK(launch_gemm_tn(sv.hpad[3], 64, dy, 64, dparams + lo.g_wct, 64, 512, 64, (long)M, st));
-    CHECK(launch_gemm_nt(dy, 64, tpack + lo.wcb, 512, gbuf[0], 64, M, 64, 512, 0, st));
-    const float* gcur = gbuf[0];
-    for (int l = 3; l >= 0; --l) {
-        const int K = l == 0 ? 512 : 64;
-        const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
-        float* gnext = gcur == gbuf[0] ? gbuf[1] : gbuf[0];
-        LstmScanArgs a;
-        a.whh = tpack + lo.whh[l]; a.G = sv.G[l]; a.c = sv.c[l]; a.g = gcur; a.dU = dU; a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
-        CHECK(launch_lstm_scan(a, true, st));
-        CHECK(launch_cl_colsum(dU, dparams + lo.g_bias[l], g.rows * 256, 256, st));
-        // recurrent weights: (dU^T . h_{t-1}) is (256, 64); the two (128, 32) diagonal blocks are the two directions
-        if (hipMemsetAsync(whh64, 0, 256 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-        CHECK(launch_gemm_tn(dU, 256, sv.hprev[l], 64, whh64, 64, 256, 64, (long)M, st));
-        for (int d = 0; d < 2; ++d)
-            if (hipMemcpy2DAsync(dparams + lo.g_whh[l] + (size_t)d * 128 * 32, 32 * sizeof(float), whh64 + (size_t)d * 128 * 64 + d * 32,
-                                 64 * sizeof(float), 32 * sizeof(float), 128, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return RTFS_ERR_LAUNCH;
-        if (l == 0) CHECK(launch_gemm_nt(dU, 256, tpack + lo.wiht[l], 256, dxn, 64, M, 512, 256, 2, st));
-        else CHECK(launch_gemm_nt(dU, 256, tpack + lo.wiht[l], 256, gnext, 64, M, 64, 256, 0, st));
-        CHECK(launch_gemm_tn(dU, 256, xin, 64, dparams + lo.g_wih[l], K, 256, K, (long)M, st));
-        gcur = gnext;
-    }
-    CHECK(launch_dp_ln_bwd(srcx, dxn, srcd, tpack + DT_G, dim == 4 ? dx : dxt, dparams + DG_G, dparams + DG_B, g.nseq, g.R, g.Ls, st));
-    if (dim == 3) CHECK(launch_transpose(dxt, dx, B * CH, F, T, st));
-    return RTFS_OK;
+    return dp_backward<LstmCell>(x, tpack, saved, dout, dx, dparams, B, T, F, dim, ws, ws_bytes, stream);
 }
-
-// ------------------------------------------------------------ DualPathRNN with the GRU cell (forward with saved state + backward)
-namespace {
-struct GruLayout {
-    size_t wih[4], wiht[4], bih[4], whh[4], bhh[4], wcf, wcb, bt, end;   // pack
-    size_t g_wih[4], g_bih[4], g_whh[4], g_bhh[4], g_wct, g_bt, g_end;   // gradients
-    GruLayout() {
-        size_t o = 128;
-        for (int l = 0; l < 4; ++l) {
-            const size_t din = l == 0 ? 512 : 64;
-            wih[l] = o; o += 192 * din;
-            wiht[l] = o; o += din * 192;
-            bih[l] = o; o += 192;
-            whh[l] = o; o += 2 * 96 * 32;
-            bhh[l] = o; o += 192;
-        }
-        wcf = o; o += 64 * 512; wcb = o; o += 64 * 512; bt = o; o += 64; end = o;
-        o = 128;
-        for (int l = 0; l < 4; ++l) {
-            const size_t din = l == 0 ? 512 : 64;
-            g_wih[l] = o; o += 192 * din;
-            g_bih[l] = o; o += 192;
-            g_whh[l] = o; o += 2 * 96 * 32;
-            g_bhh[l] = o; o += 192;
-        }
-        g_wct = o; o += 512 * 64; g_bt = o; o += 64; g_end = o;
-    }
-};
-struct GruSaved {
-    float *xn, *Sg[4], *hpad[4], *hprev[4];
-    size_t floats;
-    GruSaved(float* p, size_t rows) {
-        float* p0 = p;
-        xn = p; p += (rows + 8) * 64;
-        for (int l = 0; l < 4; ++l) { Sg[l] = p; p += rows * 256; }
-        for (int l = 0; l < 4; ++l) { hpad[l] = p; p += (rows + 8) * 64; }
-        for (int l = 0; l < 4; ++l) { hprev[l] = p; p += rows * 64; }
-        floats = (size_t)(p - p0);
-    }
-};
-}  // namespace
-
-size_t rtfs_dualpath_gru_train_pack_floats(void) { return GruLayout().end; }
-size_t rtfs_dualpath_gru_grad_floats(void) { return GruLayout().g_end; }
-size_t rtfs_dualpath_gru_saved_floats(int B, int T, int F, int dim) {
-    DpGeom g(B, T, F, dim);
-    return GruSaved(nullptr, g.rows).floats;
+size_t rtfs_dualpath_gru_train_pack_floats(void) { return GruCell::Layout().end; }
+size_t rtfs_dualpath_gru_grad_floats(void) { return GruCell::Layout().g_end; }
+size_t rtfs_dualpath_gru_saved_floats(int B, int T, int F, int dim) { return dp_saved_floats<GruCell>(B, T, F, dim); }
+size_t rtfs_dualpath_gru_train_workspace_bytes(int B, int T, int F, int dim) { return dp_workspace_bytes<GruCell>(B, T, F, dim); }
+int rtfs_dualpath_gru_forward_train_f32(const float* x, const float* tpack, float* out, float* saved, int B, int T, int F, int dim,
+                                        void* ws, size_t ws_bytes, void* stream) {
+    return dp_forward_train<GruCell>(x, tpack, out, saved, B, T, F, dim, ws, ws_bytes, stream);
 }
-size_t rtfs_dualpath_gru_train_workspace_bytes(int B, int T, int F, int dim) {
-    DpGeom g(B, T, F, dim);
-    return rtfs_dualpath_train_workspace_bytes(B, T, F, dim) + (g.rows * 2 * 192 + 192 * 64) * sizeof(float) + 4 * 256;
-}
-
-int rtfs_dualpath_gru_forward_train_f32(const float* x, const float* tpack, float* out, float* saved, int B, int T, int F, int dim, void* ws,
-                                        size_t ws_bytes, void* stream) {
-    RTFS_RETURN_IF(!x || !tpack || !out || !saved || B < 1 || (dim != 3 && dim != 4), RTFS_ERR_ARG);
-    DpGeom g(B, T, F, dim);
-    RTFS_RETURN_IF(!g.ok(), RTFS_ERR_SHAPE);
-    RTFS_RETURN_IF(!ws || ws_bytes < rtfs_dualpath_gru_train_workspace_bytes(B, T, F, dim), RTFS_ERR_WORKSPACE);
-    Arena ar(ws, ws_bytes);
-    float* xt = ar.take<float>(g.elems);
-    float* ot = ar.take<float>(g.elems);
-    float* y = ar.take<float>(g.rows * 64);
-    float* U = ar.take<float>(g.rows * 192);
-    RTFS_RETURN_IF(!ar.ok(), RTFS_ERR_WORKSPACE);
-    GruSaved sv(saved, g.rows);
-    GruLayout lo;
-    hipStream_t st = S(stream);
-    const int M = (int)g.rows;
-    const float* src = x;
-    if (dim == 3) {
-        CHECK(launch_transpose(x, xt, B * CH, T, F, st));
-        src = xt;
-    }
-    if (hipMemsetAsync(sv.xn + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    for (int l = 0; l < 4; ++l) {
-        if (hipMemsetAsync(sv.hpad[l] + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-        if (hipMemsetAsync(sv.hprev[l], 0, g.rows * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    }
-    CHECK(launch_dp_ln_fwd(src, tpack + DT_G, tpack + DT_B, sv.xn, g.nseq, g.R, g.Ls, st));
-    for (int l = 0; l < 4; ++l) {
-        const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
-        const int K = l == 0 ? 512 : 64;
-        CHECK(launch_gemm_nt(xin, 64, tpack + lo.wih[l], K, U, 192, M, 192, K, 0, st, tpack + lo.bih[l]));
-        GruScanArgs a;
-        a.U = U; a.whh = tpack + lo.whh[l]; a.bhh = tpack + lo.bhh[l]; a.S = sv.Sg[l]; a.h = sv.hpad[l] + 7 * 64; a.hprev = sv.hprev[l];
-        a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
-        CHECK(launch_gru_scan(a, false, st));
-    }
-    CHECK(launch_gemm_nt(sv.hpad[3], 64, tpack + lo.wcf, 512, y, 64, M, 64, 512, 0, st));
-    CHECK(launch_dp_out(y, tpack + lo.bt, src, dim == 4 ? out : ot, g.nseq, g.R, g.Ls, st));
-    if (dim == 3) CHECK(launch_transpose(ot, out, B * CH, F, T, st));
-    return RTFS_OK;
-}
-
 int rtfs_dualpath_gru_backward_f32(const float* x, const float* tpack, const float* saved, const float* dout, float* dx, float* dparams,
                                    int B, int T, int F, int dim, void* ws, size_t ws_bytes, void* stream) {
-    RTFS_RETURN_IF(!x || !tpack || !saved || !dout || !dx || !dparams || B < 1 || (dim != 3 && dim != 4), RTFS_ERR_ARG);
-    DpGeom g(B, T, F, dim);
-    RTFS_RETURN_IF(!g.ok_backward(), RTFS_ERR_SHAPE);
-    RTFS_RETURN_IF(!ws || ws_bytes < rtfs_dualpath_gru_train_workspace_bytes(B, T, F, dim), RTFS_ERR_WORKSPACE);
-    Arena ar(ws, ws_bytes);
-    float* xt = ar.take<float>(g.elems);
-    float* dt = ar.take<float>(g.elems);
-    float* dxt = ar.take<float>(g.elems);
-    float* dy = ar.take<float>((g.rows + 8) * 64);
-    float* dxn = ar.take<float>((g.rows + 8) * 64);
-    float* dU = ar.take<float>(g.rows * 192);
-    float* dHR = ar.take<float>(g.rows * 192);
-    float* gbuf[2] = {ar.take<float>(g.rows * 64), ar.take<float>(g.rows * 64)};
-    float* whh64 = ar.take<float>(192 * 64);
-    RTFS_RETURN_IF(!ar.ok(), RTFS_ERR_WORKSPACE);
-    GruSaved sv(const_cast<float*>(saved), g.rows);
-    GruLayout lo;
-    hipStream_t st = S(stream);
-    const int M = (int)g.rows;
-    const float *srcx = x, *srcd = dout;
-    if (dim == 3) {
-        CHECK(launch_transpose(x, xt, B * CH, T, F, st));
-        CHECK(launch_transpose(dout, dt, B * CH, T, F, st));
-        srcx = xt;
-        srcd = dt;
-    }
-    if (hipMemsetAsync(dparams, 0, lo.g_end * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    if (hipMemsetAsync(dy + g.rows * 64, 0, 8 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    if (hipMemsetAsync(dxn, 0, (g.rows + 8) * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-    CHECK(launch_dp_dy(srcd, dy, dparams + lo.g_bt, g.nseq, g.R, g.Ls, st));
-    CHECK(launch_gemm_tn(sv.hpad[3], 64, dy, 64, dparams + lo.g_wct, 64, 512, 64, (long)M, st));
-    CHECK(launch_gemm_nt(dy, 64, tpack + lo.wcb, 512, gbuf[0], 64, M, 64, 512, 0, st));
-    const float* gcur = gbuf[0];
-    for (int l = 3; l >= 0; --l) {
-        const int K = l == 0 ? 512 : 64;
-        const float* xin = l == 0 ? sv.xn : sv.hpad[l - 1] + 7 * 64;
-        float* gnext = gcur == gbuf[0] ? gbuf[1] : gbuf[0];
-        GruScanArgs a;
-        a.whh = tpack + lo.whh[l]; a.bhh = tpack + lo.bhh[l]; a.S = sv.Sg[l]; a.hprev = sv.hprev[l]; a.g = gcur; a.dU = dU; a.dHR = dHR;
-        a.L = g.L; a.N = g.nseq; a.ts = 1; a.ns = g.Ls; a.pad = 1;
-        CHECK(launch_gru_scan(a, true, st));
-        CHECK(launch_cl_colsum(dU, dparams + lo.g_bih[l], g.rows * 192, 192, st));
-        CHECK(launch_cl_colsum(dHR, dparams + lo.g_bhh[l], g.rows * 192, 192, st));
-        if (hipMemsetAsync(whh64, 0, 192 * 64 * sizeof(float), st) != hipSuccess) return RTFS_ERR_LAUNCH;
-        CHECK(launch_gemm_tn(dHR, 192, sv.hprev[l], 64, whh64, 64, 192, 64, (long)M, st));
-        for (int d = 0; d < 2; ++d)
-            if (hipMemcpy2DAsync(dparams + lo.g_whh[l] + (size_t)d * 96 * 32, 32 * sizeof(float), whh64 + (size_t)d * 96 * 64 + d * 32,
-                                 64 * sizeof(float), 32 * sizeof(float), 96, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return RTFS_ERR_LAUNCH;
-        if (l == 0) CHECK(launch_gemm_nt(dU, 192, tpack + lo.wiht[l], 192, dxn, 64, M, 512, 192, 2, st));
-        else CHECK(launch_gemm_nt(dU, 192, tpack + lo.wiht[l], 192, gnext, 64, M, 64, 192, 0, st));
-        CHECK(launch_gemm_tn(dU, 192, xin, 64, dparams + lo.g_wih[l], K, 192, K, (long)M, st));
-        gcur = gnext;
-    }
-    CHECK(launch_dp_ln_bwd(srcx, dxn, srcd, tpack + DT_G, dim == 4 ? dx : dxt, dparams + DG_G, dparams + DG_B, g.nseq, g.R, g.Ls, st));
-    if (dim == 3) CHECK(launch_transpose(dxt, dx, B * CH, F, T, st));
-    return RTFS_OK;
+    return dp_backward<GruCell>(x, tpack, saved, dout, dx, dparams, B, T, F, dim, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------ ConvNormAct, training side (channel-last rows inside)

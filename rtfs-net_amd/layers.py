@@ -665,29 +665,61 @@ class SRU(PackedModule):
 
 
 # ----------------------------------------------------------------------------- dual-path RNN
+def _sru_cell_grads(flat):
+    dg, db, dws, dwcs, dbs, dlw, dlb = packing.unpack_dualpath_grads(flat)
+    return [dg, db] + [t for i in range(4) for t in (dws[i], dwcs[i], dbs[i])] + [dlw, dlb]
+
+
+def _gated_cell_grads(unpack):
+    def grads(flat):
+        dg, db, dl, dlw, dlb = unpack(flat)
+        return [dg, db] + [dl[n] for n in packing.lstm_param_names()] + [dlw, dlb]
+    return grads
+
+
+# cell kind -> (C symbol infix, pack(gamma, beta, cell parameters, lin_w, lin_b), gradient buffer -> gradients in input order, rows layout?)
+_DP_CELLS = {
+    "sru": ("", lambda g, b, c, lw, lb: packing.pack_dualpath_train(g, b, c[0::3], c[1::3], c[2::3], lw, lb), _sru_cell_grads, True),
+    "lstm": ("lstm_", lambda g, b, c, lw, lb: packing.pack_dualpath_lstm_train(g, b, dict(zip(packing.lstm_param_names(), c)), lw, lb),
+             _gated_cell_grads(packing.unpack_dualpath_lstm_grads), False),
+    "gru": ("gru_", lambda g, b, c, lw, lb: packing.pack_dualpath_gru_train(g, b, dict(zip(packing.lstm_param_names(), c)), lw, lb),
+            _gated_cell_grads(packing.unpack_dualpath_gru_grads), False),
+}
+
+
+def _dualpath_unpack(kind, shapes):
+    def unpack(flat):
+        out = _DP_CELLS[kind][2](flat)
+        return [out[0].reshape(shapes[0]), out[1].reshape(shapes[1])] + out[2:]
+    return unpack
+
+
 class _DualPathTrainFn(torch.autograd.Function):
-    """DualPathRNN (SRU cell) forward/backward on the training kernels.  Inputs: x, dim, gamma, beta, (weight, weight_c, bias) x 4,
-    ConvTranspose1d weight, bias."""
+    """DualPathRNN forward/backward on the training kernels.  Inputs: x, dim, cell kind ("sru", "lstm", "gru"), gamma, beta, the cell's
+    parameters ((weight, weight_c, bias) x 4, or the 32 nn.LSTM / nn.GRU parameters in packing.lstm_param_names() order), ConvTranspose1d
+    weight, bias."""
 
     @staticmethod
-    def forward(ctx, x, dim, gamma, beta, *rest):
+    def forward(ctx, x, dim, kind, gamma, beta, *rest):
         lib = _lib.load()
+        infix, pack_fn, _, rows_ok = _DP_CELLS[kind]
         x = x.contiguous()
         if dim >= 10:  # rows layout (B, T, F, 64)
+            if not rows_ok:
+                raise ValueError(f"DualPathRNN with the {kind} cell has no rows layout (dim {dim})")
             B, T, Fq, _ = x.shape
         else:
             B, _, T, Fq = x.shape
-        sru, lin_w, lin_b = rest[:12], rest[12], rest[13]
-        tpack = packing.cached_train_pack("dualpath", (gamma, beta) + tuple(rest),
-                                          lambda: packing.pack_dualpath_train(gamma, beta, sru[0::3], sru[1::3], sru[2::3], lin_w, lin_b))
+        tpack = packing.cached_train_pack(("dualpath_" + infix).rstrip("_"), (gamma, beta) + tuple(rest),
+                                          lambda: pack_fn(gamma, beta, rest[:-2], rest[-2], rest[-1]))
+        fn = lambda n: getattr(lib, f"rtfs_dualpath_{infix}{n}")
         out = _lib.empty_like(x)
-        saved = _lib.empty(lib.rtfs_dualpath_saved_floats(B, T, Fq, dim % 10), device=x.device, dtype=torch.float32)
-        ws = _lib.workspace(lib.rtfs_dualpath_train_workspace_bytes(B, T, Fq, dim % 10), x.device)
-        _lib.check(lib.rtfs_dualpath_forward_train_f32(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(out), _lib.ptr(saved), B, T, Fq, dim,
-                                                       _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_dualpath_forward_train_f32")
+        saved = _lib.empty(fn("saved_floats")(B, T, Fq, dim % 10), device=x.device, dtype=torch.float32)
+        ws = _lib.workspace(fn("train_workspace_bytes")(B, T, Fq, dim % 10), x.device)
+        _lib.check(fn("forward_train_f32")(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(out), _lib.ptr(saved), B, T, Fq, dim, _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_of(x)), f"rtfs_dualpath_{infix}forward_train_f32")
         ctx.save_for_backward(x, tpack, saved)
-        ctx.dim, ctx.geom = dim, (B, T, Fq)
-        ctx.shapes = (gamma.shape, beta.shape)
+        ctx.dim, ctx.geom, ctx.kind, ctx.shapes = dim, (B, T, Fq), kind, (gamma.shape, beta.shape)
         return out
 
     @staticmethod
@@ -695,73 +727,24 @@ class _DualPathTrainFn(torch.autograd.Function):
         lib = _lib.load()
         x, tpack, saved = ctx.saved_tensors
         B, T, Fq = ctx.geom
+        infix = _DP_CELLS[ctx.kind][0]
+        fn = lambda n: getattr(lib, f"rtfs_dualpath_{infix}{n}")
         dout = dout.contiguous().to(torch.float32)
         dx = _lib.empty_like(x)
-        dpar = _lib.empty(lib.rtfs_dualpath_grad_floats(), device=x.device, dtype=torch.float32)
-        ws = _lib.workspace(lib.rtfs_dualpath_train_workspace_bytes(B, T, Fq, ctx.dim % 10), x.device)
-        _lib.check(lib.rtfs_dualpath_backward_f32(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(saved), _lib.ptr(dout), _lib.ptr(dx), _lib.ptr(dpar),
-                                                  B, T, Fq, ctx.dim, _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), "rtfs_dualpath_backward_f32")
+        dpar = _lib.empty(fn("grad_floats")(), device=x.device, dtype=torch.float32)
+        ws = _lib.workspace(fn("train_workspace_bytes")(B, T, Fq, ctx.dim % 10), x.device)
+        _lib.check(fn("backward_f32")(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(saved), _lib.ptr(dout), _lib.ptr(dx), _lib.ptr(dpar), B, T, Fq, ctx.dim,
+                                      _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), f"rtfs_dualpath_{infix}backward_f32")
         if getattr(ctx, "flat_grads", False):
             return dx, dpar
-        return (dx, None) + tuple(_dualpath_unpack(ctx.shapes)(dpar))
-
-
-def _dualpath_unpack(shapes):
-    def unpack(flat):
-        dg, db, dws, dwcs, dbs, dlw, dlb = packing.unpack_dualpath_grads(flat)
-        out = [dg.reshape(shapes[0]), db.reshape(shapes[1])]
-        for i in range(4):
-            out += [dws[i], dwcs[i], dbs[i]]
-        return out + [dlw, dlb]
-    return unpack
+        return (dx, None, None) + tuple(_dualpath_unpack(ctx.kind, ctx.shapes)(dpar))
 
 
 def dualpath_train(x, dim, gamma, beta, sru, lin_w, lin_b):
     """_DualPathTrainFn (SRU cells) with the 16 parameters behind a gradient bundle."""
     params = (gamma, beta) + tuple(sru) + (lin_w, lin_b)
-    return _apply_bundled(_DualPathTrainFn, "dualpath", x, (dim,), params, _lib.load().rtfs_dualpath_grad_floats(),
-                          _dualpath_unpack((gamma.shape, beta.shape)))
-
-
-class _DualPathLstmTrainFn(torch.autograd.Function):
-    """DualPathRNN with a stock torch cell (kind "lstm" or "gru") on the GEMM + scan kernels.  Inputs: x, dim, kind, gamma, beta, the 32
-    nn.LSTM / nn.GRU parameters in packing.lstm_param_names() order, ConvTranspose1d weight, bias."""
-
-    @staticmethod
-    def forward(ctx, x, dim, kind, gamma, beta, *rest):
-        lib = _lib.load()
-        x = x.contiguous()
-        B, _, T, Fq = x.shape
-        names = packing.lstm_param_names()
-        cell, lin_w, lin_b = dict(zip(names, rest[:len(names)])), rest[len(names)], rest[len(names) + 1]
-        pack_fn = packing.pack_dualpath_lstm_train if kind == "lstm" else packing.pack_dualpath_gru_train
-        tpack = packing.cached_train_pack("dualpath_" + kind, (gamma, beta) + tuple(rest), lambda: pack_fn(gamma, beta, cell, lin_w, lin_b))
-        fn = lambda n: getattr(lib, f"rtfs_dualpath_{kind}_{n}")
-        out = _lib.empty_like(x)
-        saved = _lib.empty(fn("saved_floats")(B, T, Fq, dim), device=x.device, dtype=torch.float32)
-        ws = _lib.workspace(fn("train_workspace_bytes")(B, T, Fq, dim), x.device)
-        _lib.check(fn("forward_train_f32")(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(out), _lib.ptr(saved), B, T, Fq, dim, _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_of(x)), f"rtfs_dualpath_{kind}_forward_train_f32")
-        ctx.save_for_backward(x, tpack, saved)
-        ctx.dim, ctx.shapes, ctx.names, ctx.kind = dim, (gamma.shape, beta.shape), names, kind
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        lib = _lib.load()
-        x, tpack, saved = ctx.saved_tensors
-        B, _, T, Fq = x.shape
-        kind = ctx.kind
-        fn = lambda n: getattr(lib, f"rtfs_dualpath_{kind}_{n}")
-        dout = dout.contiguous().to(torch.float32)
-        dx = _lib.empty_like(x)
-        dpar = _lib.empty(fn("grad_floats")(), device=x.device, dtype=torch.float32)
-        ws = _lib.workspace(fn("train_workspace_bytes")(B, T, Fq, ctx.dim), x.device)
-        _lib.check(fn("backward_f32")(_lib.ptr(x), _lib.ptr(tpack), _lib.ptr(saved), _lib.ptr(dout), _lib.ptr(dx), _lib.ptr(dpar), B, T, Fq, ctx.dim,
-                                      _lib.ptr(ws), ws.numel(), _lib.stream_of(x)), f"rtfs_dualpath_{kind}_backward_f32")
-        unpack = packing.unpack_dualpath_lstm_grads if kind == "lstm" else packing.unpack_dualpath_gru_grads
-        dg, db, dl, dlw, dlb = unpack(dpar)
-        return (dx, None, None, dg.reshape(ctx.shapes[0]), db.reshape(ctx.shapes[1])) + tuple(dl[n] for n in ctx.names) + (dlw, dlb)
+    return _apply_bundled(_DualPathTrainFn, "dualpath", x, (dim, "sru"), params, _lib.load().rtfs_dualpath_grad_floats(),
+                          _dualpath_unpack("sru", (gamma.shape, beta.shape)))
 
 
 class DualPathRNN(PackedModule):
@@ -801,8 +784,7 @@ class DualPathRNN(PackedModule):
         if _recording(x, self) or self.rnn_type == "GRU" or long_axis:  # GRU: no fused inference kernel, the GEMM + scan kernels serve both
             if self.rnn_type in ("LSTM", "GRU"):
                 cell = [getattr(self.rnn, n) for n in packing.lstm_param_names()]
-                return _DualPathLstmTrainFn.apply(x, self.dim, self.rnn_type.lower(), self.norm.gamma, self.norm.beta, *cell, self.linear.weight,
-                                                  self.linear.bias)
+                return _DualPathTrainFn.apply(x, self.dim, self.rnn_type.lower(), self.norm.gamma, self.norm.beta, *cell, self.linear.weight, self.linear.bias)
             sru = [p for cell in self.rnn.rnn_lst for p in (cell.weight, cell.weight_c, cell.bias)]
             return dualpath_train(x, self.dim, self.norm.gamma, self.norm.beta, sru, self.linear.weight, self.linear.bias)
         out = _lib.empty_like(x)

@@ -312,78 +312,69 @@ def lstm_param_names(num_layers=4):
     return [f"{n}_l{l}{suf}" for l in range(num_layers) for suf in _LSTM_SUFFIX for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
 
 
-def pack_dualpath_lstm_train(gamma, beta, lstm, lin_w, lin_b):
-    """Training-side pack of DualPathRNN with nn.LSTM(512, 32, 4 layers, bidirectional) (layout contract: include/rtfs_amd.h,
-    rtfs_dualpath_lstm_forward_train_f32).  lstm: name -> tensor with nn.LSTM's names."""
+def _pack_dualpath_gated_train(gamma, beta, cell, lin_w, lin_b, gh, sum_biases):
+    """Training-side pack of DualPathRNN with a stock torch cell (512 -> 32, 4 layers, bidirectional).  cell: name -> tensor with nn.LSTM's /
+    nn.GRU's names; gh: gate rows per direction (LSTM 128, GRU 96); sum_biases: b_ih + b_hh in one slot (LSTM) or b_hh in a slot of its own
+    behind W_hh (GRU)."""
     f32 = lambda t: t.detach().to(torch.float32)
     parts = [gamma.reshape(64), beta.reshape(64)]
     for l in range(4):
-        wih = torch.cat([f32(lstm[f"weight_ih_l{l}{suf}"]) for suf in _LSTM_SUFFIX])  # (256, Din), rows dir*128 + gate*32 + j
+        wih = torch.cat([f32(cell[f"weight_ih_l{l}{suf}"]) for suf in _LSTM_SUFFIX])  # (2 gh, Din), rows dir*gh + gate*32 + j
         if l == 0:
-            wih = wih.reshape(256, 64, 8).permute(0, 2, 1).reshape(256, 512)  # Unfold feature c*8 + k -> window order k*64 + c
-        bias = torch.cat([f32(lstm[f"bias_ih_l{l}{suf}"]) + f32(lstm[f"bias_hh_l{l}{suf}"]) for suf in _LSTM_SUFFIX])
-        whh = torch.stack([f32(lstm[f"weight_hh_l{l}{suf}"]) for suf in _LSTM_SUFFIX])
-        parts += [wih.contiguous(), wih.t().contiguous(), bias, whh.contiguous()]
+            wih = wih.reshape(2 * gh, 64, 8).permute(0, 2, 1).reshape(2 * gh, 512)  # Unfold feature c*8 + k -> window order k*64 + c
+        b = lambda n, suf: f32(cell[f"bias_{n}_l{l}{suf}"])
+        if sum_biases:
+            biases = [torch.cat([b("ih", suf) + b("hh", suf) for suf in _LSTM_SUFFIX])]
+        else:
+            biases = [torch.cat([b(n, suf) for suf in _LSTM_SUFFIX]) for n in ("ih", "hh")]
+        whh = torch.stack([f32(cell[f"weight_hh_l{l}{suf}"]) for suf in _LSTM_SUFFIX])
+        parts += [wih.contiguous(), wih.t().contiguous(), biases[0], whh.contiguous()] + biases[1:]
     lw = f32(lin_w)
     parts += [lw.flip(2).permute(1, 2, 0).reshape(64, 512).contiguous(), lw.permute(0, 2, 1).reshape(64, 512).contiguous(), lin_b]
     return _cat(parts)
+
+
+def _unpack_dualpath_gated_grads(flat, gh, sum_biases):
+    """The gated cells' gradient buffer -> (dgamma, dbeta, {cell parameter name: grad}, dlin_w, dlin_b); with sum_biases both bias names of
+    a layer and direction map to the one gradient slice."""
+    out, o = {}, 128
+    for l in range(4):
+        din = 512 if l == 0 else 64
+        dwih = flat[o:o + 2 * gh * din].reshape(2 * gh, din); o += 2 * gh * din
+        if l == 0:
+            dwih = dwih.reshape(2 * gh, 8, 64).permute(0, 2, 1).reshape(2 * gh, 512)
+        dbih = flat[o:o + 2 * gh]; o += 2 * gh
+        dwhh = flat[o:o + 2 * gh * 32].reshape(2, gh, 32); o += 2 * gh * 32
+        dbhh = dbih
+        if not sum_biases:
+            dbhh = flat[o:o + 2 * gh]; o += 2 * gh
+        for d, suf in enumerate(_LSTM_SUFFIX):
+            out[f"weight_ih_l{l}{suf}"] = dwih[d * gh:(d + 1) * gh]
+            out[f"weight_hh_l{l}{suf}"] = dwhh[d]
+            out[f"bias_ih_l{l}{suf}"] = dbih[d * gh:(d + 1) * gh]
+            out[f"bias_hh_l{l}{suf}"] = dbhh[d * gh:(d + 1) * gh]
+    dlw = flat[o:o + 512 * 64].reshape(8, 64, 64).flip(0).permute(1, 2, 0)
+    return flat[0:64], flat[64:128], out, dlw, flat[o + 512 * 64:o + 512 * 64 + 64]
+
+
+def pack_dualpath_lstm_train(gamma, beta, lstm, lin_w, lin_b):
+    """nn.LSTM(512, 32, 4 layers, bidirectional) (layout contract: include/rtfs_amd.h, rtfs_dualpath_lstm_forward_train_f32)."""
+    return _pack_dualpath_gated_train(gamma, beta, lstm, lin_w, lin_b, 128, True)
 
 
 def unpack_dualpath_lstm_grads(flat):
-    """rtfs_dualpath_lstm_backward_f32's gradient buffer -> (dgamma, dbeta, {lstm name: grad}, dlin_w, dlin_b)."""
-    out, o = {}, 128
-    for l in range(4):
-        din = 512 if l == 0 else 64
-        dwih = flat[o:o + 256 * din].reshape(256, din); o += 256 * din
-        if l == 0:
-            dwih = dwih.reshape(256, 8, 64).permute(0, 2, 1).reshape(256, 512)
-        db = flat[o:o + 256]; o += 256
-        dwhh = flat[o:o + 2 * 128 * 32].reshape(2, 128, 32); o += 2 * 128 * 32
-        for d, suf in enumerate(_LSTM_SUFFIX):
-            out[f"weight_ih_l{l}{suf}"] = dwih[d * 128:(d + 1) * 128]
-            out[f"weight_hh_l{l}{suf}"] = dwhh[d]
-            out[f"bias_ih_l{l}{suf}"] = db[d * 128:(d + 1) * 128]
-            out[f"bias_hh_l{l}{suf}"] = db[d * 128:(d + 1) * 128]
-    dlw = flat[o:o + 512 * 64].reshape(8, 64, 64).flip(0).permute(1, 2, 0)
-    return flat[0:64], flat[64:128], out, dlw, flat[o + 512 * 64:o + 512 * 64 + 64]
+    """rtfs_dualpath_lstm_backward_f32's gradient buffer (bias_ih_* and bias_hh_* share one slice)."""
+    return _unpack_dualpath_gated_grads(flat, 128, True)
 
 
 def pack_dualpath_gru_train(gamma, beta, gru, lin_w, lin_b):
-    """Pack of DualPathRNN with nn.GRU(512, 32, 4 layers, bidirectional) (layout contract: include/rtfs_amd.h,
-    rtfs_dualpath_gru_forward_train_f32).  gru: name -> tensor with nn.GRU's names (the same as nn.LSTM's)."""
-    f32 = lambda t: t.detach().to(torch.float32)
-    parts = [gamma.reshape(64), beta.reshape(64)]
-    for l in range(4):
-        wih = torch.cat([f32(gru[f"weight_ih_l{l}{suf}"]) for suf in _LSTM_SUFFIX])  # (192, Din), rows dir*96 + gate*32 + j
-        if l == 0:
-            wih = wih.reshape(192, 64, 8).permute(0, 2, 1).reshape(192, 512)
-        bih = torch.cat([f32(gru[f"bias_ih_l{l}{suf}"]) for suf in _LSTM_SUFFIX])
-        bhh = torch.cat([f32(gru[f"bias_hh_l{l}{suf}"]) for suf in _LSTM_SUFFIX])
-        whh = torch.stack([f32(gru[f"weight_hh_l{l}{suf}"]) for suf in _LSTM_SUFFIX])
-        parts += [wih.contiguous(), wih.t().contiguous(), bih, whh.contiguous(), bhh]
-    lw = f32(lin_w)
-    parts += [lw.flip(2).permute(1, 2, 0).reshape(64, 512).contiguous(), lw.permute(0, 2, 1).reshape(64, 512).contiguous(), lin_b]
-    return _cat(parts)
+    """nn.GRU(512, 32, 4 layers, bidirectional) (layout contract: include/rtfs_amd.h, rtfs_dualpath_gru_forward_train_f32)."""
+    return _pack_dualpath_gated_train(gamma, beta, gru, lin_w, lin_b, 96, False)
 
 
 def unpack_dualpath_gru_grads(flat):
-    """rtfs_dualpath_gru_backward_f32's gradient buffer -> (dgamma, dbeta, {gru name: grad}, dlin_w, dlin_b)."""
-    out, o = {}, 128
-    for l in range(4):
-        din = 512 if l == 0 else 64
-        dwih = flat[o:o + 192 * din].reshape(192, din); o += 192 * din
-        if l == 0:
-            dwih = dwih.reshape(192, 8, 64).permute(0, 2, 1).reshape(192, 512)
-        dbih = flat[o:o + 192]; o += 192
-        dwhh = flat[o:o + 2 * 96 * 32].reshape(2, 96, 32); o += 2 * 96 * 32
-        dbhh = flat[o:o + 192]; o += 192
-        for d, suf in enumerate(_LSTM_SUFFIX):
-            out[f"weight_ih_l{l}{suf}"] = dwih[d * 96:(d + 1) * 96]
-            out[f"weight_hh_l{l}{suf}"] = dwhh[d]
-            out[f"bias_ih_l{l}{suf}"] = dbih[d * 96:(d + 1) * 96]
-            out[f"bias_hh_l{l}{suf}"] = dbhh[d * 96:(d + 1) * 96]
-    dlw = flat[o:o + 512 * 64].reshape(8, 64, 64).flip(0).permute(1, 2, 0)
-    return flat[0:64], flat[64:128], out, dlw, flat[o + 512 * 64:o + 512 * 64 + 64]
+    """rtfs_dualpath_gru_backward_f32's gradient buffer."""
+    return _unpack_dualpath_gated_grads(flat, 96, False)
 
 
 def _dualpath_lstm_parts(sd):

@@ -267,6 +267,99 @@ def test_sru_and_dualpath_training_pack_layouts_roundtrip():
     assert torch.equal(dlw, lw)
 
 
+_DP_SHAPES = [(1, 8, 8, 3), (1, 8, 8, 4), (2, 11, 13, 3), (2, 11, 13, 4), (1, 125, 9, 3), (1, 5, 64, 4), (2, 251, 129, 3)]
+# symbol infix of the cell -> (pack floats, gradient floats, [(saved floats, workspace bytes) per _DP_SHAPES entry])
+_DP_SIZES = {
+    "": (402624, 201920,
+         [(92672, 188416), (92672, 188416), (405248, 813568), (405248, 813568), (1586560, 3176192), (453120, 909312),
+          (91181824, 182366720)]),
+    "lstm_": (459968, 246976,
+              [(121344, 320512), (121344, 320512), (533376, 1172992), (533376, 1172992), (2090560, 4394752), (596480, 1303552),
+               (120193408, 248745472)]),
+    "gru_": (362176, 194240,
+             [(104960, 336896), (104960, 336896), (460160, 1303040), (460160, 1303040), (1802560, 4954368), (514560, 1451008),
+              (103615360, 281885184)]),
+}
+
+
+def test_dualpath_training_size_queries_pinned():
+    """The pack, gradient, saved-state and workspace sizes of the three dual-path cells (SRU, LSTM, GRU) are part of the C ABI: callers
+    size their buffers with them.  The literals are what the library returned before its six entry points shared one scaffold."""
+    from rtfs_net_amd import _lib
+    lib = _lib.load()
+    for infix, (pack, grad, per_shape) in _DP_SIZES.items():
+        fn = lambda n: getattr(lib, f"rtfs_dualpath_{infix}{n}")
+        assert fn("train_pack_floats")() == pack and fn("grad_floats")() == grad, infix
+        for shape, (saved, ws) in zip(_DP_SHAPES, per_shape):
+            assert fn("saved_floats")(*shape) == saved, (infix, shape)
+            assert fn("train_workspace_bytes")(*shape) == ws, (infix, shape)
+
+
+@pytest.mark.parametrize("kind", ["lstm", "gru"])
+def test_gated_dualpath_training_pack_layouts_roundtrip(kind):
+    """The LSTM / GRU counterpart of the SRU round trip above: the pack has the library's size, a gradient buffer assembled from the
+    pack's own W_ih, bias, W_hh, ConvTranspose1d and bias slots has the library's gradient size and comes back from unpack_*_grads as
+    the nn.LSTM / nn.GRU-named tensors (the LSTM's two biases are summed in the pack: both names get that one slice)."""
+    from rtfs_net_amd import packing, _lib
+    lib = _lib.load()
+    gh = 128 if kind == "lstm" else 96  # gate rows per direction
+    gw = 2 * gh
+    g = torch.Generator().manual_seed(1)
+    cell = {}
+    for n in packing.lstm_param_names():
+        din = 512 if "_l0" in n else 64
+        cell[n] = torch.randn(*{"weight_ih": (gh, din), "weight_hh": (gh, 32)}.get(n[:9], (gh,)), generator=g)
+    gamma, beta = torch.randn(1, 64, 1, 1, generator=g), torch.randn(1, 64, 1, 1, generator=g)
+    lw, lb = torch.randn(64, 64, 8, generator=g), torch.randn(64, generator=g)
+    tp = getattr(packing, f"pack_dualpath_{kind}_train")(gamma, beta, cell, lw, lb)
+    assert tp.numel() == getattr(lib, f"rtfs_dualpath_{kind}_train_pack_floats")()
+    parts, o = [tp[:128]], 128
+    for l in range(4):
+        din = 512 if l == 0 else 64
+        wih = tp[o:o + gw * din]; o += gw * din
+        wiht = tp[o:o + din * gw]; o += din * gw
+        assert torch.equal(wiht.reshape(din, gw), wih.reshape(gw, din).t())
+        n = gw + gw * 32 + (gw if kind == "gru" else 0)  # bias | W_hh | (GRU) b_hh
+        parts += [wih, tp[o:o + n]]; o += n
+    wcf = tp[o:o + 64 * 512].reshape(64, 512)
+    assert o + 2 * 64 * 512 + 64 == tp.numel() and torch.equal(tp[-64:], lb)
+    gflat = torch.cat(parts + [wcf.t().reshape(-1), lb])
+    assert gflat.numel() == getattr(lib, f"rtfs_dualpath_{kind}_grad_floats")()
+    dg, db, dcell, dlw, dlb = getattr(packing, f"unpack_dualpath_{kind}_grads")(gflat)
+    assert torch.equal(dg, gamma.reshape(64)) and torch.equal(db, beta.reshape(64)) and torch.equal(dlb, lb) and torch.equal(dlw, lw)
+    assert sorted(dcell) == sorted(cell)
+    for n, t in cell.items():
+        if kind == "lstm" and n.startswith("bias"):
+            both = cell[n.replace("bias_hh", "bias_ih")] + cell[n.replace("bias_ih", "bias_hh")]
+            assert torch.equal(dcell[n], both) and dcell[n].data_ptr() == dcell[n.replace("bias_hh", "bias_ih")].data_ptr(), n
+        else:
+            assert torch.equal(dcell[n], t), n
+
+
+def test_dualpath_training_refusals_pinned():
+    """What the six dual-path training entry points refuse, and with which code, in the order argument -> shape -> workspace.  Every
+    call below returns before anything is launched (the pointers are host arrays that are never dereferenced)."""
+    from rtfs_net_amd import _lib
+    lib = _lib.load()
+    SHAPE, WORKSPACE, ARG = -1, -2, -4
+    buf = np.zeros(16, np.float32)
+    p = ctypes.c_void_p(buf.ctypes.data)
+    for infix in ("", "lstm_", "gru_"):
+        wsb = getattr(lib, f"rtfs_dualpath_{infix}train_workspace_bytes")
+        for name, nptr in ((f"rtfs_dualpath_{infix}forward_train_f32", 4), (f"rtfs_dualpath_{infix}backward_f32", 6)):
+            fn = getattr(lib, name)
+            call = lambda B, T, F, dim, ws, short=0, x=p: fn(x, *[p] * (nptr - 1), B, T, F, dim, ws, wsb(B, T, F, dim % 10) - short, None)
+            assert call(1, 8, 8, 3, p, x=None) == ARG, name
+            assert call(1, 8, 8, 5, p) == ARG, name
+            if infix:  # the rows layout exists for the SRU cell only
+                assert call(1, 8, 8, 13, p) == ARG and call(1, 8, 8, 14, p) == ARG, name
+            assert call(1, 7, 16, 3, p) == SHAPE and call(1, 16, 7, 4, p) == SHAPE, name
+            assert call(1, 8, 8, 3, None) == WORKSPACE and call(1, 8, 8, 4, p, short=1) == WORKSPACE, name
+            # the backward's layout kernels hold one sweep in LDS (<= 256 positions); the forward takes any length
+            assert call(1, 257, 8, 3, None) == (WORKSPACE if nptr == 4 else SHAPE), name
+            assert call(1, 256, 8, 3, None) == WORKSPACE, name
+
+
 def test_gradient_oracle_matches_numpy_oracle_and_finite_differences():
     """oracle/grad_oracle.py: forward equals the numpy restatement; its autograd gradient equals a central finite difference
     of the numpy restatement's own forward (so the backward kernels are checked against something that restates no backward)."""
