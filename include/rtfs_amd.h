@@ -174,6 +174,26 @@ int rtfs_separator_speakers_f32(const float* wav, const float* video_vp, const f
                                 float* out, int B, int K, int L, int Tv, int repeats, void* ws, size_t ws_bytes, void* stream,
                                 void* video_ready, int rnn_kind, int split);
 
+/* A different number of targets per mixture (AVNet.separate_speakers(counts=...)): mixture b has counts[b] targets, 1 <= counts[b] <=
+ * RTFS_MAX_SPEAKERS; the targets are mixture-major, N = sum(counts).  wav (B,L); video_vp (N,512,Tv) and out (N,1,L) per target.  Target t's
+ * result is what rtfs_separator_forward_ex_f32 returns for mixture mix_of[t] with lips t; with all counts equal to K it is bit for bit the
+ * result of rtfs_separator_speakers_f32.  counts is a HOST array of B ints (it sizes the workspace and places the batch parts); mix_of is the
+ * caller's DEVICE array of N ints, non-decreasing, mix_of[t] = the mixture of target t.  The call uploads nothing, allocates nothing and reads
+ * nothing back, so with the table in place it can be captured in a HIP graph like the fixed-K entry.  The library TRUSTS that mix_of matches
+ * counts (a table entry outside [0, B) reads outside the workspace): build it from counts.
+ * The prefix runs on the B mixtures; the CAF boundary and the tail kernel read mix_of[t] where the fixed-K entry divides t by K; the
+ * workspace is sized by B where it depends on the mixture and by N where it depends on the target.  split cuts the MIXTURES (each part >= 8
+ * of them); a part carries its mixtures' targets, starts at the target sum(counts before its first mixture) and hands its kernels that
+ * first mixture as the base the table entries are taken relative to.
+ * Same cells, length limits and -1 / -4 rules as rtfs_separator_speakers_f32, and -4 for a NULL counts or mix_of, a count outside 1 .. 16 or
+ * N != sum(counts), all before the first launch and before any device call.  The workspace query returns 0 for such arguments and, with all
+ * counts equal to K, what rtfs_separator_speakers_workspace_bytes(B, K, ...) returns. */
+size_t rtfs_separator_targets_workspace_bytes(const int* counts, int B, int L, int Tv, int split);
+int rtfs_separator_targets_f32(const float* wav, const float* video_vp, const int* counts, const int* mix_of, const float* pack_enc,
+                               const float* pack_bn, const float* pack_block, const float* pack_caf, const float* pack_s3,
+                               const float* pack_dec, float* out, int B, int N, int L, int Tv, int repeats, void* ws, size_t ws_bytes,
+                               void* stream, void* video_ready, int rnn_kind, int split);
+
 /* Operator-level seam: sru.SRU(input_size=512, hidden_size=32, num_layers=4, bidirectional=True).forward
  * (call site src/models/layers/rnn_layers.py:150; third-party asappresearch `sru`, v2 recurrence).
  * x (L,N,512) -> h (L,N,64).  pack = the DUALPATH pack (only its SRU part is read). */
@@ -462,6 +482,24 @@ int rtfs_longform_frame_many_f32(const float* const* wavs, const float* const* v
                                  int R, int total_windows, int window, int hop, void* stream);
 int rtfs_longform_overlap_add_many_f32(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
                                        int n_src, int window, int hop, void* stream);
+
+/* The pooled pass with K_r lip tracks per recording (AVNet.separate_many_speakers), 1 <= K_r <= RTFS_MAX_SPEAKERS, n_src 1.
+ * rtfs_longform_many_speakers_plan (host only): L, Tv, K (R each, host) -> total_windows = sum(N_r), total_targets = sum(N_r K_r),
+ *   out_floats, and the 7 * R int64 words [row0 | N | L | Tv | out_off | K | trow0]: the five columns of rtfs_longform_many_plan with
+ *   K_r in place of n_src (recording r's block is (K_r, L_r), same padding rule), then K_r and trow0[r] = sum of N_q K_q before r.  The K_r
+ *   targets of window n of recording r are rows trow0[r] + n K_r + k: per recording the (windows, n_src := K_r, ..) layout of the
+ *   overlap-add.  Refusals as rtfs_longform_many_plan, and -4 for a NULL K or a K_r outside 1 .. 16, -1 for total_targets > 2^31 - 1.
+ * rtfs_longform_frame_many_speakers_f32 (one launch): videos[r] = recording r's contiguous (K_r, 512, Tv_r) -> wav_win (total_windows,
+ *   window), each audio window written ONCE, and video_win (total_targets, 512, window / SPF).  max_K = the largest K_r (sizes the grid; -4
+ *   outside 1 .. 16).
+ * rtfs_longform_overlap_add_many_speakers_f32 (one launch): y (total_targets, window) -> out (out_floats), recording r at out + out_off[r]
+ *   as (K_r, L_r).  Alignment rules and trust in the device table as above. */
+int rtfs_longform_many_speakers_plan(const long long* L, const long long* Tv, const long long* K, int R, int window, int hop, long long* table,
+                                     long long* total_windows, long long* total_targets, long long* out_floats);
+int rtfs_longform_frame_many_speakers_f32(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win,
+                                          float* video_win, int R, int total_windows, int max_K, int window, int hop, void* stream);
+int rtfs_longform_overlap_add_many_speakers_f32(const float* y, float* out, const long long* table, int R, int total_windows,
+                                                long long out_floats, int window, int hop, void* stream);
 
 /* Live streams chunk by chunk (AVNet.open_streams / StreamPool; DESIGN.md "Live streams"): the stateful form of the long-form plan.  Window
  * n of a stream is run as soon as a >= n hop + window samples AND f >= n hop / SPF + window / SPF frames have arrived; after window n the

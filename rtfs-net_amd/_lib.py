@@ -52,6 +52,8 @@ SIGNATURES = {
     "rtfs_separator_forward_f32": (_i, [_p] * 9 + [_i, _i, _i, _i, _p, _z, _p, _p, _i]),
     "rtfs_separator_speakers_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "rtfs_separator_speakers_f32": (_i, [_p] * 9 + [_i, _i, _i, _i, _i, _p, _z, _p, _p, _i, _i]),
+    "rtfs_separator_targets_workspace_bytes": (_z, [_p, _i, _i, _i, _i]),
+    "rtfs_separator_targets_f32": (_i, [_p] * 11 + [_i, _i, _i, _i, _i, _p, _z, _p, _p, _i, _i]),
     "rtfs_sru_workspace_bytes": (_z, [_i, _i]),
     "rtfs_sru_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),
     "rtfs_sru_train_pack_floats": (_z, []),
@@ -126,6 +128,9 @@ SIGNATURES = {
     "rtfs_longform_many_plan": (_i, [_p, _p, _i, _i, _i, _i, _p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "rtfs_longform_frame_many_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "rtfs_longform_overlap_add_many_f32": (_i, [_p, _p, _p, _i, _i, C.c_longlong, _i, _i, _i, _p]),
+    "rtfs_longform_many_speakers_plan": (_i, [_p, _p, _p, _i, _i, _i, _p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "rtfs_longform_frame_many_speakers_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "rtfs_longform_overlap_add_many_speakers_f32": (_i, [_p, _p, _p, _i, _i, C.c_longlong, _i, _i, _p]),
     "rtfs_live_plan": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "rtfs_live_ingest_frame_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rtfs_live_overlap_add_f32": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _i, _i, _i, _i, _i, _p]),

@@ -587,10 +587,13 @@ int block_forward(const BlockPack& p, const float* x, const float* x_res, float*
 // res_has_a1 (in / out): whether w.residual currently holds residual + a1.  A boundary that has to read a1 anyway also adds it to the residual
 // it writes (unless it is the last one: the tail wants the plain residual), and the boundary after it then does not read a1 at all.
 int block_boundary(const BlockPack& p, const float* a1, int B, int T, int F, BlockWs& w, hipStream_t st, const CafArgs* caf, unsigned* ctr = nullptr,
-                   bool* res_has_a1 = nullptr, bool last = true, bool res_from_a1 = false, int xk = 1, int a1k = 1) {
+                   bool* res_has_a1 = nullptr, bool last = true, bool res_from_a1 = false, int xk = 1, int a1k = 1, const int* mix_of = nullptr,
+                   int mix_base = 0) {
     B2bArgs a;
     a.xk = xk;
     a.a1k = a1k;
+    a.mix_of = mix_of;
+    a.mix_base = mix_base;
     a.x = w.expanded;
     a.res = w.residual;
     a.a1 = a1;
@@ -618,7 +621,7 @@ int block_boundary(const BlockPack& p, const float* a1, int B, int T, int F, Blo
         return RTFS_ERR_ARG;  // (cannot happen: the head kernel that skipped the residual qualifies on the same conditions)
     }
     const int rc = launch_pws_b2b4(a, B, ctr, st);  // padded rows: the pipelined kernel (k_b2b.hip)
-    if (rc == RTFS_ERR_ARG && (xk > 1 || a1k > 1)) return RTFS_ERR_SHAPE;  // (the first-generation kernel has no mixture index; checked up front)
+    if (rc == RTFS_ERR_ARG && (xk != 1 || a1k != 1)) return RTFS_ERR_SHAPE;  // (the first-generation kernel has no mixture index; checked up front)
     return rc == RTFS_ERR_ARG ? launch_pws_b2b(a, B, st) : rc;
 }
 
@@ -967,26 +970,28 @@ struct SepWs {
     // K = 0: one target per mixture (rtfs_separator_forward_*).  K >= 1: K targets per mixture (rtfs_separator_speakers_f32, fused path
     // only): what depends on the mixture alone (spec, a1, st0) is sized by B, what depends on the target (CAF tables, z, the block
     // workspace and its statistic slots) by B * K; a0, cur and nxt exist only on the unfused path and take nothing.
-    SepWs(Arena& a, int B, int T, int Tv, int cs_, int K = 0)
+    // NT > 0 (rtfs_separator_targets_f32): the part's NT targets in place of B * K (K is then only "not the unfused path").
+    SepWs(Arena& a, int B, int T, int Tv, int cs_, int K = 0, int NT = 0) : SepWs(a, B, T, Tv, cs_, K != 0, (size_t)(K ? (NT ? NT : B * K) : B)) {}
+    SepWs(Arena& a, int B, int T, int Tv, int cs_, bool K, size_t N)
         : spec(a.take<float>((size_t)B * 2 * T * NF)),
           a0(a.take<float>(K ? 0 : (size_t)B * CA * cs_)),
           a1(a.take<float>((size_t)B * CA * cs_)),
           cur(a.take<float>(K ? 0 : (size_t)B * CA * cs_)),
           nxt(a.take<float>(K ? 0 : (size_t)B * CA * cs_)),
-          r(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
-          att(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
-          rt(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
-          attt(a.take<float>((size_t)B * (K ? K : 1) * CA * Tv)),
-          z(a.take<float>((size_t)B * (K ? K : 1) * 18 * cs_)),
+          r(a.take<float>(N * CA * Tv)),
+          att(a.take<float>(N * CA * Tv)),
+          rt(a.take<float>(N * CA * Tv)),
+          attt(a.take<float>(N * CA * Tv)),
+          z(a.take<float>(N * 18 * cs_)),
           encimg(a.take<float>(8192)),
           wpad(a.take<float>(73728)),
           wpad0(a.take<float>(73728)),
           st0(a.take<double>(2 * B + 32)),
           ctr(reinterpret_cast<unsigned*>(st0 ? st0 + 2 * B : nullptr)),
-          bstats(a.take<double>((size_t)STAT_APPS * BlockWs::NSTAT * B * (K ? K : 1) * 2)),
+          bstats(a.take<double>((size_t)STAT_APPS * BlockWs::NSTAT * N * 2)),
           B_(B),
           cs(cs_),
-          blk(a, B * (K ? K : 1), T, NF, cs_) {}
+          blk(a, (int)N, T, NF, cs_) {}
 };
 }  // namespace
 
@@ -1004,7 +1009,7 @@ struct SepPacks {
 // K >= 1 (rtfs_separator_speakers_f32, fused path only): B mixtures with K targets each, video_vp / out per target (t = b * K + k); the
 // prefix up to block 0's body runs on the B mixtures, the first boundary fans out to the B * K targets
 int separator_part(const SepPacks& k, const float* wav, const float* video_vp, float* out, int B, int L, int T, int Tv, int repeats, SepWs& w,
-                   hipStream_t st, void* video_ready, int K = 0) {
+                   hipStream_t st, void* video_ready, int K = 0, int NT = 0, const int* mix_of = nullptr, int mix_base = 0) {
     const EncPack& pe = k.pe;
     const BnPack& pb = k.pb;
     const BlockPack& pk = k.pk;
@@ -1012,7 +1017,8 @@ int separator_part(const SepPacks& k, const float* wav, const float* video_vp, f
     const S3Pack& ps = k.ps;
     const DecPack& pd = k.pd;
     const int P = T * NF, cs = w.cs;
-    const int KT = K ? K : 1, BK = B * KT;  // targets per mixture, targets
+    // mix_of (rtfs_separator_targets_f32): NT targets, target t of the part belongs to mixture mix_of[t] - mix_base of the part
+    const int KT = mix_of ? 0 : (K ? K : 1), BK = mix_of ? NT : B * KT;  // targets per mixture (0: by table), targets
     // one memset per call: the bottleneck statistics, the tile counters and the statistic slots of every block application (SepWs::bstats)
     const size_t app_stats = (size_t)BlockWs::NSTAT * BK * 2;
     const size_t zero_bytes = (size_t)(reinterpret_cast<char*>(w.bstats + SepWs::STAT_APPS * app_stats) - reinterpret_cast<char*>(w.st0));
@@ -1081,7 +1087,7 @@ int separator_part(const SepPacks& k, const float* wav, const float* video_vp, f
             CHECK(block_body(pk, i == 0 ? B : BK, T, NF, w.blk, st, !own_slots));  // block 0: the mixtures (first B samples of the workspace)
             if (i == 0) CHECK(cafv.join());
             // the first boundary fans out: target t reads expanded_0 and a1 of mixture t / K; every later one reads a1 of the mixture
-            if (i + 1 < repeats) CHECK(block_boundary(pk, w.a1, BK, T, NF, w.blk, st, i == 0 ? &ca : nullptr, nctr < 64 ? w.ctr + nctr++ : nullptr, &res_has_a1, i + 2 == repeats, head_done && i == 0, i == 0 ? KT : 1, KT));
+            if (i + 1 < repeats) CHECK(block_boundary(pk, w.a1, BK, T, NF, w.blk, st, i == 0 ? &ca : nullptr, nctr < 64 ? w.ctr + nctr++ : nullptr, &res_has_a1, i + 2 == repeats, head_done && i == 0, i == 0 ? KT : 1, KT, mix_of, mix_base));
             else {
                 // last application: residual conv + S3 mask + complex product + decoder taps in one kernel (k_s3f.hip); `refined` never exists
                 TailS3Args f;
@@ -1091,6 +1097,7 @@ int separator_part(const SepPacks& k, const float* wav, const float* video_vp, f
                 f.P = P; f.cs = cs; f.cout_live = 18;
                 f.tile_ctr = nctr < 64 ? w.ctr + nctr++ : nullptr;
                 f.K = KT;  // spectrogram and a0 statistics of the target's mixture
+                f.mix_of = mix_of; f.mix_base = mix_base;
                 if (head_done) {  // (the two launches qualify together: same P, same pitch)
                     CHECK(launch_tail_s3t(f, BK, st));
                     return launch_dec_istft(w.z, out, BK, T, NF, L, (size_t)cs, (size_t)18 * cs, st);
@@ -1152,23 +1159,33 @@ int rtfs_separator_forward_f32(const float* wav, const float* video_vp, const fl
 
 // The batch-split driver shared by the two separator entry points (arguments checked by the caller).  K = 0: one target per mixture;
 // K >= 1: K targets per mixture, video_vp / out per target - a part carries its mixtures' K * nb targets.
+// counts / mix_of (rtfs_separator_targets_f32; K = 1 then only selects the fused path): counts[b] targets of mixture b (host), mix_of the
+// DEVICE table of the call's targets.  A part's first target is the sum of the counts before its first mixture, and its launches get the
+// table from that target on together with the part's first mixture as base: the workspace of a part knows only its own mixtures.
 static int separator_run(const float* wav, const float* video_vp, const float* pack_enc, const float* pack_bn, const float* pack_block,
                          const float* pack_caf, const float* pack_s3, const float* pack_dec, float* out, int B, int K, int L, int Tv, int repeats,
-                         void* ws, size_t ws_bytes, void* stream, void* video_ready, int rnn_kind, int split) {
+                         void* ws, size_t ws_bytes, void* stream, void* video_ready, int rnn_kind, int split, const int* counts = nullptr,
+                         const int* mix_of = nullptr) {
     const int T = rtfs_num_frames(L), KT = K ? K : 1;
     const int np = separator_parts(B, split);
+    std::vector<int> tfirst(np + 1, 0);  // first target of every part (and the total behind the last)
+    for (int i = 0, b = 0; i < np; ++i) {
+        const int end = (B * (i + 1)) / np;
+        tfirst[i + 1] = tfirst[i];
+        for (; b < end; ++b) tfirst[i + 1] += counts ? counts[b] : KT;
+    }
     Arena ar(ws, ws_bytes);
     std::vector<SepWs> parts;
     parts.reserve(np);
     // padded channel rows on the fused path; the unfused A/B sequence (exact-f32 GEMMs, or a single repeat) runs kernels that know only
     // contiguous tensors
     const int cstride = (gemm_f32() || repeats == 1) ? T * NF : pitch(T * NF);
-    for (int i = 0; i < np; ++i) parts.emplace_back(ar, (B * (i + 1)) / np - (B * i) / np, T, Tv, cstride, K);
+    for (int i = 0; i < np; ++i) parts.emplace_back(ar, (B * (i + 1)) / np - (B * i) / np, T, Tv, cstride, K, counts ? tfirst[i + 1] - tfirst[i] : 0);
     RTFS_RETURN_IF(!ws || !ar.ok(), RTFS_ERR_WORKSPACE);
     hipStream_t st = S(stream);
     Cursor ce(pack_enc), cb(pack_bn), ck(pack_block), cc(pack_caf), cs(pack_s3), cd(pack_dec);
     const SepPacks k{EncPack(ce), BnPack(cb), BlockPack::make(ck, rnn_kind), CafPack(cc), S3Pack(cs), DecPack(cd)};
-    if (np == 1) return separator_part(k, wav, video_vp, out, B, L, T, Tv, repeats, parts[0], st, video_ready, K);
+    if (np == 1) return separator_part(k, wav, video_vp, out, B, L, T, Tv, repeats, parts[0], st, video_ready, K, tfirst[1], mix_of, 0);
     // part 0 on the caller's stream, parts 1.. on side streams forked from it and joined back into it
     std::vector<RtfsSide> side(np);
     for (int i = 1; i < np; ++i) {
@@ -1178,9 +1195,9 @@ static int separator_run(const float* wav, const float* video_vp, const float* p
     int rc = RTFS_OK;
     for (int i = 0; i < np && rc == RTFS_OK; ++i) {
         const int first = (B * i) / np, nb = (B * (i + 1)) / np - first;
-        const size_t t0 = (size_t)first * KT;  // first target of the part
+        const size_t t0 = (size_t)tfirst[i];  // first target of the part (first * K with K targets per mixture)
         rc = separator_part(k, wav + (size_t)first * L, video_vp + t0 * 512 * Tv, out + t0 * L, nb, L, T, Tv, repeats, parts[i],
-                            i == 0 ? st : side[i].stream, video_ready, K);
+                            i == 0 ? st : side[i].stream, video_ready, K, tfirst[i + 1] - tfirst[i], mix_of ? mix_of + t0 : nullptr, first);
     }
     for (int i = 1; i < np; ++i)  // join even after a failed launch: the caller's stream must not run ahead of work already queued
         if (hipEventRecord(side[i].join, side[i].stream) != hipSuccess || hipStreamWaitEvent(st, side[i].join, 0) != hipSuccess) return RTFS_ERR_LAUNCH;
@@ -1227,6 +1244,48 @@ int rtfs_separator_speakers_f32(const float* wav, const float* video_vp, const f
     RTFS_RETURN_IF(P < 64 || (size_t)256 * pitch(P) * 4 >= ((size_t)1 << 31), RTFS_ERR_SHAPE);
     return separator_run(wav, video_vp, pack_enc, pack_bn, pack_block, pack_caf, pack_s3, pack_dec, out, B, K, L, Tv, repeats, ws, ws_bytes, stream,
                          video_ready, rnn_kind, split);
+}
+
+// ------------------------------------------------------------ a different number of targets per mixture
+// counts (host, B) -> N = sum(counts), or -1 for a bad argument
+static long long targets_total(const int* counts, int B, int L, int Tv, int split) {
+    if (!counts || !speakers_args_ok(B, 1, L, Tv, split)) return -1;
+    long long n = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 1 || counts[b] > RTFS_MAX_SPEAKERS) return -1;
+        n += counts[b];
+    }
+    return n > 0x7fffffffLL ? -1 : n;
+}
+
+size_t rtfs_separator_targets_workspace_bytes(const int* counts, int B, int L, int Tv, int split) {
+    if (targets_total(counts, B, L, Tv, split) < 0) return 0;
+    Arena ar(nullptr, 0);
+    const int T = rtfs_num_frames(L), np = separator_parts(B, split);
+    for (int i = 0, b = 0; i < np; ++i) {
+        const int end = (B * (i + 1)) / np, nb = end - b;
+        int nt = 0;
+        for (; b < end; ++b) nt += counts[b];
+        SepWs w(ar, nb, T, Tv, pitch(T * NF), 1, nt);
+    }
+    return ar.off + 256;
+}
+
+int rtfs_separator_targets_f32(const float* wav, const float* video_vp, const int* counts, const int* mix_of, const float* pack_enc,
+                               const float* pack_bn, const float* pack_block, const float* pack_caf, const float* pack_s3, const float* pack_dec,
+                               float* out, int B, int N, int L, int Tv, int repeats, void* ws, size_t ws_bytes, void* stream, void* video_ready,
+                               int rnn_kind, int split) {
+    // every refusal comes before the first launch (and before any device call); mix_of is trusted to match counts
+    RTFS_RETURN_IF(!wav || !video_vp || !pack_enc || !pack_bn || !pack_block || !pack_caf || !pack_s3 || !pack_dec || !out, RTFS_ERR_ARG);
+    RTFS_RETURN_IF(!counts || !mix_of, RTFS_ERR_ARG);
+    RTFS_RETURN_IF(!speakers_args_ok(B, 1, L, Tv, split) || repeats < 2 || (rnn_kind != 0 && rnn_kind != 1), RTFS_ERR_ARG);
+    RTFS_RETURN_IF(targets_total(counts, B, L, Tv, split) != (long long)N, RTFS_ERR_ARG);
+    RTFS_RETURN_IF(gemm_f32(), RTFS_ERR_ARG);  // the exact-f32 A/B switch runs the unfused sequence, which has no shared prefix
+    const int T = rtfs_num_frames(L), P = T * NF;
+    RTFS_RETURN_IF(!shape_ok_block(B, T, NF, rnn_kind), RTFS_ERR_SHAPE);
+    RTFS_RETURN_IF(P < 64 || (size_t)256 * pitch(P) * 4 >= ((size_t)1 << 31), RTFS_ERR_SHAPE);  // as rtfs_separator_speakers_f32
+    return separator_run(wav, video_vp, pack_enc, pack_bn, pack_block, pack_caf, pack_s3, pack_dec, out, B, 1, L, Tv, repeats, ws, ws_bytes, stream,
+                         video_ready, rnn_kind, split, counts, mix_of);
 }
 
 // ------------------------------------------------------------ stand-alone SRU operator
@@ -1314,6 +1373,20 @@ int rtfs_longform_overlap_add_many_f32(const float* y, float* out, const long lo
                                        int n_src, int window, int hop, void* stream) {
     if (!y || !out || !table) return RTFS_ERR_ARG;
     return launch_longform_overlap_add_many(y, out, table, R, total_windows, out_floats, n_src, window, hop, (hipStream_t)stream);
+}
+int rtfs_longform_many_speakers_plan(const long long* L, const long long* Tv, const long long* K, int R, int window, int hop, long long* table,
+                                     long long* total_windows, long long* total_targets, long long* out_floats) {
+    return longform_many_speakers_plan(L, Tv, K, R, window, hop, table, total_windows, total_targets, out_floats);
+}
+int rtfs_longform_frame_many_speakers_f32(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win,
+                                          float* video_win, int R, int total_windows, int max_K, int window, int hop, void* stream) {
+    if (!wavs || !videos || !table || !wav_win || !video_win) return RTFS_ERR_ARG;
+    return launch_longform_frame_many_speakers(wavs, videos, table, wav_win, video_win, R, total_windows, max_K, window, hop, (hipStream_t)stream);
+}
+int rtfs_longform_overlap_add_many_speakers_f32(const float* y, float* out, const long long* table, int R, int total_windows,
+                                                long long out_floats, int window, int hop, void* stream) {
+    if (!y || !out || !table) return RTFS_ERR_ARG;
+    return launch_longform_overlap_add_many_speakers(y, out, table, R, total_windows, out_floats, window, hop, (hipStream_t)stream);
 }
 
 int rtfs_live_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R, int slots,

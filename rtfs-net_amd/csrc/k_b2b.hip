@@ -103,7 +103,9 @@ __global__ __launch_bounds__(B4_NT) void pws_b2b4_kernel(B2bArgs a, int ntiles, 
         const int wp0 = (tile - b * tiles_per_sample) * (B4_NT / 64 * 64) + wave * 64;  // first pixel of this wave (wave-uniform)
         if (wp0 < P) {
             // K targets per mixture (B2bArgs::xk / a1k): target b reads the mixture's expanded_0 / a1, writes its own residual / x_enc
-            const int bx = a.xk > 1 ? b / a.xk : b, ba = a.a1k > 1 ? b / a.a1k : b;
+            // a divisor of 0: the mixture comes from the target-to-mixture table (b is wave-uniform: one scalar load)
+            const int bt = (a.xk == 0 || a.a1k == 0) ? a.mix_of[b] - a.mix_base : b;
+            const int bx = a.xk > 1 ? b / a.xk : (a.xk == 0 ? bt : b), ba = a.a1k > 1 ? b / a.a1k : (a.a1k == 0 ? bt : b);
             const __amdgpu_buffer_rsrc_t xs = rsrc_of(a.x + (size_t)bx * 64 * CS + wp0);
             const __amdgpu_buffer_rsrc_t ress = rsrc_of(a.res + (size_t)b * 256 * CS + wp0);
             const __amdgpu_buffer_rsrc_t a1s = rsrc_of(a.a1 + (size_t)ba * 256 * CS + wp0);

@@ -183,6 +183,10 @@ namespace {
 
 constexpr int MANY_ALIGN = 32;  // floats: every recording's block of the flat output starts on a 128-byte line
 
+// TK (AVNet.separate_many_speakers): K_r lip tracks per recording.  The table of longform_many_speakers_plan carries two more columns,
+// [.. | K | trow0]: recording r's video is (K_r, 512, Tv_r), window n's K_r target rows are trow0[r] + n K_r + k - per recording the
+// (rows, K, 512, Wv) layout of longform_frame_speakers_kernel - and its result block is (K_r, L_r).  The audio window is written once.
+template <bool TK>
 __global__ __launch_bounds__(256) void longform_frame_many_kernel(const float* const* __restrict__ wavs, const float* const* __restrict__ videos,
                                                                   const long long* __restrict__ table, float* __restrict__ wav_win,
                                                                   float* __restrict__ video_win, int R, int window, int hop, int qa_pad) {
@@ -211,26 +215,33 @@ __global__ __launch_bounds__(256) void longform_frame_many_kernel(const float* c
         return;
     }
     q -= qa_pad;
-    if (q >= VCH * Wv / 4) return;
-    const float* src = videos[r];
+    const int per = VCH * Wv / 4;  // quads of one track's window
+    const int K = TK ? (int)table[5 * (size_t)R + r] : 1;
+    if (q >= K * per) return;
+    const int kt = TK ? q / per : 0, qk = q - kt * per;
+    const float* src = videos[r] + (size_t)kt * VCH * Tv;
+    const size_t trow = TK ? (size_t)(table[6 * (size_t)R + r] + (long long)n * K) : (size_t)row;  // the window's first target row
     const int f0 = (int)((long long)n * hop / SPF);
     float v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int j = 4 * q + k, c = j / Wv, f = j - c * Wv;
+        const int j = 4 * qk + k, c = j / Wv, f = j - c * Wv;
         const long long fr = (long long)f0 + f;
         v[k] = src[(size_t)c * Tv + (fr < Tv ? (int)fr : Tv - 1)];
     }
-    *(f32x4*)(video_win + (size_t)row * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
+    *(f32x4*)(video_win + trow * VCH * Wv + 4 * (size_t)q) = f32x4{v[0], v[1], v[2], v[3]};
 }
 
+template <bool TK>
 __global__ __launch_bounds__(256) void longform_ola_many_kernel(const float* __restrict__ y, float* __restrict__ out,
-                                                                const long long* __restrict__ table, long long out_floats, int R, int n_src,
+                                                                const long long* __restrict__ table, long long out_floats, int R, int n_src_,
                                                                 int window, int hop) {
     const long long g = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;  // flat index into the padded output
     if (g >= out_floats) return;
     const int r = many_find(table + 4 * (size_t)R, R, g);
-    const long long row0 = table[r];
+    // y rows of window n: (row0 + n) n_src + s; with K_r tracks trow0 + n K_r + s (n_src := K_r, row0 n_src := trow0)
+    const int n_src = TK ? (int)table[5 * (size_t)R + r] : n_src_;
+    const size_t yrow0 = TK ? (size_t)table[6 * (size_t)R + r] : (size_t)table[r] * n_src;
     const int N = (int)table[R + r], L = (int)table[2 * R + r];
     const long long total = (long long)n_src * L, e = g - table[4 * (size_t)R + r];  // this recording's (n_src, L) block, and the index into it
     if (e >= total) return;  // padding up to the next recording's line: never written
@@ -245,7 +256,7 @@ __global__ __launch_bounds__(256) void longform_ola_many_kernel(const float* __r
         float acc[4] = {0.f, 0.f, 0.f, 0.f}, ws[4] = {0.f, 0.f, 0.f, 0.f};
         for (int n = n_lo; n <= n_hi; ++n) {
             const int i = t0 - n * hop;
-            const f32x4 v = *(const f32x4*)(y + (((size_t)row0 + n) * n_src + s0) * window + i);
+            const f32x4 v = *(const f32x4*)(y + (yrow0 + (size_t)n * n_src + s0) * window + i);
             const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -272,7 +283,7 @@ __global__ __launch_bounds__(256) void longform_ola_many_kernel(const float* __r
             for (int n = n_lo; n <= n_hi; ++n) {
                 const int i = t - n * hop;
                 const float w = V == 0 ? 1.f : ola_weight(i, window, Vf);
-                acc += w * y[(((size_t)row0 + n) * n_src + s) * window + i];
+                acc += w * y[(yrow0 + (size_t)n * n_src + s) * window + i];
                 ws += w;
             }
             res[k] = acc / ws;
@@ -287,12 +298,16 @@ __global__ __launch_bounds__(256) void longform_ola_many_kernel(const float* __r
 
 }  // namespace
 
-int longform_many_plan(const long long* L, const long long* Tv, int R, int window, int hop, int n_src, long long* table, long long* total_windows,
-                       long long* out_floats) {
-    if (!L || !Tv || R < 1 || n_src < 1) return RTFS_ERR_ARG;
-    long long rows = 0, off = 0;
+// K null: n_src result rows per recording, 5 R table words.  K (longform_many_speakers_plan): K[r] lip tracks and result rows of
+// recording r, 7 R words [.. | K | trow0], trow0 the recording's first target row (targets of window n: trow0 + n K .. + K - 1).
+static int many_plan(const long long* L, const long long* Tv, const long long* K, int R, int window, int hop, int n_src_, long long* table,
+                     long long* total_windows, long long* total_targets, long long* out_floats) {
+    if (!L || !Tv || R < 1 || n_src_ < 1) return RTFS_ERR_ARG;
+    long long rows = 0, trows = 0, off = 0;
     for (int r = 0; r < R; ++r) {
         if (L[r] < 1 || Tv[r] < 1 || L[r] > 0x7fffffffLL || Tv[r] > 0x7fffffffLL) return RTFS_ERR_ARG;
+        if (K && (K[r] < 1 || K[r] > RTFS_MAX_SPEAKERS)) return RTFS_ERR_ARG;
+        const int n_src = K ? (int)K[r] : n_src_;
         int N = 0;
         const int e = longform_plan((int)L[r], (int)Tv[r], window, hop, &N);
         if (e != RTFS_OK) return e;
@@ -302,16 +317,33 @@ int longform_many_plan(const long long* L, const long long* Tv, int R, int windo
             table[2 * (size_t)R + r] = L[r];
             table[3 * (size_t)R + r] = Tv[r];
             table[4 * (size_t)R + r] = off;
+            if (K) {
+                table[5 * (size_t)R + r] = K[r];
+                table[6 * (size_t)R + r] = trows;
+            }
         }
         rows += N;
-        if (rows > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+        trows += (long long)N * n_src;
+        if (rows > 0x7fffffffLL || (K && trows > 0x7fffffffLL)) return RTFS_ERR_SHAPE;
         const long long block = ((long long)n_src * L[r] + MANY_ALIGN - 1) / MANY_ALIGN * MANY_ALIGN;  // n_src, L < 2^31: below 2^62
         if (off > (1LL << 62) - block) return RTFS_ERR_SHAPE;
         off += block;
     }
     if (total_windows) *total_windows = rows;
+    if (total_targets) *total_targets = trows;
     if (out_floats) *out_floats = off;
     return RTFS_OK;
+}
+
+int longform_many_plan(const long long* L, const long long* Tv, int R, int window, int hop, int n_src, long long* table, long long* total_windows,
+                       long long* out_floats) {
+    return many_plan(L, Tv, nullptr, R, window, hop, n_src, table, total_windows, nullptr, out_floats);
+}
+
+int longform_many_speakers_plan(const long long* L, const long long* Tv, const long long* K, int R, int window, int hop, long long* table,
+                                long long* total_windows, long long* total_targets, long long* out_floats) {
+    if (!K) return RTFS_ERR_ARG;
+    return many_plan(L, Tv, K, R, window, hop, 1, table, total_windows, total_targets, out_floats);
 }
 
 int launch_longform_frame_many(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win, float* video_win,
@@ -322,8 +354,25 @@ int launch_longform_frame_many(const float* const* wavs, const float* const* vid
     if ((((uintptr_t)wav_win) | ((uintptr_t)video_win)) & 15) return RTFS_ERR_ARG;
     if ((((uintptr_t)wavs) | ((uintptr_t)videos) | ((uintptr_t)table)) & 7) return RTFS_ERR_ARG;
     const int qa_pad = cdiv(window / 4, 64) * 64, qv = VCH * (window / SPF) / 4;
-    hipLaunchKernelGGL(longform_frame_many_kernel, dim3(total_windows, cdiv(qa_pad + qv, 256)), dim3(256), 0, st, wavs, videos, table, wav_win,
+    hipLaunchKernelGGL(longform_frame_many_kernel<false>, dim3(total_windows, cdiv(qa_pad + qv, 256)), dim3(256), 0, st, wavs, videos, table, wav_win,
                        video_win, R, window, hop, qa_pad);
+    return rtfs_launch_status();
+}
+
+// max_K: the largest K_r of the table (sizes the grid; a recording with fewer tracks leaves its surplus blocks idle)
+int launch_longform_frame_many_speakers(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win,
+                                        float* video_win, int R, int total_windows, int max_K, int window, int hop, hipStream_t st) {
+    const int e = longform_plan(1, 1, window, hop, nullptr);
+    if (e != RTFS_OK) return e;
+    if (max_K < 1 || max_K > RTFS_MAX_SPEAKERS) return RTFS_ERR_ARG;
+    if (R < 1 || total_windows < R) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)wav_win) | ((uintptr_t)video_win)) & 15) return RTFS_ERR_ARG;
+    if ((((uintptr_t)wavs) | ((uintptr_t)videos) | ((uintptr_t)table)) & 7) return RTFS_ERR_ARG;
+    const int qa_pad = cdiv(window / 4, 64) * 64;
+    const long long quads = qa_pad + (long long)max_K * VCH * (window / SPF) / 4;
+    if ((quads + 255) / 256 > 65535) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(longform_frame_many_kernel<true>, dim3(total_windows, (unsigned)((quads + 255) / 256)), dim3(256), 0, st, wavs, videos, table,
+                       wav_win, video_win, R, window, hop, qa_pad);
     return rtfs_launch_status();
 }
 
@@ -336,6 +385,19 @@ int launch_longform_overlap_add_many(const float* y, float* out, const long long
     if (((uintptr_t)table) & 7) return RTFS_ERR_ARG;
     const long long blocks = (out_floats + 1023) / 1024;
     if (blocks > 0x7fffffffLL) return RTFS_ERR_SHAPE;
-    hipLaunchKernelGGL(longform_ola_many_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, out, table, out_floats, R, n_src, window, hop);
+    hipLaunchKernelGGL(longform_ola_many_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, y, out, table, out_floats, R, n_src, window, hop);
+    return rtfs_launch_status();
+}
+
+int launch_longform_overlap_add_many_speakers(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
+                                              int window, int hop, hipStream_t st) {
+    const int e = longform_plan(1, 1, window, hop, nullptr);
+    if (e != RTFS_OK) return e;
+    if (R < 1 || total_windows < R || out_floats < MANY_ALIGN || out_floats % MANY_ALIGN) return RTFS_ERR_SHAPE;
+    if ((((uintptr_t)y) | ((uintptr_t)out)) & 15) return RTFS_ERR_ARG;
+    if (((uintptr_t)table) & 7) return RTFS_ERR_ARG;
+    const long long blocks = (out_floats + 1023) / 1024;
+    if (blocks > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(longform_ola_many_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, y, out, table, out_floats, R, 1, window, hop);
     return rtfs_launch_status();
 }

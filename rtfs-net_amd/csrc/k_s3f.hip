@@ -259,7 +259,7 @@ __global__ __launch_bounds__(F_NT) void tail_s3t_kernel(TailS3Args a, int ntiles
         }
         mfma_v_fence(acc1[0], acc1[1]);  // the dropped tile of "chunk 9" is still being written: nothing may move into its registers yet (tools/isa_check.py)
         // the epilogue's spectrogram taps and first encoder fragments (the residual-conv operand is dead now: their registers)
-        const int bm = a.K > 1 ? b / a.K : b;  // the mixture of target b (TailS3Args::K)
+        const int bm = a.K > 1 ? b / a.K : (a.K == 0 ? a.mix_of[b] - a.mix_base : b);  // the mixture of target b (TailS3Args::K; 0: by table)
         patch_load(spec_rsrc(a.spec + (size_t)bm * 2 * P, P), wp0 + 2 * r, h, P, a.F, V);
         load_ea(0);
         // ---- mask, complex product with the encoder output, taps GEMM (k_pwr.hip PWR_S3T), eight encoder rows (one K step of the taps GEMM) at a time

@@ -84,7 +84,11 @@ struct B2bArgs {
     int a1_mode = 1;
     // k_b2b.hip only, separation of K targets per mixture (rtfs_separator_speakers_f32): the launch runs over targets t, and reads `x` of
     // sample t / xk and `a1` of sample t / a1k (1 = the sample itself).  `res` and `xenc` are always the target's own.
+    // A different number of targets per mixture (rtfs_separator_targets_f32): a divisor of 0 reads the sample from the table instead,
+    // mix_of[t] - mix_base (mix_of: DEVICE, one int per target of this launch; mix_base: the first mixture of the launch's batch part).
     int xk = 1, a1k = 1;
+    const int* mix_of = nullptr;
+    int mix_base = 0;
 };
 int launch_pws_b2b(const B2bArgs& a, int B, hipStream_t st);
 bool launch_pws_b2b4_qualifies(const B2bArgs& a);
@@ -134,6 +138,9 @@ struct TailS3Args {
     int P = 0, cs = 0, cout_live = 0;
     unsigned* tile_ctr = nullptr;
     int K = 1;  // targets per mixture: target t reads `spec` and `stats` of mixture t / K (the a0 it rebuilds is the mixture's)
+    // K = 0 (rtfs_separator_targets_f32): the mixture is mix_of[t] - mix_base, as in B2bArgs
+    const int* mix_of = nullptr;
+    int mix_base = 0;
 };
 int launch_tail_s3t(const TailS3Args& a, int B, hipStream_t st);
 int launch_pws_head4(const PwArgs& a, int B, hipStream_t st);  // block head on padded rows (k_b2b.hip); RTFS_ERR_ARG = use launch_pws_gateway_proj
@@ -340,6 +347,13 @@ int launch_longform_frame_many(const float* const* wavs, const float* const* vid
                                int R, int total_windows, int window, int hop, hipStream_t st);
 int launch_longform_overlap_add_many(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
                                      int n_src, int window, int hop, hipStream_t st);
+// the same with K_r lip tracks per recording (AVNet.separate_many_speakers): 7 R table words [.. | K | trow0], target row trow0 + n K + k
+int longform_many_speakers_plan(const long long* L, const long long* Tv, const long long* K, int R, int window, int hop, long long* table,
+                                long long* total_windows, long long* total_targets, long long* out_floats);
+int launch_longform_frame_many_speakers(const float* const* wavs, const float* const* videos, const long long* table, float* wav_win,
+                                        float* video_win, int R, int total_windows, int max_K, int window, int hop, hipStream_t st);
+int launch_longform_overlap_add_many_speakers(const float* y, float* out, const long long* table, int R, int total_windows, long long out_floats,
+                                              int window, int hop, hipStream_t st);
 
 // live streams chunk by chunk (k_live.hip): tick plan (host), chunk ingest + framing in one launch, overlap-add with a carried accumulator
 int live_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R, int slots,

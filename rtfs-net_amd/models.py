@@ -595,6 +595,36 @@ def _window_args(model, who, window, hop, max_batch, L=1, Tv=1):
     return window, hop, max_batch, n_win.value
 
 
+def mixture_counts(counts, B, N, who="separate_speakers"):
+    """``counts`` of a ragged ``separate_speakers`` call as a tuple of B ints, checked: one count per mixture, each 1 .. MAX_SPEAKERS,
+    summing to the N lip tracks.  ValueError otherwise."""
+    try:
+        counts = tuple(int(c) for c in counts)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: counts must be a sequence of integers") from None
+    if len(counts) != B:
+        raise ValueError(f"{who}: {B} mixture(s) but {len(counts)} count(s)")
+    if any(not 1 <= c <= MAX_SPEAKERS for c in counts):
+        raise ValueError(f"{who}: counts {counts}: every mixture needs 1 .. {MAX_SPEAKERS} targets")
+    if sum(counts) != N:
+        raise ValueError(f"{who}: counts sum to {sum(counts)} but there are {N} lip tracks")
+    return counts
+
+
+def chunk_windows(counts, max_batch):
+    """The chunks of ``separate_many_speakers``: consecutive windows whose targets total at most ``max_batch``; a window with more
+    targets than ``max_batch`` goes alone.  counts[w] = targets of window w -> [(w0, w1, t0, t1)], windows [w0, w1) = targets [t0, t1)."""
+    chunks, w0, t0, t = [], 0, 0, 0
+    for w, c in enumerate(counts):
+        if w > w0 and t - t0 + c > max_batch:
+            chunks.append((w0, w, t0, t))
+            w0, t0 = w, t
+        t += c
+    if len(counts) > w0:
+        chunks.append((w0, len(counts), t0, t))
+    return chunks
+
+
 
 # ----------------------------------------------------------------------------- top-level model
 class BaseAVModel(nn.Module):
@@ -707,14 +737,23 @@ class AVNet(BaseAVModel):
                    "rtfs_separator_forward_ex_f32")
         return out
 
-    def separate_speakers(self, audio_mixture, mouth_embeddings):
+    def separate_speakers(self, audio_mixture, mouth_embeddings, counts=None):
         """K target speakers of each mixture in one pass (inference only).  audio_mixture (B,L)|(L)|(B,1,L), mouth_embeddings (B,K,512,Tv)
         -> (B,K,L), where [b, k] is what ``forward`` returns for mixture b with lips k.  The reference separates a mixture once per speaker
         (its evaluation batch lists each mixture once per speaker: test.py:128-140, avspeech_dataset.py:81-84); only the part before the
         CAF depends on the audio alone (refinement_module.py:45-62), so the encoder, the bottleneck and block 0 run once per mixture here.
         Wherever ``forward`` takes the fused separator this is one C call (rtfs_separator_speakers_f32); otherwise (GRU cell, past the
         fused length, a single repeat, ``fused = False``, RTFS_GEMM_F32=1, K > 16) the same modules composed, with block 0's output, the
-        a1 residual and the encoder output repeated K times after block 0."""
+        a1 residual and the encoder output repeated K times after block 0.
+
+        ``counts`` (a sequence of B ints, DESIGN.md "A different number of faces per mixture"): mixture b has counts[b] targets, 1 .. 16
+        each; mouth_embeddings is then (N,512,Tv) with N = sum(counts), mixture-major, and the result is (N,L): row t is what ``forward``
+        returns for the mixture of target t with lips t.  One C call (rtfs_separator_targets_f32) wherever the fixed-K call is one, the
+        composed modules with ``repeat_interleave(counts)`` wherever it composes.  The device table of the targets' mixtures is cached per
+        (counts, device): a repeated call with the same counts uploads nothing and can be captured in a HIP graph.  ValueError, before any
+        launch, for counts of the wrong length, a count outside 1 .. 16, sum(counts) != N or n_src != 1."""
+        if counts is not None:
+            return self._separate_targets(audio_mixture, mouth_embeddings, counts)
         if audio_mixture.ndim not in (1, 2, 3) or (audio_mixture.ndim == 3 and audio_mixture.shape[1] != 1):
             raise ValueError(f"separate_speakers: audio_mixture must be (B,L), (L) or (B,1,L); got {tuple(audio_mixture.shape)}")
         wav = STFTEncoder.unsqueeze_to_2D(audio_mixture)
@@ -759,9 +798,63 @@ class AVNet(BaseAVModel):
                    "rtfs_separator_speakers_f32")
         return out
 
-    def _separate_speakers_composed(self, wav, video, K, train_kernels):
+    def _mix_table(self, counts, device):
+        """(host int array of the counts, DEVICE int32 table mix_of[t] = mixture of target t), built and uploaded once per (counts, device)."""
+        tables = self.__dict__.setdefault("_mix_tables", {})
+        key = (counts, device.type, device.index)
+        if key not in tables:
+            mix_of = [b for b, c in enumerate(counts) for _ in range(c)]
+            tables[key] = ((ctypes.c_int * len(counts))(*counts), torch.tensor(mix_of, dtype=torch.int32).to(device))
+        return tables[key]
+
+    def _separate_targets(self, audio_mixture, lips, counts):
+        """``separate_speakers`` with ``counts``: (B,L), (N,512,Tv) -> (N,L)."""
+        if audio_mixture.ndim not in (1, 2, 3) or (audio_mixture.ndim == 3 and audio_mixture.shape[1] != 1):
+            raise ValueError(f"separate_speakers: audio_mixture must be (B,L), (L) or (B,1,L); got {tuple(audio_mixture.shape)}")
+        wav = STFTEncoder.unsqueeze_to_2D(audio_mixture)
+        if lips.ndim != 3:
+            raise ValueError(f"separate_speakers: with counts, mouth_embeddings must be (N,512,Tv); got {tuple(lips.shape)}")
+        B, L = wav.shape
+        N = int(lips.shape[0])
+        counts = mixture_counts(counts, B, N)
+        if self.n_src != 1:
+            raise ValueError("separate_speakers: target-speaker models only (n_src 1)")
+        if self.training:
+            raise RuntimeError("AVNet.separate_speakers is inference only: call .eval()")
+        _lib.need_gpu(wav, lips)
+        rm = self.refinement_module
+        blk = rm.audio_net.get_block(0)
+        repeats = int(self.audio_params["repeats"])
+        lib = _lib.load()
+        too_long = int(lib.rtfs_num_frames(int(L))) // 2 > layers.fused_max_block_sweep(blk.rnn_kind)
+        if not self.fused or too_long or repeats < 2 or os.environ.get("RTFS_GEMM_F32", "")[:1] == "1":
+            return self._separate_speakers_composed(wav, lips, None, too_long, counts)
+        wav = wav.contiguous()
+        n_of, mix_of = self._mix_table(counts, wav.device)
+        # VP block of the N tracks on the side stream, as in forward
+        main = torch.cuda.current_stream(wav.device)
+        side = self._side_stream(wav.device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            vp = rm.video_net.get_block(0)(self.video_bottleneck(lips)).contiguous()
+            ready = torch.cuda.Event()
+            ready.record(side)
+        vp.record_stream(main)
+        Tv = vp.shape[-1]
+        out = _lib.empty(N, L, device=wav.device, dtype=torch.float32)
+        split = int(getattr(self, "batch_split", 0) or 0)
+        ws = _lib.workspace(lib.rtfs_separator_targets_workspace_bytes(n_of, B, L, Tv, split), wav.device)
+        packs = [self.encoder.pack(), self.audio_bottleneck.pack(), blk.pack(), rm.crossmodal_fusion.get_fusion_block(0).audio_lstm.pack(),
+                 self.mask_generator.pack(), self.decoder.pack()]
+        _lib.check(lib.rtfs_separator_targets_f32(_lib.ptr(wav), _lib.ptr(vp), n_of, _lib.ptr(mix_of), *[_lib.ptr(p) for p in packs],
+                                                  _lib.ptr(out), B, N, L, Tv, repeats, _lib.ptr(ws), ws.numel(), _lib.stream_of(wav),
+                                                  ctypes.c_void_p(ready.cuda_event), blk.rnn_kind, split),
+                   "rtfs_separator_targets_f32")
+        return out
+
+    def _separate_speakers_composed(self, wav, video, K, train_kernels, counts=None):
         """separate_speakers from the modules: the prefix on the B mixtures, then K copies of block 0's output, the a1 residual and the
-        encoder output.  ``train_kernels``: the routes ``forward`` takes with the unfused kernels (forward_train under force_train_kernels);
+        encoder output (``counts``: counts[b] copies of mixture b's, result (N,L)).  ``train_kernels``: the routes ``forward`` takes with the unfused kernels (forward_train under force_train_kernels);
         otherwise the per-module inference entry points of forward_modular."""
         rm = self.refinement_module
         blk = rm.audio_net.get_block(0)
@@ -775,11 +868,14 @@ class AVNet(BaseAVModel):
                 emb, stats = self.encoder(wav, return_stats=True)
                 a_res = self.audio_bottleneck(emb, stats)
             audio = blk(a_res)
-            audio, a_res, emb = (t.repeat_interleave(K, 0) for t in (audio, a_res, emb))
+            rep = K if counts is None else torch.tensor(counts, device=wav.device)
+            audio, a_res, emb = (t.repeat_interleave(rep, 0) for t in (audio, a_res, emb))
             audio, _ = rm.crossmodal_fusion.get_fusion_block(0)(audio, video)
             for _ in range(rm.audio_repeats):
                 audio = blk(audio, a_res)
             sep = self.mask_generator(audio, emb)
+            if counts is not None:
+                return self.decoder(sep, (sum(counts), L)).view(sum(counts), L)
             return self.decoder(sep, (B * K, L)).view(B, K, L)
 
     def separate_long(self, audio_mixture, mouth_embedding, window=32000, hop=None, max_batch=32):
@@ -964,6 +1060,99 @@ class AVNet(BaseAVModel):
             _lib.check(lib.rtfs_longform_overlap_add_many_f32(_lib.ptr(y), _lib.ptr(out), _lib.ptr(tab), R, S, int(floats.value), n_src,
                                                               window, hop, _lib.stream_of(xw)), "rtfs_longform_overlap_add_many_f32")
             return [out[int(o):int(o) + n_src * int(w.shape[0])].view(n_src, int(w.shape[0])) for o, w in zip(offs, wavs)]
+
+    def separate_many_speakers(self, mixtures, lips, window=32000, hop=None, max_batch=32):
+        """R recordings of different lengths, each with its own number of faces, in one pooled pass with one audio pass per window
+        (inference only; DESIGN.md "A different number of faces per mixture").  mixtures: R float32 tensors (L_r)|(1,L_r); lips: R
+        contiguous-able tensors (K_r,512,Tv_r) at 25 fps, 1 <= K_r <= 16; n_src 1 -> a list of R tensors (K_r,L_r), where [r][k] is what
+        ``separate_many`` gives for recording r with lips [r][k].
+
+        Every recording is planned as in ``separate_many`` (rtfs_longform_many_speakers_plan, the single place with the arithmetic): the
+        sum(N_r) windows lie in recording order, then window order, and window n of recording r owns the K_r target rows trow0[r] + n K_r
+        + k.  One launch frames each audio window once and its K_r video windows (rtfs_longform_frame_many_speakers_f32).  Chunks are
+        consecutive windows whose targets total at most ``max_batch`` (a window with K_r > max_batch goes alone), so they straddle
+        recordings; each chunk is ONE ragged ``separate_speakers`` call with its windows' counts.  One launch cross-fades into one flat
+        output (rtfs_longform_overlap_add_many_speakers_f32) whose (K_r, L_r) blocks start on 128-byte lines.  ``separate_long_speakers``
+        with a different K per recording is the special case of equal lengths.
+
+        Peak memory on top of the inputs, with S = sum(N_r) and T = sum(N_r K_r): the framed audio, S*window floats, the framed video and
+        the results, T*(512*(window/640) + window) floats, the flat output, sum_r 32*ceil(K_r*L_r/32) floats, 72 R bytes of tables, and
+        ONE chunk's ragged call.  Not capturable in a HIP graph (the table upload), like ``separate_many``.
+
+        ValueError, before the first launch, for what ``separate_many`` refuses and for a K_r outside 1 .. 16 or n_src != 1; RuntimeError
+        in ``.train()`` mode.  With ``fused = False``, or on CPU tensors, the same plan runs with ``forward_modular`` on the windows
+        repeated K_r times and the gathers restated in torch."""
+        who = "separate_many_speakers"
+        try:
+            mixtures, lips = list(mixtures), list(lips)
+        except TypeError:
+            raise ValueError(f"{who}: mixtures and lips must be sequences of tensors") from None
+        R = len(mixtures)
+        if R < 1 or len(lips) != R:
+            raise ValueError(f"{who}: {R} mixture(s) and {len(lips)} lip tensor(s); need the same number, at least 1")
+        if self.n_src != 1:
+            raise ValueError(f"{who}: target-speaker models only (n_src 1)")
+        wavs, videos = [], []
+        for r, (w, v) in enumerate(zip(mixtures, lips)):
+            if not isinstance(w, torch.Tensor) or not isinstance(v, torch.Tensor):
+                raise ValueError(f"{who}: recording {r} is not a pair of tensors")
+            if w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1) or w.shape[-1] < 1:
+                raise ValueError(f"{who}: mixture {r} must be (L) or (1,L) with L >= 1; got {tuple(w.shape)}")
+            if v.ndim != 3 or v.shape[1] != 512 or v.shape[2] < 1:
+                raise ValueError(f"{who}: lips {r} must be (K,512,Tv) with Tv >= 1; got {tuple(v.shape)}")
+            if not 1 <= v.shape[0] <= MAX_SPEAKERS:
+                raise ValueError(f"{who}: recording {r} has K = {v.shape[0]} target speakers; 1 .. {MAX_SPEAKERS}")
+            if w.dtype != torch.float32 or v.dtype != torch.float32:
+                raise ValueError(f"{who}: recording {r} is {w.dtype} / {v.dtype}; the kernels are float32")
+            if w.device != mixtures[0].device or v.device != mixtures[0].device:
+                raise ValueError(f"{who}: recording {r} lies on {w.device} / {v.device}, recording 0 on {mixtures[0].device}")
+            wavs.append(w.reshape(-1))
+            videos.append(v)
+        window, hop, max_batch, _ = _window_args(self, who, window, hop, max_batch)
+        lib = _lib.load()
+        Ls = (ctypes.c_longlong * R)(*[int(w.shape[0]) for w in wavs])
+        Tvs = (ctypes.c_longlong * R)(*[int(v.shape[2]) for v in videos])
+        Ks = (ctypes.c_longlong * R)(*[int(v.shape[0]) for v in videos])
+        table = (ctypes.c_longlong * (7 * R))()
+        rows, targets, floats = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_longlong(0)
+        if lib.rtfs_longform_many_speakers_plan(Ls, Tvs, Ks, R, window, hop, table, ctypes.byref(rows), ctypes.byref(targets),
+                                                ctypes.byref(floats)) != 0:
+            raise ValueError(f"{who}: {R} recordings with window = {window}, hop = {hop} need more than 2^31 - 1 windows or targets "
+                             f"(or a length is past int32)")
+        S, T, Wv, device = int(rows.value), int(targets.value), window // LONGFORM_SPF, wavs[0].device
+        Ns, offs, trow0 = table[R:2 * R], table[4 * R:5 * R], table[6 * R:7 * R]
+        counts = [int(K) for K, N in zip(Ks, Ns) for _ in range(int(N))]  # targets of every window, in row order
+        on_hip = self.fused and device.type == "cuda"
+        with torch.no_grad():
+            if on_hip:
+                wavs, videos = [w.contiguous() for w in wavs], [v.contiguous() for v in videos]
+                words = list(table) + [w.data_ptr() for w in wavs] + [v.data_ptr() for v in videos]
+                tab = torch.tensor(words, dtype=torch.int64).to(device)  # the one host-to-device copy
+                t_wav, t_vid = tab[7 * R:8 * R], tab[8 * R:9 * R]
+                xw = _lib.empty(S, window, device=device, dtype=torch.float32)
+                vw = _lib.empty(T, 512, Wv, device=device, dtype=torch.float32)
+                _lib.check(lib.rtfs_longform_frame_many_speakers_f32(_lib.ptr(t_wav), _lib.ptr(t_vid), _lib.ptr(tab), _lib.ptr(xw), _lib.ptr(vw),
+                                                                     R, S, max(Ks), window, hop, _lib.stream_of(xw)),
+                           "rtfs_longform_frame_many_speakers_f32")
+            else:
+                framed = [_longform_frame_torch(w[None], v.reshape(1, -1, v.shape[2]), int(N), window, hop) for w, v, N in zip(wavs, videos, Ns)]
+                xw = torch.cat([f[0] for f in framed])
+                vw = torch.cat([f[1].reshape(-1, 512, Wv) for f in framed])
+            y = _lib.empty(T, window, device=device, dtype=torch.float32)
+            for w0, w1, t0, t1 in chunk_windows(counts, max_batch):
+                if on_hip:
+                    y[t0:t1].copy_(self.separate_speakers(xw[w0:w1], vw[t0:t1], counts=counts[w0:w1]))
+                else:  # target k of a window = the model on that window with lips k
+                    rep = torch.tensor(counts[w0:w1], device=device)
+                    y[t0:t1].copy_(self.forward_modular(xw[w0:w1].repeat_interleave(rep, 0), vw[t0:t1])[:, 0])
+            if not on_hip:
+                return [_longform_overlap_add_torch(y[int(a):int(a) + int(N) * int(K)], 1, int(N), int(w.shape[0]), window, hop)[0]
+                        for a, N, K, w in zip(trow0, Ns, Ks, wavs)]
+            out = _lib.empty(int(floats.value), device=device, dtype=torch.float32)
+            _lib.check(lib.rtfs_longform_overlap_add_many_speakers_f32(_lib.ptr(y), _lib.ptr(out), _lib.ptr(tab), R, S, int(floats.value),
+                                                                       window, hop, _lib.stream_of(xw)),
+                       "rtfs_longform_overlap_add_many_speakers_f32")
+            return [out[int(o):int(o) + int(K) * int(w.shape[0])].view(int(K), int(w.shape[0])) for o, K, w in zip(offs, Ks, wavs)]
 
     def open_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000, speakers=1):
         """``slots`` live streams separated chunk by chunk (inference only; DESIGN.md "Live streams") -> ``streaming.StreamPool``.  The

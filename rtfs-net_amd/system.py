@@ -36,10 +36,22 @@ class System(nn.Module):
             mouth_emb = self.video_model(mouth.type_as(wav))
         return self.audio_model(wav, mouth_emb)
 
-    def separate_speakers(self, wav, mouths):
+    def separate_speakers(self, wav, mouths, counts=None):
         """Every target speaker of each mixture with one audio pass (inference): wav (B,L), mouths (B,K,1,Tv,88,88) -> (B,K,L).  The video
         front-end runs on the B*K mouth tracks (no_grad, as in ``forward``), then ``AVNet.separate_speakers``.  Without a video model the
-        mouth slot holds lip embeddings (B,K,512,Tv)."""
+        mouth slot holds lip embeddings (B,K,512,Tv).
+
+        ``counts`` (B ints): mixture b has counts[b] faces; mouths is (N,1,Tv,88,88), N = sum(counts), mixture-major, and the result (N,L).
+        The video front-end runs ONCE on the N tracks.  Without a video model the mouth slot holds lip embeddings (N,512,Tv)."""
+        if counts is not None:
+            if self.video_model is None:
+                return self.audio_model.separate_speakers(wav, mouths, counts=counts)
+            from .models import mixture_counts
+            B = 1 if wav.ndim == 1 else int(wav.shape[0])
+            counts = mixture_counts(counts, B, int(mouths.shape[0]), "System.separate_speakers")  # before the video model's launches
+            with torch.no_grad():
+                emb = self.video_model(mouths.type_as(wav))
+            return self.audio_model.separate_speakers(wav, emb, counts=counts)
         if mouths.ndim < 3:
             raise ValueError(f"System.separate_speakers: mouths must be (B,K,...); got {tuple(mouths.shape)}")
         B, K = int(mouths.shape[0]), int(mouths.shape[1])
@@ -113,6 +125,31 @@ class System(nn.Module):
                 for g, r in enumerate(rs):
                     embs[r] = emb[g]
         return self.audio_model.separate_many(wavs, embs, **kw)
+
+    def separate_many_speakers(self, wavs, mouths, **kw):
+        """Many recordings, each with its own number of faces, in one pooled pass (inference): wavs = R tensors (L_r)|(1,L_r), mouths = R
+        tensors (K_r,1,Tv_r,88,88) at 25 fps -> a list of R tensors (K_r,L_r).  The video front-end runs under no_grad ONCE PER GROUP of
+        recordings with equal Tv_r, all tracks of the group as one batch, as in ``separate_many``; the embeddings and ``**kw`` go to
+        ``AVNet.separate_many_speakers``.  Without a video model the mouth slot holds lip embeddings (K_r,512,Tv_r)."""
+        wavs, mouths = list(wavs), list(mouths)
+        if self.video_model is None:
+            return self.audio_model.separate_many_speakers(wavs, mouths, **kw)
+        if len(wavs) < 1 or len(mouths) != len(wavs):
+            raise ValueError(f"System.separate_many_speakers: {len(wavs)} recording(s) and {len(mouths)} lip tensor(s); need the same "
+                             f"number, at least 1")
+        groups = {}
+        for r, m in enumerate(mouths):
+            if not isinstance(m, torch.Tensor) or m.ndim != 5 or m.shape[0] < 1 or m.shape[1] != 1 or m.shape[2] < 1:
+                raise ValueError(f"System.separate_many_speakers: lip tracks {r} must be (K,1,Tv,88,88) with K, Tv >= 1; "
+                                 f"got {tuple(m.shape) if isinstance(m, torch.Tensor) else type(m).__name__}")
+            groups.setdefault(int(m.shape[2]), []).append(r)
+        embs = [None] * len(mouths)
+        with torch.no_grad():
+            for rs in groups.values():
+                emb = self.video_model(torch.cat([mouths[r] for r in rs]).type_as(wavs[rs[0]]))  # (sum K,1,Tv,88,88) -> (sum K,512,Tv)
+                for r, e in zip(rs, emb.split([int(mouths[r].shape[0]) for r in rs])):
+                    embs[r] = e
+        return self.audio_model.separate_many_speakers(wavs, embs, **kw)
 
     def open_streams(self, sample_rate=16000, **kw):
         """Live streams chunk by chunk (inference): ``AVNet.open_streams(**kw)`` of the audio model.  The caller pushes lip EMBEDDINGS
@@ -193,19 +230,23 @@ class System(nn.Module):
         """``forward`` for a batch that may list each mixture once per target speaker, as the reference's test batches do (test.py:128-140,
         avspeech_dataset.py:81-84: n_src 1, no shuffling, the entries of one mixture side by side).  wav (N,L) or (N,1,L) -> (N,1,L) in
         input order.  Runs of bit-identical consecutive mixture rows are found with one device reduction and one host read; if every run has
-        the same length K > 1, the batch goes through ``separate_speakers`` (the audio prefix once per mixture), otherwise through
-        ``forward``.  Not capturable in a HIP graph: the routing reads the batch's contents back to the host."""
+        the same length K > 1, the batch goes through ``separate_speakers`` (the audio prefix once per mixture); runs of different lengths
+        (at most 16, at least one of 2 or more) go through ``separate_speakers`` with the run lengths as ``counts``; a batch without a
+        repeated mixture goes through ``forward``.  Not capturable in a HIP graph: the routing reads the batch's contents back to the host."""
         if mouth is None or wav.ndim not in (2, 3) or wav.shape[0] < 2 or wav.dtype != torch.float32:
             return self(wav, mouth)
         N = int(wav.shape[0])
         bits = wav.reshape(N, -1).contiguous().view(torch.int32)
         same = (bits[1:] == bits[:-1]).all(dim=1).tolist()  # row i + 1 repeats row i
         starts = [0] + [i + 1 for i, s in enumerate(same) if not s] + [N]
-        runs = {b - a for a, b in zip(starts[:-1], starts[1:])}
-        if len(runs) != 1 or min(runs) < 2:
-            return self(wav, mouth)
-        K = runs.pop()
+        counts = [b - a for a, b in zip(starts[:-1], starts[1:])]
+        runs = set(counts)
         L = bits.shape[1]
+        if max(runs) < 2 or (len(runs) != 1 and max(runs) > 16):
+            return self(wav, mouth)
+        if len(runs) != 1:  # a different number of targets per mixture: the first row of every run, the lips as they lie
+            return self.separate_speakers(wav.reshape(N, L)[starts[:-1]].contiguous(), mouth, counts=counts).reshape(N, 1, L)
+        K = runs.pop()
         out = self.separate_speakers(wav.reshape(N, L)[::K].contiguous(), mouth.reshape(N // K, K, *mouth.shape[1:]))
         return out.reshape(N, 1, L)
 
