@@ -573,6 +573,37 @@ int rtfs_live_ingest_frame_speakers_f32(const long long* table, float* aring, fl
 int rtfs_live_reset_speakers_f32(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int window, int max_chunk,
                                  void* stream);
 
+/* Faces that come and go (AVNet.open_streams(max_speakers = Kmax) / FaceStreamPool; DESIGN.md "Faces that come and go").  State is laid
+ * out as for K = Kmax above (rtfs_live_speakers_sizes_ok(window, hop, max_chunk, Kmax) is the size rule, rtfs_live_reset_speakers_f32 with
+ * K = Kmax the reset); a FACE is a plane 0 .. Kmax - 1 of its slot with a birth window b (host state, -1 = the plane is free): it takes
+ * part in window n iff n >= b, and its output is the stream from sample b hop on.  The counters (a, f, e, o) stay the slot's.
+ * rtfs_live_faces_plan (host only, the single place with the arithmetic): rtfs_live_plan plus births (R x Kmax, row-major, plane j of
+ *   named slot r) -> new_counters (R x 4), row_counts[rows] = the targets of every ready window in row order (row_cap = its capacity),
+ *   sizes[6] = [rows | targets | out_floats | max_span | largest n_audio | largest n_video] and the tick table,
+ *   RTFS_LIVE_FACES_PLAN_WORDS(Kmax) = 15 + 2 Kmax int64 words per named slot, column-major: the 13 words of rtfs_live_plan (row0 counts
+ *   window rows; out_off steps by the slot's (P, end - o) block) | P = faces present | trow0 = the slot's first target row | Kmax columns
+ *   plane of present face i, ascending, -1 behind the P-th | Kmax columns birth of present face i.  Present are the active faces of a
+ *   push; of a flush the faces with N > b and f > b hop / SPF (a window and a frame of their own).  Targets are window-major, within a
+ *   window the present faces with b <= n in ascending plane; face i of the block owns samples [max(o, b hop), end), the cells before are
+ *   never written.  Refusals as rtfs_live_plan's, and: Kmax outside [1, RTFS_MAX_SPEAKERS] or more ready windows than row_cap
+ *   (RTFS_LIVE_BAD_ARGUMENT), a birth below -1 or above ceil(f SPF / hop) (RTFS_LIVE_BAD_COUNTERS), a push to a slot without a face
+ *   (RTFS_LIVE_NO_FACES), a flush of a slot with samples in which no face takes part (RTFS_LIVE_NO_FRAMES).
+ * rtfs_live_ingest_frame_faces_f32 (one launch): table = the plan's words followed by 1 + Kmax columns [aptr | vptr of present face 0 |
+ *   ..], DEVICE addresses as for rtfs_live_ingest_frame_speakers_f32 (0 behind the P-th).  Appends the audio chunk once and each present
+ *   face's chunk to its plane; writes wav_win (rows, window) and video_win (targets, 512, window / SPF) at the ragged target rows.
+ * rtfs_live_overlap_add_faces_f32 (one launch): y (targets, window) -> the flat output; rtfs_live_overlap_add_f32 with the sums of face i
+ *   running over windows n >= b only; with every plane present and all births 0 it is that kernel operation for operation.
+ * Kmax outside [1, RTFS_MAX_SPEAKERS] or sizes rtfs_live_speakers_sizes_ok refuses: -4; an empty tick: RTFS_OK without a launch. */
+#define RTFS_LIVE_FACES_PLAN_WORDS(Kmax) (15 + 2 * (Kmax))
+#define RTFS_LIVE_NO_FACES 9
+int rtfs_live_faces_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R,
+                         int slots, int flush, int window, int hop, int max_chunk, int Kmax, const long long* births, int row_cap,
+                         long long* new_counters, long long* table, long long* row_counts, long long* sizes, int* refused);
+int rtfs_live_ingest_frame_faces_f32(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
+                                     int Kmax, int max_na, int max_nf, int window, int hop, int max_chunk, void* stream);
+int rtfs_live_overlap_add_faces_f32(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int Kmax,
+                                    int window, int hop, int max_chunk, int flush, void* stream);
+
 /* Video front-end (the step before the path): FRCNNVideoModel.forward with backbone_type "resnet",
  * relu_type "prelu", eval mode (src/models/videomodels/frcnn_videomodel.py:61-72, resnet.py:23-118).
  * lips (B, 1, T, 88, 88) grey-scale mouth crops -> out (B, 512, T), the lip embedding AVNet.forward takes.

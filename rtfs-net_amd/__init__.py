@@ -7,8 +7,8 @@ path runs in ``librtfs_amd.so`` (hand-written gfx950 HIP kernels behind the C AB
 from . import _lib, configs, datas, layers, losses, metrics, optimizers, packing, streaming, system, torch_utils, videomodels  # noqa: F401
 from .packing import invalidate_packs  # noqa: F401
 from .system import System  # noqa: F401
-from .streaming import (CameraStreamPool, LipStreamPool, RateStreamPool, ResampleStreamPool, SpeakerCameraStreamPool,  # noqa: F401
-                        SpeakerStreamPool, StreamPool)
+from .streaming import (CameraStreamPool, FaceCameraStreamPool, FaceStreamPool, LipStreamPool, RateStreamPool,  # noqa: F401
+                        ResampleStreamPool, SpeakerCameraStreamPool, SpeakerStreamPool, StreamPool)
 from .optimizers import make_optimizer  # noqa: F401
 from .metrics import ALLMetricsTracker, stoi  # noqa: F401
 from .datas import (Compose, Normalize, CenterCrop, RandomCrop, HorizontalFlip, get_preprocessing_pipelines, normalize_mixture,  # noqa: F401

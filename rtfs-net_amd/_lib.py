@@ -138,6 +138,9 @@ SIGNATURES = {
     "rtfs_live_speakers_sizes_ok": (_i, [_i, _i, _i, _i]),
     "rtfs_live_ingest_frame_speakers_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "rtfs_live_reset_speakers_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "rtfs_live_faces_plan": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p]),
+    "rtfs_live_ingest_frame_faces_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "rtfs_live_overlap_add_faces_f32": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _i, _i, _i, _i, _i, _p]),
     "rtfs_video_pack_floats": (_z, []),
     "rtfs_video_workspace_bytes": (_z, [_i, _i]),
     "rtfs_video_frontend_f32": (_i, [_p, _p, _p, _i, _i, _p, _z, _p]),

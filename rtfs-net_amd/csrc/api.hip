@@ -1422,6 +1422,24 @@ int rtfs_live_reset_speakers_f32(const long long* ids, float* aring, float* vrin
     return launch_live_reset(ids, aring, vring, acc, R, K, K, window, max_chunk, (hipStream_t)stream);
 }
 
+int rtfs_live_faces_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R,
+                         int slots, int flush, int window, int hop, int max_chunk, int Kmax, const long long* births, int row_cap,
+                         long long* new_counters, long long* table, long long* row_counts, long long* sizes, int* refused) {
+    return live_faces_plan(slot_ids, counters, n_audio, n_video, R, slots, flush, window, hop, max_chunk, Kmax, births, row_cap, new_counters,
+                           table, row_counts, sizes, refused);
+}
+int rtfs_live_ingest_frame_faces_f32(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
+                                     int Kmax, int max_na, int max_nf, int window, int hop, int max_chunk, void* stream) {
+    if (!table || !aring || !vring || !wav_win || !video_win) return RTFS_ERR_ARG;
+    return launch_live_ingest_frame_faces(table, aring, vring, wav_win, video_win, R, rows, Kmax, max_na, max_nf, window, hop, max_chunk,
+                                          (hipStream_t)stream);
+}
+int rtfs_live_overlap_add_faces_f32(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int Kmax,
+                                    int window, int hop, int max_chunk, int flush, void* stream) {
+    if (!table || !y || !acc || (!out && max_span > 0)) return RTFS_ERR_ARG;
+    return launch_live_overlap_add_faces(table, y, out, acc, R, max_span, Kmax, window, hop, max_chunk, flush, (hipStream_t)stream);
+}
+
 size_t rtfs_video_pack_floats(void) { return video_pack_floats(); }
 size_t rtfs_video_workspace_bytes(int B, int T) { return video_workspace_bytes(B, T); }
 int rtfs_video_frontend_f32(const float* lips, const float* pack, float* out, int B, int T, void* ws, size_t ws_bytes, void* stream) {

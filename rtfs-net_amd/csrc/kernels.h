@@ -369,6 +369,15 @@ int launch_live_overlap_add(const long long* table, const float* y, float* out, 
 int launch_live_reset(const long long* ids, float* aring, float* vring, float* acc, int R, int K, int n_acc, int window, int max_chunk,
                       hipStream_t st);
 
+// faces that come and go: Kmax planes per slot, a birth window per face; the table is documented at the faces section of k_live.hip
+int live_faces_plan(const long long* slot_ids, const long long* counters, const long long* n_audio, const long long* n_video, int R, int slots,
+                    int flush, int window, int hop, int max_chunk, int Kmax, const long long* births, int row_cap, long long* new_counters,
+                    long long* table, long long* row_counts, long long* sizes, int* refused);
+int launch_live_ingest_frame_faces(const long long* table, float* aring, float* vring, float* wav_win, float* video_win, int R, int rows,
+                                   int Kmax, int max_na, int max_nf, int window, int hop, int max_chunk, hipStream_t st);
+int launch_live_overlap_add_faces(const long long* table, const float* y, float* out, float* acc, int R, long long max_span, int Kmax,
+                                  int window, int hop, int max_chunk, int flush, hipStream_t st);
+
 // preparing raw recordings (k_prep.hip): uint8 mouth ROIs -> normalised lips, waveform normalisation, polyphase resampling
 int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,
                         hipStream_t st);

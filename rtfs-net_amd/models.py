@@ -1154,7 +1154,7 @@ class AVNet(BaseAVModel):
                        "rtfs_longform_overlap_add_many_speakers_f32")
             return [out[int(o):int(o) + int(K) * int(w.shape[0])].view(int(K), int(w.shape[0])) for o, K, w in zip(offs, Ks, wavs)]
 
-    def open_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000, speakers=1):
+    def open_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000, speakers=1, max_speakers=None):
         """``slots`` live streams separated chunk by chunk (inference only; DESIGN.md "Live streams") -> ``streaming.StreamPool``.  The
         stateful form of ``separate_long``: ``pool.push(slot_ids, audio_chunks, video_chunks)`` takes what arrived (audio chunks of at most
         ``max_chunk`` samples, default ``window``; lip embeddings (512,m) at 25 fps) and returns the samples no later window can touch;
@@ -1174,8 +1174,18 @@ class AVNet(BaseAVModel):
         ``flush`` return (K,k) per slot, and target k equals the single-track pool on the same audio with lips k.  The audio is stored,
         framed and run through the audio-only prefix once per window (``separate_speakers`` in chunks of max(1, max_batch // K) windows).
         ValueError for K outside 1 .. 16, n_src != 1, K * (window + max_chunk) > 2^24, and for ``speakers`` > 1 together with a
-        ``sample_rate`` other than 16000, which this pool does not take.  ``speakers`` = 1 is today's pool."""
+        ``sample_rate`` other than 16000, which this pool does not take.  ``speakers`` = 1 is today's pool.
+
+        ``max_speakers`` = Kmax (DESIGN.md "Faces that come and go"; 1 <= Kmax <= 16, n_src 1, 16 kHz) -> ``streaming.FaceStreamPool``:
+        every slot has room for Kmax faces, declared and ended with ``pool.add_face`` / ``pool.drop_face`` on an idle slot or in
+        mid-stream; a tick runs only the (window, face) targets that exist and ``push`` / ``flush`` return a dict face id -> samples per
+        slot.  ValueError together with ``speakers``, and for what ``speakers`` = Kmax would refuse."""
         from . import streaming
+        if max_speakers is not None:
+            if streaming.speakers_of(speakers) != 1:
+                raise ValueError("open_streams: speakers and max_speakers exclude each other")
+            return streaming.open_face_streams(self, slots, max_speakers, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch,
+                                               sample_rate=sample_rate)
         if streaming.speakers_of(speakers) == 1:
             return streaming.open_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, sample_rate=sample_rate)
         return streaming.open_speaker_streams(self, slots, speakers, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch,

@@ -20,11 +20,12 @@ SPF = 640  # samples per video frame: 16 kHz audio, 25 fps video
 FS = 16000  # the model's sample rate
 MAX_CAPACITY = 1 << 24  # RTFS_LIVE_MAX_CAPACITY: speakers * (window + max_chunk) at most, so that every launch grid fits
 MAX_SPEAKERS = 16  # RTFS_MAX_SPEAKERS: the most targets per mixture rtfs_separator_speakers_f32 fans out to
+FACES_PLAN_WORDS = 15  # RTFS_LIVE_FACES_PLAN_WORDS(Kmax) - 2 Kmax: the 13 of PLAN_WORDS | faces present | first target row
 PLAN_WORDS = 13  # RTFS_LIVE_PLAN_WORDS: [slot | a | na | f | nf | e | cnt | row0 | o | end | out_off | apos | fpos]
 _REASONS = {1: "bad argument", 2: "unknown slot id", 3: "slot named twice", 4: "chunk larger than max_chunk",
             5: "audio ran too far ahead of video: the push would overwrite samples a not-yet-emitted window needs",
             6: "video ran too far ahead of audio: the push would overwrite frames a not-yet-emitted window needs",
-            7: "flush of a stream with samples but no video frame", 8: "inconsistent counters"}
+            7: "flush of a stream with samples but no video frame", 8: "inconsistent counters", 9: "push to a slot without a face"}
 
 
 def _weights(window, hop, device):
@@ -355,6 +356,265 @@ class SpeakerStreamPool(StreamPool):
         return tracks
 
 
+
+class FaceStreamPool(StreamPool):
+    """``slots`` live streams whose faces come and go, on one target-speaker model (n_src 1, inference only; DESIGN.md "Faces that come
+    and go").  Built by ``AVNet.open_streams(..., max_speakers=Kmax)``.
+
+    Device state is a ``SpeakerStreamPool``'s with K = Kmax: every slot has Kmax PLANES of the video ring and of the accumulator, and a
+    *face* is a plane that is in use.  Host state per slot is the four counters plus a birth window per plane (-1 = free); nothing is
+    read back.  ``add_face`` / ``drop_face`` are host only, on an idle slot and in mid-stream: a face added when the slot has received
+    f frames is born at window b = ceil(f / (hop / 640)), takes part in the windows n >= b only, and its concatenated output equals
+    ``separate_long(audio[b hop:], lips[:, b hop / 640:])`` - what a single-track ``StreamPool`` started at that position gives; a
+    dropped face's output is the leading part of that.  Each tick runs exactly the (window, face) targets that exist, through
+    ``AVNet.separate_speakers(counts=)`` in the chunks of ``models.chunk_windows``; ``flush`` and ``reset`` clear the slot's faces."""
+
+    def __init__(self, model, slots, window, hop, max_chunk, max_batch, max_speakers):
+        super().__init__(model, slots, window, hop, max_chunk, max_batch, max_speakers)
+        self.max_speakers = self.speakers
+        self._births = [[-1] * self.speakers for _ in range(slots)]
+        self._yt = self._y.view(-1, window)  # the ragged target rows of a tick
+
+    # -- faces (host only)
+    def _slot(self, slot, who):
+        s = self._check_ids([slot])[0]
+        if not 0 <= s < self.slots:
+            raise ValueError(f"FaceStreamPool.{who}: slot {s} is not in [0, {self.slots})")
+        return s
+
+    def faces(self, slot):
+        """The active face ids of a slot, ascending."""
+        return [j for j, b in enumerate(self._births[self._slot(slot, "faces")]) if b >= 0]
+
+    def birth(self, slot, face):
+        """The birth window of an active face: its output starts at sample birth * hop of the slot's stream."""
+        b = self._births[self._slot(slot, "birth")][operator.index(face)]
+        if b < 0:
+            raise ValueError(f"FaceStreamPool.birth: face {face} of slot {slot} is not active")
+        return b
+
+    def add_face(self, slot, face=None):
+        """Declare a face on ``slot`` -> its id (the lowest free plane unless ``face`` names one).  No launch.  From the next push on
+        the slot's video chunk carries this face's track too; its first frame is stream frame f.  ValueError when no plane is free or
+        the plane is active."""
+        s = self._slot(slot, "add_face")
+        births = self._births[s]
+        if face is None:
+            free = [j for j, b in enumerate(births) if b < 0]
+            if not free:
+                raise ValueError(f"FaceStreamPool.add_face: slot {s} already has max_speakers = {self.max_speakers} faces")
+            j = free[0]
+        else:
+            j = self._check_ids([face])[0]
+            if not 0 <= j < self.max_speakers or births[j] >= 0:
+                raise ValueError(f"FaceStreamPool.add_face: face {j} of slot {s} is active or not in [0, {self.max_speakers})")
+        births[j] = -(-self._counters[s][1] // (self.hop // SPF))
+        return j
+
+    def drop_face(self, slot, face):
+        """End a face: it takes part in no later tick, what was returned for it is final, its plane is free.  No launch.  ValueError
+        for a face that is not active and for the last face of a slot that has received anything (flush or reset that slot)."""
+        s = self._slot(slot, "drop_face")
+        j = self._check_ids([face])[0]
+        births = self._births[s]
+        if not 0 <= j < self.max_speakers or births[j] < 0:
+            raise ValueError(f"FaceStreamPool.drop_face: face {j} of slot {s} is not active")
+        if sum(b >= 0 for b in births) == 1 and (self._counters[s][0] or self._counters[s][1]):
+            raise ValueError(f"FaceStreamPool.drop_face: face {j} is the last of slot {s}, which has received data; flush or reset the slot")
+        births[j] = -1
+
+    def push(self, slot_ids, audio_chunks, video_chunks):
+        """As ``SpeakerStreamPool.push``, with the video chunk of a slot holding one (512,m) track per ACTIVE face in ascending face id - a
+        sequence of separate allocations or one (faces,512,m) tensor - with one m.  Returns, per named slot, a dict face id -> (k_j,)
+        newly final samples of that face: views of one flat output whose per-slot blocks start on 128-byte lines.  ValueError - before
+        any launch, all state unchanged - for what ``StreamPool.push`` refuses, for a slot without a face, a wrong number of tracks and
+        tracks that differ in m."""
+        return super().push(slot_ids, audio_chunks, video_chunks)
+
+    def flush(self, slot_ids):
+        """End the named streams.  A face takes part if the long-form plan of the samples received has a window at or behind its birth
+        and it has a frame at or behind that window's start; another face returns (0,).  A slot with samples in which no face takes
+        part is refused (state unchanged).  The slots' faces are cleared: a new stream declares them again."""
+        return super().flush(slot_ids)
+
+    # -- checks
+    def _check_chunks(self, slot_ids, audio_chunks, video_chunks):
+        ids = self._check_ids(slot_ids)
+        if any(not 0 <= s < self.slots for s in ids):
+            raise ValueError(f"FaceStreamPool.push: slot ids {ids} must be in [0, {self.slots})")
+        self._expected = [sum(b >= 0 for b in self._births[s]) for s in ids]  # what _tracks_of(r, ..) asks of chunk r
+        return super()._check_chunks(ids, audio_chunks, video_chunks)
+
+    def _tracks_of(self, r, v):
+        K = self._expected[r] if r < len(self._expected) else 0
+        if K == 0:
+            raise ValueError(f"FaceStreamPool.push: the slot of chunk {r} has no face; add_face first")
+        if isinstance(v, torch.Tensor):
+            if v.ndim != 3:
+                raise ValueError(f"FaceStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m); got {tuple(v.shape)}")
+            tracks = list(v.unbind(0))
+        else:
+            try:
+                tracks = list(v)
+            except TypeError:
+                raise ValueError(f"FaceStreamPool.push: video chunk {r} must be ({K},512,m) or {K} tensors (512,m)") from None
+        if len(tracks) != K:
+            raise ValueError(f"FaceStreamPool.push: video chunk {r} holds {len(tracks)} track(s); its slot has {K} active face(s)")
+        return tracks
+
+    def _plan_faces(self, ids, na, nf, flush):
+        """``rtfs_live_faces_plan`` for the named slots -> (new counters, table, sizes, row_counts).  Nothing is changed."""
+        LL, Kmax, cap = ctypes.c_longlong, self.max_speakers, int(self._xw.shape[0])
+        births = (LL * (len(ids) * Kmax))(*[b for s in ids for b in (self._births[s] if 0 <= s < self.slots else [-1] * Kmax)])
+        row_counts = (LL * cap)()
+        plan = _lib.load().rtfs_live_faces_plan
+        fn = lambda *a: plan(*a[:15], row_counts, *a[15:])  # noqa: E731  (.., new_counters, table | row_counts | sizes, refused)
+        new, table, sizes = self._call_planner(fn, ids, (na, nf), flush, (self.window, self.hop, self.max_chunk, Kmax, births, cap),
+                                               FACES_PLAN_WORDS + 2 * Kmax, 6)
+        return new, table, sizes, [int(c) for c in row_counts[:sizes[0]]]
+
+    def _plan(self, ids, na, nf, flush):
+        return self._plan_faces(ids, na, nf, flush)[:3]
+
+    # -- one tick
+    def _present(self, table, R, r):
+        """[(plane, birth)] of the faces present in row r of a tick table."""
+        Kmax, P = self.max_speakers, table[13 * R + r]
+        return [(table[(15 + i) * R + r], table[(15 + Kmax + i) * R + r]) for i in range(P)]
+
+    @staticmethod
+    def _target_row(trow0, e, present, n, i):
+        """The ragged row of (window n, present face i): the kernels' faces_target_row."""
+        return trow0 + sum(max(0, n - max(e, b)) for _, b in present) + sum(b <= n for _, b in present[:i])
+
+    def _tick(self, ids, na, nf, wavs, vids, flush):
+        if self.model.training:
+            raise RuntimeError("FaceStreamPool is inference only: call .eval() on the model")
+        R = len(ids)
+        if R == 0:
+            return []
+        new, table, sizes, row_counts = self._plan_faces(ids, na, nf, flush)
+        floats, max_span, max_na, max_nf = sizes[2:]
+        with torch.no_grad():
+            if self.on_hip:
+                out = self._tick_hip(R, table, row_counts, floats, max_span, max_na, max_nf, wavs, vids, flush)
+            else:
+                out = self._tick_torch(R, table, row_counts, floats, wavs, vids, flush)
+        res = []
+        for r, s in enumerate(ids):
+            o, end, off = table[8 * R + r], table[9 * R + r], table[10 * R + r]
+            k, where = end - o, {j: (i, b) for i, (j, b) in enumerate(self._present(table, R, r))}
+            views = {}
+            for j in self.faces(s):
+                if j in where:  # the face's slice of its row of the slot's (P, end - o) block
+                    i, b = where[j]
+                    views[j] = out[off + i * k + min(k, max(o, b * self.hop) - o):off + (i + 1) * k]
+                else:
+                    views[j] = out[:0]
+            res.append(views)
+            self._counters[s] = new[4 * r:4 * r + 4]
+            if flush:
+                self._births[s] = [-1] * self.max_speakers
+        return res
+
+    def _drop(self, ids):
+        super()._drop(ids)
+        for s in ids:
+            self._births[s] = [-1] * self.max_speakers
+
+    def _forward_targets(self, row_counts):
+        """The separator on a tick's framed windows: ``_xw[w]`` with ``row_counts[w]`` targets, their lips in ``_vw`` and results in
+        ``_yt`` at the ragged target rows.  A window without a target (its faces were dropped, the next is not born yet) is skipped."""
+        live = [w for w, c in enumerate(row_counts) if c]
+        if not live:
+            return
+        xw, counts = self._xw[:len(row_counts)], row_counts
+        if len(live) != len(row_counts):
+            xw, counts = xw[torch.tensor(live, device=self.device)], [row_counts[w] for w in live]
+        for w0, w1, t0, t1 in models.chunk_windows(counts, self.max_batch):
+            if self.on_hip:
+                self._yt[t0:t1].copy_(self.model.separate_speakers(xw[w0:w1], self._vw[t0:t1], counts=counts[w0:w1]))
+            else:  # a target = the model on its window with its own lips
+                rep = torch.tensor(counts[w0:w1], device=self.device)
+                self._yt[t0:t1].copy_(self.model.forward_modular(xw[w0:w1].repeat_interleave(rep, 0), self._vw[t0:t1])[:, 0])
+
+    def _tick_hip(self, R, table, row_counts, floats, max_span, max_na, max_nf, wavs, vids, flush):
+        lib, dev, Kmax = _lib.load(), self.device, self.max_speakers
+        if flush:
+            ptrs = [0] * ((1 + Kmax) * R)
+        else:  # columns [aptr | vptr of present face 0 | ..]: the active faces of a push are its present faces, in the order pushed
+            ptrs = [w.data_ptr() for w in wavs] + [v[i].data_ptr() if i < len(v) else 0 for i in range(Kmax) for v in vids]
+        tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
+        st = _lib.stream_of(self._xw)
+        _lib.check(lib.rtfs_live_ingest_frame_faces_f32(_lib.ptr(tab), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._xw),
+                                                        _lib.ptr(self._vw), R, len(row_counts), Kmax, max_na, max_nf, self.window, self.hop,
+                                                        self.max_chunk, st), "rtfs_live_ingest_frame_faces_f32")
+        if row_counts:
+            self._forward_targets(row_counts)
+        out = _lib.empty(floats, device=dev)
+        if max_span > 0:
+            _lib.check(lib.rtfs_live_overlap_add_faces_f32(_lib.ptr(tab), _lib.ptr(self._yt), _lib.ptr(out), _lib.ptr(self._acc), R, max_span, Kmax,
+                                                           self.window, self.hop, self.max_chunk, int(flush), st),
+                       "rtfs_live_overlap_add_faces_f32")
+        if flush:
+            self._reset_state(tab[:R], R)
+        return out
+
+    def _reset_state(self, ids, R):
+        if not self.on_hip:
+            return super()._reset_state(ids, R)
+        _lib.check(_lib.load().rtfs_live_reset_speakers_f32(_lib.ptr(ids), _lib.ptr(self._aring), _lib.ptr(self._vring), _lib.ptr(self._acc), R,
+                                                            self.speakers, self.window, self.max_chunk, _lib.stream_of(self._aring)),
+                   "rtfs_live_reset_speakers_f32")
+
+    # -- the same tick in torch ops
+    def _tick_torch(self, R, table, row_counts, floats, wavs, vids, flush):
+        W, H, C, dev = self.window, self.hop, self.capacity, self.device
+        Cv, Wv, Hv = C // SPF, W // SPF, H // SPF
+        slot, a0, na, f0, nf, e0, cnt, row0, o0, end, off, apos, fpos, _, trow0 = (table[k * R:(k + 1) * R] for k in range(FACES_PLAN_WORDS))
+        iw, ifr = torch.arange(W, device=dev), torch.arange(Wv, device=dev)
+        present = [self._present(table, R, r) for r in range(R)]
+        for r in range(R):
+            if not flush:
+                self._aring[slot[r], (apos[r] + torch.arange(na[r], device=dev)) % C] = wavs[r]
+                for i, (j, _) in enumerate(present[r]):
+                    self._vring[slot[r], j][:, (fpos[r] + torch.arange(nf[r], device=dev)) % Cv] = vids[r][i]
+            lim_a, lim_f = a0[r] + na[r], f0[r] + nf[r]
+            for n in range(e0[r], e0[r] + cnt[r]):
+                p = n * H + iw
+                self._xw[row0[r] + n - e0[r]] = torch.where(p < lim_a, self._aring[slot[r], p % C], torch.zeros((), device=dev))
+                for i, (j, b) in enumerate(present[r]):
+                    if b <= n:
+                        t = self._target_row(trow0[r], e0[r], present[r], n, i)
+                        self._vw[t] = self._vring[slot[r], j][:, (n * Hv + ifr).clamp(max=lim_f - 1) % Cv]
+        if row_counts:
+            self._forward_targets(row_counts)
+        out = _lib.empty(floats, device=dev)
+        w, V = _weights(W, H, dev), W - H
+        for r in range(R):
+            k = end[r] - o0[r]
+            for i, (j, b) in enumerate(present[r]):
+                acc = self._acc[slot[r], j]
+                for n in range(max(e0[r], b), e0[r] + cnt[r]):  # ascending n; a cell no earlier window OF THIS FACE reached starts afresh
+                    wy, idx = w * self._yt[self._target_row(trow0[r], e0[r], present[r], n, i)], (n * H + iw) % C
+                    first = V if n > b else 0
+                    acc[idx[:first]] += wy[:first]
+                    acc[idx[first:]] = wy[first:]
+                lo = max(o0[r], b * H)
+                if lo >= end[r]:
+                    continue
+                den = torch.zeros(end[r] - lo, device=dev)
+                for n in range(max(b, -(-(lo - W + 1) // H)), e0[r] + cnt[r]):
+                    u0, u1 = max(lo, n * H), min(end[r], n * H + W)
+                    if u0 < u1:
+                        den[u0 - lo:u1 - lo] += w[u0 - n * H:u1 - n * H]
+                t = torch.arange(lo, end[r], device=dev)
+                out[off[r] + i * k + lo - o0[r]:off[r] + (i + 1) * k] = acc[t % C] / den
+        if flush:
+            self._reset_state(torch.tensor(slot, dtype=torch.int64, device=dev), R)
+        return out
+
+
 def speakers_of(speakers):
     """``speakers`` as an integer in 1 .. MAX_SPEAKERS; ValueError otherwise."""
     try:
@@ -397,6 +657,19 @@ def open_speaker_streams(model, slots, speakers, window=32000, hop=None, max_chu
     if int(model.n_src) != 1:
         raise ValueError("open_streams: speakers > 1 needs a target-speaker model (n_src 1)")
     return _open(SpeakerStreamPool, model, slots, K, window, hop, max_chunk, max_batch)
+
+
+def open_face_streams(model, slots, max_speakers, window=32000, hop=None, max_chunk=None, max_batch=32, sample_rate=16000):
+    """``AVNet.open_streams(max_speakers=Kmax)``: the checks of ``open_speaker_streams``, then the pool whose faces come and go."""
+    try:
+        Kmax = speakers_of(max_speakers)
+    except ValueError:
+        raise ValueError(f"open_streams: max_speakers = {max_speakers!r}; an integer in 1 .. {MAX_SPEAKERS}") from None
+    if _rate(sample_rate) != FS:
+        raise ValueError(f"open_streams: max_speakers = {Kmax} with sample_rate = {sample_rate}: this pool takes 16 kHz audio only")
+    if int(model.n_src) != 1:
+        raise ValueError("open_streams: max_speakers needs a target-speaker model (n_src 1)")
+    return _open(FaceStreamPool, model, slots, Kmax, window, hop, max_chunk, max_batch)
 
 
 # ================================================================ live streams from camera frames (DESIGN.md "Live streams from camera frames")
@@ -707,9 +980,144 @@ class SpeakerCameraStreamPool(CameraStreamPool):
         return (ids, *self.lips._check_chunks(self._tracks(ids), [t for c in roi_chunks for t in c.contiguous().unbind(0)])[1:])
 
 
-def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1):
+class FaceCameraStreamPool(CameraStreamPool):
+    """``CameraStreamPool`` whose slots hold up to ``max_speakers`` = Kmax faces each.  Built by
+    ``System.open_camera_streams(..., max_speakers=Kmax)``.
+
+    The audio pool is a ``FaceStreamPool`` and the lip pool has slots * Kmax tracks, track s Kmax + j for face j of slot s.  The ROI
+    chunk of a slot holds one (m,H,W) uint8 block - or one (m,88,88) float32 block - per active face in ascending face id, as a
+    sequence or as one tensor with a leading face axis.  ``add_face`` is allowed on an idle slot only: a lip track that joined in
+    mid-stream would lag its slot by the stem's two look-ahead frames (DESIGN.md "Faces that come and go", the remaining follow-up).
+    ``drop_face`` is allowed at any time and resets the face's lip track.  For any chunking the output of face j of a slot equals
+    ``System.separate_recording(wav, 16000, rois[j])``; a dropped face's is the leading part of it."""
+
+    def faces(self, slot):
+        return self.audio.faces(slot)
+
+    def add_face(self, slot, face=None):
+        s = self.audio._slot(slot, "add_face")
+        if any(self.audio._counters[s]) or any(any(self.lips._counters[s * self.speakers + j][:2]) for j in range(self.speakers)):
+            raise ValueError(f"FaceCameraStreamPool.add_face: slot {s} is in mid-stream; a face joins a camera stream on an idle slot only")
+        return self.audio.add_face(s, face)
+
+    def drop_face(self, slot, face):
+        s = self.audio._slot(slot, "drop_face")
+        self.audio.drop_face(s, face)
+        self.lips.reset([s * self.speakers + self._check_ids([face])[0]])
+
+    def counters(self, slot):
+        """((a, f, e, o) of the audio pool, (g, v) of the slot's lip tracks, which move together; (0, 0) without a face)."""
+        s, faces = int(slot), self.audio.faces(slot)
+        return self.audio.counters(s), self.lips.counters(s * self.speakers + faces[0]) if faces else (0, 0)
+
+    def _slot_tracks(self, ids):
+        return [[s * self.speakers + j for j in self.audio.faces(s)] for s in ids]
+
+    def _regroup(self, embs, groups):
+        out, at = [], 0
+        for g in groups:
+            out.append(embs[at:at + len(g)])
+            at += len(g)
+        return out
+
+    def _check_rois(self, slot_ids, roi_chunks):
+        """-> slot ids, the lip tracks of every named slot, and frames per track, chunks per track and their kind."""
+        ids = self._check_slots(slot_ids)
+        try:
+            roi_chunks = list(roi_chunks)
+        except TypeError:
+            raise ValueError("FaceCameraStreamPool.push: roi_chunks must be a sequence") from None
+        if len(roi_chunks) != len(ids):
+            raise ValueError(f"FaceCameraStreamPool.push: {len(ids)} slot id(s) and {len(roi_chunks)} ROI chunk(s)")
+        groups, flat = self._slot_tracks(ids), []
+        for r, (c, g) in enumerate(zip(roi_chunks, groups)):
+            if not g:
+                raise ValueError(f"FaceCameraStreamPool.push: slot {ids[r]} has no face; add_face first")
+            if isinstance(c, torch.Tensor):
+                blocks = list(c.contiguous().unbind(0)) if c.ndim == 4 else None
+            else:
+                try:
+                    blocks = list(c)
+                except TypeError:
+                    blocks = None
+            if blocks is None or len(blocks) != len(g) or any(not isinstance(b, torch.Tensor) or b.ndim != 3 for b in blocks):
+                raise ValueError(f"FaceCameraStreamPool.push: ROI chunk {r} must hold one (m,H,W) block for each of the {len(g)} active face(s)")
+            if len({int(b.shape[0]) for b in blocks}) != 1:
+                raise ValueError(f"FaceCameraStreamPool.push: the faces of ROI chunk {r} hold {[int(b.shape[0]) for b in blocks]} frames; one m per slot")
+            flat += blocks
+        tracks = [t for g in groups for t in g]
+        return (ids, groups, *self.lips._check_chunks(tracks, flat)[1:])
+
+    def _plan_faces_push(self, ids, groups, na, ms):
+        """The dry run of a push on both planners (ms: frames per track): ValueError for what either refuses."""
+        tracks = [t for g in groups for t in g]
+        T = len(tracks)
+        _, vtab, _ = self.lips._plan(tracks, ms, False)
+        ks, at = [], 0
+        room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
+        for s, g in zip(ids, groups):  # the tracks of a slot share their counters: one k per slot
+            ks.append(vtab[4 * T + at])
+            if self.lips._counters[g[0]][0] + ms[at] - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
+                raise ValueError(f"FaceCameraStreamPool.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
+            at += len(g)
+        return self.audio._plan_push(ids, na, ks)
+
+    def push(self, slot_ids, audio_chunks, roi_chunks):
+        """As ``CameraStreamPool.push`` with one block of mouth frames per active face of each slot.  Returns, per named slot, a dict
+        face id -> (k_j,) newly final samples.  ValueError - before any launch, all state unchanged - for what either pool refuses,
+        for a slot without a face and for a chunk that does not hold one block per active face."""
+        ids, groups, ms, rois, u8 = self._check_rois(slot_ids, roi_chunks)
+        wavs = self._check_audio(ids, audio_chunks)
+        if not ids:
+            return []
+        self._plan_faces_push(ids, groups, [int(w.numel()) for w in wavs], ms)
+        if self.audio.model.training:
+            raise RuntimeError("FaceCameraStreamPool is inference only: call .eval() on the model")
+        embs = self.lips._tick([t for g in groups for t in g], ms, rois, u8, flush=False)
+        return self.audio.push(ids, wavs, self._regroup(embs, groups))
+
+    def flush(self, slot_ids):
+        """End the named streams, as ``CameraStreamPool.flush``: per slot a dict face id -> the remaining samples of that face.  A slot
+        without a face (it has received nothing) returns {}.  The slots' faces are cleared."""
+        named = self._check_slots(slot_ids)
+        ids = [s for s in named if self.audio.faces(s)]
+        res = {s: {} for s in named}
+        if ids:
+            groups = self._slot_tracks(ids)
+            tracks, R = [t for g in groups for t in g], len(ids)
+            _, vtab, _ = self.lips._plan(tracks, None, True)
+            firsts = [sum(len(g) for g in groups[:r]) for r in range(R)]
+            new, _, _ = self.audio._plan_push(ids, [0] * R, [vtab[4 * len(tracks) + i] for i in firsts])
+            with _counters_as(self.audio, ids, new, 4):
+                self.audio._plan_flush(ids)
+            if self.audio.model.training:
+                raise RuntimeError("FaceCameraStreamPool is inference only: call .eval() on the model")
+            embs = self.lips.flush(tracks)
+            empty = _lib.empty(0, device=self.device)
+            mid = self.audio.push(ids, [empty] * R, self._regroup(embs, groups))
+            last = self.audio.flush(ids)
+            for s, m, t in zip(ids, mid, last):
+                res[s] = {j: torch.cat([m[j], t[j]]) if m[j].shape[0] else t[j] for j in t}
+        return [res[s] for s in named]
+
+    def _drop(self, ids):
+        self.lips.reset([s * self.speakers + j for s in ids for j in range(self.speakers)])
+        self.audio.reset(ids)
+
+
+def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1,
+                        max_speakers=None):
     """``System.open_camera_streams``: the lip pool and the audio pool of one set of slots."""
     K = speakers_of(speakers)
+    if max_speakers is not None:
+        if K != 1:
+            raise ValueError("open_camera_streams: speakers and max_speakers exclude each other")
+        try:
+            K = speakers_of(max_speakers)
+        except ValueError:
+            raise ValueError(f"open_camera_streams: max_speakers = {max_speakers!r}; an integer in 1 .. {MAX_SPEAKERS}") from None
+        if _rate(sample_rate) != FS:
+            raise ValueError(f"open_camera_streams: max_speakers = {K} with sample_rate = {sample_rate}: this pool takes 16 kHz audio only")
     if K > 1 and _rate(sample_rate) != FS:
         raise ValueError(f"open_camera_streams: speakers = {K} with sample_rate = {sample_rate}: several speakers take 16 kHz audio only")
     if _rate(sample_rate) != FS:
@@ -725,10 +1133,12 @@ def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, m
     if max_chunk < SPF or max_chunk % SPF:
         raise ValueError(f"open_camera_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF}")
     audio = system.audio_model.open_streams(slots, window=window, hop=hop, max_chunk=max_chunk + LOOKAHEAD * SPF, max_batch=max_batch,
-                                            speakers=K)
+                                            **(dict(speakers=K) if max_speakers is None else dict(max_speakers=K)))
     lips = system.video_model.open_streams(audio.slots * K, max_frames=max_chunk // SPF, roi_hw=roi_hw)
     if lips.device != audio.device:
         raise ValueError(f"open_camera_streams: the video model lies on {lips.device}, the audio model on {audio.device}")
+    if max_speakers is not None:
+        return FaceCameraStreamPool(lips, audio, max_chunk)
     return (SpeakerCameraStreamPool if K > 1 else CameraStreamPool)(lips, audio, max_chunk)
 
 

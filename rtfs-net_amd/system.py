@@ -156,10 +156,12 @@ class System(nn.Module):
         (512,m): the video stem is a 3-D convolution with temporal context, so frames embedded chunk by chunk are not the whole-track
         embedding without look-ahead state.  ``open_camera_streams`` is the entry that takes the camera's frames and keeps that state.
         ``sample_rate``: the rate of the audio chunks, as ``AVNet.open_streams`` takes it.  ``speakers=K`` (in ``**kw``): K lip tracks per
-        slot -> ``streaming.SpeakerStreamPool``, as ``AVNet.open_streams`` describes."""
+        slot -> ``streaming.SpeakerStreamPool``; ``max_speakers=Kmax``: faces that come and go -> ``streaming.FaceStreamPool``, both as
+        ``AVNet.open_streams`` describes."""
         return self.audio_model.open_streams(sample_rate=sample_rate, **kw)
 
-    def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1):
+    def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1,
+                            max_speakers=None):
         """Live streams from microphone samples and camera frames (inference; DESIGN.md "Live streams from camera frames") ->
         ``streaming.CameraStreamPool``.  ``pool.push(slot_ids, audio_chunks, roi_chunks)`` takes 16 kHz audio chunks of at most
         ``max_chunk`` samples (default ``window``) and uint8 mouth ROIs (m,H,W) with (H,W) == ``roi_hw`` at 25 fps (or float32 prepared lips
@@ -174,10 +176,14 @@ class System(nn.Module):
 
         ``speakers`` = K > 1 (DESIGN.md "Every face of a stream") -> ``streaming.SpeakerCameraStreamPool``: the ROI chunk of a slot is
         (K,m,H,W) uint8 or (K,m,88,88) float32, the results are (K,k), and output k of a slot equals ``separate_recording(wav, 16000,
-        rois[k])``; 16 kHz audio only (ValueError with another ``sample_rate``)."""
+        rois[k])``; 16 kHz audio only (ValueError with another ``sample_rate``).
+
+        ``max_speakers`` = Kmax (DESIGN.md "Faces that come and go") -> ``streaming.FaceCameraStreamPool``: up to Kmax faces per slot,
+        declared with ``pool.add_face`` on an idle slot and ended with ``pool.drop_face`` at any time; the ROI chunk of a slot holds one
+        block per active face and the results are dicts face id -> samples.  Excludes ``speakers``; 16 kHz audio only."""
         from . import streaming
         return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
-                                             sample_rate=sample_rate, speakers=speakers)
+                                             sample_rate=sample_rate, speakers=speakers, max_speakers=max_speakers)
 
     def separate_recordings(self, wavs, sample_rates, mouth_rois, normalize_audio=False, **kw):
         """The list form of ``separate_recording``: wavs = R raw recordings (L_r) at ``sample_rates[r]`` Hz, mouth_rois = R uint8
