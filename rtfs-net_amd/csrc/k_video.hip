@@ -417,6 +417,9 @@ int conv_launch(int mode, const VidConvArgs& a, hipStream_t st) {
     // LDS-resident input tile (nine taps per load): pays off for the large-plane 64-channel layer only -- the deeper layers'
     // small planes give too few, too LDS-heavy workgroups (measured 376 us against 243 for the gather kernel)
     if (mode == VM_C3 && a.stride == 1 && a.Hi == a.Ho && a.Wi == a.Wo && a.Cout == 64) return conv3l_launch<2>(a, st);
+    // rounds of 8 pixel tiles x ncb channel blocks (the decode at the top of vid_conv_kernel).  A stage leaves its first round once
+    // N Ho Wo > 1024: stem N >= 1, layer 2 (121 px / frame, ncb 1) N >= 9, layer 3 (36 px, ncb 2) N >= 29, layer 4 (9 px, ncb 4)
+    // N >= 114 and a third round at N >= 228 -- the frame counts of tests/test_hip_video_edges.py (video front-end)
     auto grid1 = [&](int ncb) { return dim3((unsigned)(cdiv(px, 8) * 8 * ncb)); };
     if (mode == VM_STEM) hipLaunchKernelGGL((vid_conv_kernel<VM_STEM, 2>), grid1(1), dim3(256), 0, st, a);
     else if (a.Cout % 128 == 0) {  // (CG = 2, a 256-channel tile on 8 waves, measured slower: 309 us against 243)  // 128 output channels per workgroup: the gathered activations are reused twice as often

@@ -175,6 +175,37 @@ def test_video_oracle_matches_reference(k, B, T):
         assert np.abs(it[f"layer{li}"][:, ::16] - ref).max() / np.abs(ref).max() < 2e-5
 
 
+@pytest.mark.parametrize("B,T,seed", [(1, 1, 0), (3, 2, 1)])
+def test_video_ref64_matches_numpy_oracle(B, T, seed):
+    """oracle/video_ref64.py (stock torch ops in float64, nothing rounded between layers: the reference of tests/test_hip_video_edges.py)
+    vs oracle/video_oracle.py on clips shorter than the stem's 5-frame kernel, one of them with clip boundaries inside the batch.  The
+    difference is the numpy oracle's float32 rounding after every layer (~1e-7); bar 1e-6 on max-rel and l2-rel."""
+    from oracle import video_oracle as V
+    from oracle.video_ref64 import video_frontend64
+    from tests.util import frame_rel_err, l2_rel
+    sd = V.make_video_state_dict(0)
+    x = V.make_video_input(B, T, seed)
+    ref = video_frontend64(x, sd)
+    y = V.video_frontend(x, sd)
+    assert ref.shape == (B, 512, T) and ref.dtype == np.float64
+    e, l2, fe = rel_err(y, ref), l2_rel(y, ref), frame_rel_err(y, ref)
+    print(f"numpy oracle vs video_ref64 (B={B}, T={T}): max-rel {e:.3e}  l2-rel {l2:.3e}  worst frame {fe:.3e}")
+    assert e <= 1e-6 and l2 <= 1e-6, (e, l2)
+
+
+@pytest.mark.parametrize("k,B,T", [(0, 1, 3), (1, 2, 5)])
+def test_video_ref64_matches_reference(k, B, T):
+    """oracle/video_ref64.py vs the reference module's own outputs (tests/golden/video_cases.npz), at the bar the numpy oracle meets
+    for the same cases (test_video_oracle_matches_reference: 2e-5 relative; the reference computes in float32)."""
+    from oracle import video_oracle as V
+    from oracle.video_ref64 import video_frontend64
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "video_cases.npz"))
+    y = video_frontend64(V.make_video_input(B, T, k), V.make_video_state_dict(0))
+    e = np.abs(y - g[f"c{k}_out"]).max() / np.abs(g[f"c{k}_out"]).max()
+    print(f"video_ref64 vs reference output, case {k}: max-rel {e:.3e}")
+    assert y.shape == g[f"c{k}_out"].shape and e < 2e-5, e
+
+
 @pytest.mark.parametrize("case", ["eval", "train"])
 def test_gradient_oracle_against_reference_autograd(case):
     """oracle/grad_oracle.py (the float64 torch restatement the HIP backward kernels are tested against) vs golden gradients produced by

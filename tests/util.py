@@ -35,6 +35,14 @@ def l2_rel(a, b):
     return float(np.sqrt(((a - b) ** 2).sum()) / max(np.sqrt((b ** 2).sum()), 1e-30))
 
 
+def frame_rel_err(a, b):
+    """Worst frame of a (B, C, T) tensor: max over (b, t) of max_c |a - b| / max_c |b[b, :, t]|.  rel_err divides by the largest value
+    anywhere, so one wrong low-magnitude frame can hide behind it; this measure cannot."""
+    a = np.asarray(a, np.float64)
+    b = np.asarray(b, np.float64)
+    return float((np.abs(a - b).max(1) / np.maximum(np.abs(b).max(1), 1e-30)).max())
+
+
 def check_probe(g, tag, x, tol, what=""):
     """Compare a full tensor ``x`` with the probe ``tag`` stored in golden file ``g``."""
     x = np.asarray(x, np.float32)
