@@ -655,6 +655,38 @@ int rtfs_video_frontend_windows_f32(const float* windows, const float* pack, con
                                     int n, void* ws, size_t ws_bytes, void* stream);
 int rtfs_live_video_reset(const long long* ids, float* hist, int R, void* stream);
 
+/* Live streams and recordings at the camera's own frame rate (DESIGN.md "Live streams at the camera's frame rate"; csrc/frame_rate.h).
+ * The rule: camera frame i of a stream at a / b fps (reduced) has the 25 fps tick r(i) = floor(i 25 b / a + 1/2); model frame p shows
+ * c(p) = max{i : r(i) <= p} = ceil(a (2p + 1) / (50 b)) - 1, and n camera frames give the model frames p with c(p) < n,
+ * P(n) = floor((50 b n + a) / (2 a)) of them.  No frame is blended; at 25 / 1, c(p) = p and P(n) = n.
+ * rtfs_frame_rate_map (host only): *n_out = P(n_in) and, when src is not NULL, src[p] = c(p) for p < P(n_in).  -4 for a rate outside
+ *   [1, 240] fps, a reduced numerator or denominator above 2^20, n_in outside [0, 2^36] or n_out NULL; nothing is written then.
+ * rtfs_live_video_rate_plan (host only): rtfs_live_video_plan with n_frames and max_frames in CAMERA frames.  counters (R x 4):
+ *   [g | v | side | n camera frames received], g == P(n); new_counters likewise.  g, m, v, k, row0, out_off, side keep their meaning in
+ *   model frames, m = P(n + n_frames) - g (it may be 0: then g, v and side stay and only n advances).  The table has
+ *   RTFS_LIVE_VIDEO_RATE_PLAN_WORDS = 9 columns, the eight of rtfs_live_video_plan and n0 = n; sizes[4] = [rows | out_floats | largest
+ *   chunk in camera frames | largest m in model frames], the last one sizes the window volume (it exceeds the chunk below 25 fps).  A
+ *   flush emits v .. P(n) - 1.  Refusals as rtfs_live_video_plan, and RTFS_LIVE_BAD_RATE (refused[0] = -1) for a rate
+ *   rtfs_frame_rate_map refuses; g != P(n) or n + n_frames > 2^36: BAD_COUNTERS.  At 25 / 1 the first eight columns, the first three
+ *   counters and sizes[0..2] are those of rtfs_live_video_plan.
+ * rtfs_live_video_ingest_rate_u8 / _f32 (one launch each): rtfs_live_video_ingest_* on the 9 R words of the rate plan followed by the
+ *   column of chunk addresses; chunks hold CAMERA frames and model frame p >= g is read from chunk index c(p) - n0.  Camera frames that
+ *   no model frame shows are not read, nor anything behind the chunk; max_m is sizes[3]; a slot with m == 0 keeps its history untouched.
+ * rtfs_lips_prepare_rate_u8: rtfs_lips_prepare_u8 on roi (N,Tv_in,H,W) at rate_num / rate_den fps -> out (N,1,P(Tv_in),88,88),
+ *   out[n,0,p] = the prepared roi[n,c(p)].  P(Tv_in) == 0 (a single frame above 50 fps): -1. */
+#define RTFS_LIVE_VIDEO_RATE_PLAN_WORDS 9
+#define RTFS_LIVE_BAD_RATE 10
+int rtfs_frame_rate_map(int rate_num, int rate_den, long long n_in, long long* n_out, long long* src);
+int rtfs_live_video_rate_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                              int max_frames, int rate_num, int rate_den, long long* new_counters, long long* table, long long* sizes,
+                              int* refused);
+int rtfs_live_video_ingest_rate_u8(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, int H, int W,
+                                   int dy, int dx, double mean, double std, int rate_num, int rate_den, void* stream);
+int rtfs_live_video_ingest_rate_f32(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, int rate_num,
+                                    int rate_den, void* stream);
+int rtfs_lips_prepare_rate_u8(const unsigned char* roi, const int* table, float* out, int N, int Tv_in, int H, int W, double mean,
+                              double std, int rate_num, int rate_den, void* stream);
+
 /* Optimizer step on the device (rtfs-net_amd/optimizers.py AdamW; the reference builds torch.optim.AdamW through
  * src/system/optimizers.py:58-108 and Lightning clips at gradient_clip_val 5.0, train.py:142): gather of the per-tensor gradients into
  * one flat buffer, global-norm clip and AdamW in a number of launches that does not depend on the number of tensors.

@@ -7,7 +7,7 @@ path runs in ``librtfs_amd.so`` (hand-written gfx950 HIP kernels behind the C AB
 from . import _lib, configs, datas, layers, losses, metrics, optimizers, packing, streaming, system, torch_utils, videomodels  # noqa: F401
 from .packing import invalidate_packs  # noqa: F401
 from .system import System  # noqa: F401
-from .streaming import (CameraStreamPool, FaceCameraStreamPool, FaceStreamPool, LipStreamPool, RateStreamPool,  # noqa: F401
+from .streaming import (CameraStreamPool, FaceCameraStreamPool, FaceStreamPool, LipStreamPool, RateLipStreamPool, RateStreamPool,  # noqa: F401
                         ResampleStreamPool, SpeakerCameraStreamPool, SpeakerStreamPool, StreamPool)
 from .optimizers import make_optimizer  # noqa: F401
 from .metrics import ALLMetricsTracker, stoi  # noqa: F401

@@ -150,6 +150,11 @@ SIGNATURES = {
     "rtfs_video_windows_workspace_bytes": (_z, [_i]),
     "rtfs_video_frontend_windows_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _z, _p]),
     "rtfs_live_video_reset": (_i, [_p, _p, _i, _p]),
+    "rtfs_frame_rate_map": (_i, [_i, _i, C.c_longlong, _p, _p]),
+    "rtfs_live_video_rate_plan": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "rtfs_live_video_ingest_rate_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i, _p]),
+    "rtfs_live_video_ingest_rate_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "rtfs_lips_prepare_rate_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i, _p]),
     "rtfs_optim_plan": (_i, [_p, _i, _p, _p, _p]),
     "rtfs_optim_gather_f32": (_i, [_p, _p, _i, _i, _p, _p, _i, _p]),
     "rtfs_optim_sumsq_f32": (_i, [_p, _i, _i, _p, _p, _p]),

@@ -27,7 +27,15 @@
 // when m < 4, and a ring of 8 does the same with m > 4: the read and written index ranges are m - 3 .. m + 3 apart.)
 // A plane of buffer `side` is read only for a frame index in [max(0, g - 4), g): it was written by the push that made it current or
 // carried over by it, so no kernel depends on what reset wrote.
+//
+// AT THE CAMERA'S OWN FRAME RATE (frame_rate.h; DESIGN.md "Live streams at the camera's frame rate") a slot has one more counter, n camera
+// frames received, and g = P(n): everything above stays in MODEL frames.  live_video_rate_plan is live_video_plan with chunk sizes in
+// camera frames; its table has one more column, n0 = the camera frames received before the push, in front of the chunk pointers.  The
+// ingest kernel's RATE instantiation differs in one line: a frame p >= g comes from chunk index c(p) - n0, which is >= 0 because
+// p >= g = P(n0) means c(p) >= n0, and < the chunk's camera frames because p < g + m = P(n0 + chunk).  Camera frames that no model frame
+// shows are never read.  A push whose frames give no model frame (m = 0) advances n only: no history block runs for it.
 #include "common.h"
+#include "frame_rate.h"
 #include "kernels.h"
 #include "longform_common.h"  // VCH, many_find
 #include "../../include/rtfs_amd.h"  // RTFS_LIVE_*
@@ -37,7 +45,12 @@ namespace {
 constexpr int LV_CROP = 88, LV_PAD = 94, LV_PLANE = LV_PAD * LV_PAD, LV_IMG = LV_CROP * LV_CROP, LV_HIST = 4, LV_WIN = 5;
 constexpr int LV_ALIGN = RTFS_LIVE_ALIGN;
 // columns of the tick table
-enum { V_SLOT, V_G, V_M, V_V, V_K, V_ROW0, V_OFF, V_SIDE, V_PTR };
+enum { V_SLOT, V_G, V_M, V_V, V_K, V_ROW0, V_OFF, V_SIDE, V_PTR, V_N0 = V_PTR, V_RATE_PTR };
+
+// a / b fps, reduced; 25 / 1 where the chunk already is at the model's rate
+struct FrameRate {
+    long long a, b;
+};
 
 // where frame p of the slot of table row r comes from in this launch: nowhere (a zero plane), buffer `side`, or the chunk
 template <bool U8>
@@ -46,26 +59,31 @@ struct FrameSrc {
     const unsigned char* b;  // uint8 plane (H, W) at the crop offset, or null
 };
 
-template <bool U8>
+template <bool U8, bool RATE>
 __device__ __forceinline__ FrameSrc<U8> frame_src(const long long* __restrict__ table, const float* hist, int R, int r, long long p, int H,
-                                                  int W, int dy, int dx) {
+                                                  int W, int dy, int dx, FrameRate fr) {
     const long long g = table[(size_t)V_G * R + r], lim = g + table[(size_t)V_M * R + r];  // at a flush m = 0: frames >= g are zeros
     FrameSrc<U8> s{nullptr, nullptr};
     if (p < 0 || p >= lim) return s;
     if (p < g) {
         const size_t slot = (size_t)table[(size_t)V_SLOT * R + r], side = (size_t)table[(size_t)V_SIDE * R + r];
         s.f = hist + ((slot * 2 + side) * LV_HIST + (size_t)(p & 3)) * LV_IMG;
-    } else if (U8) {
-        s.b = (const unsigned char*)(uintptr_t)table[(size_t)V_PTR * R + r] + ((size_t)(p - g) * H + dy) * W + dx;
+        return s;
+    }
+    // the frame's index in the chunk and the chunk's address (block-uniform)
+    const size_t i = RATE ? (size_t)(fr_source(fr.a, fr.b, p) - table[(size_t)V_N0 * R + r]) : (size_t)(p - g);
+    const uintptr_t chunk = (uintptr_t)table[(size_t)(RATE ? V_RATE_PTR : V_PTR) * R + r];
+    if (U8) {
+        s.b = (const unsigned char*)chunk + (i * H + dy) * W + dx;
     } else {
-        s.f = (const float*)(uintptr_t)table[(size_t)V_PTR * R + r] + (size_t)(p - g) * LV_IMG;
+        s.f = (const float*)chunk + i * LV_IMG;
     }
     return s;
 }
 
-template <bool U8>
+template <bool U8, bool RATE>
 __global__ __launch_bounds__(256) void live_video_ingest_kernel(const long long* __restrict__ table, float* hist, float* __restrict__ win, int R,
-                                                                int rows, int H, int W, int dy, int dx, double mean, double stdv) {
+                                                                int rows, int H, int W, int dy, int dx, double mean, double stdv, FrameRate fr) {
     __shared__ float lut[256];
     const int tid = threadIdx.x;
     if (U8) {  // the 256 possible values through the reference's float64 arithmetic, as lips_prepare_kernel (k_prep.hip)
@@ -79,7 +97,7 @@ __global__ __launch_bounds__(256) void live_video_ingest_kernel(const long long*
         const int nl = row - (int)table[(size_t)V_ROW0 * R + r];
         if (nl >= (int)table[(size_t)V_K * R + r]) return;  // a table that does not cover this row: write nothing
         const long long p = table[(size_t)V_V * R + r] + nl - 2 + j;
-        const FrameSrc<U8> s = frame_src<U8>(table, hist, R, r, p, H, W, dy, dx);
+        const FrameSrc<U8> s = frame_src<U8, RATE>(table, hist, R, r, p, H, W, dy, dx, fr);
         float* dst = win + (size_t)blockIdx.x * LV_PLANE;
         for (int i = tid; i < LV_PLANE; i += 256) {
             const int yy = i / LV_PAD, y = yy - 3, x = i - yy * LV_PAD - 3;
@@ -99,7 +117,7 @@ __global__ __launch_bounds__(256) void live_video_ingest_kernel(const long long*
     const long long g1 = table[(size_t)V_G * R + r] + m;
     const long long p = g1 - LV_HIST + ((c - (g1 - LV_HIST)) & 3);  // the frame of [g' - 4, g') that lives in plane c
     if (p < 0) return;
-    const FrameSrc<U8> s = frame_src<U8>(table, hist, R, r, p, H, W, dy, dx);
+    const FrameSrc<U8> s = frame_src<U8, RATE>(table, hist, R, r, p, H, W, dy, dx, fr);
     const size_t slot = (size_t)table[(size_t)V_SLOT * R + r], other = 1 - (size_t)table[(size_t)V_SIDE * R + r];
     float* dst = hist + ((slot * 2 + other) * LV_HIST + c) * LV_IMG;
     for (int i = tid; i < LV_IMG; i += 256) {
@@ -130,8 +148,13 @@ __global__ __launch_bounds__(256) void live_video_reset_kernel(const long long* 
 
 }  // namespace
 
-int live_video_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
-                    int max_frames, long long* new_counters, long long* table, long long* sizes, int* refused) {
+// The one planner.  rate == nullptr: the chunk sizes are model frames, 3 counters per slot (g, v, side), 8 table columns, 3 sizes.
+// Otherwise n_frames and max_frames count camera frames at rate->a / rate->b fps, a slot has a fourth counter n (camera frames
+// received; g == P(n)), the table a ninth column n0 = n and sizes a fourth word, the largest m in model frames.
+static int live_video_plan_any(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                               int max_frames, const FrameRate* rate, long long* new_counters, long long* table, long long* sizes,
+                               int* refused) {
+    const int CW = rate ? 4 : 3, TW = rate ? RTFS_LIVE_VIDEO_RATE_PLAN_WORDS : RTFS_LIVE_VIDEO_PLAN_WORDS;
     auto refuse = [&](int r, int reason) {
         if (refused) {
             refused[0] = r;
@@ -146,49 +169,85 @@ int live_video_plan(const long long* slot_ids, const long long* counters, const 
         for (int q = 0; q < r; ++q)
             if (slot_ids[q] == slot_ids[r]) return refuse(r, RTFS_LIVE_REPEATED_SLOT);
     }
-    long long rows = 0, off = 0, max_m = 0;
+    long long rows = 0, off = 0, max_m = 0, max_in = 0;
     // two passes, so that a refusal at any slot leaves every output unwritten: pass 0 only checks, pass 1 only writes
     for (int pass = 0; pass < 2; ++pass) {
-        rows = off = max_m = 0;
+        rows = off = max_m = max_in = 0;
         for (int r = 0; r < R; ++r) {
-            const long long g = counters[3 * r], v = counters[3 * r + 1], side = counters[3 * r + 2];
+            const long long g = counters[CW * r], v = counters[CW * r + 1], side = counters[CW * r + 2], n0 = rate ? counters[CW * r + 3] : g;
             if (g < 0 || v < 0 || g > LIMIT || v > g || v < (g > 2 ? g - 2 : 0) || (side != 0 && side != 1))
                 return refuse(r, RTFS_LIVE_BAD_COUNTERS);
-            long long m = 0, v1;
+            if (rate && (n0 < 0 || n0 > FR_MAX_FRAMES || g != fr_count(rate->a, rate->b, n0))) return refuse(r, RTFS_LIVE_BAD_COUNTERS);
+            long long m = 0, m_in = 0, v1;
             if (!flush) {
-                m = n_frames[r];
-                if (m < 0 || m > max_frames) return refuse(r, RTFS_LIVE_CHUNK_SIZE);
+                m = m_in = n_frames[r];
+                if (m_in < 0 || m_in > max_frames) return refuse(r, RTFS_LIVE_CHUNK_SIZE);
+                if (rate) {
+                    if (n0 + m_in > FR_MAX_FRAMES) return refuse(r, RTFS_LIVE_BAD_COUNTERS);
+                    m = fr_count(rate->a, rate->b, n0 + m_in) - g;  // the model frames these camera frames complete; may be 0
+                }
                 v1 = g + m - 2 > v ? g + m - 2 : v;
             } else {
                 v1 = g;
             }
             const long long k = v1 - v;
             if (pass && table) {
-                const long long col[RTFS_LIVE_VIDEO_PLAN_WORDS] = {slot_ids[r], g, m, v, k, rows, off, side};
-                for (int w = 0; w < RTFS_LIVE_VIDEO_PLAN_WORDS; ++w) table[(size_t)w * R + r] = col[w];
+                const long long col[RTFS_LIVE_VIDEO_RATE_PLAN_WORDS] = {slot_ids[r], g, m, v, k, rows, off, side, n0};
+                for (int w = 0; w < TW; ++w) table[(size_t)w * R + r] = col[w];
             }
             if (pass && new_counters) {
-                new_counters[3 * r] = flush ? 0 : g + m;
-                new_counters[3 * r + 1] = flush ? 0 : v1;
-                new_counters[3 * r + 2] = flush ? 0 : (m > 0 ? 1 - side : side);
+                new_counters[CW * r] = flush ? 0 : g + m;
+                new_counters[CW * r + 1] = flush ? 0 : v1;
+                new_counters[CW * r + 2] = flush ? 0 : (m > 0 ? 1 - side : side);
+                if (rate) new_counters[CW * r + 3] = flush ? 0 : n0 + m_in;
             }
             rows += k;
             off += ((long long)VCH * k + LV_ALIGN - 1) / LV_ALIGN * LV_ALIGN;
             if (rows > 0x7fffffffLL / LV_WIN || off > LIMIT) return refuse(r, RTFS_LIVE_BAD_ARGUMENT);
             max_m = m > max_m ? m : max_m;
+            max_in = m_in > max_in ? m_in : max_in;
         }
     }
     if (sizes) {
         sizes[0] = rows;
         sizes[1] = off;
-        sizes[2] = max_m;
+        sizes[2] = max_in;
+        if (rate) sizes[3] = max_m;
     }
     if (refused) refused[0] = -1, refused[1] = 0;
     return RTFS_OK;
 }
 
+int live_video_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                    int max_frames, long long* new_counters, long long* table, long long* sizes, int* refused) {
+    return live_video_plan_any(slot_ids, counters, n_frames, R, slots, flush, max_frames, nullptr, new_counters, table, sizes, refused);
+}
+
+int live_video_rate_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                         int max_frames, int rate_num, int rate_den, long long* new_counters, long long* table, long long* sizes,
+                         int* refused) {
+    FrameRate fr;
+    if (!fr_reduce(rate_num, rate_den, &fr.a, &fr.b)) {
+        if (refused) refused[0] = -1, refused[1] = RTFS_LIVE_BAD_RATE;
+        return RTFS_ERR_ARG;
+    }
+    return live_video_plan_any(slot_ids, counters, n_frames, R, slots, flush, max_frames, &fr, new_counters, table, sizes, refused);
+}
+
+int frame_rate_map(int rate_num, int rate_den, long long n_in, long long* n_out, long long* src) {
+    long long a, b;
+    if (!fr_reduce(rate_num, rate_den, &a, &b) || n_in < 0 || n_in > FR_MAX_FRAMES || !n_out) return RTFS_ERR_ARG;
+    *n_out = fr_count(a, b, n_in);
+    if (src)
+        for (long long p = 0; p < *n_out; ++p) src[p] = fr_source(a, b, p);
+    return RTFS_OK;
+}
+
 int launch_live_video_ingest(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, bool u8, int H, int W,
-                             int dy, int dx, double mean, double stdv, hipStream_t st) {
+                             int dy, int dx, double mean, double stdv, int rate_num, int rate_den, hipStream_t st) {
+    FrameRate fr{25, 1};
+    const bool rate = rate_num != 0 || rate_den != 0;  // 0 / 0: the chunks hold model frames (table of 8 columns + the pointers)
+    if (rate && !fr_reduce(rate_num, rate_den, &fr.a, &fr.b)) return RTFS_ERR_ARG;
     if (R < 1 || rows < 0 || max_m < 0 || (flush && max_m != 0)) return RTFS_ERR_SHAPE;
     if (u8) {
         if (H < LV_CROP || W < LV_CROP || H > 0x7fff || W > 0x7fff) return RTFS_ERR_SHAPE;
@@ -198,12 +257,17 @@ int launch_live_video_ingest(const long long* table, float* hist, float* windows
     if (rows == 0 && max_m == 0) return RTFS_OK;  // nothing arrived, nothing is ready
     const long long blocks = (long long)rows * LV_WIN + (max_m > 0 ? (long long)R * LV_HIST : 0);
     if (blocks > 0x7fffffffLL) return RTFS_ERR_SHAPE;
-    if (u8)
-        hipLaunchKernelGGL(live_video_ingest_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, table, hist, windows, R, rows, H, W, dy, dx,
-                           mean, stdv);
-    else
-        hipLaunchKernelGGL(live_video_ingest_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, table, hist, windows, R, rows, LV_CROP,
-                           LV_CROP, 0, 0, 0.0, 1.0);
+    auto go = [&](auto kernel) {
+        if (u8)
+            hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, table, hist, windows, R, rows, H, W, dy, dx, mean, stdv, fr);
+        else
+            hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, table, hist, windows, R, rows, LV_CROP, LV_CROP, 0, 0, 0.0, 1.0,
+                               fr);
+    };
+    if (u8 && rate) go(live_video_ingest_kernel<true, true>);
+    else if (u8) go(live_video_ingest_kernel<true, false>);
+    else if (rate) go(live_video_ingest_kernel<false, true>);
+    else go(live_video_ingest_kernel<false, false>);
     return rtfs_launch_status();
 }
 
@@ -231,12 +295,37 @@ int rtfs_live_video_plan(const long long* slot_ids, const long long* counters, c
 int rtfs_live_video_ingest_u8(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, int H, int W,
                               int dy, int dx, double mean, double std, void* stream) {
     if (!table || !hist || (!windows && rows > 0)) return RTFS_ERR_ARG;
-    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, true, H, W, dy, dx, mean, std, (hipStream_t)stream);
+    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, true, H, W, dy, dx, mean, std, 0, 0, (hipStream_t)stream);
 }
 
 int rtfs_live_video_ingest_f32(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, void* stream) {
     if (!table || !hist || (!windows && rows > 0)) return RTFS_ERR_ARG;
-    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, false, 0, 0, 0, 0, 0.0, 1.0, (hipStream_t)stream);
+    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, false, 0, 0, 0, 0, 0.0, 1.0, 0, 0, (hipStream_t)stream);
+}
+
+int rtfs_frame_rate_map(int rate_num, int rate_den, long long n_in, long long* n_out, long long* src) {
+    return frame_rate_map(rate_num, rate_den, n_in, n_out, src);
+}
+
+int rtfs_live_video_rate_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                              int max_frames, int rate_num, int rate_den, long long* new_counters, long long* table, long long* sizes,
+                              int* refused) {
+    return live_video_rate_plan(slot_ids, counters, n_frames, R, slots, flush, max_frames, rate_num, rate_den, new_counters, table, sizes,
+                                refused);
+}
+
+int rtfs_live_video_ingest_rate_u8(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, int H, int W,
+                                   int dy, int dx, double mean, double std, int rate_num, int rate_den, void* stream) {
+    if (!table || !hist || (!windows && rows > 0) || rate_num < 1 || rate_den < 1) return RTFS_ERR_ARG;
+    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, true, H, W, dy, dx, mean, std, rate_num, rate_den,
+                                    (hipStream_t)stream);
+}
+
+int rtfs_live_video_ingest_rate_f32(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, int rate_num,
+                                    int rate_den, void* stream) {
+    if (!table || !hist || (!windows && rows > 0) || rate_num < 1 || rate_den < 1) return RTFS_ERR_ARG;
+    return launch_live_video_ingest(table, hist, windows, R, rows, max_m, flush, false, 0, 0, 0, 0, 0.0, 1.0, rate_num, rate_den,
+                                    (hipStream_t)stream);
 }
 
 size_t rtfs_video_windows_workspace_bytes(int rows) { return video_windows_workspace_bytes(rows); }

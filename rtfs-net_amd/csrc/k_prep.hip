@@ -1,6 +1,7 @@
 // Preparing raw recordings on the device (rtfs-net_amd/datas.py; DESIGN.md "Preparing recordings"): what the reference does on the host in
 // front of the model inputs (src/datas/transform.py:151-167, avspeech_dataset.py:18-22, infer_any_video.py:63-80).
-//   lips_prepare_kernel     uint8 mouth ROIs (N,Tv,H,W) -> float32 lips (N,1,Tv,88,88): scale, crop, flip, normalise, one launch
+//   lips_prepare_kernel     uint8 mouth ROIs (N,Tv,H,W) -> float32 lips (N,1,Tv,88,88): scale, crop, flip, normalise, one launch; its RATE
+//                           form also selects the frames of a track at another frame rate (frame_rate.h): output frame p reads c(p)
 //   wavnorm_stats_kernel    per-chunk (sum, sum of squares) of every mixture / source row in float64, shifted by the row's first sample
 //   wavnorm_apply_kernel    every workgroup re-reduces its row's partials in a fixed order, then (x - mean) / (std_mix + eps)
 //   resample_kernel         polyphase FIR with torchaudio's Hann-windowed sinc bank; bank rows and the input segment resident in LDS
@@ -10,6 +11,7 @@
 
 #include "../../include/rtfs_amd.h"
 #include "common.h"
+#include "frame_rate.h"
 #include "kernels.h"
 
 namespace {
@@ -28,8 +30,11 @@ struct LipsTable {
 // A lane produces 4 adjacent output pixels: it reads the (at most two) ALIGNED dwords that hold its 4 source bytes and funnel-shifts
 // them together (dx is arbitrary, so row starts are not aligned); a dword that holds a byte of the ROI tensor lies in the same page as
 // that byte.  Stores: 16 bytes per lane, 1024 contiguous bytes per wave; a frame is 30976 bytes = 242 whole 128-byte lines.
+// RATE: the track holds Tv_in camera frames at a / b fps and output frame t of its Tv reads camera frame c(t) < Tv_in (block-uniform).
+template <bool RATE>
 __global__ __launch_bounds__(256) void lips_prepare_kernel(const unsigned char* __restrict__ roi, LipsTable tab, float* __restrict__ out,
-                                                            int track0, int Tv, int H, int W, double mean, double stdv) {
+                                                            int track0, int Tv, int H, int W, double mean, double stdv, int Tv_in,
+                                                            long long a, long long b) {
     __shared__ float lut[256];
     const int tid = threadIdx.x;
     lut[tid] = (float)((((double)tid - 0.0) / 255.0 - mean) / stdv);
@@ -39,7 +44,8 @@ __global__ __launch_bounds__(256) void lips_prepare_kernel(const unsigned char* 
     const int dy = e & 0x7fff, dx = (e >> 15) & 0x7fff;
     const bool flip = (e >> 30) & 1;
     const size_t img = (size_t)(track0 + nl) * Tv + t;
-    const unsigned char* src = roi + img * H * W + (size_t)dy * W + dx;
+    const size_t img_in = RATE ? (size_t)(track0 + nl) * Tv_in + (size_t)fr_source(a, b, t) : img;
+    const unsigned char* src = roi + img_in * H * W + (size_t)dy * W + dx;
     float* dst = out + img * (CROP * CROP);
     for (int q = tid; q < IMG_QUADS; q += 256) {
         const int y = q / (CROP / 4), x0 = 4 * (q - y * (CROP / 4));
@@ -238,10 +244,11 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
 }  // namespace
 
 // ================================================================ launchers
-int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,
-                        hipStream_t st) {
+// a == 0: no selection, Tv frames in and out; otherwise Tv = P(Tv_in) at a / b fps (reduced)
+static int launch_lips_prepare_any(const unsigned char* roi, const int* table, float* out, int N, int Tv, int Tv_in, long long a, long long b,
+                                   int H, int W, double mean, double stdv, hipStream_t st) {
     if (!roi || !table || !out) return RTFS_ERR_ARG;
-    if (N < 1 || Tv < 1 || H < CROP || W < CROP || H > 0x7fff || W > 0x7fff || (long long)N * Tv > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    if (N < 1 || Tv < 1 || Tv_in < 1 || (long long)N * Tv_in > 0x7fffffffLL || H < CROP || W < CROP || H > 0x7fff || W > 0x7fff || (long long)N * Tv > 0x7fffffffLL) return RTFS_ERR_SHAPE;
     if (((uintptr_t)out) & 15) return RTFS_ERR_ARG;
     if (!(stdv != 0.0)) return RTFS_ERR_ARG;
     for (int i = 0; i < N; ++i) {  // an offset that leaves the ROI is refused before anything is launched
@@ -255,11 +262,28 @@ int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, 
         for (int i = 0; i < LIPS_TRACKS; ++i)
             tab.v[i] = i < nt ? (unsigned)table[3 * (t0 + i)] | ((unsigned)table[3 * (t0 + i) + 1] << 15) | ((unsigned)table[3 * (t0 + i) + 2] << 30)
                               : 0u;
-        hipLaunchKernelGGL(lips_prepare_kernel, dim3(nt * Tv), dim3(256), 0, st, roi, tab, out, t0, Tv, H, W, mean, stdv);
+        if (a)
+            hipLaunchKernelGGL(lips_prepare_kernel<true>, dim3(nt * Tv), dim3(256), 0, st, roi, tab, out, t0, Tv, H, W, mean, stdv, Tv_in, a, b);
+        else
+            hipLaunchKernelGGL(lips_prepare_kernel<false>, dim3(nt * Tv), dim3(256), 0, st, roi, tab, out, t0, Tv, H, W, mean, stdv, Tv, 0LL, 0LL);
         const int e = rtfs_launch_status();
         if (e != RTFS_OK) return e;
     }
     return RTFS_OK;
+}
+
+int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,
+                        hipStream_t st) {
+    return launch_lips_prepare_any(roi, table, out, N, Tv, Tv, 0, 0, H, W, mean, stdv, st);
+}
+
+int launch_lips_prepare_rate(const unsigned char* roi, const int* table, float* out, int N, int Tv_in, int H, int W, double mean, double stdv,
+                             int rate_num, int rate_den, hipStream_t st) {
+    long long a, b;
+    if (!fr_reduce(rate_num, rate_den, &a, &b) || Tv_in < 1) return RTFS_ERR_ARG;
+    const long long Tv = fr_count(a, b, Tv_in);
+    if (Tv < 1 || Tv > 0x7fffffffLL) return RTFS_ERR_SHAPE;  // a single frame at more than 50 fps shows in no model frame
+    return launch_lips_prepare_any(roi, table, out, N, (int)Tv, Tv_in, a, b, H, W, mean, stdv, st);
 }
 
 size_t wav_normalize_workspace_bytes(int B, int K, int L) {
@@ -336,6 +360,11 @@ extern "C" {
 int rtfs_lips_prepare_u8(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double std,
                          void* stream) {
     return launch_lips_prepare(roi, table, out, N, Tv, H, W, mean, std, (hipStream_t)stream);
+}
+
+int rtfs_lips_prepare_rate_u8(const unsigned char* roi, const int* table, float* out, int N, int Tv_in, int H, int W, double mean, double std,
+                              int rate_num, int rate_den, void* stream) {
+    return launch_lips_prepare_rate(roi, table, out, N, Tv_in, H, W, mean, std, rate_num, rate_den, (hipStream_t)stream);
 }
 
 size_t rtfs_wav_normalize_workspace_bytes(int B, int K, int L) { return wav_normalize_workspace_bytes(B, K, L); }

@@ -381,6 +381,9 @@ int launch_live_overlap_add_faces(const long long* table, const float* y, float*
 // preparing raw recordings (k_prep.hip): uint8 mouth ROIs -> normalised lips, waveform normalisation, polyphase resampling
 int launch_lips_prepare(const unsigned char* roi, const int* table, float* out, int N, int Tv, int H, int W, double mean, double stdv,
                         hipStream_t st);
+// the same with frame selection: roi (N,Tv_in,H,W) at rate_num / rate_den fps -> out (N,1,P(Tv_in),88,88)
+int launch_lips_prepare_rate(const unsigned char* roi, const int* table, float* out, int N, int Tv_in, int H, int W, double mean, double stdv,
+                             int rate_num, int rate_den, hipStream_t st);
 size_t wav_normalize_workspace_bytes(int B, int K, int L);
 int launch_wav_normalize(const float* mix, const float* src, const float* std_in, float* mix_out, float* src_out, int B, int K, int L,
                          double eps, void* ws, size_t ws_bytes, hipStream_t st);
@@ -399,8 +402,14 @@ int video_frontend_windows(const float* windows, const float* pack, float* emb, 
 // live streams from camera frames (k_live_video.hip): tick plan (host), chunk ingest + stem windows in one launch, embedding scatter
 int live_video_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
                     int max_frames, long long* new_counters, long long* table, long long* sizes, int* refused);
+// ... and at the camera's own frame rate (frame_rate.h): chunk sizes in camera frames, a fourth counter and a ninth table column
+int live_video_rate_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, int R, int slots, int flush,
+                         int max_frames, int rate_num, int rate_den, long long* new_counters, long long* table, long long* sizes,
+                         int* refused);
+int frame_rate_map(int rate_num, int rate_den, long long n_in, long long* n_out, long long* src);
+// rate_num = rate_den = 0: the chunks hold model frames (the table of live_video_plan)
 int launch_live_video_ingest(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, bool u8, int H, int W,
-                             int dy, int dx, double mean, double stdv, hipStream_t st);
+                             int dy, int dx, double mean, double stdv, int rate_num, int rate_den, hipStream_t st);
 int launch_live_video_scatter(const float* emb, const long long* table, float* out, int R, int row_begin, int n, hipStream_t st);
 int launch_live_video_reset(const long long* ids, float* hist, int R, hipStream_t st);
 

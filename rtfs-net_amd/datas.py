@@ -10,6 +10,8 @@ in float64 numpy."""
 from __future__ import annotations
 
 import ctypes as C
+import fractions
+import operator
 import random
 
 import torch
@@ -17,7 +19,7 @@ import torch
 from . import _lib
 
 __all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
-           "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams"]
+           "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams", "frame_rate_of", "frame_rate_map"]
 
 CROP = 88
 MAX_RATIO = 640
@@ -81,6 +83,44 @@ def open_resample_streams(slots, orig_freq, new_freq=16000, max_chunk=None, devi
     every chunk edge with zeros and rounds every chunk's length up.  ValueError for equal rates and for what ``resample_plan`` refuses."""
     from . import streaming
     return streaming.open_resample_streams(slots, orig_freq, new_freq, max_chunk=max_chunk, device=device)
+
+
+# ---------------------------------------------------------------- frame rates
+def frame_rate_of(frame_rate):
+    """A camera's frame rate as a reduced ``Fraction``: an int, a ``Fraction``, (num, den), or a float, which is taken as
+    ``Fraction(x).limit_denominator(1001)`` (29.97 -> 2997/100, 29.97002997 -> 30000/1001).  ValueError for anything else, a rate
+    outside [1, 240] fps or a term above 2^20 (what ``rtfs_frame_rate_map`` refuses)."""
+    f = frame_rate
+    try:
+        if isinstance(f, bool):
+            raise TypeError
+        if isinstance(f, fractions.Fraction):
+            rate = f
+        elif isinstance(f, float):
+            rate = fractions.Fraction(f).limit_denominator(1001)
+        elif isinstance(f, (tuple, list)):
+            if len(f) != 2 or any(isinstance(v, bool) for v in f):
+                raise TypeError
+            rate = fractions.Fraction(operator.index(f[0]), operator.index(f[1]))
+        else:
+            rate = fractions.Fraction(operator.index(f))
+    except (TypeError, ValueError, ZeroDivisionError, OverflowError):
+        raise ValueError(f"frame_rate = {frame_rate!r}; an int, a Fraction, (num, den) or a float") from None
+    if not 1 <= rate <= 240 or max(rate.numerator, rate.denominator) > 1 << 20:
+        raise ValueError(f"frame_rate = {frame_rate!r}; between 1 and 240 fps, numerator and denominator at most 2^20")
+    return rate
+
+
+def frame_rate_map(n, frame_rate):
+    """The camera frames that the model's 25 fps frames show, for a track of ``n`` camera frames at ``frame_rate``: a list of P(n)
+    indices, entry p = c(p) (``rtfs_frame_rate_map``; DESIGN.md "Live streams at the camera's frame rate").  At 25 fps it is 0 .. n - 1."""
+    rate, n = frame_rate_of(frame_rate), operator.index(n)
+    lib, out = _lib.load(), C.c_longlong(0)
+    if n < 0 or lib.rtfs_frame_rate_map(rate.numerator, rate.denominator, n, C.byref(out), None) != 0:
+        raise ValueError(f"frame_rate_map: n = {n} frames at {rate} fps")
+    src = (C.c_longlong * max(out.value, 1))()
+    _lib.check(lib.rtfs_frame_rate_map(rate.numerator, rate.denominator, n, C.byref(out), src), "rtfs_frame_rate_map")
+    return list(src[:out.value])
 
 
 # ---------------------------------------------------------------- waveform normalisation
@@ -213,10 +253,12 @@ class Compose:
             rows.append((dy, dx, flip.draw(rng) if flip is not None else 0))
         return rows
 
-    def __call__(self, sample, rng=None, table=None):
+    def __call__(self, sample, rng=None, table=None, frame_rate=25):
         """sample uint8 (Tv,H,W) | (N,Tv,H,W) on the device -> float32 (N,1,Tv,88,88).  ``rng``: a ``random.Random`` for the draws (default:
-        the ``random`` module); ``table``: explicit (dy, dx, flip) rows instead of the chain's own."""
+        the ``random`` module); ``table``: explicit (dy, dx, flip) rows instead of the chain's own.  ``frame_rate`` other than 25: the
+        track holds the camera's frames at that rate and the result the P(Tv) frames ``frame_rate_map`` selects, in the same launch."""
         _, _, mean, std = self.collapse()
+        rate = frame_rate_of(frame_rate)
         if not isinstance(sample, torch.Tensor) or not sample.is_cuda:
             raise RuntimeError("rtfs_net_amd.datas pipelines run on the MI355X only: got a host array (there is no CPU fallback)")
         if sample.dtype != torch.uint8:
@@ -231,6 +273,17 @@ class Compose:
         if len(rows) != N or any(len(r) != 3 for r in rows):
             raise ValueError(f"offset table must hold {N} rows of (dy, dx, flip)")
         tab = (C.c_int * (3 * N))(*[v for r in rows for v in r])
+        if rate != 25:
+            Tv_out = len(frame_rate_map(Tv, rate))
+            if Tv_out < 1:
+                raise ValueError(f"mouth ROIs of {Tv} frame(s) at {rate} fps hold no 25 fps frame")
+            out = _lib.empty(N, 1, Tv_out, CROP, CROP, device=roi.device)
+            code = _lib.load().rtfs_lips_prepare_rate_u8(C.c_void_p(roi.data_ptr()), tab, _lib.ptr(out), N, Tv, H, W, mean, std,
+                                                         rate.numerator, rate.denominator, _lib.stream_of(roi))
+            if code == -4:
+                raise ValueError(f"rtfs_lips_prepare_rate_u8: an offset of {rows} leaves the {H} x {W} ROI")
+            _lib.check(code, "rtfs_lips_prepare_rate_u8")
+            return out
         out = _lib.empty(N, 1, Tv, CROP, CROP, device=roi.device)
         code = _lib.load().rtfs_lips_prepare_u8(C.c_void_p(roi.data_ptr()), tab, _lib.ptr(out), N, Tv, H, W, mean, std, _lib.stream_of(roi))
         if code == -4:

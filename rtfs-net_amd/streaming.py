@@ -25,7 +25,8 @@ PLAN_WORDS = 13  # RTFS_LIVE_PLAN_WORDS: [slot | a | na | f | nf | e | cnt | row
 _REASONS = {1: "bad argument", 2: "unknown slot id", 3: "slot named twice", 4: "chunk larger than max_chunk",
             5: "audio ran too far ahead of video: the push would overwrite samples a not-yet-emitted window needs",
             6: "video ran too far ahead of audio: the push would overwrite frames a not-yet-emitted window needs",
-            7: "flush of a stream with samples but no video frame", 8: "inconsistent counters", 9: "push to a slot without a face"}
+            7: "flush of a stream with samples but no video frame", 8: "inconsistent counters", 9: "push to a slot without a face",
+            10: "frame rate outside [1, 240] fps or not a fraction of terms up to 2^20"}
 
 
 def _weights(window, hop, device):
@@ -674,6 +675,7 @@ def open_face_streams(model, slots, max_speakers, window=32000, hop=None, max_ch
 
 # ================================================================ live streams from camera frames (DESIGN.md "Live streams from camera frames")
 VIDEO_PLAN_WORDS = 8  # RTFS_LIVE_VIDEO_PLAN_WORDS: [slot | g | m | v | k | row0 | out_off | side]
+RATE_PLAN_WORDS = 9  # RTFS_LIVE_VIDEO_RATE_PLAN_WORDS: the same in model frames | n0 camera frames received before the push
 LOOKAHEAD = 2  # frames: the stem's temporal kernel is 5 with padding 2, so embedding q needs the prepared frames q - 2 .. q + 2
 CROP = 88
 
@@ -696,10 +698,14 @@ class LipStreamPool(_Pool):
         self.model, self.slots, self.max_frames, self.roi_hw, self.max_batch_frames = model, slots, max_frames, roi_hw, max_batch_frames
         self.device = next(model.parameters()).device
         self.on_hip = self.device.type == "cuda"
-        self._counters = [[0, 0, 0] for _ in range(slots)]
+        self._counters = [[0] * self._WORDS for _ in range(slots)]
         self._hist = _lib.empty(slots, 2, 4, CROP, CROP, device=self.device)
-        self._win = _lib.empty(slots * max(max_frames, LOOKAHEAD), 5, 94, 94, device=self.device)
+        self._win = _lib.empty(slots * max(self._max_model_frames(), LOOKAHEAD), 5, 94, 94, device=self.device)
         self._reset_state(None, slots)
+
+    def _max_model_frames(self):
+        """The most model frames one push can complete."""
+        return self.max_frames
 
     # -- public
     def counters(self, slot):
@@ -769,7 +775,8 @@ class LipStreamPool(_Pool):
         R = len(ids)
         if R == 0:
             return []
-        new, table, (rows, floats, max_m) = self._plan(ids, ms, flush)
+        new, table, sizes = self._plan(ids, ms, flush)
+        (rows, floats), max_m, W = sizes[:2], sizes[-1], self._WORDS  # max_m: the largest m in model frames
         if not self.on_hip:
             raise RuntimeError("rtfs_net_amd kernels run on the MI355X only: the pool lies on a CPU device (there is no CPU fallback)")
         lib, dev = _lib.load(), self.device
@@ -777,16 +784,7 @@ class LipStreamPool(_Pool):
         with torch.no_grad():
             tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
             st = _lib.stream_of(self._win)
-            if u8:
-                from . import datas
-                H, W = self.roi_hw
-                crop, _, mean, std = datas.get_preprocessing_pipelines()["val"].collapse()
-                dy, dx = crop.offsets(H, W)
-                _lib.check(lib.rtfs_live_video_ingest_u8(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush), H, W,
-                                                         dy, dx, mean, std, st), "rtfs_live_video_ingest_u8")
-            else:
-                _lib.check(lib.rtfs_live_video_ingest_f32(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush), st),
-                           "rtfs_live_video_ingest_f32")
+            self._ingest(lib, tab, R, rows, max_m, flush, u8, st)
             out = _lib.empty(floats, device=dev)
             pk = self.model.pack()
             for c0 in range(0, rows, self.max_batch_frames):  # the trunk in pieces: the workspace is ~1.7 MB per frame
@@ -797,9 +795,22 @@ class LipStreamPool(_Pool):
             if flush:
                 self._reset_state(tab[:R], R)
         for r, s in enumerate(ids):
-            self._counters[s] = new[3 * r:3 * r + 3]
+            self._counters[s] = new[W * r:W * r + W]
         ks, offs = table[4 * R:5 * R], table[6 * R:7 * R]
         return [out[off:off + 512 * k].view(512, k) for k, off in zip(ks, offs)]
+
+    def _ingest(self, lib, tab, R, rows, max_m, flush, u8, st):
+        """The ingest launch of a tick: the chunks (or, at a flush, the end padding) -> the stem windows and the new history."""
+        if u8:
+            from . import datas
+            H, W = self.roi_hw
+            crop, _, mean, std = datas.get_preprocessing_pipelines()["val"].collapse()
+            dy, dx = crop.offsets(H, W)
+            _lib.check(lib.rtfs_live_video_ingest_u8(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush), H, W,
+                                                     dy, dx, mean, std, st), "rtfs_live_video_ingest_u8")
+        else:
+            _lib.check(lib.rtfs_live_video_ingest_f32(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush), st),
+                       "rtfs_live_video_ingest_f32")
 
     def _reset_state(self, ids, R):
         """Give both history buffers of R slots (a device tensor of ids; None = the first R) defined contents.  Which planes hold a frame
@@ -810,8 +821,54 @@ class LipStreamPool(_Pool):
         _lib.check(_lib.load().rtfs_live_video_reset(_lib.ptr(ids), _lib.ptr(self._hist), R, _lib.stream_of(self._hist)), "rtfs_live_video_reset")
 
 
-def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=1600):
+class RateLipStreamPool(LipStreamPool):
+    """``LipStreamPool`` for a camera at ``frame_rate`` other than 25 fps (DESIGN.md "Live streams at the camera's frame rate").  Built
+    by ``FRCNNVideoModel.open_streams(..., frame_rate=...)``.
+
+    Chunks hold CAMERA frames, at most ``max_frames`` of them; the model frames they complete are selected inside the ingest launch by
+    the rule of ``datas.frame_rate_map``, so for any chunking the outputs equal those of a ``LipStreamPool`` fed the selected frames of
+    the whole track.  A slot keeps one more host counter, n camera frames received; everything downstream counts model frames.  A
+    push may complete no model frame (one frame at 60 fps): it returns (512, 0) and leaves the history alone."""
+
+    _WORDS, _NAMES = 4, ("g", "v", "side", "n")
+
+    def __init__(self, model, slots, max_frames, roi_hw, max_batch_frames, rate):
+        self.frame_rate = rate
+        super().__init__(model, slots, max_frames, roi_hw, max_batch_frames)
+
+    def _max_model_frames(self):
+        """P(n0 + max_frames) - P(n0) <= ceil(25 max_frames / rate)."""
+        return -(-25 * self.max_frames * self.frame_rate.denominator // self.frame_rate.numerator)
+
+    def counters(self, slot):
+        """(n, v) of a slot: camera frames received, embeddings emitted."""
+        c = self._counters[int(slot)]
+        return c[3], c[1]
+
+    def _plan(self, ids, ms, flush):
+        if not ids:
+            return [], [], [0, 0, 0, 0]
+        num, den = self.frame_rate.numerator, self.frame_rate.denominator
+        return self._call_planner(_lib.load().rtfs_live_video_rate_plan, ids, (ms,), flush, (self.max_frames, num, den), RATE_PLAN_WORDS, 4)
+
+    def _ingest(self, lib, tab, R, rows, max_m, flush, u8, st):
+        num, den = self.frame_rate.numerator, self.frame_rate.denominator
+        if u8:
+            from . import datas
+            H, W = self.roi_hw
+            crop, _, mean, std = datas.get_preprocessing_pipelines()["val"].collapse()
+            dy, dx = crop.offsets(H, W)
+            _lib.check(lib.rtfs_live_video_ingest_rate_u8(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush),
+                                                          H, W, dy, dx, mean, std, num, den, st), "rtfs_live_video_ingest_rate_u8")
+        else:
+            _lib.check(lib.rtfs_live_video_ingest_rate_f32(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._win), R, rows, max_m, int(flush),
+                                                           num, den, st), "rtfs_live_video_ingest_rate_f32")
+
+
+def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=1600, frame_rate=25):
     """``FRCNNVideoModel.open_streams``: check the arguments, then allocate the pool."""
+    from . import datas
+    rate = datas.frame_rate_of(frame_rate)
     try:
         slots, max_frames, max_batch_frames = operator.index(slots), operator.index(max_frames), operator.index(max_batch_frames)
         roi_hw = None if roi_hw is None else (operator.index(roi_hw[0]), operator.index(roi_hw[1]))
@@ -825,6 +882,10 @@ def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=
         raise ValueError(f"open_streams: roi_hw = {roi_hw}; mouth ROIs must be at least {CROP} x {CROP}")
     if model.training:
         raise RuntimeError("FRCNNVideoModel.open_streams is inference only: call .eval()")
+    if rate != 25:
+        if slots * max(-(-25 * max_frames * rate.denominator // rate.numerator), LOOKAHEAD) > 0x7fffffff // 5:
+            raise ValueError(f"open_streams: slots = {slots}, max_frames = {max_frames} at {rate} fps: too many frames per tick")
+        return RateLipStreamPool(model, slots, max_frames, roi_hw, max_batch_frames, rate)
     return LipStreamPool(model, slots, max_frames, roi_hw, max_batch_frames)
 
 
@@ -868,7 +929,8 @@ class CameraStreamPool(_Pool):
         return embs if K == 1 else [embs[r:r + K] for r in range(0, len(embs), K)]
 
     def counters(self, slot):
-        """((a, f, e, o) of the audio pool, (g, v) of the lip pool); f == v between calls."""
+        """((a, f, e, o) of the audio pool, (g, v) of the lip pool - (n, v) with n camera frames at another ``frame_rate``); f == v between
+        calls."""
         return self.audio.counters(slot), self.lips.counters(slot)
 
     def _check_audio(self, ids, audio_chunks):
@@ -894,7 +956,7 @@ class CameraStreamPool(_Pool):
 
     def push(self, slot_ids, audio_chunks, roi_chunks):
         """One chunk of 16 kHz audio ((n)|(1,n) float32, 0 <= n <= max_chunk) and one of mouth frames (as ``LipStreamPool.push`` takes them,
-        at most max_chunk // 640) for each slot named; either may be empty.  Returns, per named slot, the (n_src, k) newly final samples,
+        at most max_chunk // 640; at another ``frame_rate`` camera frames, at most ``lips.max_frames``) for each slot named; either may be empty.  Returns, per named slot, the (n_src, k) newly final samples,
         as ``StreamPool.push`` does.  ValueError - before any launch, all state unchanged - for what either pool refuses."""
         ids, ms, rois, u8 = self._check_rois(slot_ids, roi_chunks)
         wavs = self._check_audio(ids, audio_chunks)
@@ -912,11 +974,12 @@ class CameraStreamPool(_Pool):
         K, R = self.speakers, len(ids)
         _, vtab, _ = self.lips._plan(self._tracks(ids), ms, False)
         ks = vtab[4 * R * K:5 * R * K][::K]  # the tracks of a slot share their counters: one k per slot
+        gs, mm = vtab[R * K:2 * R * K][::K], vtab[2 * R * K:3 * R * K][::K]  # ... one g and one m, both in model frames
         # frames may run (window + max_chunk) / 640 + 2 ahead of the first window not yet emitted: the two embeddings a flush still owes
         # then always fit the inner pool's ring
         room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
-        for s, m in zip(ids, ms[::K]):
-            if self.lips._counters[s * K][0] + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
+        for s, g, m in zip(ids, gs, mm):
+            if g + m - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
                 raise ValueError(f"{type(self).__name__}.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
         return self.audio._plan_push(ids, na, ks)
 
@@ -996,7 +1059,7 @@ class FaceCameraStreamPool(CameraStreamPool):
 
     def add_face(self, slot, face=None):
         s = self.audio._slot(slot, "add_face")
-        if any(self.audio._counters[s]) or any(any(self.lips._counters[s * self.speakers + j][:2]) for j in range(self.speakers)):
+        if any(self.audio._counters[s]) or any(any(self.lips.counters(s * self.speakers + j)) for j in range(self.speakers)):
             raise ValueError(f"FaceCameraStreamPool.add_face: slot {s} is in mid-stream; a face joins a camera stream on an idle slot only")
         return self.audio.add_face(s, face)
 
@@ -1057,7 +1120,7 @@ class FaceCameraStreamPool(CameraStreamPool):
         room = (self.audio.window + self.max_chunk) // SPF + LOOKAHEAD
         for s, g in zip(ids, groups):  # the tracks of a slot share their counters: one k per slot
             ks.append(vtab[4 * T + at])
-            if self.lips._counters[g[0]][0] + ms[at] - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:
+            if vtab[T + at] + vtab[2 * T + at] - self.audio._counters[s][2] * (self.audio.hop // SPF) > room:  # g + m in model frames
                 raise ValueError(f"FaceCameraStreamPool.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
             at += len(g)
         return self.audio._plan_push(ids, na, ks)
@@ -1106,8 +1169,10 @@ class FaceCameraStreamPool(CameraStreamPool):
 
 
 def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1,
-                        max_speakers=None):
+                        max_speakers=None, frame_rate=25):
     """``System.open_camera_streams``: the lip pool and the audio pool of one set of slots."""
+    from . import datas
+    rate = datas.frame_rate_of(frame_rate)
     K = speakers_of(speakers)
     if max_speakers is not None:
         if K != 1:
@@ -1122,7 +1187,8 @@ def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, m
         raise ValueError(f"open_camera_streams: speakers = {K} with sample_rate = {sample_rate}: several speakers take 16 kHz audio only")
     if _rate(sample_rate) != FS:
         mc = (window if max_chunk is None else max_chunk)
-        return _open_at_rate(lambda room: open_camera_streams(system, slots, window, hop, mc + room, max_batch, roi_hw), sample_rate, mc)
+        return _open_at_rate(lambda room: open_camera_streams(system, slots, window, hop, mc + room, max_batch, roi_hw, frame_rate=rate),
+                             sample_rate, mc)
     if system.video_model is None:
         raise ValueError("open_camera_streams: the system has no video model; push lip embeddings through open_streams")
     try:
@@ -1132,9 +1198,16 @@ def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, m
         raise ValueError("open_camera_streams: window and max_chunk must be integers") from None
     if max_chunk < SPF or max_chunk % SPF:
         raise ValueError(f"open_camera_streams: max_chunk = {max_chunk} must be a positive multiple of {SPF}")
+    # the most camera frames whose model frames still number at most max_chunk // 640 per push: ceil(25 mc / rate) <= max_chunk // 640
+    mc = (max_chunk // SPF) * rate.numerator // (25 * rate.denominator)
+    if mc < 1:
+        raise ValueError(f"open_camera_streams: max_chunk = {max_chunk} holds no camera frame at {rate} fps")
     audio = system.audio_model.open_streams(slots, window=window, hop=hop, max_chunk=max_chunk + LOOKAHEAD * SPF, max_batch=max_batch,
                                             **(dict(speakers=K) if max_speakers is None else dict(max_speakers=K)))
-    lips = system.video_model.open_streams(audio.slots * K, max_frames=max_chunk // SPF, roi_hw=roi_hw)
+    if rate != 25:
+        lips = system.video_model.open_streams(audio.slots * K, max_frames=mc, roi_hw=roi_hw, frame_rate=rate)
+    else:
+        lips = system.video_model.open_streams(audio.slots * K, max_frames=max_chunk // SPF, roi_hw=roi_hw)
     if lips.device != audio.device:
         raise ValueError(f"open_camera_streams: the video model lies on {lips.device}, the audio model on {audio.device}")
     if max_speakers is not None:
@@ -1307,6 +1380,10 @@ class RateStreamPool(_Pool):
         self.slots, self.device, self.n_src = inner.slots, inner.device, inner.n_src
         self.sample_rate, self.max_chunk_in = resampler.orig_freq, resampler.max_chunk
         self.tail = -(-resampler.n * resampler.width // resampler.o) + 1
+        self.max_frames = max_chunk // SPF  # per push; in camera frames where the lip pool runs at the camera's own frame rate
+        rate = getattr(inner.lips, "frame_rate", None) if self.camera else None
+        if rate is not None:
+            self.max_frames = max(1, self.max_frames * rate.numerator // (25 * rate.denominator))
 
     def counters(self, slot):
         """((a, g) of the resampler, the inner pool's counters)."""
@@ -1335,8 +1412,8 @@ class RateStreamPool(_Pool):
         ids, ms, wavs, i16, rplan = self.resampler._check_chunks(slot_ids, audio_chunks)
         if self.camera:
             _, nf, rois, u8 = self.inner.lips._check_chunks(ids, video_chunks)
-            if any(f > self.max_chunk // SPF for f in nf):
-                raise ValueError(f"RateStreamPool.push: a chunk of {max(nf)} frames; at most max_chunk // {SPF} = {self.max_chunk // SPF}")
+            if any(f > self.max_frames for f in nf):
+                raise ValueError(f"RateStreamPool.push: a chunk of {max(nf)} frames; at most {self.max_frames} (max_chunk // {SPF} model frames)")
         else:
             _, _, nf, _, _ = self.audio._check_chunks(ids, [_lib.empty(0, device=self.device)] * len(ids), video_chunks)
         if not ids:

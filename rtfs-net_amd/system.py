@@ -86,19 +86,27 @@ class System(nn.Module):
             emb = self.video_model(mouths.reshape(B * K, *mouths.shape[2:]).type_as(wav))
         return self.audio_model.separate_long_speakers(wav, emb.reshape(B, K, *emb.shape[1:]), **kw)
 
-    def separate_recording(self, wav, sample_rate, mouth_rois, normalize_audio=False, **kw):
+    def separate_recording(self, wav, sample_rate, mouth_rois, normalize_audio=False, frame_rate=25, **kw):
         """A raw recording end to end on the device (inference), the whole of ``infer_any_video.py:63-86``: wav (L) | (B,L) at
         ``sample_rate`` Hz, mouth_rois uint8 (Tv,H,W) | (B,Tv,H,W) at 25 fps -> (B, n_src, L at 16 kHz).  ``datas.resample`` to 16 kHz, the
         ``"val"`` pipeline on the ROIs (one launch), the video model once on the whole track, then ``separate_long(**kw)``.  Without a
         video model the mouth slot holds lip embeddings (B,512,Tv), as in ``separate_long``; a floating mouth slot is taken as prepared
         lips.  ``normalize_audio`` (``datas.normalize_mixture`` on the resampled mixture) is off by default: the reference's script computes
-        the mixture's deviation and never applies it."""
+        the mixture's deviation and never applies it.
+
+        ``frame_rate`` other than 25 (DESIGN.md "Live streams at the camera's frame rate"): the uint8 ROIs are the camera's frames at that
+        rate and the ``"val"`` launch selects the frames ``datas.frame_rate_map`` names, where the reference converts the file with
+        ``ffmpeg -r 25`` first.  Prepared lips and embeddings are model frames already: ValueError with another rate."""
         from . import datas
+        rate = datas.frame_rate_of(frame_rate)
         wav = datas.resample(wav, sample_rate, 16000)
         if normalize_audio:
             wav = datas.normalize_mixture(wav)
         if self.video_model is not None and mouth_rois.dtype == torch.uint8:
-            mouth_rois = datas.get_preprocessing_pipelines()["val"](mouth_rois)
+            val = datas.get_preprocessing_pipelines()["val"]
+            mouth_rois = val(mouth_rois) if rate == 25 else val(mouth_rois, frame_rate=rate)
+        elif rate != 25:
+            raise ValueError(f"System.separate_recording: frame_rate = {rate} needs uint8 mouth ROIs and a video model")
         return self.separate_long(wav, mouth_rois, **kw)
 
     def separate_many(self, wavs, mouths, **kw):
@@ -161,7 +169,7 @@ class System(nn.Module):
         return self.audio_model.open_streams(sample_rate=sample_rate, **kw)
 
     def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1,
-                            max_speakers=None):
+                            max_speakers=None, frame_rate=25):
         """Live streams from microphone samples and camera frames (inference; DESIGN.md "Live streams from camera frames") ->
         ``streaming.CameraStreamPool``.  ``pool.push(slot_ids, audio_chunks, roi_chunks)`` takes 16 kHz audio chunks of at most
         ``max_chunk`` samples (default ``window``) and uint8 mouth ROIs (m,H,W) with (H,W) == ``roi_hw`` at 25 fps (or float32 prepared lips
@@ -180,23 +188,36 @@ class System(nn.Module):
 
         ``max_speakers`` = Kmax (DESIGN.md "Faces that come and go") -> ``streaming.FaceCameraStreamPool``: up to Kmax faces per slot,
         declared with ``pool.add_face`` on an idle slot and ended with ``pool.drop_face`` at any time; the ROI chunk of a slot holds one
-        block per active face and the results are dicts face id -> samples.  Excludes ``speakers``; 16 kHz audio only."""
-        from . import streaming
-        return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
-                                             sample_rate=sample_rate, speakers=speakers, max_speakers=max_speakers)
+        block per active face and the results are dicts face id -> samples.  Excludes ``speakers``; 16 kHz audio only.
 
-    def separate_recordings(self, wavs, sample_rates, mouth_rois, normalize_audio=False, **kw):
+        ``frame_rate`` other than 25 (an int, a ``Fraction``, (num, den) or a float; DESIGN.md "Live streams at the camera's frame rate"),
+        with any of the above: the ROI chunks hold the camera's frames at that rate, at most floor(max_chunk / 640 * frame_rate / 25) per
+        push, and the frames the model sees are selected inside the ingest launch (``datas.frame_rate_map``); for any chunking the
+        outputs equal ``separate_recording(..., frame_rate=frame_rate)``.  The lip pool is a ``streaming.RateLipStreamPool`` whose
+        ``counters`` report camera frames received; ``window``, ``hop`` and ``max_chunk`` stay in 16 kHz samples."""
+        from . import streaming
+        if frame_rate == 25:
+            return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
+                                                 sample_rate=sample_rate, speakers=speakers, max_speakers=max_speakers)
+        return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
+                                             sample_rate=sample_rate, speakers=speakers, max_speakers=max_speakers, frame_rate=frame_rate)
+
+    def separate_recordings(self, wavs, sample_rates, mouth_rois, normalize_audio=False, frame_rates=None, **kw):
         """The list form of ``separate_recording``: wavs = R raw recordings (L_r) at ``sample_rates[r]`` Hz, mouth_rois = R uint8
         tracks (Tv_r,H,W) at 25 fps -> a list of R tensors (n_src, L_r at 16 kHz).  Per recording ``datas.resample`` to 16 kHz and the ``"val"`` pipeline on the ROIs, then ``separate_many(**kw)``.  Without a video model the mouth
-        slot holds lip embeddings (512,Tv_r); a floating mouth slot is taken as prepared lips (1,Tv_r,88,88)."""
+        slot holds lip embeddings (512,Tv_r); a floating mouth slot is taken as prepared lips (1,Tv_r,88,88).  ``frame_rates``: one camera
+        frame rate per recording, as ``separate_recording`` takes it (None: all 25)."""
         from . import datas
         wavs, mouth_rois = list(wavs), list(mouth_rois)
         rates = list(sample_rates)
         if len(wavs) < 1 or len(rates) != len(wavs) or len(mouth_rois) != len(wavs):
             raise ValueError(f"System.separate_recordings: {len(wavs)} recording(s), {len(rates)} sample rate(s), {len(mouth_rois)} mouth track(s)")
+        fps = [25] * len(wavs) if frame_rates is None else [datas.frame_rate_of(f) for f in frame_rates]
+        if len(fps) != len(wavs):
+            raise ValueError(f"System.separate_recordings: {len(wavs)} recording(s) and {len(fps)} frame rate(s)")
         val = datas.get_preprocessing_pipelines()["val"]
         prepared, mouths = [], []
-        for w, fs, roi in zip(wavs, rates, mouth_rois):
+        for w, fs, roi, fr in zip(wavs, rates, mouth_rois, fps):
             if not isinstance(w, torch.Tensor) or w.ndim not in (1, 2) or (w.ndim == 2 and w.shape[0] != 1):
                 raise ValueError("System.separate_recordings: every recording must be a tensor (L) or (1,L)")
             w = datas.resample(w.reshape(-1), fs, 16000)
@@ -204,7 +225,9 @@ class System(nn.Module):
             if self.video_model is not None and roi.dtype == torch.uint8:
                 if roi.ndim != 3:
                     raise ValueError(f"System.separate_recordings: uint8 mouth ROIs must be (Tv,H,W) per recording; got {tuple(roi.shape)}")
-                roi = val(roi)[0]  # (1,Tv,88,88)
+                roi = (val(roi) if fr == 25 else val(roi, frame_rate=fr))[0]  # (1,Tv,88,88)
+            elif fr != 25:
+                raise ValueError(f"System.separate_recordings: frame rate {fr} needs uint8 mouth ROIs and a video model")
             mouths.append(roi)
         return self.separate_many(prepared, mouths, **kw)
 

@@ -137,16 +137,23 @@ class FRCNNVideoModel(nn.Module):
                    "rtfs_video_frontend_f32")
         return out
 
-    def open_streams(self, slots, max_frames=50, roi_hw=None, max_batch_frames=1600):
+    def open_streams(self, slots, max_frames=50, roi_hw=None, max_batch_frames=1600, frame_rate=25):
         """``slots`` live lip tracks embedded chunk by chunk (inference only; DESIGN.md "Live streams from camera frames") ->
         ``streaming.LipStreamPool``.  ``pool.push(slot_ids, chunks)`` takes what the camera delivered - uint8 mouth ROIs (m,H,W) with
         (H,W) == ``roi_hw`` (None: fixed by the first ROIs pushed), or float32 prepared lips (m,88,88), at most ``max_frames`` per chunk -
         and returns the (512,k) embeddings that became final; ``pool.flush(slot_ids)`` ends tracks.  For any chunking the concatenated
         outputs equal ``forward`` on the whole track: the state per slot is four prepared frames, the look-ahead two frames.  A tick's
         frames go through the trunk in pieces of at most ``max_batch_frames``.  ValueError for sizes below 1 or ROIs under 88 x 88;
-        RuntimeError in ``.train()`` mode."""
+        RuntimeError in ``.train()`` mode.
+
+        ``frame_rate`` other than 25 (an int, a ``Fraction``, (num, den) or a float; DESIGN.md "Live streams at the camera's frame rate")
+        -> ``streaming.RateLipStreamPool``: the chunks hold the camera's frames at that rate, at most ``max_frames`` of them, and the
+        frames the model sees are selected on the device by the rule of ``datas.frame_rate_map``, whatever the chunking."""
         from . import streaming
-        return streaming.open_lip_streams(self, slots, max_frames=max_frames, roi_hw=roi_hw, max_batch_frames=max_batch_frames)
+        if frame_rate == 25:
+            return streaming.open_lip_streams(self, slots, max_frames=max_frames, roi_hw=roi_hw, max_batch_frames=max_batch_frames)
+        return streaming.open_lip_streams(self, slots, max_frames=max_frames, roi_hw=roi_hw, max_batch_frames=max_batch_frames,
+                                          frame_rate=frame_rate)
 
     def init_from(self, path):
         """frcnn_videomodel.py:74-76 + update_frcnn_parameter (:103-115), with a non-executing loader."""
