@@ -397,6 +397,12 @@ int rtfs_debug_sweep_stamps(const float* x, const float* pack, float* out, int B
  * all DEVICE pointers, row-major; exact for small integer data. */
 int rtfs_selftest_mfma_f16(const float* A, const float* B, float* D, void* stream);
 
+/* Self test of the nearest up-sampling index rule every kernel shares (torch's float32 rule).  All DEVICE pointers,
+ * int32.  pairs[2p], pairs[2p+1] = (n_in, n_out) with 1 <= n_in <= n_out; offsets[2p], offsets[2p+1] = where pair p's tables start in
+ * out_src / out_first_dst.  One launch writes out_src[offsets[2p] + d] = source index read by destination d (d < n_out) and
+ * out_first_dst[offsets[2p+1] + j] = first destination whose source is >= j (j <= n_in; n_out at j = n_in). */
+int rtfs_selftest_nearest_index(const int* pairs, int n_pairs, const int* offsets, int* out_src, int* out_first_dst, void* stream);
+
 /* Measurement hook (bench.py roofline leg; no reference counterpart).  While enabled (on = n > 0), every n-th launch of the fused
  * dual-path sweep kernel is bracketed by HIP events recorded on the stream it is launched on (on = 0: off).  collect() waits for
  * the recorded launches (host-side, call it outside any timed region / graph capture), writes per-launch

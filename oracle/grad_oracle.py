@@ -11,6 +11,20 @@ from __future__ import annotations
 import torch
 
 
+def nearest_up_torch(x, size):
+    """F.interpolate(x, size=size, mode="nearest") as the reference's FLOAT32 run indexes it, for a tensor of any dtype: an explicit gather
+    through rtfs_oracle.nearest_index over the trailing len(size) axes.  Calling F.interpolate on the float64 tensors used here would
+    not do: torch computes the source index in the tensor's dtype, and on float64 that is floor(dst * n_in / n_out) exactly, which
+    differs from the float32 rule at e.g. (32 -> 164) (tests/test_nearest_host.py)."""
+    from .rtfs_oracle import nearest_index
+    size = (size,) if isinstance(size, int) else tuple(size)
+    for ax, n_out in zip(range(x.dim() - len(size), x.dim()), size):
+        n_in = x.shape[ax]
+        if n_in != n_out:
+            x = x.index_select(ax, torch.from_numpy(nearest_index(n_in, int(n_out))).to(x.device))
+    return x
+
+
 def sru_forward_torch(x, layers):
     """rtfs_oracle.sru_forward in torch (call site reference rnn_layers.py:99-105,150).
     x (L,N,Din); layers = [(weight (Din, 2d*k), weight_c (4d), bias (4d))]; returns h (L,N,2d)."""
@@ -177,10 +191,10 @@ def injection_multi_sum_torch(local, glob, p):
     kw = dict(k=4, depthwise=True, norm=True)
     le = _cna(local, _sub(p, "local_embedding"), **kw)
     if local.shape[-2] * local.shape[-1] > glob.shape[-2] * glob.shape[-1]:
-        ge = F.interpolate(_cna(glob, _sub(p, "global_embedding"), **kw), size=local.shape[-2:], mode="nearest")
-        gate = F.interpolate(_cna(glob, _sub(p, "global_gate"), act=3, **kw), size=local.shape[-2:], mode="nearest")
+        ge = nearest_up_torch(_cna(glob, _sub(p, "global_embedding"), **kw), local.shape[-2:])
+        gate = nearest_up_torch(_cna(glob, _sub(p, "global_gate"), act=3, **kw), local.shape[-2:])
     else:
-        gi = F.interpolate(glob, size=local.shape[-2:], mode="nearest")
+        gi = nearest_up_torch(glob, local.shape[-2:])
         ge, gate = _cna(gi, _sub(p, "global_embedding"), **kw), _cna(gi, _sub(p, "global_gate"), act=3, **kw)
     return le * gate + ge
 
@@ -256,11 +270,11 @@ def caf_torch(a, v, p, bn_train=False):
         y = F.batch_norm(y, p[pre + ".full_layer.3.running_mean"].detach(), p[pre + ".full_layer.3.running_var"].detach(),
                          p[pre + ".full_layer.3.weight"], p[pre + ".full_layer.3.bias"], bn_train, 0.1, 1e-5)
         return torch.relu(y) if relu else y
-    b_t = F.interpolate(video_conv("resize"), size=T, mode="nearest").unsqueeze(-1)
+    b_t = nearest_up_torch(video_conv("resize"), T).unsqueeze(-1)
     k1 = audio_conv("key_embed", True) * b_t
     val = audio_conv("value_embed", False)
     att = video_conv("attention_embed").reshape(B, C, 4, -1).mean(2)
-    att = F.interpolate(torch.softmax(att, -1), size=T, mode="nearest").unsqueeze(-1)
+    att = nearest_up_torch(torch.softmax(att, -1), T).unsqueeze(-1)
     return k1 + att * val
 
 
@@ -358,10 +372,10 @@ def vp_block_torch(v, p, depth=4, bn_train=False):
         q = _sub(p, name)
         le = _cna1d(loc, _sub(q, "local_embedding"), **kw)
         if loc.shape[-1] > glo.shape[-1]:
-            ge = F.interpolate(_cna1d(glo, _sub(q, "global_embedding"), **kw), size=loc.shape[-1], mode="nearest")
-            gate = F.interpolate(_cna1d(glo, _sub(q, "global_gate"), act=3, **kw), size=loc.shape[-1], mode="nearest")
+            ge = nearest_up_torch(_cna1d(glo, _sub(q, "global_embedding"), **kw), loc.shape[-1])
+            gate = nearest_up_torch(_cna1d(glo, _sub(q, "global_gate"), act=3, **kw), loc.shape[-1])
         else:
-            gi = F.interpolate(glo, size=loc.shape[-1], mode="nearest")
+            gi = nearest_up_torch(glo, loc.shape[-1])
             ge, gate = _cna1d(gi, _sub(q, "global_embedding"), **kw), _cna1d(gi, _sub(q, "global_gate"), act=3, **kw)
         return le * gate + ge
     xf = [ims(downs[i], g, f"fusion_layers.{i}") for i in range(depth)]

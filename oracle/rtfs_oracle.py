@@ -205,7 +205,17 @@ def adaptive_avg_pool_axis(x, out, axis):
 
 
 def nearest_index(n_in, n_out):
-    """Legacy ``mode='nearest'`` source index: floor(dst * in / out)."""
+    """``F.interpolate(mode='nearest')`` source index as stock torch computes it on float32 tensors - what the reference runs:
+    min(int(floorf(dst * (float(n_in) / float(n_out)))), n_in - 1), the quotient and the product each rounded to float32.
+    Not the exact-arithmetic floor(dst * n_in / n_out) (``nearest_index_integer``): the two differ at e.g. (16, 82), dst 41."""
+    scale = np.float32(n_in) / np.float32(n_out)
+    src = np.floor(np.arange(n_out, dtype=np.float32) * scale)
+    return np.minimum(src.astype(np.int64), n_in - 1)
+
+
+def nearest_index_integer(n_in, n_out):
+    """floor(dst * n_in / n_out) in exact integer arithmetic: what torch falls back to on float64 tensors.  Nothing on the model's
+    path uses it; it is kept to state where the two rules differ (tests/test_nearest_host.py)."""
     return np.minimum((np.arange(n_out) * n_in) // n_out, n_in - 1)
 
 

@@ -1323,6 +1323,11 @@ int rtfs_selftest_mfma_f16(const float* A, const float* B, float* D, void* strea
     RTFS_RETURN_IF(!A || !B || !D, RTFS_ERR_ARG);
     return launch_mfma_f16_selftest(A, B, D, S(stream));
 }
+int rtfs_selftest_nearest_index(const int* pairs, int n_pairs, const int* offsets, int* out_src, int* out_first_dst, void* stream) {
+    RTFS_RETURN_IF(!pairs || !offsets || !out_src || !out_first_dst, RTFS_ERR_ARG);
+    RTFS_RETURN_IF(n_pairs < 1, RTFS_ERR_SHAPE);
+    return launch_nearest_index_selftest(pairs, n_pairs, offsets, out_src, out_first_dst, S(stream));
+}
 
 // ------------------------------------------------------------ measurement hook
 int rtfs_sweep_timing_enable(int on) { return dualpath_timing_enable(on); }

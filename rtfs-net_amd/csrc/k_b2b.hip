@@ -111,7 +111,7 @@ __global__ __launch_bounds__(B4_NT) void pws_b2b4_kernel(B2bArgs a, int ntiles, 
             const __amdgpu_buffer_rsrc_t a1s = rsrc_of(a.a1 + (size_t)ba * 256 * CS + wp0);
             const __amdgpu_buffer_rsrc_t xes = rsrc_of(a.xenc + (size_t)b * 64 * CS + wp0);
             const unsigned CS4 = CS * 4u;  // row pitch in bytes
-            // CAF: this lane's two video frames (legacy nearest: tv = floor(t Tv / T), t = pixel / F) in the (B, Tv, 256) tables
+            // CAF: this lane's two video frames (nearest: tv = nearest_src(t, Tv, T), t = pixel / F) in the (B, Tv, 256) tables
             const float *crt0 = nullptr, *crt1 = nullptr, *cat0 = nullptr, *cat1 = nullptr;
             if (CAF) {
                 const int px = wp0 + 2 * r;

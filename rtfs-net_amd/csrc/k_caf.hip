@@ -4,7 +4,7 @@
 //       att = softmax_Tv( mean_k gLN(Conv1d(512->1024, k1, groups 256))(video) )    (attention_embed, :261-264)
 //   caf_apply_kernel  audio side, one pass over the (B,256,T,F) features:
 //       out = ReLU(BN(dw1x1 audio)) * r[tv(t)] + att[tv(t)] * BN(dw1x1 audio)       (:258-259,268-272)
-//     with tv(t) = floor(t*Tv/T) (legacy nearest) and the eval-mode BatchNorm folded into one FMA.
+//     with tv(t) = nearest_src(t, Tv, T), torch's float32 'nearest' rule (common.h), and the eval-mode BatchNorm folded into one FMA.
 #include "common.h"
 #include "kernels.h"
 
@@ -114,5 +114,23 @@ int launch_caf_video(const CafArgs& a, int B, hipStream_t st) {
 }
 int launch_caf_apply(const CafArgs& a, int B, hipStream_t st) {
     hipLaunchKernelGGL(caf_apply_kernel, dim3(cdiv(a.T * a.F, 256 * 4), 256, B), dim3(256), 0, st, a);
+    return rtfs_launch_status();
+}
+
+// ---------------------------------------------------------------- nearest index rule self test
+// One workgroup per pair p, (n_in, n_out) = (pairs[2p], pairs[2p + 1]); the host passes two prefix sums interleaved:
+//   out_src[offsets[2p] + d]           = nearest_src(d, n_in, n_out)        d in [0, n_out)
+//   out_first_dst[offsets[2p + 1] + j] = nearest_first_dst(j, n_in, n_out)  j in [0, n_in]
+__global__ __launch_bounds__(256) void nearest_index_selftest_kernel(const int* __restrict__ pairs, const int* __restrict__ offsets,
+                                                                    int* __restrict__ out_src, int* __restrict__ out_first_dst) {
+    const int p = blockIdx.x, n_in = pairs[2 * p], n_out = pairs[2 * p + 1];
+    int* s = out_src + offsets[2 * p];
+    int* f = out_first_dst + offsets[2 * p + 1];
+    for (int d = threadIdx.x; d < n_out; d += 256) s[d] = nearest_src(d, n_in, n_out);
+    for (int j = threadIdx.x; j <= n_in; j += 256) f[j] = nearest_first_dst(j, n_in, n_out);
+}
+int launch_nearest_index_selftest(const int* pairs, int n_pairs, const int* offsets, int* out_src, int* out_first_dst, hipStream_t st) {
+    if (n_pairs < 1) return RTFS_ERR_SHAPE;
+    hipLaunchKernelGGL(nearest_index_selftest_kernel, dim3(n_pairs), dim3(256), 0, st, pairs, offsets, out_src, out_first_dst);
     return rtfs_launch_status();
 }

@@ -16,7 +16,7 @@
 // overlapping row segments of neighbouring lanes are served by L1, HBM sees each element once per band).
 // MODE 0: write pre-norm outputs + stats.  MODE 1: stats only.  MODE 2: TFAR apply:
 //   out = gLN_loc(conv(x)) * sigmoid(gLN_gate(G_gate)^) + gLN_emb(G_emb)^ [+ gLN_add(addend)]
-// where ^ is legacy nearest up-sampling from (Hg, Wg) to (H, W).
+// where ^ is nearest up-sampling from (Hg, Wg) to (H, W), source index nearest_src (common.h: torch's float32 rule).
 template <int NCONV, bool IN_AFFINE, int MODE>
 __device__ __forceinline__ void dw_s1_body(const DwArgs& a, const float* __restrict__ X, const float* __restrict__ GATE,
                                            const float* __restrict__ EMB, const float* __restrict__ ADD, float* __restrict__ O0,
@@ -278,8 +278,8 @@ __device__ __forceinline__ void dw1p_body(const DwArgs& a, const float* __restri
 #pragma unroll
         for (int n = 0; n < NCONV; ++n) os[n] = buf_rsrc((n == 0 ? OUT : n == 1 ? OUT1 : n == 2 ? OUT2 : OUT3) + sample);
     }
-    // MODE 2: the gate / embedding tensors live at low resolution (Hg x Wg); output (t, x) reads ('nearest', legacy) row floor(t Hg / H),
-    // column floor(x Wg / W).  When 2 Wg <= W the pair's two source columns are s0 and s0 or s0 + 1, and s0 + 1 is then exactly the NEXT
+    // MODE 2: the gate / embedding tensors live at low resolution (Hg x Wg); output (t, x) reads row floor(t Hg / H),
+    // column floor(x Wg / W): 'nearest' up-sampling on the pairs where that quotient is torch's index (launch_dw_s1 sends no other here).  When 2 Wg <= W the pair's two source columns are s0 and s0 or s0 + 1, and s0 + 1 is then exactly the NEXT
     // lane's s0: one load per lane and row, the neighbour's by DPP.
     unsigned fga = 0, fgb = 0;
     bool gnext = false;
@@ -987,12 +987,34 @@ static int launch_dw1p_t(const DwArgs& a_, int B, hipStream_t st) {
     return rtfs_launch_status();
 }
 
+// The packed kernels' MODE 2 takes its low-resolution row from an incremental integer quotient floor(t Hg / H) (and its columns from
+// floor(x Wg / W)): that is nearest_src (common.h, torch's float32 rule) on every pair the model meets - T / 2 -> T, 64 -> 129 - but not on
+// every pair (14 -> 46, 26 -> 44, ...).  Host mirror of nearest_src, same float32 operations; the few pairs a process meets are remembered.
+static bool nearest_is_integer_quotient(int n_in, int n_out) {
+    struct Seen { int n_in, n_out; bool same; };
+    static thread_local Seen seen[4] = {};
+    static thread_local int next = 0;
+    for (const Seen& s : seen)
+        if (s.n_in == n_in && s.n_out == n_out) return s.same;
+    bool same = n_in >= 1 && n_out >= n_in;
+    const float scale = (float)n_in / (float)n_out;
+    for (int d = 0; same && d < n_out; ++d) {
+        const int f = (int)floorf((float)d * scale), q = (int)(((long long)d * n_in) / n_out);
+        same = (f < n_in - 1 ? f : n_in - 1) == (q < n_in - 1 ? q : n_in - 1);
+    }
+    seen[next] = Seen{n_in, n_out, same};
+    next = (next + 1) & 3;
+    return same;
+}
+
 int launch_dw_s1(const DwArgs& a_, int nconv, bool in_affine, int mode, int B, hipStream_t st) {
     if (a_.cs && a_.cs < a_.H * a_.W) return RTFS_ERR_SHAPE;
     DwArgs a = a_;
     if (!a.cs) a.cs = a.H * a.W;
     if ((size_t)a.C * a.cs * 4 >= ((size_t)1 << 31)) return RTFS_ERR_SHAPE;  // 32-bit lane offsets
-    if (a.W >= 16) {  // packed two-column variant (v_pk_fma_f32); the scalar kernel below only serves very narrow inputs
+    // (a pair where the integer quotient is not torch's index goes to the one-column kernel below, which calls nearest_src)
+    const bool packed_ok = mode != 2 || (nearest_is_integer_quotient(a.Hg, a.H) && nearest_is_integer_quotient(a.Wg, a.W));
+    if (a.W >= 16 && packed_ok) {  // packed two-column variant (v_pk_fma_f32); the scalar kernel below only serves very narrow inputs
         // row variant (a wave = one 129-column channel row, stores leave as aligned 512-byte chunks: dw1p_body): the three full-resolution
         // read + write passes of a block
         const bool row_ok = nconv == 1 && a.W == 129 && a.C % 4 == 0 && a.cs % 32 == 0 && a.out[0] && ((size_t)a.out[0] & 127) == 0;

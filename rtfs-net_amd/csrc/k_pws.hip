@@ -78,7 +78,7 @@ __device__ __forceinline__ void pws_body(const PwArgs& a, int ntiles, int tiles_
         const bool tail = S == 2 && p0 == P - 1;  // lane holds pixel P-1 in .y
         const size_t xb = (size_t)b * CIN * CS + pl;
         size_t cafb[S];
-        if (CAF) {  // nearest up-sampling of the video-side terms: tv = floor(t * Tv / T)
+        if (CAF) {  // nearest up-sampling of the video-side terms: tv = nearest_src(t, Tv, T)
 #pragma unroll
             for (int sl = 0; sl < S; ++sl) {
                 const int t = min(p0 + sl, P - 1) / a.caf_F;

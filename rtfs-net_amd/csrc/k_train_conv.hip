@@ -1047,9 +1047,10 @@ __global__ __launch_bounds__(256) void tfar_combine_bwd_kernel(const float* __re
         const size_t p = i / CV;
         const int wg = (int)(p % Wg), hg = (int)((p / Wg) % Hg);
         const size_t n = p / ((size_t)Wg * Hg);
-        // local h reads global floor(h * Hg / H) == hg  <=>  h in [ceil(hg*H/Hg), ceil((hg+1)*H/Hg))
-        const int h0 = (int)(((long)hg * H + Hg - 1) / Hg), h1 = min(H, (int)(((long)(hg + 1) * H + Hg - 1) / Hg));
-        const int w0 = (int)(((long)wg * W + Wg - 1) / Wg), w1 = min(W, (int)(((long)(wg + 1) * W + Wg - 1) / Wg));
+        // local h reads global nearest_src(h, Hg, H) == hg  <=>  h in [nearest_first_dst(hg), nearest_first_dst(hg + 1)): the inverse is
+        // taken from the forward's own (float32) index rule, not from ceil(hg * H / Hg), which departs from it at e.g. (14 -> 46)
+        const int h0 = nearest_first_dst(hg, Hg, H), h1 = nearest_first_dst(hg + 1, Hg, H);
+        const int w0 = nearest_first_dst(wg, Wg, W), w1 = nearest_first_dst(wg + 1, Wg, W);
         float g[V], sg[V], se[V];
         ldv<V>(gate + p * C + c, 0, g);
 #pragma unroll
@@ -1253,7 +1254,7 @@ __global__ __launch_bounds__(256) void caf_combine_bwd_kernel(const float* __res
     if (id >= N * Tv) return;
     const size_t n = id / Tv;
     const int tv = (int)(id % Tv);
-    const int t0 = (int)(((long)tv * T + Tv - 1) / Tv), t1 = min(T, (int)(((long)(tv + 1) * T + Tv - 1) / Tv));
+    const int t0 = nearest_first_dst(tv, Tv, T), t1 = nearest_first_dst(tv + 1, Tv, T);  // the forward's own index rule, inverted
     const float rv = r[id], av = att[id];
     float sr = 0.f, sa = 0.f;
     for (int t = t0; t < t1; ++t)

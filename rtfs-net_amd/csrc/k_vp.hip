@@ -290,7 +290,7 @@ __global__ __launch_bounds__(VP_NT) void vp_block_kernel(const float* __restrict
     auto ims = [&](const Ims& m, const float* loc, int n, const float* glob, int ng, const float* add, float* dst) {
         for (int i = tid; i < VC * n; i += VP_NT) {
             const int c = i / n, t = i - c * n;
-            const int tg = min((t * ng) / n, ng - 1);
+            const int tg = nearest_src(t, ng, n);  // torch's float32 rule (common.h), as the per-layer route's F.interpolate
             const float l = fmaf(dw3(loc + c * n, n, t, m.lw + c * 3), m.ls[c], m.lb[c]);
             const float e = fmaf(dw3(glob + c * ng, ng, tg, m.ew + c * 3), m.es[c], m.eb[c]);
             const float g = sigmoidf_(fmaf(dw3(glob + c * ng, ng, tg, m.gw + c * 3), m.gs[c], m.gb[c]));

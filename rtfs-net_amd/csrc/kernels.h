@@ -147,6 +147,7 @@ int launch_pws_head4(const PwArgs& a, int B, hipStream_t st);  // block head on 
 int launch_pws_gateway_proj(const PwArgs& a, int B, hipStream_t st);
 int launch_pws_residual(const PwArgs& a, int B, hipStream_t st);
 int launch_mfma_f16_selftest(const float* A, const float* B, float* D, hipStream_t st);
+int launch_nearest_index_selftest(const int* pairs, int n_pairs, const int* offsets, int* out_src, int* out_first_dst, hipStream_t st);  // k_caf.hip
 
 // Depthwise 4x4 family.  Tensors are (B, C, H, W) contiguous.
 struct DwArgs {

@@ -256,3 +256,74 @@ def test_end_to_end_lstm_ragged_5s():
     out = O.avnet_forward(wav, emb, _lstm_sd(), repeats=4)
     e = rel_err(out, g["out"])
     assert e <= 1e-4, f"5.3 s LSTM end-to-end rel err {e:.3e}"
+
+
+# ---------------- lengths where torch's float32 nearest index departs from floor(dst * n_in / n_out) (oracle/make_golden_nearest.py)
+@pytest.mark.parametrize("name,T,Tv,seed,frames", [("mod_caf_T82_Tv16", 82, 16, 201, (41,)), ("mod_caf_T164_Tv32", 164, 32, 203, (41, 82))])
+def test_caf_departing_lengths(name, T, Tv, seed, frames):
+    """The CAF cell where frame 41 (and 82) reads video frame 7 (15), not 8 (16) as exact arithmetic would have it.  Besides the probe, the
+    departing output frames are compared whole.  With the integer rule in the oracle frame 41 misses by 1.9 (T = 82) and 1.0 (T = 164) of
+    the frame's scale, and the probe by 0.23 and 0.78."""
+    y = O.caf(rand((2, 256, T, 129), seed), rand((2, 512, Tv), seed + 1), CELL)
+    g = load_golden(name)
+    check_probe(g, "out", y, TOL)
+    for fr in frames:
+        ref = g[f"out.frame{fr}"] if f"out.frame{fr}" in g else load_golden(f"{name}_frame{fr}")[f"out.frame{fr}"]
+        e = rel_err(y[:, :, fr], ref)
+        assert e <= TOL, f"{name}: frame {fr} rel err {e:.3e}"
+
+
+def test_vp_block_departing_length():
+    """The VP block at Tv = 122: its 16 -> 122 up-sampling departs at output frames 60..62 (stored whole, with their neighbours 59 and 63)."""
+    y = O.vp_block(rand((2, 512, 122), 205), VBLK)
+    g = load_golden("mod_vp122")
+    check_probe(g, "out", y, TOL)
+    for fr in range(59, 64):
+        e = rel_err(y[:, :, fr], g[f"out.frame{fr}"])
+        assert e <= TOL, f"mod_vp122: frame {fr} rel err {e:.3e}"
+
+
+def test_end_to_end_departing_length():
+    """Whole model at L = 20900: (Tv, T) = (32, 164), the CAF reads other video frames at t = 41 and 82 than the integer rule."""
+    g = load_golden("e2e_R4_L20900_B1")
+    wav, emb = make_inputs(1, 20900, 32, 41)
+    out, ints = O.avnet_forward(wav, emb, SD, repeats=4, return_internals=True)
+    for k in ["a0", "a1", "refined", "sep"]:
+        check_probe(g, k, ints[k], 5 * TOL, "e2e_R4_L20900_B1.")
+    e = rel_err(out, g["out"])
+    assert e <= 5 * TOL, f"e2e_R4_L20900_B1: out rel err {e:.3e}"
+
+
+def test_gradient_oracle_at_departing_length():
+    """test_gradient_oracle_against_reference_autograd's eval case at L = 10400, (Tv, T) = (16, 82), B = 1 (grad_R2_L10400_B1: the reference
+    in float64 with the float32 nearest indices its float32 training takes; tensors over 1024 elements as 1024 samples + L2).  Same bars."""
+    import zlib
+    import torch
+    from oracle import grad_oracle as G
+    gold = load_golden("grad_R2_L10400_B1")
+    B, Ls, Tv = 1, 10400, 16
+    wav, emb = make_inputs(B, Ls, Tv, seed=42)
+    tgt = (0.05 * np.random.default_rng(43).standard_normal((B, 1, Ls))).astype(np.float32)
+    pt = {k: torch.tensor(v, dtype=torch.float64, requires_grad=("running" not in k and not k.endswith("pos_enc.pe")))
+          for k, v in SD.items() if "num_batches" not in k}
+    out = G.avnet_torch(torch.tensor(wav, dtype=torch.float64), torch.tensor(emb, dtype=torch.float64), pt, 2, vp_trainable=True)
+    loss = G.pit_loss_torch(out, torch.tensor(tgt, dtype=torch.float64), "snr")
+    loss.backward()
+    assert abs(float(loss) - float(gold["eval/loss"])) <= 1e-7 * abs(float(gold["eval/loss"]))
+    assert rel_err(out.detach().numpy(), gold["eval/est"]) <= 1e-6
+    names = [k for k, v in pt.items() if v.requires_grad]
+    assert len(names) == 264
+    gscale = max(np.abs(gold[f"eval/{k}"]).max() for k in names)
+    worst = 0.0
+    for k in names:
+        g = pt[k].grad.numpy().reshape(-1)
+        ref = gold[f"eval/{k}"]
+        if g.size > 1024:
+            rs = np.random.RandomState(zlib.crc32(k.encode()) & 0x7FFFFFFF)
+            idx = rs.choice(g.size, 1024, replace=False).astype(np.int64)
+            assert abs(np.sqrt((g ** 2).sum()) - gold[f"eval/{k}#l2"]) <= 1e-6 * max(gold[f"eval/{k}#l2"], 1e-12 * gscale), k
+            g = g[idx]
+        err = np.abs(g - ref).max() / max(np.abs(ref).max(), 1e-9 * gscale)
+        worst = max(worst, err)
+        assert err <= 1e-6, (k, err)
+    print(f"gradient oracle vs reference autograd at (Tv, T) = (16, 82): worst relative error {worst:.2e} over {len(names)} tensors")
