@@ -693,6 +693,54 @@ int rtfs_live_video_ingest_rate_f32(const long long* table, float* hist, float* 
 int rtfs_lips_prepare_rate_u8(const unsigned char* roi, const int* table, float* out, int N, int Tv_in, int H, int W, double mean,
                               double std, int rate_num, int rate_den, void* stream);
 
+/* Live streams with per-frame timestamps (DESIGN.md "Live streams with per-frame timestamps"; csrc/frame_rate.h): cameras that drop
+ * frames or change rate.  Camera frame i carries an integer stamp tau_i in a timebase of tb ticks per second, 1 <= tb <= 2^30,
+ * 0 <= tau < 2^40, strictly increasing within a stream.  Its 25 fps tick is r(i) = G(tau_i), G(W) = floor((50 W + tb) / (2 tb)); model
+ * frame p shows c(p) = max(0, max{i : 50 tau_i < tb (2p + 1)}), the last camera frame whose tick is at or before p and the first camera
+ * frame before that.  Once every frame stamped below a watermark W is in, exactly the model frames p < G(W) are final.  With
+ * tau_i = i tb b / a this is the rule of rtfs_frame_rate_map.
+ * rtfs_timestamp_map (host only): the whole-track rule.  n stamps and the largest `until` of the stream (0: none) -> *n_out =
+ *   g_end = max(G(max(tau_{n-1}, until)), r(n - 1) + 1) (0 for n == 0) and, when src is not NULL, src[p] = c(p) for p < g_end.  -4 for a
+ *   timebase, a stamp or an until outside the bounds, stamps that do not increase, n or g_end above 2^36, or n_out NULL.
+ * rtfs_live_video_stamp_plan (host only): rtfs_live_video_rate_plan with stamps.  counters (R x 7): [g | v | side | n | last stamp |
+ *   watermark W | hside], g == G(W) once n > 0 (g == 0 before).  n_frames (R): camera frames per chunk, at most max_frames; stamps: the
+ *   stamps of all chunks one behind the other in the order the slots are named; until (R, or NULL for none): the caller's promise that
+ *   every later frame of the slot is stamped >= until[r] (0: no promise).  A push gives W' = max(W, the chunk's last stamp, until),
+ *   g' = max(g, G(W')) - but g' = 0 while no camera frame has ever arrived - v' = max(v, g' - 2), side flips iff m = g' - g > 0, hside
+ *   flips iff n_frames > 0.  A flush (n_frames and stamps ignored) ends the stream at g_end = max(g, G(max(W, until)), r(n - 1) + 1), so
+ *   the last camera frame is shown at least by its own tick: it finalises m = g_end - g frames, emits v .. g_end - 1 and returns zero
+ *   counters.  The table has RTFS_LIVE_VIDEO_STAMP_PLAN_WORDS = 12 columns, the nine of the rate plan | hside | soff | m_cam = n_frames;
+ *   sources (at most R max_frames words) holds at soff + (p - g), for each newly final model frame p of the slot, the chunk-local index
+ *   of c(p) or -1 for camera frame n - 1, the held frame; sizes[5] = [rows | out_floats | largest chunk | largest m | words of sources].
+ *   Refusals as rtfs_live_video_rate_plan, and: a timebase outside [1, 2^30] (RTFS_LIVE_BAD_TIMEBASE, refused[0] = -1); a stamp outside
+ *   [0, 2^40) or an until outside [0, 2^40] (RTFS_LIVE_BAD_STAMP); a stamp below W, or not above its predecessor
+ *   (RTFS_LIVE_STAMP_ORDER); m > max_frames (RTFS_LIVE_TOO_MANY_FINAL: advance until in smaller steps); counters this planner cannot have
+ *   produced (BAD_COUNTERS).
+ * rtfs_live_video_ingest_stamp_u8 / _f32 (one launch each): table = the plan's 12 R words, the column of chunk addresses and the
+ *   sizes[4] source words, 13 R + sizes[4] words in all.  State: hist as above and held (slots, 2, 88, 88), 16-byte aligned: buffer hside
+ *   holds the prepared last camera frame received.  A model frame p >= g is read from the chunk at its source index or, for -1, from
+ *   held[slot, hside]; one more block per slot with m_cam > 0 writes the chunk's last frame, prepared, into held[slot, 1 - hside].  All
+ *   reads of held go to hside and the one write to 1 - hside, so no block reads a cell another block of the launch writes.  Camera
+ *   frames that no model frame shows are not read, except the chunk's last.  max_m = sizes[3], max_cam = sizes[2]; flush != 0: max_cam
+ *   must be 0, frames in [g, g + m) come from held, frames behind are zero planes, and neither history nor held is written.  A
+ *   timebase outside [1, 2^30], a NULL or misaligned pointer: -4 before any launch.
+ * rtfs_live_video_stamp_reset (two launches): rtfs_live_video_reset, and zeroes both held planes of the same slots.  No kernel depends
+ *   on those contents: held[hside] is read only after a push wrote it. */
+#define RTFS_LIVE_VIDEO_STAMP_PLAN_WORDS 12
+#define RTFS_LIVE_BAD_TIMEBASE 11
+#define RTFS_LIVE_BAD_STAMP 12
+#define RTFS_LIVE_STAMP_ORDER 13
+#define RTFS_LIVE_TOO_MANY_FINAL 14
+int rtfs_timestamp_map(const long long* stamps, long long n, long long timebase, long long until, long long* n_out, long long* src);
+int rtfs_live_video_stamp_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, const long long* stamps,
+                               const long long* until, int R, int slots, int flush, int max_frames, long long timebase,
+                               long long* new_counters, long long* table, long long* sources, long long* sizes, int* refused);
+int rtfs_live_video_ingest_stamp_u8(const long long* table, float* hist, float* held, float* windows, int R, int rows, int max_m, int max_cam,
+                                    int flush, int H, int W, int dy, int dx, double mean, double std, long long timebase, void* stream);
+int rtfs_live_video_ingest_stamp_f32(const long long* table, float* hist, float* held, float* windows, int R, int rows, int max_m, int max_cam,
+                                     int flush, long long timebase, void* stream);
+int rtfs_live_video_stamp_reset(const long long* ids, float* hist, float* held, int R, void* stream);
+
 /* Optimizer step on the device (rtfs-net_amd/optimizers.py AdamW; the reference builds torch.optim.AdamW through
  * src/system/optimizers.py:58-108 and Lightning clips at gradient_clip_val 5.0, train.py:142): gather of the per-tensor gradients into
  * one flat buffer, global-norm clip and AdamW in a number of launches that does not depend on the number of tensors.

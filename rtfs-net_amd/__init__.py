@@ -8,7 +8,7 @@ from . import _lib, configs, datas, layers, losses, metrics, optimizers, packing
 from .packing import invalidate_packs  # noqa: F401
 from .system import System  # noqa: F401
 from .streaming import (CameraStreamPool, FaceCameraStreamPool, FaceStreamPool, LipStreamPool, RateLipStreamPool, RateStreamPool,  # noqa: F401
-                        ResampleStreamPool, SpeakerCameraStreamPool, SpeakerStreamPool, StreamPool)
+                        ResampleStreamPool, SpeakerCameraStreamPool, SpeakerStreamPool, StampLipStreamPool, StreamPool)
 from .optimizers import make_optimizer  # noqa: F401
 from .metrics import ALLMetricsTracker, stoi  # noqa: F401
 from .datas import (Compose, Normalize, CenterCrop, RandomCrop, HorizontalFlip, get_preprocessing_pipelines, normalize_mixture,  # noqa: F401

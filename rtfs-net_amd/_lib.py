@@ -156,6 +156,11 @@ SIGNATURES = {
     "rtfs_live_video_ingest_rate_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i, _p]),
     "rtfs_live_video_ingest_rate_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "rtfs_lips_prepare_rate_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i, _p]),
+    "rtfs_timestamp_map": (_i, [_p, C.c_longlong, C.c_longlong, C.c_longlong, _p, _p]),
+    "rtfs_live_video_stamp_plan": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_longlong, _p, _p, _p, _p, _p]),
+    "rtfs_live_video_ingest_stamp_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_longlong, _p]),
+    "rtfs_live_video_ingest_stamp_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_longlong, _p]),
+    "rtfs_live_video_stamp_reset": (_i, [_p, _p, _p, _i, _p]),
     "rtfs_optim_plan": (_i, [_p, _i, _p, _p, _p]),
     "rtfs_optim_gather_f32": (_i, [_p, _p, _i, _i, _p, _p, _i, _p]),
     "rtfs_optim_sumsq_f32": (_i, [_p, _i, _i, _p, _p, _p]),

@@ -24,6 +24,24 @@ FR_HD long long fr_source(long long a, long long b, long long p) { return (a * (
 // P(n): the model frames that n camera frames give
 FR_HD long long fr_count(long long a, long long b, long long n) { return (50 * b * n + a) / (2 * a); }
 
+// PER-FRAME TIMESTAMPS (DESIGN.md "Live streams with per-frame timestamps"; tests/timestamp_oracle.py restates this by brute force).  The
+// same rule with t_i = tau_i / tb seconds in place of i b / a: camera frame i, stamped tau_i in a timebase of tb ticks per second, has the
+// 25 fps tick r(i) = floor(25 tau_i / tb + 1/2) = G(tau_i) with G(W) = floor((50 W + tb) / (2 tb)), and model frame p shows
+// c(p) = max(0, max{i : r(i) <= p}): the last camera frame whose tick is at or before p, and the first camera frame before that.
+//   r(i) <= p  <=>  25 tau_i / tb + 1/2 < p + 1  <=>  50 tau_i < tb (2p + 1)
+// Once every frame stamped below W is in, exactly the model frames p < G(W) are final: p < G(W) <=> tb (2p + 1) <= 50 W, so every
+// frame the predicate admits for such a p is stamped below W.  Conversely p >= G(W) <=> tb (2p + 1) > 50 W: any frame stamped <= W is
+// admitted, so c(p) is the last frame received or a later one.
+// Exact in 64-bit integers for 1 <= tb <= 2^30 and 0 <= tau, W <= 2^40 (50 W + tb < 2^46; p <= G(W) gives tb (2p + 1) <= 50 W + 2 tb).
+constexpr long long FR_MAX_TIMEBASE = 1LL << 30;  // ticks per second
+constexpr long long FR_MAX_STAMP = 1LL << 40;     // stamps lie below it, watermarks at or below it
+
+// G(W): the model frames that are final once every camera frame stamped below W is in; G(tau) is also the tick of a frame stamped tau
+FR_HD long long fr_stamp_count(long long tb, long long W) { return (50 * W + tb) / (2 * tb); }
+
+// the source predicate: the tick of a frame stamped tau is at or before model frame p
+FR_HD bool fr_stamp_shows(long long tb, long long tau, long long p) { return 50 * tau < tb * (2 * p + 1); }
+
 // num / den -> reduced a / b; false for what the rule does not cover
 inline bool fr_reduce(long long num, long long den, long long* a, long long* b) {
     if (num < 1 || den < 1) return false;

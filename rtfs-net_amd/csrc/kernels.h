@@ -411,6 +411,14 @@ int frame_rate_map(int rate_num, int rate_den, long long n_in, long long* n_out,
 // rate_num = rate_den = 0: the chunks hold model frames (the table of live_video_plan)
 int launch_live_video_ingest(const long long* table, float* hist, float* windows, int R, int rows, int max_m, int flush, bool u8, int H, int W,
                              int dy, int dx, double mean, double stdv, int rate_num, int rate_den, hipStream_t st);
+// ... and with per-frame timestamps (frame_rate.h): seven counters, twelve table columns, the source list and the held plane
+int live_video_stamp_plan(const long long* slot_ids, const long long* counters, const long long* n_frames, const long long* stamps,
+                          const long long* until, int R, int slots, int flush, int max_frames, long long timebase, long long* new_counters,
+                          long long* table, long long* sources, long long* sizes, int* refused);
+int timestamp_map(const long long* stamps, long long n, long long timebase, long long until, long long* n_out, long long* src);
+int launch_live_video_ingest_stamp(const long long* table, float* hist, float* held, float* windows, int R, int rows, int max_m, int max_cam,
+                                   int flush, bool u8, int H, int W, int dy, int dx, double mean, double stdv, hipStream_t st);
+int launch_live_video_stamp_reset(const long long* ids, float* hist, float* held, int R, hipStream_t st);
 int launch_live_video_scatter(const float* emb, const long long* table, float* out, int R, int row_begin, int n, hipStream_t st);
 int launch_live_video_reset(const long long* ids, float* hist, int R, hipStream_t st);
 

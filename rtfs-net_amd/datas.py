@@ -19,7 +19,8 @@ import torch
 from . import _lib
 
 __all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
-           "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams", "frame_rate_of", "frame_rate_map"]
+           "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams", "frame_rate_of", "frame_rate_map",
+           "timestamp_map"]
 
 CROP = 88
 MAX_RATIO = 640
@@ -120,6 +121,36 @@ def frame_rate_map(n, frame_rate):
         raise ValueError(f"frame_rate_map: n = {n} frames at {rate} fps")
     src = (C.c_longlong * max(out.value, 1))()
     _lib.check(lib.rtfs_frame_rate_map(rate.numerator, rate.denominator, n, C.byref(out), src), "rtfs_frame_rate_map")
+    return list(src[:out.value])
+
+
+def timestamp_map(timestamps, timebase, until=None):
+    """The camera frames that the model's 25 fps frames show, for a whole track whose frames were taken at ``timestamps`` (increasing
+    ints, or a CPU int64 tensor, in ticks of 1 / ``timebase`` s): a list, entry p = c(p), the last camera frame whose tick
+    floor(25 t + 1/2) is at or before p and the first frame before that (``rtfs_timestamp_map``; DESIGN.md "Live streams with
+    per-frame timestamps").  The track ends as a flushed stream does: with the last frame's own tick, or with the last model frame
+    that ``until`` - the largest the stream was given - makes final.  ValueError for stamps that do not increase, are negative or
+    reach 2^40, and for a timebase outside [1, 2^30]."""
+    from .streaming import timebase_of
+    tb = timebase_of(timebase)
+    if tb is None:
+        raise ValueError("timestamp_map: timebase must be an integer number of ticks per second")
+    try:
+        ts = timestamps.tolist() if isinstance(timestamps, torch.Tensor) else list(timestamps)
+        if any(isinstance(t, bool) for t in ts):
+            raise TypeError
+        ts = [operator.index(t) for t in ts]
+        u = 0 if until is None else operator.index(until)
+    except TypeError:
+        raise ValueError("timestamp_map: timestamps must be a sequence of integers and until an integer or None") from None
+    n, LL = len(ts), C.c_longlong
+    if any(not 0 <= t < 1 << 40 for t in ts) or not 0 <= u <= 1 << 40:
+        raise ValueError("timestamp_map: timestamps lie in [0, 2^40), until in [0, 2^40]")
+    lib, out, arr = _lib.load(), LL(0), (LL * max(n, 1))(*ts)
+    if lib.rtfs_timestamp_map(arr, n, tb, u, C.byref(out), None) != 0:
+        raise ValueError(f"timestamp_map: {n} timestamp(s) at {tb} ticks per second must increase (and give at most 2^36 model frames)")
+    src = (LL * max(out.value, 1))()
+    _lib.check(lib.rtfs_timestamp_map(arr, n, tb, u, C.byref(out), src), "rtfs_timestamp_map")
     return list(src[:out.value])
 
 

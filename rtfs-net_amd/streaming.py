@@ -26,7 +26,10 @@ _REASONS = {1: "bad argument", 2: "unknown slot id", 3: "slot named twice", 4: "
             5: "audio ran too far ahead of video: the push would overwrite samples a not-yet-emitted window needs",
             6: "video ran too far ahead of audio: the push would overwrite frames a not-yet-emitted window needs",
             7: "flush of a stream with samples but no video frame", 8: "inconsistent counters", 9: "push to a slot without a face",
-            10: "frame rate outside [1, 240] fps or not a fraction of terms up to 2^20"}
+            10: "frame rate outside [1, 240] fps or not a fraction of terms up to 2^20", 11: "timebase outside [1, 2^30] ticks per second",
+            12: "timestamp outside [0, 2^40) or until outside [0, 2^40]",
+            13: "timestamps must increase and none may lie below an earlier until or stamp of the stream",
+            14: "more than max_frames model frames would become final at once: advance until in smaller steps"}
 
 
 def _weights(window, hop, device):
@@ -87,10 +90,15 @@ class _Pool:
         rc = fn((LL * R)(*ids), (LL * (W * R))(*cnt), *(None if flush else (LL * R)(*v) for v in inputs), R, self.slots, int(flush), *consts,
                 new, table, sizes, refused)
         if rc != 0:
-            r, why = refused[0], _REASONS.get(refused[1], refused[1])
-            at = f" at slot {ids[r]}, counters ({', '.join(self._NAMES)}) = {tuple(cnt[W * r:W * r + len(self._NAMES)])}" if 0 <= r < R else ""
-            raise ValueError(f"{type(self).__name__}.{'flush' if flush else 'push'}: refused ({why}){at}; no slot was changed")
+            self._refused(ids, cnt, refused, flush)
         return list(new), list(table), [int(v) for v in sizes]
+
+    def _refused(self, ids, cnt, refused, flush):
+        """ValueError with the reason a planner gave in ``refused`` = [index into ids or -1 | RTFS_LIVE_* code]."""
+        R, W = len(ids), self._WORDS
+        r, why = refused[0], _REASONS.get(refused[1], refused[1])
+        at = f" at slot {ids[r]}, counters ({', '.join(self._NAMES)}) = {tuple(cnt[W * r:W * r + len(self._NAMES)])}" if 0 <= r < R else ""
+        raise ValueError(f"{type(self).__name__}.{'flush' if flush else 'push'}: refused ({why}){at}; no slot was changed")
 
 
 class StreamPool(_Pool):
@@ -693,6 +701,7 @@ class LipStreamPool(_Pool):
     is uploaded per call)."""
 
     _WORDS, _NAMES = 3, ("g", "v")
+    _PLAN_WORDS = VIDEO_PLAN_WORDS  # the columns of the tick table; the chunk pointers follow them
 
     def __init__(self, model, slots, max_frames, roi_hw, max_batch_frames):
         self.model, self.slots, self.max_frames, self.roi_hw, self.max_batch_frames = model, slots, max_frames, roi_hw, max_batch_frames
@@ -729,7 +738,9 @@ class LipStreamPool(_Pool):
         return self._tick(self._check_ids(slot_ids), None, None, False, flush=True)
 
     # -- checks (no launch, no state change)
-    def _check_chunks(self, slot_ids, chunks):
+    def _check_chunks(self, slot_ids, chunks, *stamps):
+        """-> slot ids, what each chunk brings as ``_plan`` takes it (``_sizes``: its frames), the chunks, their kind.  ``stamps``: the
+        timestamps and ``until`` of a ``StampLipStreamPool``."""
         ids = self._check_ids(slot_ids)
         try:
             chunks = list(chunks)
@@ -758,10 +769,14 @@ class LipStreamPool(_Pool):
                 raise ValueError(f"LipStreamPool.push: float32 chunk {r} must be prepared lips (m,{CROP},{CROP}); got {tuple(c.shape)}")
             if c.shape[0] > self.max_frames:
                 raise ValueError(f"LipStreamPool.push: chunk {r} holds {c.shape[0]} frames; max_frames = {self.max_frames}")
-        self._plan(ids, [int(c.shape[0]) for c in chunks], False)  # unknown / repeated ids
+        ms = self._sizes(chunks, *stamps)
+        self._plan(ids, ms, False)  # unknown / repeated ids
         if u8 and self.roi_hw is None:
             self.roi_hw = hw  # fixed by the first ROIs the pool sees
-        return ids, [int(c.shape[0]) for c in chunks], [c.contiguous() for c in chunks], u8
+        return ids, ms, [c.contiguous() for c in chunks], u8
+
+    def _sizes(self, chunks):
+        return [int(c.shape[0]) for c in chunks]
 
     def _plan(self, ids, ms, flush):
         if not ids:
@@ -776,15 +791,16 @@ class LipStreamPool(_Pool):
         if R == 0:
             return []
         new, table, sizes = self._plan(ids, ms, flush)
-        (rows, floats), max_m, W = sizes[:2], sizes[-1], self._WORDS  # max_m: the largest m in model frames
+        (rows, floats, max_in), max_m, W = sizes[:3], sizes[-1], self._WORDS  # max_m: the largest m in model frames
         if not self.on_hip:
             raise RuntimeError("rtfs_net_amd kernels run on the MI355X only: the pool lies on a CPU device (there is no CPU fallback)")
         lib, dev = _lib.load(), self.device
         ptrs = [0] * R if flush else [c.data_ptr() for c in chunks]
         with torch.no_grad():
-            tab = torch.tensor(table + ptrs, dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
+            P = self._PLAN_WORDS * R  # whatever a planner wrote behind its columns (a source list) follows the pointers
+            tab = torch.tensor(table[:P] + ptrs + table[P:], dtype=torch.int64).to(dev)  # the one host-to-device copy of the tick
             st = _lib.stream_of(self._win)
-            self._ingest(lib, tab, R, rows, max_m, flush, u8, st)
+            self._ingest(lib, tab, R, rows, max_m, flush, u8, st, max_in)
             out = _lib.empty(floats, device=dev)
             pk = self.model.pack()
             for c0 in range(0, rows, self.max_batch_frames):  # the trunk in pieces: the workspace is ~1.7 MB per frame
@@ -799,7 +815,7 @@ class LipStreamPool(_Pool):
         ks, offs = table[4 * R:5 * R], table[6 * R:7 * R]
         return [out[off:off + 512 * k].view(512, k) for k, off in zip(ks, offs)]
 
-    def _ingest(self, lib, tab, R, rows, max_m, flush, u8, st):
+    def _ingest(self, lib, tab, R, rows, max_m, flush, u8, st, max_in):
         """The ingest launch of a tick: the chunks (or, at a flush, the end padding) -> the stem windows and the new history."""
         if u8:
             from . import datas
@@ -831,6 +847,7 @@ class RateLipStreamPool(LipStreamPool):
     push may complete no model frame (one frame at 60 fps): it returns (512, 0) and leaves the history alone."""
 
     _WORDS, _NAMES = 4, ("g", "v", "side", "n")
+    _PLAN_WORDS = RATE_PLAN_WORDS
 
     def __init__(self, model, slots, max_frames, roi_hw, max_batch_frames, rate):
         self.frame_rate = rate
@@ -851,7 +868,7 @@ class RateLipStreamPool(LipStreamPool):
         num, den = self.frame_rate.numerator, self.frame_rate.denominator
         return self._call_planner(_lib.load().rtfs_live_video_rate_plan, ids, (ms,), flush, (self.max_frames, num, den), RATE_PLAN_WORDS, 4)
 
-    def _ingest(self, lib, tab, R, rows, max_m, flush, u8, st):
+    def _ingest(self, lib, tab, R, rows, max_m, flush, u8, st, max_in):
         num, den = self.frame_rate.numerator, self.frame_rate.denominator
         if u8:
             from . import datas
@@ -865,10 +882,180 @@ class RateLipStreamPool(LipStreamPool):
                                                            num, den, st), "rtfs_live_video_ingest_rate_f32")
 
 
-def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=1600, frame_rate=25):
+STAMP_PLAN_WORDS = 12  # RTFS_LIVE_VIDEO_STAMP_PLAN_WORDS: the nine of the rate plan | hside | offset into the sources | camera frames
+MAX_TIMEBASE, MAX_STAMP = 1 << 30, 1 << 40  # FR_MAX_TIMEBASE, FR_MAX_STAMP (csrc/frame_rate.h)
+
+
+def _stamp(x, what):
+    """A timestamp or an ``until`` as a Python int that fits the planner's int64 words; the planner judges its value."""
+    try:
+        if isinstance(x, bool) or str(getattr(x, "dtype", "")) in ("bool", "torch.bool"):
+            raise TypeError
+        x = operator.index(x)
+    except TypeError:
+        raise ValueError(f"StampLipStreamPool: {what} must be integers in the pool's timebase; got {x!r}") from None
+    if not -(1 << 62) <= x <= 1 << 62:
+        raise ValueError(f"StampLipStreamPool: {what} = {x} is out of range")
+    return x
+
+
+class StampLipStreamPool(LipStreamPool):
+    """``LipStreamPool`` for a camera that stamps its frames: dropped frames, a changing rate, a tracker that loses the face (DESIGN.md
+    "Live streams with per-frame timestamps").  Built by ``FRCNNVideoModel.open_streams(..., timebase=tb)``.
+
+    Every camera frame comes with an integer capture time in ticks of 1 / ``timebase`` s, increasing within a stream.  Model frame p
+    shows the last camera frame whose 25 fps tick is at or before p (the first camera frame before that), whatever the chunking: the
+    outputs equal those of a ``LipStreamPool`` fed ``rois[datas.timestamp_map(stamps, timebase, until)]``.  A model frame is final once
+    no frame that could change it is still to come: every push moves the slot's watermark W to its last stamp, and ``until`` moves it
+    further - the caller's promise that every later frame of the slot is stamped ``>= until``, which keeps a stream going while the
+    camera delivers nothing.  Without ``until`` a model frame on the last camera frame's own tick waits for the next frame: one camera
+    frame more latency than ``frame_rate=``; with ``until`` at the next frame's nominal time the emission is that pool's.
+
+    Next to the history a slot keeps ``held``, the prepared last camera frame received (two buffers of 88 x 88 floats, read one and
+    write the other: 62 KB per slot): a model frame may show it although no earlier model frame did.  Host state per slot: g, v, the
+    history side, n camera frames received, the last stamp, W and the held side; ``rtfs_live_video_stamp_plan`` (host only) decides
+    which camera frame every new model frame shows and the source list goes up with the tick table in the one copy of a tick."""
+
+    _WORDS, _NAMES = 7, ("g", "v", "side", "n", "last stamp", "W")
+    _PLAN_WORDS = STAMP_PLAN_WORDS
+
+    def __init__(self, model, slots, max_frames, roi_hw, max_batch_frames, timebase):
+        self.timebase = timebase
+        self._held = _lib.empty(slots, 2, CROP, CROP, device=next(model.parameters()).device)
+        super().__init__(model, slots, max_frames, roi_hw, max_batch_frames)
+
+    def _max_model_frames(self):
+        """A flush emits the frames it finalises, at most max_frames, and the two embeddings that waited for their look-ahead."""
+        return self.max_frames + LOOKAHEAD
+
+    # -- public
+    def counters(self, slot):
+        """(n, v) of a slot: camera frames received, embeddings emitted."""
+        c = self._counters[int(slot)]
+        return c[3], c[1]
+
+    def push(self, slot_ids, chunks, timestamps, until=None):
+        """One chunk of camera frames for each slot named, as ``LipStreamPool.push`` takes them, with ``timestamps``: per named slot the
+        m capture times of its chunk (a sequence of ints or a CPU int64 tensor; None for an empty chunk).  ``until``: None, one int for
+        every named slot, or per named slot an int or None.  Returns, per named slot, the (512, k) embeddings that became final.
+
+        ValueError - before any launch, all state unchanged - for what ``LipStreamPool.push`` refuses, for stamps that are not m
+        integers, do not increase or lie below the slot's last stamp or an earlier ``until``, for a negative stamp or ``until``, and for
+        a push that would make more than ``max_frames`` model frames final (advance ``until`` in smaller steps)."""
+        ids, ms, chunks, u8 = self._check_chunks(slot_ids, chunks, timestamps, until)
+        return self._tick(ids, ms, chunks, u8, flush=False)
+
+    def flush(self, slot_ids, until=None):
+        """End the named tracks at g_end = max(g, G(max(W, until)), the last camera frame's tick + 1): the last camera frame is shown
+        at least by its own tick.  Returns the embeddings still owed and resets the slots; the next stream of a slot may start at any
+        stamp.  A slot that received no frame returns (512, 0)."""
+        ids = self._check_ids(slot_ids)
+        return self._tick(ids, self._flush_sizes(len(ids), until), None, False, flush=True)
+
+    # -- checks (no launch, no state change)
+    @staticmethod
+    def _untils(R, until):
+        if until is None:
+            return [0] * R  # no promise: the watermark is a maximum
+        if isinstance(until, (list, tuple)):
+            if len(until) != R:
+                raise ValueError(f"StampLipStreamPool: {R} slot id(s) and {len(until)} until value(s)")
+            return [0 if u is None else _stamp(u, "until") for u in until]
+        return [_stamp(until, "until")] * R
+
+    def _flush_sizes(self, R, until):
+        return [(0, (), u) for u in self._untils(R, until)]
+
+    def _sizes(self, chunks, timestamps=None, until=None):
+        """What each chunk brings, as ``_plan`` takes it: (camera frames, their stamps, until)."""
+        R = len(chunks)
+        if timestamps is None:
+            timestamps = [None] * R
+        try:
+            timestamps = list(timestamps)
+        except TypeError:
+            raise ValueError("StampLipStreamPool.push: timestamps must hold one sequence of integers per named slot") from None
+        if len(timestamps) != R:
+            raise ValueError(f"StampLipStreamPool.push: {R} chunk(s) and {len(timestamps)} timestamp sequence(s)")
+        out = []
+        for r, (c, ts, u) in enumerate(zip(chunks, timestamps, self._untils(R, until))):
+            if isinstance(ts, torch.Tensor):
+                if ts.device.type != "cpu" or ts.dtype != torch.int64 or ts.ndim != 1:
+                    raise ValueError(f"StampLipStreamPool.push: timestamps {r} must be a CPU int64 tensor (m) or a sequence of ints: stamps are "
+                                     f"host data")
+                ts = ts.tolist()
+            try:
+                ts = () if ts is None else tuple(_stamp(t, "timestamps") for t in ts)
+            except TypeError:
+                raise ValueError(f"StampLipStreamPool.push: timestamps {r} must be a sequence of integers") from None
+            if len(ts) != c.shape[0]:
+                raise ValueError(f"StampLipStreamPool.push: chunk {r} holds {c.shape[0]} frames and has {len(ts)} timestamp(s)")
+            out.append((int(c.shape[0]), ts, u))
+        return out
+
+    def _plan(self, ids, ms, flush):
+        """``ms``: per named slot (camera frames, stamps, until); None: a flush without ``until``.  The table comes back with the source
+        list behind its columns."""
+        if not ids:
+            return [], [], [0, 0, 0, 0]
+        R, W, LL = len(ids), self._WORDS, ctypes.c_longlong
+        ms = self._flush_sizes(R, None) if ms is None else ms
+        stamps = [t for _, ts, _ in ms for t in ts]
+        cnt = [c for s in ids for c in (self._counters[s] if 0 <= s < self.slots else (0,) * W)]
+        new, table, src = (LL * (W * R))(), (LL * (STAMP_PLAN_WORDS * R))(), (LL * (self.max_frames * R))()
+        sizes, refused = (LL * 5)(), (ctypes.c_int * 2)()
+        rc = _lib.load().rtfs_live_video_stamp_plan((LL * R)(*ids), (LL * (W * R))(*cnt), (LL * R)(*(m for m, _, _ in ms)),
+                                                    (LL * max(len(stamps), 1))(*stamps), (LL * R)(*(u for _, _, u in ms)), R, self.slots,
+                                                    int(flush), self.max_frames, self.timebase, new, table, src, sizes, refused)
+        if rc != 0:
+            self._refused(ids, cnt, refused, flush)
+        return list(new), list(table) + list(src[:sizes[4]]), [int(v) for v in sizes[:4]]
+
+    def _ingest(self, lib, tab, R, rows, max_m, flush, u8, st, max_in):
+        if u8:
+            from . import datas
+            H, W = self.roi_hw
+            crop, _, mean, std = datas.get_preprocessing_pipelines()["val"].collapse()
+            dy, dx = crop.offsets(H, W)
+            _lib.check(lib.rtfs_live_video_ingest_stamp_u8(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._held), _lib.ptr(self._win), R, rows,
+                                                           max_m, max_in, int(flush), H, W, dy, dx, mean, std, self.timebase, st),
+                       "rtfs_live_video_ingest_stamp_u8")
+        else:
+            _lib.check(lib.rtfs_live_video_ingest_stamp_f32(_lib.ptr(tab), _lib.ptr(self._hist), _lib.ptr(self._held), _lib.ptr(self._win), R, rows,
+                                                            max_m, max_in, int(flush), self.timebase, st), "rtfs_live_video_ingest_stamp_f32")
+
+    def _reset_state(self, ids, R):
+        """Defined contents for the history and the held planes of R slots; nothing depends on them (held is read only after a push
+        wrote it)."""
+        if not self.on_hip:
+            self._hist[slice(0, R) if ids is None else ids] = 0
+            self._held[slice(0, R) if ids is None else ids] = 0
+            return
+        _lib.check(_lib.load().rtfs_live_video_stamp_reset(_lib.ptr(ids), _lib.ptr(self._hist), _lib.ptr(self._held), R,
+                                                           _lib.stream_of(self._hist)), "rtfs_live_video_stamp_reset")
+
+
+def timebase_of(timebase):
+    """``timebase=`` of the entries: None, or the ticks per second of the stamps, an int in [1, 2^30]."""
+    if timebase is None:
+        return None
+    try:
+        if isinstance(timebase, bool):
+            raise TypeError
+        tb = operator.index(timebase)
+    except TypeError:
+        raise ValueError(f"timebase = {timebase!r}; an integer number of ticks per second") from None
+    if not 1 <= tb <= MAX_TIMEBASE:
+        raise ValueError(f"timebase = {tb}; between 1 and 2^30 ticks per second")
+    return tb
+
+
+def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=1600, frame_rate=25, timebase=None):
     """``FRCNNVideoModel.open_streams``: check the arguments, then allocate the pool."""
     from . import datas
-    rate = datas.frame_rate_of(frame_rate)
+    rate, timebase = datas.frame_rate_of(frame_rate), timebase_of(timebase)
+    if timebase is not None and rate != 25:
+        raise ValueError(f"open_streams: timebase = {timebase} with frame_rate = {rate}: the stamps say when a frame was taken, give one or the other")
     try:
         slots, max_frames, max_batch_frames = operator.index(slots), operator.index(max_frames), operator.index(max_batch_frames)
         roi_hw = None if roi_hw is None else (operator.index(roi_hw[0]), operator.index(roi_hw[1]))
@@ -886,6 +1073,10 @@ def open_lip_streams(model, slots, max_frames=50, roi_hw=None, max_batch_frames=
         if slots * max(-(-25 * max_frames * rate.denominator // rate.numerator), LOOKAHEAD) > 0x7fffffff // 5:
             raise ValueError(f"open_streams: slots = {slots}, max_frames = {max_frames} at {rate} fps: too many frames per tick")
         return RateLipStreamPool(model, slots, max_frames, roi_hw, max_batch_frames, rate)
+    if timebase is not None:
+        if slots * (max_frames + LOOKAHEAD) > 0x7fffffff // 5:
+            raise ValueError(f"open_streams: slots = {slots}, max_frames = {max_frames} with timestamps: too many frames per tick")
+        return StampLipStreamPool(model, slots, max_frames, roi_hw, max_batch_frames, timebase)
     return LipStreamPool(model, slots, max_frames, roi_hw, max_batch_frames)
 
 
@@ -950,15 +1141,26 @@ class CameraStreamPool(_Pool):
                 raise ValueError(f"{who}: audio chunk {r} holds {w.numel()} samples; max_chunk = {self.max_chunk}")
         return audio_chunks
 
-    def _check_rois(self, slot_ids, roi_chunks):
+    def _check_rois(self, slot_ids, roi_chunks, *stamps):
         """-> slot ids, and frames per TRACK, chunks per track and their kind as ``LipStreamPool._check_chunks`` returns them."""
-        return self.lips._check_chunks(slot_ids, roi_chunks)
+        return self.lips._check_chunks(slot_ids, roi_chunks, *stamps)
 
-    def push(self, slot_ids, audio_chunks, roi_chunks):
+    def _stamps(self, who, timestamps, until):
+        """The timestamps and ``until`` of a push as the lip pool's extra arguments: none unless the pool was opened with ``timebase=``."""
+        if isinstance(self.lips, StampLipStreamPool):
+            return (timestamps, until)
+        if timestamps is not None or until is not None:
+            raise ValueError(f"{type(self).__name__}.{who}: timestamps and until need a pool opened with timebase=")
+        return ()
+
+    def push(self, slot_ids, audio_chunks, roi_chunks, timestamps=None, until=None):
         """One chunk of 16 kHz audio ((n)|(1,n) float32, 0 <= n <= max_chunk) and one of mouth frames (as ``LipStreamPool.push`` takes them,
         at most max_chunk // 640; at another ``frame_rate`` camera frames, at most ``lips.max_frames``) for each slot named; either may be empty.  Returns, per named slot, the (n_src, k) newly final samples,
-        as ``StreamPool.push`` does.  ValueError - before any launch, all state unchanged - for what either pool refuses."""
-        ids, ms, rois, u8 = self._check_rois(slot_ids, roi_chunks)
+        as ``StreamPool.push`` does.  ValueError - before any launch, all state unchanged - for what either pool refuses.
+
+        A pool opened with ``timebase=`` (DESIGN.md "Live streams with per-frame timestamps") takes the frames' capture times and
+        ``until`` as ``StampLipStreamPool.push`` does; stamp 0 is audio sample 0.  The audio side counts model frames and is untouched."""
+        ids, ms, rois, u8 = self._check_rois(slot_ids, roi_chunks, *self._stamps("push", timestamps, until))
         wavs = self._check_audio(ids, audio_chunks)
         if not ids:
             return []
@@ -983,25 +1185,27 @@ class CameraStreamPool(_Pool):
                 raise ValueError(f"{type(self).__name__}.push: refused ({_REASONS[6]}) at slot {s}; no slot was changed")
         return self.audio._plan_push(ids, na, ks)
 
-    def flush(self, slot_ids):
+    def flush(self, slot_ids, until=None):
         """End the named streams: the lip pool's flush of the slots' tracks, its at most two remaining embeddings per track pushed with
         empty audio, then the audio pool's flush.  Returns the remaining samples per slot (the samples the middle step made final in
-        front of the flush's own)."""
+        front of the flush's own).  ``until``: with ``timebase=``, as ``StampLipStreamPool.flush`` takes it."""
         ids = self._check_slots(slot_ids)
         if not ids:
             return []
-        self._plan_flush(ids)
+        ms = self.lips._flush_sizes(len(ids), until) if self._stamps("flush", None, until) else None
+        self._plan_flush(ids, ms)
         if self.audio.model.training:
             raise RuntimeError(f"{type(self).__name__} is inference only: call .eval() on the model")
-        embs = self.lips.flush(self._tracks(ids))
+        embs = self.lips._tick(self._tracks(ids), ms, None, False, flush=True)
         empty = _lib.empty(0, device=self.device)
         mid = self.audio.push(ids, [empty] * len(ids), self._group(embs))
         return _join(mid, self.audio.flush(ids))
 
-    def _plan_flush(self, ids):
-        """The dry run of a flush on both planners: ValueError for what either refuses."""
+    def _plan_flush(self, ids, ms=None):
+        """The dry run of a flush on both planners: ValueError for what either refuses.  ``ms``: what a ``StampLipStreamPool`` is flushed
+        with."""
         K, R = self.speakers, len(ids)
-        _, vtab, _ = self.lips._plan(self._tracks(ids), None, True)
+        _, vtab, _ = self.lips._plan(self._tracks(ids), ms, True)
         new, _, _ = self.audio._plan_push(ids, [0] * R, vtab[4 * R * K:5 * R * K][::K])
         with _counters_as(self.audio, ids, new, 4):  # the inner flush is planned on the counters the middle push leaves
             self.audio._plan_flush(ids)
@@ -1169,11 +1373,14 @@ class FaceCameraStreamPool(CameraStreamPool):
 
 
 def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1,
-                        max_speakers=None, frame_rate=25):
+                        max_speakers=None, frame_rate=25, timebase=None):
     """``System.open_camera_streams``: the lip pool and the audio pool of one set of slots."""
     from . import datas
-    rate = datas.frame_rate_of(frame_rate)
+    rate, timebase = datas.frame_rate_of(frame_rate), timebase_of(timebase)
     K = speakers_of(speakers)
+    if timebase is not None and (K != 1 or max_speakers is not None or _rate(sample_rate) != FS or rate != 25):
+        raise ValueError(f"open_camera_streams: timebase = {timebase} takes one face per slot, 16 kHz audio and no frame_rate (speakers = "
+                         f"{speakers}, max_speakers = {max_speakers}, sample_rate = {sample_rate}, frame_rate = {rate})")
     if max_speakers is not None:
         if K != 1:
             raise ValueError("open_camera_streams: speakers and max_speakers exclude each other")
@@ -1206,6 +1413,8 @@ def open_camera_streams(system, slots, window=32000, hop=None, max_chunk=None, m
                                             **(dict(speakers=K) if max_speakers is None else dict(max_speakers=K)))
     if rate != 25:
         lips = system.video_model.open_streams(audio.slots * K, max_frames=mc, roi_hw=roi_hw, frame_rate=rate)
+    elif timebase is not None:
+        lips = system.video_model.open_streams(audio.slots * K, max_frames=max_chunk // SPF, roi_hw=roi_hw, timebase=timebase)
     else:
         lips = system.video_model.open_streams(audio.slots * K, max_frames=max_chunk // SPF, roi_hw=roi_hw)
     if lips.device != audio.device:

@@ -86,7 +86,8 @@ class System(nn.Module):
             emb = self.video_model(mouths.reshape(B * K, *mouths.shape[2:]).type_as(wav))
         return self.audio_model.separate_long_speakers(wav, emb.reshape(B, K, *emb.shape[1:]), **kw)
 
-    def separate_recording(self, wav, sample_rate, mouth_rois, normalize_audio=False, frame_rate=25, **kw):
+    def separate_recording(self, wav, sample_rate, mouth_rois, normalize_audio=False, frame_rate=25, timestamps=None, timebase=None, until=None,
+                           **kw):
         """A raw recording end to end on the device (inference), the whole of ``infer_any_video.py:63-86``: wav (L) | (B,L) at
         ``sample_rate`` Hz, mouth_rois uint8 (Tv,H,W) | (B,Tv,H,W) at 25 fps -> (B, n_src, L at 16 kHz).  ``datas.resample`` to 16 kHz, the
         ``"val"`` pipeline on the ROIs (one launch), the video model once on the whole track, then ``separate_long(**kw)``.  Without a
@@ -96,9 +97,22 @@ class System(nn.Module):
 
         ``frame_rate`` other than 25 (DESIGN.md "Live streams at the camera's frame rate"): the uint8 ROIs are the camera's frames at that
         rate and the ``"val"`` launch selects the frames ``datas.frame_rate_map`` names, where the reference converts the file with
-        ``ffmpeg -r 25`` first.  Prepared lips and embeddings are model frames already: ValueError with another rate."""
+        ``ffmpeg -r 25`` first.  Prepared lips and embeddings are model frames already: ValueError with another rate.
+
+        ``timestamps`` with ``timebase`` (DESIGN.md "Live streams with per-frame timestamps"): the capture time of every frame of
+        ``mouth_rois`` in ticks of 1 / timebase s, for a camera that dropped frames or changed rate.  The frames
+        ``datas.timestamp_map(timestamps, timebase, until)`` names are selected on the device (``index_select``), then the 25 fps path
+        runs as above.  ValueError with another ``frame_rate``, or with one of the two missing."""
         from . import datas
         rate = datas.frame_rate_of(frame_rate)
+        if timestamps is not None or timebase is not None or until is not None:
+            if timestamps is None or timebase is None or rate != 25:
+                raise ValueError("System.separate_recording: timestamps and timebase go together, without a frame_rate")
+            idx = datas.timestamp_map(timestamps, timebase, until)
+            if len(idx) == 0 or mouth_rois.shape[-3] != len(timestamps):
+                raise ValueError(f"System.separate_recording: {len(timestamps)} timestamp(s) for {mouth_rois.shape[-3]} frame(s); need one per "
+                                 f"frame, at least 1")
+            mouth_rois = mouth_rois.index_select(mouth_rois.ndim - 3, torch.tensor(idx, dtype=torch.int64, device=mouth_rois.device))
         wav = datas.resample(wav, sample_rate, 16000)
         if normalize_audio:
             wav = datas.normalize_mixture(wav)
@@ -169,7 +183,7 @@ class System(nn.Module):
         return self.audio_model.open_streams(sample_rate=sample_rate, **kw)
 
     def open_camera_streams(self, slots, window=32000, hop=None, max_chunk=None, max_batch=32, roi_hw=(96, 96), sample_rate=16000, speakers=1,
-                            max_speakers=None, frame_rate=25):
+                            max_speakers=None, frame_rate=25, timebase=None):
         """Live streams from microphone samples and camera frames (inference; DESIGN.md "Live streams from camera frames") ->
         ``streaming.CameraStreamPool``.  ``pool.push(slot_ids, audio_chunks, roi_chunks)`` takes 16 kHz audio chunks of at most
         ``max_chunk`` samples (default ``window``) and uint8 mouth ROIs (m,H,W) with (H,W) == ``roi_hw`` at 25 fps (or float32 prepared lips
@@ -194,8 +208,19 @@ class System(nn.Module):
         with any of the above: the ROI chunks hold the camera's frames at that rate, at most floor(max_chunk / 640 * frame_rate / 25) per
         push, and the frames the model sees are selected inside the ingest launch (``datas.frame_rate_map``); for any chunking the
         outputs equal ``separate_recording(..., frame_rate=frame_rate)``.  The lip pool is a ``streaming.RateLipStreamPool`` whose
-        ``counters`` report camera frames received; ``window``, ``hop`` and ``max_chunk`` stay in 16 kHz samples."""
+        ``counters`` report camera frames received; ``window``, ``hop`` and ``max_chunk`` stay in 16 kHz samples.
+
+        ``timebase`` = ticks per second (DESIGN.md "Live streams with per-frame timestamps"): for cameras that drop frames or change
+        rate.  ``pool.push(slot_ids, audio_chunks, roi_chunks, timestamps=None, until=None)`` takes the capture time of every frame
+        (stamp 0 is audio sample 0) and ``until``, the promise that no frame before that instant is still coming, which keeps a stream
+        moving through a camera dropout; ``pool.flush(slot_ids, until=None)``.  The lip pool is a ``streaming.StampLipStreamPool`` and
+        for any chunking the outputs equal ``separate_recording(..., timestamps=, timebase=, until=)``.  One face per slot, 16 kHz
+        audio, no ``frame_rate``: ValueError with ``speakers``, ``max_speakers``, another ``sample_rate`` or another ``frame_rate``."""
         from . import streaming
+        if timebase is not None:
+            return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
+                                                 sample_rate=sample_rate, speakers=speakers, max_speakers=max_speakers, frame_rate=frame_rate,
+                                                 timebase=timebase)
         if frame_rate == 25:
             return streaming.open_camera_streams(self, slots, window=window, hop=hop, max_chunk=max_chunk, max_batch=max_batch, roi_hw=roi_hw,
                                                  sample_rate=sample_rate, speakers=speakers, max_speakers=max_speakers)

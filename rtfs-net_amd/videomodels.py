@@ -137,7 +137,7 @@ class FRCNNVideoModel(nn.Module):
                    "rtfs_video_frontend_f32")
         return out
 
-    def open_streams(self, slots, max_frames=50, roi_hw=None, max_batch_frames=1600, frame_rate=25):
+    def open_streams(self, slots, max_frames=50, roi_hw=None, max_batch_frames=1600, frame_rate=25, timebase=None):
         """``slots`` live lip tracks embedded chunk by chunk (inference only; DESIGN.md "Live streams from camera frames") ->
         ``streaming.LipStreamPool``.  ``pool.push(slot_ids, chunks)`` takes what the camera delivered - uint8 mouth ROIs (m,H,W) with
         (H,W) == ``roi_hw`` (None: fixed by the first ROIs pushed), or float32 prepared lips (m,88,88), at most ``max_frames`` per chunk -
@@ -148,8 +148,16 @@ class FRCNNVideoModel(nn.Module):
 
         ``frame_rate`` other than 25 (an int, a ``Fraction``, (num, den) or a float; DESIGN.md "Live streams at the camera's frame rate")
         -> ``streaming.RateLipStreamPool``: the chunks hold the camera's frames at that rate, at most ``max_frames`` of them, and the
-        frames the model sees are selected on the device by the rule of ``datas.frame_rate_map``, whatever the chunking."""
+        frames the model sees are selected on the device by the rule of ``datas.frame_rate_map``, whatever the chunking.
+
+        ``timebase`` = ticks per second (an int up to 2^30; DESIGN.md "Live streams with per-frame timestamps") ->
+        ``streaming.StampLipStreamPool`` for cameras that drop frames or change rate: ``pool.push(slot_ids, chunks, timestamps,
+        until=None)`` takes the capture time of every frame and the frames the model sees follow ``datas.timestamp_map``, whatever the
+        chunking.  ValueError together with a ``frame_rate`` other than 25."""
         from . import streaming
+        if timebase is not None:
+            return streaming.open_lip_streams(self, slots, max_frames=max_frames, roi_hw=roi_hw, max_batch_frames=max_batch_frames,
+                                              frame_rate=frame_rate, timebase=timebase)
         if frame_rate == 25:
             return streaming.open_lip_streams(self, slots, max_frames=max_frames, roi_hw=roi_hw, max_batch_frames=max_batch_frames)
         return streaming.open_lip_streams(self, slots, max_frames=max_frames, roi_hw=roi_hw, max_batch_frames=max_batch_frames,
