@@ -843,6 +843,32 @@ int rtfs_live_resample_i16(const long long* table, const float* bank, float* his
                            int flush, int orig_freq, int new_freq, void* stream);
 int rtfs_live_resample_reset(const long long* ids, float* hist, int R, int orig_freq, int new_freq, void* stream);
 
+/* Mouth ROIs from whole camera frames (datas.mouth_affine / mouth_rois; DESIGN.md "Mouth ROIs from camera frames"; csrc/k_mouth.hip):
+ * the reference's step between a face tracker's landmarks and the uint8 mouth ROIs (RTFSNet_file.py:20-73, 111-118) as ONE affine map
+ * per (frame, face) and ONE bilinear sampling of the source frame.  All arithmetic is IEEE float64 in a fixed order without fused
+ * multiply-add; tests/mouth_oracle.py restates it and both entries are bit-equal to it.
+ * rtfs_mouth_affine (host only, no device call): eyes (n,2,2) = the eye corner on the left in the image, then the right one, lips
+ *   (n,4,2) = the four points whose bounding box is the mouth, float64 (x, y) in source pixels -> A (n,2,3), the map from ROI pixel
+ *   (j, i) to the source point sx = A00 j + A01 i + A02, sy = A10 j + A11 i + A12.  With d = right - left, dist = |d|, s = 76.8 / dist,
+ *   a = s dx / dist, b = s dy / dist, c the eyes' midpoint and t = (128, 89.6), a point p lies at q = [[a, b], [-b, a]] (p - c) + t in the
+ *   reference's 256 x 256 aligned face; the lip box there is x0 = min qx, w = max qx - x0 + 1 (likewise y0, h); ROI pixel (j, i) shows
+ *   the aligned point x0 + (j - (out_w - crop_w) / 2 + 0.5) w / crop_w - 0.5 (likewise y): the box fills the central crop_h x crop_w of
+ *   the ROI; and p = c + R^T (q - t) / (a a + b b).  -4 for a missing array, crop outside [1, out], out > 4096 (refused[0] = -1) and for
+ *   a set with a non-finite landmark, dist == 0 or a non-finite matrix entry (refused[0] = its index).  refused may be NULL.
+ * rtfs_mouth_rois_u8 (one launch): J jobs of RTFS_MOUTH_JOB_WORDS = 12 int64 words, row-major: [source plane address | destination
+ *   address | H | W | row pitch in bytes | pixel stride in bytes + 65536 * order (0 grey, 1 BGR, 2 RGB) | the six doubles of A].  jobs is
+ *   the table on the DEVICE, host_jobs the same words on the host or NULL; with host_jobs every job is checked before the launch (-4: a
+ *   null address, H or W outside [1, 32767], pitch outside [0, 2^31), an unknown order, a colour pixel stride below 3, a non-finite
+ *   matrix entry).  Jobs may differ in everything and may share a source.  Every job writes out_h * out_w contiguous bytes at any
+ *   alignment: per pixel x0 = floor(sx), fx = sx - x0 (likewise y; sx, sy clamped to [-2, W + 1], [-2, H + 1] in double first), taps
+ *   (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1), a tap outside the frame 0, a colour tap (1868 B + 9617 G + 4899 R + 8192) >> 14 first,
+ *   v = (1-fy) ((1-fx) p00 + fx p01) + fy ((1-fx) p10 + fx p11), out = rint(v) clamped to 0 .. 255.  Takes the caller's stream,
+ *   allocates nothing, reads nothing back, no atomics.  out_h, out_w outside [1, 4096] or a grid that would not fit: -1. */
+#define RTFS_MOUTH_JOB_WORDS 12
+int rtfs_mouth_affine(const double* eyes, const double* lips, long long n, int out_h, int out_w, int crop_h, int crop_w, double* A,
+                      long long* refused);
+int rtfs_mouth_rois_u8(const long long* jobs, const long long* host_jobs, int J, int out_h, int out_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ from .streaming import (CameraStreamPool, FaceCameraStreamPool, FaceStreamPool, 
 from .optimizers import make_optimizer  # noqa: F401
 from .metrics import ALLMetricsTracker, stoi  # noqa: F401
 from .datas import (Compose, Normalize, CenterCrop, RandomCrop, HorizontalFlip, get_preprocessing_pipelines, normalize_mixture,  # noqa: F401
-                    normalize_tensor_wav, resample)
+                    normalize_tensor_wav, resample, mouth_affine, mouth_rois)
 from .videomodels import FRCNNVideoModel  # noqa: F401
 from .models import (AVNet, ATTNFusion, BaseAVModel, CAFBlock, MaskGenerator, MultiModalFusion, RefinementModule, RTFSBlock, RTFSNet,  # noqa: F401
                      S3Block, STFTDecoder, STFTEncoder, TDANet, TDANetBlock, get, register_model)

@@ -171,6 +171,8 @@ SIGNATURES = {
     "rtfs_resample_plan": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _p]),
     "rtfs_resample_out_len": (C.c_longlong, [_i, _i, C.c_longlong]),
     "rtfs_resample_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "rtfs_mouth_affine": (_i, [_p, _p, C.c_longlong, _i, _i, _i, _i, _p, C.POINTER(C.c_longlong)]),
+    "rtfs_mouth_rois_u8": (_i, [_p, _p, _i, _i, _i, _p]),
     "rtfs_live_resample_plan": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, C.c_longlong, _p, _p, _p, _p]),
     "rtfs_live_resample_f32": (_i, [_p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _p]),
     "rtfs_live_resample_i16": (_i, [_p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _p]),

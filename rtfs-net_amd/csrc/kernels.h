@@ -392,6 +392,11 @@ int resample_plan(int orig, int neu, int* o, int* n, int* width, int* taps, floa
 long long resample_out_len(int orig, int neu, long long L);
 int launch_resample(const float* x, const float* bank, float* y, int B, int L, int orig, int neu, hipStream_t st);
 
+// mouth ROIs from whole camera frames (k_mouth.hip): landmarks -> one affine map per (frame, face) (host), one sampling launch for J jobs
+int mouth_affine(const double* eyes, const double* lips, long long n, int out_h, int out_w, int crop_h, int crop_w, double* A,
+                 long long* refused);
+int launch_mouth_rois(const long long* jobs, const long long* host_jobs, int J, int out_h, int out_w, hipStream_t st);
+
 // video front-end (k_video.hip): FRCNNVideoModel, ResNet-18 trunk, PReLU, eval
 size_t video_pack_floats();
 size_t video_workspace_bytes(int B, int T);

@@ -4,6 +4,8 @@
 * ``normalize_tensor_wav`` / ``normalize_mixture``   ``src/datas/avspeech_dataset.py:18-22`` and its joint use at ``:145-148, 206-209``
 * ``Compose``, ``Normalize``, ``CenterCrop``, ``RandomCrop``, ``HorizontalFlip``, ``get_preprocessing_pipelines``
                                      ``src/datas/transform.py``: on ``uint8`` device ROIs a pipeline is ONE ``rtfs_lips_prepare_u8`` launch
+* ``mouth_affine`` / ``mouth_rois``  ``RTFSNet_file.py:20-73, 111-118`` (``align_face``, lip box, ``cv2.resize``, grey) as one affine map per
+                                     (frame, face) and ONE ``rtfs_mouth_rois_u8`` launch on whole camera frames (``csrc/k_mouth.hip``)
 
 All arithmetic runs in ``librtfs_amd.so`` (``csrc/k_prep.hip``); there is no host fallback.  ``tests/prep_oracle.py`` restates the three
 in float64 numpy."""
@@ -20,7 +22,7 @@ from . import _lib
 
 __all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
            "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams", "frame_rate_of", "frame_rate_map",
-           "timestamp_map"]
+           "timestamp_map", "mouth_affine", "mouth_rois"]
 
 CROP = 88
 MAX_RATIO = 640
@@ -152,6 +154,201 @@ def timestamp_map(timestamps, timebase, until=None):
     src = (LL * max(out.value, 1))()
     _lib.check(lib.rtfs_timestamp_map(arr, n, tb, u, C.byref(out), src), "rtfs_timestamp_map")
     return list(src[:out.value])
+
+
+# ---------------------------------------------------------------- mouth ROIs from whole camera frames (DESIGN.md "Mouth ROIs from camera frames")
+MOUTH_ORDERS = {"gray": 0, "bgr": 1, "rgb": 2}
+MOUTH_JOB_WORDS = 12  # RTFS_MOUTH_JOB_WORDS: [source | destination | H | W | pitch | pixel stride + 65536 order | the six doubles of A]
+MOUTH_MAX_DIM, MOUTH_MAX_OUT = 0x7fff, 4096
+
+
+def _hw(v, what):
+    try:
+        h, w = v
+        return operator.index(h), operator.index(w)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} = {v!r}; a pair of integers (H, W)") from None
+
+
+def _mouth_sizes(out_hw, crop_hw, who):
+    (Ho, Wo), (Hc, Wc) = _hw(out_hw, f"{who}: out_hw"), _hw(crop_hw, f"{who}: crop_hw")
+    if not (1 <= Hc <= Ho <= MOUTH_MAX_OUT and 1 <= Wc <= Wo <= MOUTH_MAX_OUT):
+        raise ValueError(f"{who}: crop_hw = {(Hc, Wc)} must lie in [1, out_hw = {(Ho, Wo)}] per axis, out_hw at most {MOUTH_MAX_OUT}")
+    return Ho, Wo, Hc, Wc
+
+
+def _landmarks(x, tail, what):
+    """A host array of landmarks (numpy, a CPU tensor, nested lists) as a contiguous float64 CPU tensor (..., *tail)."""
+    if isinstance(x, torch.Tensor) and x.is_cuda:
+        raise ValueError(f"{what} lie on {x.device}: landmarks are host arrays (they come from a host-side tracker and feed the host planner)")
+    try:
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=torch.float64)  # Python floats are float64 already
+        if t.is_complex() or t.dtype == torch.bool:
+            raise TypeError
+        t = t.detach().to(torch.float64).contiguous()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what} must be a numeric host array (..., {tail[0]}, {tail[1]})") from None
+    if t.ndim < 2 or tuple(t.shape[-2:]) != tail:
+        raise ValueError(f"{what} must be (..., {tail[0]}, {tail[1]}); got {tuple(t.shape)}")
+    return t
+
+
+def _mouth_affine(e, l, Ho, Wo, Hc, Wc, who):
+    """The C planner on checked float64 CPU tensors e (...,2,2), l (...,4,2) -> A (...,2,3)."""
+    if e.shape[:-2] != l.shape[:-2]:
+        raise ValueError(f"{who}: eyes {tuple(e.shape)} and lips {tuple(l.shape)} do not name the same landmark sets")
+    A = _lib.empty(*e.shape[:-2], 2, 3, device="cpu", dtype=torch.float64)
+    n = e.numel() // 4
+    if n:
+        bad = C.c_longlong(-1)
+        if _lib.load().rtfs_mouth_affine(_lib.ptr(e), _lib.ptr(l), n, Ho, Wo, Hc, Wc, _lib.ptr(A), C.byref(bad)) != 0:
+            raise ValueError(f"{who}: landmark set {bad.value} of {n} is refused: a non-finite landmark, eye corners that coincide "
+                             f"(dist == 0) or a map with a non-finite entry")
+    return A
+
+
+def mouth_affine(eyes, lips, out_hw=(96, 96), crop_hw=(88, 88)):
+    """Landmarks -> the affine map of every (frame, face), on the host in float64 (``rtfs_mouth_affine``; DESIGN.md "Mouth ROIs from
+    camera frames").  eyes (...,2,2): the eye corner that lies on the left IN THE IMAGE, then the right one (mediapipe 130, 359 in the
+    reference); lips (...,4,2): the four points whose bounding box is the mouth (187, 411, 136, 365); both (x, y) in pixels of the source
+    frame, numpy arrays or CPU tensors.  Returns A (...,2,3) of the same kind: ROI pixel (i, j) of an ``out_hw`` ROI shows the source point
+    sx = A00 j + A01 i + A02, sy = A10 j + A11 i + A12, and the lip box of the reference's 256 x 256 aligned face fills the central
+    ``crop_hw``.  ValueError for wrong shapes, ``crop_hw`` outside [1, ``out_hw``], non-finite landmarks, eye corners that coincide and
+    a map with a non-finite entry."""
+    Ho, Wo, Hc, Wc = _mouth_sizes(out_hw, crop_hw, "mouth_affine")
+    A = _mouth_affine(_landmarks(eyes, (2, 2), "mouth_affine: eyes"), _landmarks(lips, (4, 2), "mouth_affine: lips"), Ho, Wo, Hc, Wc,
+                      "mouth_affine")
+    return A if isinstance(eyes, torch.Tensor) else A.numpy()
+
+
+def _mouth_plan(frames, eyes, lips, out_hw, crop_hw, order, who, faces=None):
+    """Everything of a ``mouth_rois`` call that needs no launch: checks the frame tensors and their landmarks and runs the host planner.
+    frames, eyes, lips: equally long lists.  faces: None (the landmarks say whether they carry a face axis) or True (they must).
+    -> {"items": [(frames (n,H,W[,3]), A (n,K,2,3) float64, has a face axis)], "hw": (Ho, Wo), "order": code, "device"}."""
+    Ho, Wo, Hc, Wc = _mouth_sizes(out_hw, crop_hw, who)
+    if not isinstance(order, str) or order not in MOUTH_ORDERS:
+        raise ValueError(f"{who}: order = {order!r}; one of {tuple(MOUTH_ORDERS)}")
+    if not (len(frames) == len(eyes) == len(lips)):
+        raise ValueError(f"{who}: {len(frames)} frame tensor(s), {len(eyes)} eyes and {len(lips)} lips array(s)")
+    items, device = [], None
+    for r, (f, e, l) in enumerate(zip(frames, eyes, lips)):
+        if not isinstance(f, torch.Tensor) or not f.is_cuda or f.dtype != torch.uint8:
+            raise ValueError(f"{who}: frames {r} must be a uint8 tensor on the device; got "
+                             f"{(f.dtype, f.device) if isinstance(f, torch.Tensor) else type(f).__name__}")
+        device = f.device if device is None else device
+        if f.device != device:
+            raise ValueError(f"{who}: frames {r} lie on {f.device}, frames 0 on {device}")
+        if f.ndim not in (3, 4) or (f.ndim == 4 and (f.shape[3] != 3 or f.stride(3) != 1 or order == "gray")):
+            raise ValueError(f"{who}: frames {r} must be (n,H,W,3) with the channels adjacent (order bgr | rgb) or a grey plane (n,H,W); "
+                             f"got {tuple(f.shape)} with strides {tuple(f.stride())}, order {order!r}")
+        n, H, W = (int(v) for v in f.shape[:3])
+        if not (1 <= H <= MOUTH_MAX_DIM and 1 <= W <= MOUTH_MAX_DIM):
+            raise ValueError(f"{who}: frames {r} are {H} x {W}; between 1 and {MOUTH_MAX_DIM} pixels a side")
+        if f.stride(1) >= 1 << 31 or f.stride(2) > 0xffff or (f.ndim == 4 and W > 1 and f.stride(2) < 3):
+            raise ValueError(f"{who}: frames {r} have strides {tuple(f.stride())}: a row pitch below 2^31, a pixel stride in [3 | 1, 65535]")
+        e, l = _landmarks(e, (2, 2), f"{who}: eyes {r}"), _landmarks(l, (4, 2), f"{who}: lips {r}")
+        if e.ndim not in (3, 4) or l.ndim != e.ndim or e.shape[0] != n or (faces and e.ndim != 4):
+            raise ValueError(f"{who}: frames {r} hold {n} frame(s); eyes must be ({n},{'K,' if faces else '[K,]'}2,2) and lips "
+                             f"({n},{'K,' if faces else '[K,]'}4,2); got {tuple(e.shape)} and {tuple(l.shape)}")
+        A = _mouth_affine(e, l, Ho, Wo, Hc, Wc, f"{who}: frames {r}")
+        items.append((f, A.reshape(n, int(e.shape[1]) if e.ndim == 4 else 1, 2, 3), e.ndim == 4))
+    return {"items": items, "hw": (Ho, Wo), "order": MOUTH_ORDERS[order], "device": device}
+
+
+def _mouth_alloc(plan):
+    """The ROI tensors of a plan, (n,K,Ho,Wo) uint8 per item: views of ONE new allocation."""
+    Ho, Wo = plan["hw"]
+    sizes = [int(A.shape[0]) * int(A.shape[1]) * Ho * Wo for _, A, _ in plan["items"]]
+    flat = _lib.empty(sum(sizes), device=plan["device"], dtype=torch.uint8)
+    return [c.view(int(A.shape[0]), int(A.shape[1]), Ho, Wo) for c, (_, A, _) in zip(flat.split(sizes), plan["items"])]
+
+
+_MOUTH_TABLES = {}    # device -> (the job table of the last launch on the host, the same on the device)
+_MOUTH_CAPTURED = []  # device tables that a captured graph reads: kept for the life of the process
+
+
+def _mouth_run(plan, outs):
+    """The one launch of a plan.  outs: per item a uint8 device tensor (n,K,Ho,Wo) whose (Ho,Wo) planes are contiguous; the other
+    strides and the alignment are free.  The job table is built on the host and goes up in one copy; a call that repeats the previous
+    call's table (the same tensors and landmarks, as a warmed-up call under HIP-graph capture does) reuses the copy on the device."""
+    (Ho, Wo), dev, rows = plan["hw"], plan["device"], []
+    for r, ((f, A, _), o) in enumerate(zip(plan["items"], outs)):
+        n, K = int(A.shape[0]), int(A.shape[1])
+        if not isinstance(o, torch.Tensor) or o.dtype != torch.uint8 or o.device != dev or tuple(o.shape) != (n, K, Ho, Wo) or \
+                (Ho > 1 and o.stride(2) != Wo) or (Wo > 1 and o.stride(3) != 1):
+            raise ValueError(f"mouth_rois: out {r} must be a uint8 tensor {(n, K, Ho, Wo)} on {dev} with contiguous ({Ho},{Wo}) planes")
+        if n * K == 0:
+            continue
+        t = _lib.empty(n, K, MOUTH_JOB_WORDS, device="cpu", dtype=torch.int64)  # host table, every word written below
+        idx = torch.arange(n, dtype=torch.int64).view(n, 1)
+        t[:, :, 0] = f.data_ptr() + idx * f.stride(0)
+        t[:, :, 1] = o.data_ptr() + idx * o.stride(0) + torch.arange(K, dtype=torch.int64).view(1, K) * o.stride(1)
+        colour = f.ndim == 4
+        t[:, :, 2], t[:, :, 3], t[:, :, 4] = int(f.shape[1]), int(f.shape[2]), int(f.stride(1))
+        t[:, :, 5] = (max(int(f.stride(2)), 3) if colour else max(int(f.stride(2)), 1)) + 65536 * (plan["order"] if colour else 0)
+        t[:, :, 6:] = A.reshape(n, K, 6).view(torch.int64)
+        rows.append(t.view(n * K, MOUTH_JOB_WORDS))
+    if not rows:
+        return
+    table = torch.cat(rows) if len(rows) > 1 else rows[0]
+    J = int(table.shape[0])
+    capturing = torch.cuda.is_current_stream_capturing()
+    last = _MOUTH_TABLES.get(dev)
+    if last is not None and last[0].shape == table.shape and torch.equal(last[0], table):
+        tab = last[1]
+        if capturing:
+            _MOUTH_CAPTURED.append(tab)
+    elif capturing:
+        raise RuntimeError("mouth_rois under HIP-graph capture: the job table cannot be uploaded while capturing; run the same call "
+                           "(the same frame, landmark and out= tensors) once before the capture")
+    else:
+        tab = table.to(dev)  # the one host-to-device copy of the call
+        _MOUTH_TABLES[dev] = (table, tab)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().rtfs_mouth_rois_u8(_lib.ptr(tab), _lib.ptr(table), J, Ho, Wo, _lib.stream_of(tab)), "rtfs_mouth_rois_u8")
+
+
+def mouth_rois(frames, eyes, lips, out_hw=(96, 96), crop_hw=(88, 88), order="bgr", out=None):
+    """Whole camera frames + landmarks -> uint8 mouth ROIs on the device, ONE ``rtfs_mouth_rois_u8`` launch (DESIGN.md "Mouth ROIs from
+    camera frames"): the reference's ``align_face``, lip box, ``cv2.resize`` and grey (``RTFSNet_file.py:20-73, 111-118``) composed
+    into one affine map per (frame, face) (``mouth_affine``) and one bilinear sampling of the frame, bit-equal to
+    ``tests/mouth_oracle.py``.  Agreement with the OpenCV chain itself is not measured (``cv2`` is no dependency).
+
+    frames: a uint8 device tensor (n,H,W,3) in ``order`` "bgr" | "rgb", or a grey / luma plane (n,H,W) (any ``order``; "gray" takes
+    nothing else).  The channels must be adjacent; row, pixel and frame strides are taken as they lie: nothing is copied.  eyes
+    (n,2,2), lips (n,4,2): host arrays as ``mouth_affine`` takes them -> (n,Ho,Wo); with a face axis, eyes (n,K,2,2), lips (n,K,4,2)
+    -> (n,K,Ho,Wo), the K faces reading the same frame.  ``out``: a uint8 device tensor of that shape to write into, its (Ho,Wo) planes
+    contiguous, any other strides and any alignment; otherwise a new one (``_lib.empty``).
+
+    frames may also be a SEQUENCE of such tensors of different resolutions and channel counts, eyes and lips (and ``out``) sequences
+    with one entry per tensor: everything runs in the one launch and a list comes back.
+
+    The default ``out_hw`` is the pools' default ``roi_hw``, whose 4-pixel rim is what ``CenterCrop`` / ``RandomCrop`` cut later; at
+    ``out_hw == crop_hw == (88, 88)`` the ROI is the reference's crop.  A tap outside the frame is 0.  Reductions past about 2x alias
+    (one bilinear tap set, no area filter).  ValueError - before the launch - for wrong dtypes, devices, ranks or counts, an unknown
+    ``order`` and what ``mouth_affine`` refuses.  Capturable in a HIP graph once the same call has run before the capture."""
+    single = isinstance(frames, torch.Tensor)
+    try:
+        fl, el, ll = ([frames], [eyes], [lips]) if single else (list(frames), list(eyes), list(lips))
+        ol = None if out is None else ([out] if single else list(out))
+    except TypeError:
+        raise ValueError("mouth_rois: frames is a tensor or a sequence of tensors, with eyes, lips (and out) sequences of the same length") from None
+    if not fl or (ol is not None and len(ol) != len(fl)):
+        raise ValueError(f"mouth_rois: {len(fl)} frame tensor(s) and {0 if ol is None else len(ol)} out tensor(s); need at least one, as many")
+    plan = _mouth_plan(fl, el, ll, out_hw, crop_hw, order, "mouth_rois")
+    if ol is None:
+        full = _mouth_alloc(plan)
+    else:
+        full = []
+        for r, (o, (_, A, faces)) in enumerate(zip(ol, plan["items"])):
+            if not isinstance(o, torch.Tensor) or o.ndim != (4 if faces else 3):
+                raise ValueError(f"mouth_rois: out {r} must be a tensor ({A.shape[0]},{f'{A.shape[1]},' if faces else ''}{plan['hw'][0]},{plan['hw'][1]})")
+            full.append(o if faces else o.unsqueeze(1))
+    _mouth_run(plan, full)
+    res = [o if faces else o.squeeze(1) for o, (_, _, faces) in zip(full, plan["items"])]
+    if ol is not None:
+        res = ol
+    return res[0] if single else res
 
 
 # ---------------------------------------------------------------- waveform normalisation

@@ -1094,6 +1094,14 @@ def _counters_as(pool, ids, new, words):
             pool._counters[s] = c
 
 
+def _as_list(x):
+    """A sequence that is read twice (by the dry run and by the call itself) as a list; anything else as it is, for the checks to name."""
+    try:
+        return list(x)
+    except TypeError:
+        return x
+
+
 class CameraStreamPool(_Pool):
     """``slots`` live streams from microphone samples and camera frames (inference only).  Built by ``System.open_camera_streams``.
 
@@ -1170,6 +1178,81 @@ class CameraStreamPool(_Pool):
         embs = self.lips._tick(self._tracks(ids), ms, rois, u8, flush=False)
         return self.audio.push(ids, wavs, self._group(embs))
 
+    # -- whole camera frames (DESIGN.md "Mouth ROIs from camera frames")
+    def push_frames(self, slot_ids, audio_chunks, frame_chunks, eyes, lips, order="bgr", crop_hw=(CROP, CROP), timestamps=None, until=None):
+        """``push`` from WHOLE camera frames: per named slot one chunk of frames, uint8 (m,H,W,3) in ``order`` "bgr" | "rgb" or a grey
+        plane (m,H,W) on the pool's device - any resolution per slot, read where they lie - and that chunk's landmarks, host arrays eyes
+        (m,2,2) and lips (m,4,2) as ``datas.mouth_affine`` takes them.  ONE ``rtfs_mouth_rois_u8`` launch cuts the mouth ROIs of all
+        named slots at the pool's ``roi_hw`` (the lip box in its central ``crop_hw``); they then go into ``push`` as they are, so the
+        outputs are bit-equal to ``push`` fed ``datas.mouth_rois`` of the same frames.  ``timestamps`` / ``until`` pass through on a pool
+        opened with ``timebase=``.  At another ``frame_rate`` the chunk holds camera frames and ALL of them are cropped; the ingest
+        launch selects afterwards, so at 30 fps about one crop in six is wasted.
+
+        ValueError - before any launch, all state unchanged - for wrong frame or landmark shapes, counts, dtypes or devices, for what
+        ``datas.mouth_affine`` refuses and for everything ``push`` refuses (both planners run dry on the chunk sizes first)."""
+        audio_chunks = _as_list(audio_chunks)
+        ids, plan, rois = self._plan_frames("one", slot_ids, frame_chunks, eyes, lips, order, crop_hw)
+        chunks = [v[0] for v in rois]
+        self._check_push(ids, audio_chunks, chunks, timestamps, until)
+        self._crop(plan, rois)
+        return self.push(ids, audio_chunks, chunks, timestamps, until)
+
+    def _plan_frames(self, faces, slot_ids, frame_chunks, eyes, lips, order, crop_hw):
+        """The host part of ``push_frames``: -> slot ids, the ``datas`` plan of the one crop launch (checked frames, one affine map per
+        frame and face) and per named slot a new, still unwritten ROI tensor (K,m,Ho,Wo).  ``faces``: "one" (landmarks without a face
+        axis) or the faces per named slot (a face axis of that length).  Launches nothing and changes nothing."""
+        from . import datas
+        who = f"{type(self).__name__}.push_frames"
+        ids = self._check_slots(slot_ids)
+        try:
+            frame_chunks, eyes, lips = list(frame_chunks), list(eyes), list(lips)
+        except TypeError:
+            raise ValueError(f"{who}: frame_chunks, eyes and lips must be sequences with one entry per named slot") from None
+        if not (len(ids) == len(frame_chunks) == len(eyes) == len(lips)):
+            raise ValueError(f"{who}: {len(ids)} slot id(s), {len(frame_chunks)} frame chunk(s), {len(eyes)} eyes and {len(lips)} lips array(s)")
+        if self.lips.roi_hw is None:
+            raise ValueError(f"{who}: the pool was opened without roi_hw; the crop needs the ROI size")
+        if not ids:
+            return ids, None, []
+        if faces != "one":  # a sequence of per-face arrays (m,2,2) / (m,4,2) is taken as (m,K,2,2) / (m,K,4,2)
+            eyes = [self._face_axis(e) for e in eyes]
+            lips = [self._face_axis(l) for l in lips]
+        plan = datas._mouth_plan(frame_chunks, eyes, lips, self.lips.roi_hw, crop_hw, order, who, faces=None if faces == "one" else True)
+        if plan["device"] != self.device:
+            raise ValueError(f"{who}: the frames lie on {plan['device']}, the pool on {self.device}")
+        Ho, Wo = plan["hw"]
+        for r, (_, A, axis) in enumerate(plan["items"]):
+            K = 1 if faces == "one" else faces[r]
+            if (faces == "one") == axis or int(A.shape[1]) != K:
+                raise ValueError(f"{who}: the landmarks of slot {ids[r]} must name {K} face(s) per frame"
+                                 f"{' without a face axis' if faces == 'one' else ''}; got {'a face axis of ' + str(int(A.shape[1])) if axis else 'no face axis'}")
+        sizes = [int(A.shape[0]) * int(A.shape[1]) * Ho * Wo for _, A, _ in plan["items"]]
+        flat = _lib.empty(sum(sizes), device=self.device, dtype=torch.uint8)
+        return ids, plan, [c.view(int(A.shape[1]), int(A.shape[0]), Ho, Wo) for c, (_, A, _) in zip(flat.split(sizes), plan["items"])]
+
+    @staticmethod
+    def _face_axis(x):
+        if isinstance(x, (list, tuple)) and x and all(getattr(v, "ndim", 0) == 3 for v in x):
+            return torch.stack([torch.as_tensor(v, dtype=torch.float64) if not isinstance(v, torch.Tensor) else v.to(torch.float64) for v in x], dim=1)
+        return x
+
+    @staticmethod
+    def _crop(plan, rois):
+        """The one crop launch: ROI tensor (K,m,Ho,Wo) of every named slot <- its frames."""
+        if plan is not None:
+            from . import datas
+            datas._mouth_run(plan, [v.permute(1, 0, 2, 3) for v in rois])
+
+    def _check_push(self, slot_ids, audio_chunks, roi_chunks, timestamps=None, until=None):
+        """Everything ``push`` checks before its first launch, on ROI chunks whose contents do not matter yet: shapes, kinds and the dry
+        run of both planners.  ValueError for what ``push`` would refuse; nothing is changed."""
+        ids, ms, _, _ = self._check_rois(slot_ids, roi_chunks, *self._stamps("push_frames", timestamps, until))
+        wavs = self._check_audio(ids, audio_chunks)
+        if ids:
+            self._plan_push(ids, [int(w.numel()) for w in wavs], ms)
+        if self.audio.model.training:
+            raise RuntimeError(f"{type(self).__name__} is inference only: call .eval() on the model")
+
     def _plan_push(self, ids, na, ms):
         """The dry run of a push of na samples per named slot and ms frames per named TRACK on both planners: ValueError for what
         either refuses."""
@@ -1231,6 +1314,16 @@ class SpeakerCameraStreamPool(CameraStreamPool):
         per named slot, the (K, k) newly final samples.  ValueError - before any launch, all state unchanged - for what either pool
         refuses and for a chunk that does not hold K tracks."""
         return super().push(slot_ids, audio_chunks, roi_chunks)
+
+    def push_frames(self, slot_ids, audio_chunks, frame_chunks, eyes, lips, order="bgr", crop_hw=(CROP, CROP)):
+        """As ``CameraStreamPool.push_frames`` with K faces in every frame: the landmarks of a slot carry a face axis, eyes (m,K,2,2) and
+        lips (m,K,4,2).  Still ONE crop launch for all named slots and faces, the K faces of a frame reading the same frame; the ROIs
+        are written as the (K,m,H,W) tensor ``push`` takes."""
+        audio_chunks = _as_list(audio_chunks)
+        ids, plan, rois = self._plan_frames([self.speakers] * len(self._check_slots(slot_ids)), slot_ids, frame_chunks, eyes, lips, order, crop_hw)
+        self._check_push(ids, audio_chunks, rois)
+        self._crop(plan, rois)
+        return self.push(ids, audio_chunks, rois)
 
     def _check_rois(self, slot_ids, roi_chunks):
         K = self.speakers
@@ -1314,6 +1407,28 @@ class FaceCameraStreamPool(CameraStreamPool):
             flat += blocks
         tracks = [t for g in groups for t in g]
         return (ids, groups, *self.lips._check_chunks(tracks, flat)[1:])
+
+    def push_frames(self, slot_ids, audio_chunks, frame_chunks, eyes, lips, order="bgr", crop_hw=(CROP, CROP)):
+        """As ``CameraStreamPool.push_frames`` with one landmark entry per ACTIVE face of the slot in ascending face id: eyes
+        (m,Ka,2,2) and lips (m,Ka,4,2), or sequences of Ka arrays (m,2,2) / (m,4,2).  Still ONE crop launch for all named slots and
+        faces; the ROIs go into ``push`` as one (Ka,m,H,W) tensor per slot."""
+        audio_chunks = _as_list(audio_chunks)
+        named = self._check_slots(slot_ids)
+        for s in named:
+            if not self.audio.faces(s):
+                raise ValueError(f"FaceCameraStreamPool.push_frames: slot {s} has no face; add_face first")
+        ids, plan, rois = self._plan_frames([len(self.audio.faces(s)) for s in named], slot_ids, frame_chunks, eyes, lips, order, crop_hw)
+        self._check_push(ids, audio_chunks, rois)
+        self._crop(plan, rois)
+        return self.push(ids, audio_chunks, rois)
+
+    def _check_push(self, slot_ids, audio_chunks, roi_chunks, timestamps=None, until=None):
+        ids, groups, ms, _, _ = self._check_rois(slot_ids, roi_chunks)
+        wavs = self._check_audio(ids, audio_chunks)
+        if ids:
+            self._plan_faces_push(ids, groups, [int(w.numel()) for w in wavs], ms)
+        if self.audio.model.training:
+            raise RuntimeError("FaceCameraStreamPool is inference only: call .eval() on the model")
 
     def _plan_faces_push(self, ids, groups, na, ms):
         """The dry run of a push on both planners (ms: frames per track): ValueError for what either refuses."""

@@ -123,6 +123,26 @@ class System(nn.Module):
             raise ValueError(f"System.separate_recording: frame_rate = {rate} needs uint8 mouth ROIs and a video model")
         return self.separate_long(wav, mouth_rois, **kw)
 
+    def separate_video(self, wav, sample_rate, frames, eyes, lips, order="bgr", **kw):
+        """A raw recording from whole camera frames (inference; DESIGN.md "Mouth ROIs from camera frames"): ``infer_any_video.py:63-86``
+        including its line 76, the landmark-aligned mouth crop.  wav (L) at ``sample_rate`` Hz, frames uint8 (Tv,H,W,3) in ``order``
+        "bgr" | "rgb" or a grey plane (Tv,H,W) on the device, eyes (Tv,2,2) and lips (Tv,4,2) host landmarks as ``datas.mouth_affine``
+        takes them (the detector stays the caller's).  ``datas.mouth_rois`` cuts the (Tv,96,96) ROIs in one launch, then
+        ``separate_recording(wav, sample_rate, rois, **kw)``: ``frame_rate``, ``timestamps``, ``timebase``, ``until``,
+        ``normalize_audio``, ``window`` ... pass through untouched, and at another ``frame_rate`` every camera frame is cropped before
+        the ``"val"`` launch selects.  A batch: wav (B,L) with frames a sequence of B tensors of equal Tv (any resolutions), eyes and
+        lips sequences; still one crop launch."""
+        from . import datas
+        rois = datas.mouth_rois(frames, eyes, lips, order=order)
+        if not isinstance(rois, torch.Tensor):
+            if len({tuple(r.shape) for r in rois}) != 1 or any(r.ndim != 3 for r in rois):
+                raise ValueError(f"System.separate_video: the frame tensors of a batch must hold the same number of frames, one face "
+                                 f"each; got ROIs {[tuple(r.shape) for r in rois]}")
+            rois = torch.stack(list(rois))
+        elif rois.ndim != 3:
+            raise ValueError("System.separate_video: one face per recording (eyes (Tv,2,2), lips (Tv,4,2)); separate_long_speakers takes several")
+        return self.separate_recording(wav, sample_rate, rois, **kw)
+
     def separate_many(self, wavs, mouths, **kw):
         """Many recordings of different lengths in one pooled pass (inference): wavs = R tensors (L_r)|(1,L_r), mouths = R lip tracks
         (1,Tv_r,88,88) at 25 fps -> a list of R tensors (n_src,L_r).  The video front-end runs under no_grad ONCE PER GROUP of tracks with
