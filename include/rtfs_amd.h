@@ -264,7 +264,8 @@ int rtfs_dualpath_gru_forward_train_f32(const float* x, const float* tpack, floa
 int rtfs_dualpath_gru_backward_f32(const float* x, const float* tpack, const float* saved, const float* dout, float* dx, float* dparams,
                                    int B, int T, int F, int dim, void* ws, size_t ws_bytes, void* stream);
 /* ConvNormAct.forward / backward for training (src/models/layers/conv_layers.py:65-129: pre_norm -> pre_act -> conv -> norm -> act),
- * 1x1 dense (channels up to 1024) or depthwise k x k (taps up to 4 x 5, stride 1 "same" or stride 2 symmetric), norms: none | gLN |
+ * 1x1 dense (channels up to 1024) or depthwise k x k (taps up to 4 x 5, stride 1 "same" or stride 2 symmetric; stride 2 on a map whose
+ * padded height or width is below k is RTFS_ERR_SHAPE, as in nn.Conv), norms: none | gLN |
  * BatchNorm (post-norm only; frozen running statistics, or train mode = statistics of the batch), acts: none | ReLU | PReLU | Sigmoid.
  * cfg (HOST int[15]): Cin, Cout, k, stride, depthwise, pre_norm (0/1), pre_act (0 none, 1 ReLU, 2 PReLU, 3 Sigmoid), norm (0 none, 1 gLN,
  *   2 frozen BatchNorm, 3 train-mode BatchNorm), act, has_bias, is2d, phase, world, in_rows, out_rows.

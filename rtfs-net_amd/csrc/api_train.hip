@@ -459,6 +459,8 @@ struct CnaCfg {
         auto pow2 = [](int v, int cap) { return v >= 1 && v <= cap && !(v & (v - 1)); };
         ok = pow2(Cin, 1024) && pow2(Cout, 1024) && k >= 1 && kh <= 4 && kw <= 5 &&
              (stride == 1 || stride == 2) && Ho >= 1 && Wo >= 1 &&
+             // stride 2: the padded map holds one whole window, as nn.Conv demands (H + 2p - k = -1 divides to 0 above, not to -1)
+             (stride == 1 || (H + 2 * pt >= kh && W + 2 * pl >= kw)) &&
              (depthwise ? Cin == Cout : (k == 1 && stride == 1 && Cin % 16 == 0 && Cout % 64 == 0 && Cin % 64 == 0)) &&
              pre_norm >= 0 && pre_norm <= 1 && norm >= 0 && norm <= 3 && phase >= 0 && phase <= 2 && (phase == 0 || norm == 3) && pre_act >= 0 && pre_act <= 3 && act >= 0 && act <= 3 &&
              rows_in * (size_t)(Cin > Cout ? Cin : Cout) < 0x7fffffffu;
@@ -596,7 +598,9 @@ int rtfs_cna_backward_f32(const float* x, const float* params, const float* save
     float* d2 = ar.take<float>(c.rows_in * c.Cin);
     float* d0 = ar.take<float>(c.rows_in * c.Cin);
     double* Sb = ar.take<double>(2 * (size_t)B);
-    float* wg_scratch = ar.take<float>(c.depthwise ? (size_t)CL_DW_WGRAD_MAX_WG * c.kh * c.kw * c.Cin : 0);
+    // launch_cl_dw runs tensors wider than 256 channels as 256-channel slices that reuse the scratch one after the other, so a slice's
+    // kh * kw * 256 floats per workgroup is the most it ever holds (what rtfs_cna_workspace_bytes budgets: at most 4 x 5 taps)
+    float* wg_scratch = ar.take<float>(c.depthwise ? (size_t)CL_DW_WGRAD_MAX_WG * c.kh * c.kw * (c.Cin < 256 ? c.Cin : 256) : 0);
     float* stage_partial = ar.take<float>(cl_stage_partial_floats(B, c.Cin > c.Cout ? c.Cin : c.Cout));
     RTFS_RETURN_IF(!ar.ok(), RTFS_ERR_WORKSPACE);
     hipStream_t st = S(stream);
