@@ -389,6 +389,29 @@ int rtfs_mha_core_backward_f32(const float* qkv, const float* pmask, const float
  * kind 1: C (M,N) += A (K,M)^T . B (K,N), M % 64 == 0, N % 64 == 0. */
 int rtfs_debug_gemm_f32(int kind, const float* A, const float* B, float* C, int M, int N, int K, int accumulate, void* stream);
 
+/* The inference depthwise family's launchers one at a time, exposed for tests (tests/test_hip_dw_edges.py).  It fills the launcher's
+ * argument struct from the flat description, calls the production launcher, and returns the launcher's status unchanged (so the
+ * RTFS_ERR_ARG "not eligible, fall back" answers of the fused launchers stay visible).  It zeroes no statistics: the caller does.
+ *   op 0 stride-1 conv (nconv / in_affine / mode), 1 the three-job low-resolution launch (two descriptions: the 4-conv job, the folded
+ *   1-conv job), 2 stride-2 + pool beside a MODE 1 statistics pass (two descriptions), 3 stride-2 + pool, 4 g = p0 + gLN(c1),
+ *   5 the same-size combine gLN(l) * sigmoid(gLN(gate)) + gLN(emb).
+ * One conv description is 35 device pointers, 14 ints and 4 doubles (a second one follows the first in each array):
+ *   ptrs  0 x | 1 in_stats 2 in_gamma 3 in_beta | 4-7 w[k] | 8-11 bias[k] | 12-15 out[k] | 16-19 stats_out[k] | 20 loc_stats 21 loc_gamma
+ *         22 loc_beta | 23 gate 24 gate_stats 25 gate_gamma 26 gate_beta | 27 emb 28 emb_stats 29 emb_gamma 30 emb_beta | 31 addend
+ *         32 add_stats 33 add_gamma 34 add_beta
+ *   ints  0 B 1 C 2 H 3 W 4 Hg 5 Wg 6 TH (requested band height) 7 cs (channel stride in floats, 0 = H * W) 8 rev 9 nconv 10 in_affine
+ *         11 mode 12 in_combine 13 present (bits 0-3: bias[k], bit 4: addend; a pointer whose bit is clear is ignored)
+ *   dbls  0 in_inv_count 1 loc_inv_count 2 g_inv_count 3 add_inv_count
+ * op 4: ptrs p0, c1, c1_stats, gamma, beta, g; ints B, C, HW; dbls inv_count.
+ * op 5: ptrs l, gate, emb, l_stats, gate_stats, emb_stats, l_gamma, l_beta, gate_gamma, gate_beta, emb_gamma, emb_beta, out; ints B, C, HW;
+ *       dbls inv_count.
+ * route (host ints, route_cap >= 33): route[0] = jobs launched (0 after a refusal), then per job family (1 one-column stride-1, 2 packed
+ * stride-1, 3 three-job launch, 4 packed stride-2, 5 one-column stride-2, 6 stride-2 + statistics launch, 7 g_form, 8 g_combine), nconv,
+ * in_affine, mode, var (bit 0 addend, 1 shared gathers, 2 combined input, 3 row mapping, 4 whole-row mapping), effective TH, gx, gy.
+ * Refused: RTFS_ERR_ARG (null array, short array, unknown op, B / C / H / W < 1) before any launcher runs. */
+int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, int n_ints, const double* dbls, int n_dbls, int* route,
+                      int route_cap, void* stream);
+
 /* Diagnostic build of the dual-path sweep with s_memtime stamps at phase boundaries (profiling aid only).
  * x, out: (B, 64, R, Ls) with sequences along the last axis; stamps: DEVICE u64 [ceil(B*R/seqs_per_wg)][16]. */
 int rtfs_debug_sweep_stamps(const float* x, const float* pack, float* out, int B, int R, int Ls, unsigned long long* stamps,

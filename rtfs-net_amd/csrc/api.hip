@@ -1318,6 +1318,80 @@ int rtfs_debug_sweep_stamps(const float* x, const float* pack, float* out, int B
     return launch_dualpath16(a, S(stream));
 }
 
+// The depthwise family's launchers (k_dw.hip) by op code, from a flat description (layout: include/rtfs_amd.h).  Tests only: it fills the
+// argument structs, calls the production launcher and hands back the launcher's status and route record; it zeroes no statistics.
+namespace {
+constexpr int DW_DBG_PTRS = 35, DW_DBG_INTS = 14, DW_DBG_DBLS = 4;
+DwArgs dw_debug_args(void* const* p, const int* n, const double* d) {
+    const int present = n[13];  // bits 0-3: bias[k], bit 4: addend
+    DwArgs a;
+    a.x = (const float*)p[0];
+    a.in_stats = (const double*)p[1]; a.in_gamma = (const float*)p[2]; a.in_beta = (const float*)p[3];
+    for (int k = 0; k < 4; ++k) {
+        a.w[k] = (const float*)p[4 + k];
+        a.bias[k] = (present >> k) & 1 ? (const float*)p[8 + k] : nullptr;
+        a.out[k] = (float*)p[12 + k];
+        a.stats_out[k] = (double*)p[16 + k];
+    }
+    a.loc_stats = (const double*)p[20]; a.loc_gamma = (const float*)p[21]; a.loc_beta = (const float*)p[22];
+    a.gate = (const float*)p[23]; a.gate_stats = (const double*)p[24]; a.gate_gamma = (const float*)p[25]; a.gate_beta = (const float*)p[26];
+    a.emb = (const float*)p[27]; a.emb_stats = (const double*)p[28]; a.emb_gamma = (const float*)p[29]; a.emb_beta = (const float*)p[30];
+    if ((present >> 4) & 1) {
+        a.addend = (const float*)p[31]; a.add_stats = (const double*)p[32]; a.add_gamma = (const float*)p[33]; a.add_beta = (const float*)p[34];
+    }
+    a.C = n[1]; a.H = n[2]; a.W = n[3]; a.Hg = n[4]; a.Wg = n[5]; a.TH = n[6]; a.cs = n[7]; a.rev = n[8]; a.in_combine = n[12];
+    a.in_inv_count = d[0]; a.loc_inv_count = d[1]; a.g_inv_count = d[2]; a.add_inv_count = d[3];
+    return a;
+}
+}  // namespace
+
+int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, int n_ints, const double* dbls, int n_dbls, int* route,
+                      int route_cap, void* stream) {
+    RTFS_RETURN_IF(!ptrs || !ints || !dbls || !route || route_cap < 1 + 8 * 4, RTFS_ERR_ARG);
+    route[0] = 0;
+    const int jobs = op == 1 || op == 2 ? 2 : 1;
+    int rc;
+    if (op >= 0 && op <= 3) {
+        RTFS_RETURN_IF(n_ptrs < jobs * DW_DBG_PTRS || n_ints < jobs * DW_DBG_INTS || n_dbls < jobs * DW_DBG_DBLS, RTFS_ERR_ARG);
+        const int B = ints[0];
+        RTFS_RETURN_IF(B < 1 || ints[1] < 1 || ints[2] < 1 || ints[3] < 1, RTFS_ERR_ARG);
+        const DwArgs a = dw_debug_args(ptrs, ints, dbls);
+        if (op == 0) {
+            rc = launch_dw_s1(a, ints[9], ints[10] != 0, ints[11], B, S(stream));
+        } else if (op == 3) {
+            rc = launch_dw_s2_pool(a, B, S(stream));
+        } else {
+            const DwArgs b = dw_debug_args(ptrs + DW_DBG_PTRS, ints + DW_DBG_INTS, dbls + DW_DBG_DBLS);
+            rc = op == 1 ? launch_dw_g3(a, b, B, S(stream)) : launch_dw_s2_stats(a, b, B, S(stream));
+        }
+    } else if (op == 4) {
+        RTFS_RETURN_IF(n_ptrs < 6 || n_ints < 3 || n_dbls < 1 || ints[0] < 1 || ints[1] < 1 || ints[2] < 1, RTFS_ERR_ARG);
+        rc = launch_g_form((const float*)ptrs[0], (const float*)ptrs[1], (const double*)ptrs[2], dbls[0], (const float*)ptrs[3],
+                           (const float*)ptrs[4], (float*)ptrs[5], ints[0], ints[1], ints[2], S(stream));
+    } else if (op == 5) {
+        RTFS_RETURN_IF(n_ptrs < 13 || n_ints < 3 || n_dbls < 1 || ints[0] < 1 || ints[1] < 1 || ints[2] < 1, RTFS_ERR_ARG);
+        GCombineArgs g;
+        g.l = (const float*)ptrs[0]; g.gate = (const float*)ptrs[1]; g.emb = (const float*)ptrs[2];
+        g.l_stats = (const double*)ptrs[3]; g.gate_stats = (const double*)ptrs[4]; g.emb_stats = (const double*)ptrs[5];
+        g.l_gamma = (const float*)ptrs[6]; g.l_beta = (const float*)ptrs[7]; g.gate_gamma = (const float*)ptrs[8];
+        g.gate_beta = (const float*)ptrs[9]; g.emb_gamma = (const float*)ptrs[10]; g.emb_beta = (const float*)ptrs[11];
+        g.out = (float*)ptrs[12];
+        g.inv_count = dbls[0];
+        g.C = ints[1]; g.HW = ints[2];
+        rc = launch_g_combine(g, ints[0], S(stream));
+    } else {
+        return RTFS_ERR_ARG;
+    }
+    const DwRoute& r = dw_route_last();
+    route[0] = r.n;
+    for (int i = 0; i < r.n; ++i) {
+        const DwRouteJob& j = r.job[i];
+        const int v[8] = {j.family, j.nconv, j.in_affine, j.mode, j.var, j.TH, j.gx, j.gy};
+        for (int k = 0; k < 8; ++k) route[1 + 8 * i + k] = v[k];
+    }
+    return rc;
+}
+
 // ------------------------------------------------------------ self test
 int rtfs_selftest_mfma_f16(const float* A, const float* B, float* D, void* stream) {
     RTFS_RETURN_IF(!A || !B || !D, RTFS_ERR_ARG);

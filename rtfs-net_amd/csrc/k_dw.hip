@@ -957,8 +957,17 @@ __global__ __launch_bounds__(256) void stats_kernel(const float* __restrict__ x,
 }
 
 // ---------------------------------------------------------------- launchers
+// the route record (kernels.h): a few host-side integer stores beside each launch, nothing the device sees
+static thread_local DwRoute g_route = {};
+const DwRoute& dw_route_last() { return g_route; }
+static void route_clear() { g_route.n = 0; }
+static void route_add(int family, int nconv, int in_affine, int mode, int var, int TH, int gx, int gy) {
+    if (g_route.n < 4) g_route.job[g_route.n++] = DwRouteJob{family, nconv, in_affine, mode, var, TH, gx, gy};
+}
+
 template <int NCONV, bool IN_AFFINE, int MODE>
 static int launch_dw_s1_t(const DwArgs& a, int B, hipStream_t st) {
+    route_add(DW_FAM_S1, NCONV, IN_AFFINE, MODE, 0, a.TH, cdiv(a.C * a.W, 256), cdiv(a.H, a.TH));
     hipLaunchKernelGGL((dw_s1_kernel<NCONV, IN_AFFINE, MODE>), dim3(cdiv(a.C * a.W, 256), cdiv(a.H, a.TH), B), dim3(256), 0, st, a);
     return rtfs_launch_status();
 }
@@ -983,6 +992,7 @@ static int launch_dw1p_t(const DwArgs& a_, int B, hipStream_t st) {
     a.TH = band_rows(a.TH, a.H, a.gx, B, MODE == 2 ? 768 : 320);
     a.gy = cdiv(a.H, a.TH);
     a.nblk = a.gx * a.gy * B;
+    route_add(DW_FAM_1P, NCONV, IN_AFFINE, MODE, VAR, a.TH, a.gx, a.gy);
     hipLaunchKernelGGL((dw1p_kernel<NCONV, IN_AFFINE, MODE, VAR>), dim3((a.nblk + 7) / 8 * 8), dim3(256), 0, st, a);
     return rtfs_launch_status();
 }
@@ -1008,6 +1018,7 @@ static bool nearest_is_integer_quotient(int n_in, int n_out) {
 }
 
 int launch_dw_s1(const DwArgs& a_, int nconv, bool in_affine, int mode, int B, hipStream_t st) {
+    route_clear();
     if (a_.cs && a_.cs < a_.H * a_.W) return RTFS_ERR_SHAPE;
     DwArgs a = a_;
     if (!a.cs) a.cs = a.H * a.W;
@@ -1069,6 +1080,7 @@ int launch_dw_s1(const DwArgs& a_, int nconv, bool in_affine, int mode, int B, h
 }
 
 int launch_dw_g3(const DwArgs& conv4, const DwArgs& aff1, int B, hipStream_t st) {
+    route_clear();
     DwArgs j[3] = {conv4, conv4, aff1};
     const bool nohalo = 64 % ((conv4.W + 1) / 2) == 0 && conv4.W == aff1.W;  // whole rows per wave (dw1p_body NOHALO)
     for (int i = 0; i < 2; ++i) {
@@ -1080,6 +1092,7 @@ int launch_dw_g3(const DwArgs& conv4, const DwArgs& aff1, int B, hipStream_t st)
         if (a.W < 16 || (a.cs && a.cs < a.H * a.W)) return RTFS_ERR_ARG;  // the caller falls back to separate launches
         if (!a.cs) a.cs = a.H * a.W;
         if ((size_t)a.C * a.cs * 4 >= ((size_t)1 << 31)) return RTFS_ERR_ARG;
+        a.rev = 0;  // dw_g3_kernel picks the job from the front-to-back block order; a job that mapped its blocks back to front would disagree with it
         a.gx = cdiv(cdiv(a.C * ((a.W + 1) / 2), nohalo ? 64 : DW1P_PAIRS), 4);
         a.TH = band_rows(a.TH, a.H, a.gx, 3 * B, 640);  // (three jobs share the launch)
         a.gy = cdiv(a.H, a.TH);
@@ -1087,12 +1100,14 @@ int launch_dw_g3(const DwArgs& conv4, const DwArgs& aff1, int B, hipStream_t st)
         a.blk0 = off;
         off += a.nblk;
     }
+    for (int i = 0; i < 3; ++i) route_add(DW_FAM_G3, i < 2 ? 2 : 1, i == 2, 0, nohalo ? 16 : 0, j[i].TH, j[i].gx, j[i].gy);
     if (nohalo) hipLaunchKernelGGL(dw_g3_kernel<16>, dim3((off + 7) / 8 * 8), dim3(256), 0, st, j[0], j[1], j[2]);
     else hipLaunchKernelGGL(dw_g3_kernel<0>, dim3((off + 7) / 8 * 8), dim3(256), 0, st, j[0], j[1], j[2]);
     return rtfs_launch_status();
 }
 
 int launch_dw_s2_stats(const DwArgs& s2_, const DwArgs& st_, int B, hipStream_t st) {
+    route_clear();
     DwArgs a = s2_, b = st_;
     if ((a.cs && a.cs < a.H * a.W) || a.x != b.x || a.cs != b.cs || a.H != b.H || a.W != b.W || a.C != b.C) return RTFS_ERR_ARG;
     if (!a.cs) a.cs = b.cs = a.H * a.W;
@@ -1110,11 +1125,14 @@ int launch_dw_s2_stats(const DwArgs& s2_, const DwArgs& st_, int B, hipStream_t 
     b.job_off = ca;
     b.rev = a.rev;
     const long total = (long)(ca + cb) * B;
+    route_add(DW_FAM_S2_STATS, 1, 1, 0, 0, a.TH, a.gx, a.gy);  // job 0: the stride-2 + pool body
+    route_add(DW_FAM_S2_STATS, 1, 1, 1, 0, b.TH, b.gx, b.gy);  // job 1: MODE 1 statistics
     hipLaunchKernelGGL(dw_s2_stats_kernel, dim3((unsigned)((total + 7) / 8 * 8)), dim3(256), 0, st, a, b);
     return rtfs_launch_status();
 }
 
 int launch_dw_s2_pool(const DwArgs& a_, int B, hipStream_t st) {
+    route_clear();
     if (a_.cs && a_.cs < a_.H * a_.W) return RTFS_ERR_SHAPE;
     DwArgs a = a_;
     if (!a.cs) a.cs = a.H * a.W;
@@ -1123,20 +1141,26 @@ int launch_dw_s2_pool(const DwArgs& a_, int B, hipStream_t st) {
         a.TH = band_rows(a.TH, a.Hg, a.gx, B, 320);
         a.gy = cdiv(a.Hg, a.TH);
         a.nblk = a.gx * a.gy * B;
+        route_add(DW_FAM_S2X, 1, 1, 0, 0, a.TH, a.gx, a.gy);
         hipLaunchKernelGGL(dw_s2x_kernel, dim3((a.nblk + 7) / 8 * 8), dim3(256), 0, st, a);
         return rtfs_launch_status();
     }
+    route_add(DW_FAM_S2_POOL, 1, 1, 0, 0, a.TH, cdiv(a.C * a.Wg, 256), cdiv(a.Hg, a.TH));
     hipLaunchKernelGGL(dw_s2_pool_kernel, dim3(cdiv(a.C * a.Wg, 256), cdiv(a.Hg, a.TH), B), dim3(256), 0, st, a);
     return rtfs_launch_status();
 }
 
 int launch_g_form(const float* p0, const float* c1, const double* st1, double inv_count, const float* gamma,
                   const float* beta, float* g, int B, int C, int HW, hipStream_t st) {
+    route_clear();
+    route_add(DW_FAM_G_FORM, 0, 1, 0, 0, 0, B * C >= 1024 ? 1 : 4, C);
     hipLaunchKernelGGL(g_form_kernel, dim3(B * C >= 1024 ? 1 : 4, C, B), dim3(256), 0, st, p0, c1, st1, inv_count, gamma, beta, g, C, HW);
     return rtfs_launch_status();
 }
 
 int launch_g_combine(const GCombineArgs& a, int B, hipStream_t st) {
+    route_clear();
+    route_add(DW_FAM_G_COMBINE, 0, 1, 0, 0, 0, B * a.C >= 1024 ? 1 : 4, a.C);
     hipLaunchKernelGGL(g_combine_kernel, dim3(B * a.C >= 1024 ? 1 : 4, a.C, B), dim3(256), 0, st, a);
     return rtfs_launch_status();
 }

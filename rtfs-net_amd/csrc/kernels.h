@@ -202,6 +202,15 @@ struct GCombineArgs {
     int C, HW;
 };
 
+// What the launchers below chose on their last call from this thread (host side only; rtfs_debug_dw_f32 hands it to the tests, which assert
+// the route every case is meant to take: a shape that silently falls to the one-column kernel must not pass for coverage of the packed one).
+// Every launcher clears the record on entry and appends one job per kernel job it launches, so a refusal leaves n == 0.
+enum DwFamily { DW_FAM_S1 = 1, DW_FAM_1P = 2, DW_FAM_G3 = 3, DW_FAM_S2X = 4, DW_FAM_S2_POOL = 5, DW_FAM_S2_STATS = 6, DW_FAM_G_FORM = 7,
+                DW_FAM_G_COMBINE = 8 };
+struct DwRouteJob { int family, nconv, in_affine, mode, var, TH, gx, gy; };  // TH, gx, gy: the effective band height and logical grid
+struct DwRoute { int n; DwRouteJob job[4]; };
+const DwRoute& dw_route_last();
+
 int launch_dw_s1(const DwArgs& a, int nconv, bool in_affine, int mode, int B, hipStream_t st);
 // One launch for the block's three independent low-resolution conv jobs (steps 10 and 11: four plain convs on one input as two 2-conv
 // jobs + one conv on a gLN-folded input): each alone is 576 workgroups, too few to fill the chip
