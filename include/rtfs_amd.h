@@ -412,6 +412,34 @@ int rtfs_debug_gemm_f32(int kind, const float* A, const float* B, float* C, int 
 int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, int n_ints, const double* dbls, int n_dbls, int* route,
                       int route_cap, void* stream);
 
+/* The inference pointwise (1x1 conv) family's launchers one at a time, exposed for tests (tests/test_hip_pw_edges.py).  It fills PwArgs,
+ * B2bArgs, BnHeadArgs or TailS3Args (k_bnh.hip, k_s3f.hip: ops 8 and 9) from the flat description, calls ONE production launcher and returns the launcher's status unchanged (RTFS_ERR_ARG "does not
+ * qualify, fall back" and RTFS_ERR_SHAPE stay visible).
+ *   op 0 the exact-f32 launchers, 1 the first f16x3 generation (both: ints[11] = kind 0 audio bottleneck, 1 gateway + projection, 2 residual
+ *   conv, 3 S3 mask, 4 decoder taps; contiguous rows only, cs must be 0), 2 streaming gateway + projection (x2 / CAF by the pointers given),
+ *   3 block head on padded rows, 4 streaming residual conv, 5 first-generation block boundary, 6 block boundary on padded rows,
+ *   7 register-resident 256 -> 256 (kind 0 audio bottleneck, 1 S3 mask, 2 S3 mask + decoder taps),
+ *   8 fused bottleneck + first block head (launch_bn_head), 9 fused residual conv + S3 mask + decoder taps (launch_tail_s3t).  Ops 8 and 9
+ *   first run the production launch_enc_stats on ints[14] mixtures, as the separator does: it adds the a0 statistics into `stats` (zeroed by
+ *   the caller), writes the encoder fragment image (enc_img, 8192 floats) and the padded copy (wpad, 73728 floats) of the 256 -> 256 weight
+ *   image w16 that the kernel reads.  Op 8: a1 = ptr 24 (written), res_out may be null.  Op 9: x, res_out (read only), out = z, w2_16 / bp =
+ *   the residual conv's image and bias, w16 / bias = the mask conv's, xk = K (0: mix_of / mix_base), kind bit 0 = launch with stats null.
+ *   ptrs (32)  0 x | 1 x2 | 2 res_out (ops 5, 6: res, in and out) | 3 wt | 4 w16 (ops 5, 6: w1_16) | 5 w16b | 6 bias (ops 5, 6: b1) | 7 aux
+ *              8 out (ops 5, 6: xenc) | 9 stats 10 gamma 11 beta | 12 gw 13 gb 14 slope | 15 tile_ctr (null or one zeroed word)
+ *              16 caf_r 17 caf_att 18 caf_w_key 19 caf_bn_key 20 caf_w_val 21 caf_bn_val 22 caf_rt 23 caf_attt | 24 a1 25 w2_16 26 bp 27 mix_of
+ *              28 spec (mixtures, 2, T, F) 29 enc_w (256, 18) 30 enc_img 31 wpad
+ *   ints (15)  0 B (ops 5, 6: targets of the launch) 1 P 2 cs (floats, 0 = P) 3 cout_live 4 caf_T 5 caf_F 6 caf_Tv 7 a1_mode 8 xk 9 a1k
+ *              10 mix_base 11 kind 12 T 13 F 14 mixtures (ops 8, 9)
+ *   dbls (1)   0 inv_count
+ * route (host ints, route_cap >= 25): route[0] = kernels launched (0 after a refusal), then per kernel family (1 exact f32, 2 first f16x3
+ * generation, 3 streaming gateway + projection, 4 streaming residual conv, 5 first-generation boundary, 6 boundary on padded rows, 7 head on
+ * padded rows, 8 register-resident 256 -> 256), CIN, COUT, PRO, EPI, CAF, a1_mode, mode (family 8: MODE; family 3: HAS_X2), tiles per
+ * sample, tiles, workgroups, 1 = tiles from the counter word / 0 = static stride.  Families 9 (fused head; mode = res written) and 10
+ * (fused tail; mode = K) likewise; launch_enc_stats is not part of the record.
+ * Refused: RTFS_ERR_ARG (null or short array, unknown op or kind, B / P < 1, cs != 0 for ops 0 and 1) before any launcher runs. */
+int rtfs_debug_pw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, int n_ints, const double* dbls, int n_dbls, int* route,
+                      int route_cap, void* stream);
+
 /* Diagnostic build of the dual-path sweep with s_memtime stamps at phase boundaries (profiling aid only).
  * x, out: (B, 64, R, Ls) with sequences along the last axis; stamps: DEVICE u64 [ceil(B*R/seqs_per_wg)][16]. */
 int rtfs_debug_sweep_stamps(const float* x, const float* pack, float* out, int B, int R, int Ls, unsigned long long* stamps,

@@ -1392,6 +1392,103 @@ int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, in
     return rc;
 }
 
+// The pointwise family's launchers (k_pw / k_pw16 / k_pwr / k_pws / k_b2b / k_bnh / k_s3f .hip) by op code, from a flat description (layout:
+// include/rtfs_amd.h).  Tests only: it fills PwArgs, B2bArgs, BnHeadArgs or TailS3Args, calls one production launcher (the fused head and tail
+// behind launch_enc_stats) and hands back its status and route record.
+namespace {
+constexpr int PW_DBG_PTRS = 32, PW_DBG_INTS = 15, PW_DBG_DBLS = 1;
+}  // namespace
+
+int rtfs_debug_pw_f32(int op, void* const* p, int n_ptrs, const int* n, int n_ints, const double* d, int n_dbls, int* route, int route_cap,
+                      void* stream) {
+    RTFS_RETURN_IF(!p || !n || !d || !route || route_cap < 1 + 12 * 2, RTFS_ERR_ARG);
+    route[0] = 0;
+    RTFS_RETURN_IF(n_ptrs < PW_DBG_PTRS || n_ints < PW_DBG_INTS || n_dbls < PW_DBG_DBLS, RTFS_ERR_ARG);
+    const int B = n[0], kind = n[11];
+    RTFS_RETURN_IF(B < 1 || n[1] < 1 || n[2] < 0, RTFS_ERR_ARG);
+    pw_route_clear();
+    int rc;
+    if (op == 5 || op == 6) {
+        B2bArgs a;
+        a.x = (const float*)p[0]; a.res = (float*)p[2]; a.a1 = (const float*)p[24]; a.xenc = (float*)p[8];
+        a.w1_16 = p[4]; a.b1 = (const float*)p[6]; a.w2_16 = p[25]; a.bp = (const float*)p[26];
+        a.gw = (const float*)p[12]; a.gb = (const float*)p[13]; a.slope = (const float*)p[14];
+        a.P = n[1]; a.cs = n[2];
+        a.caf_r = (const float*)p[16]; a.caf_att = (const float*)p[17];
+        a.caf_w_key = (const float*)p[18]; a.caf_bn_key = (const float*)p[19]; a.caf_w_val = (const float*)p[20]; a.caf_bn_val = (const float*)p[21];
+        a.caf_rt = (const float*)p[22]; a.caf_attt = (const float*)p[23];
+        a.caf_T = n[4]; a.caf_F = n[5]; a.caf_Tv = n[6];
+        a.a1_mode = n[7]; a.xk = n[8]; a.a1k = n[9]; a.mix_of = (const int*)p[27]; a.mix_base = n[10];
+        rc = op == 5 ? launch_pws_b2b(a, B, S(stream)) : launch_pws_b2b4(a, B, (unsigned*)p[15], S(stream));
+    } else if (op == 8 || op == 9) {
+        // the fused head and tail kernels rebuild a0 from the spectrogram: first the production launch_enc_stats, as separator_part runs it - the
+        // statistics (zeroed by the caller), the encoder's fragment image and the padded copy of this kernel's 256 -> 256 weight image
+        const int T = n[12], F = n[13], nmix = n[14];
+        RTFS_RETURN_IF(T < 1 || F < 1 || nmix < 1 || !p[28] || !p[29] || !p[30] || !p[31] || !p[9] || !p[4], RTFS_ERR_ARG);
+        EncPadJobs pad;
+        pad.src[op - 8] = p[4]; pad.dst[op - 8] = p[31];
+        const int rc0 = launch_enc_stats((const float*)p[28], (const float*)p[29], (double*)p[9], p[30], pad, nmix, T, F, S(stream));
+        if (rc0 != RTFS_OK) return rc0;
+        if (op == 8) {
+            BnHeadArgs f;
+            f.spec = (const float*)p[28]; f.enc_img = p[30]; f.T = T; f.F = F;
+            f.a1 = (float*)p[24]; f.res = (float*)p[2]; f.xenc = (float*)p[8];
+            f.stats = (const double*)p[9]; f.inv_count = d[0]; f.gamma = (const float*)p[10]; f.beta = (const float*)p[11];
+            f.w16 = p[31]; f.bias = (const float*)p[6];
+            f.gw = (const float*)p[12]; f.gb = (const float*)p[13]; f.slope = (const float*)p[14]; f.w2_16 = p[25]; f.bp = (const float*)p[26];
+            f.P = n[1]; f.cs = n[2]; f.tile_ctr = (unsigned*)p[15];
+            rc = launch_bn_head(f, B, S(stream));
+        } else {
+            TailS3Args f;
+            f.x = (const float*)p[0]; f.res = (const float*)p[2]; f.spec = (const float*)p[28]; f.enc_img = p[30]; f.T = T; f.F = F;
+            f.z = (float*)p[8]; f.w1_16 = p[25]; f.b1 = (const float*)p[26]; f.w16 = p[31]; f.bias = (const float*)p[6];
+            f.slope = (const float*)p[14]; f.w16b = p[5];
+            f.stats = kind & 1 ? nullptr : (const double*)p[9]; f.inv_count = d[0];
+            f.P = n[1]; f.cs = n[2]; f.cout_live = n[3]; f.tile_ctr = (unsigned*)p[15];
+            f.K = n[8]; f.mix_of = (const int*)p[27]; f.mix_base = n[10];
+            RTFS_RETURN_IF(f.cout_live < 1 || f.K < 0 || (f.K == 0 && !f.mix_of), RTFS_ERR_ARG);
+            rc = launch_tail_s3t(f, B, S(stream));
+        }
+    } else if (op >= 0 && op <= 7) {
+        PwArgs a;
+        a.x = (const float*)p[0]; a.x2 = (const float*)p[1]; a.res_out = (float*)p[2]; a.wt = (const float*)p[3]; a.w16 = p[4]; a.w16b = p[5];
+        a.bias = (const float*)p[6]; a.aux = (const float*)p[7]; a.out = (float*)p[8]; a.stats = (const double*)p[9]; a.inv_count = d[0];
+        a.gamma = (const float*)p[10]; a.beta = (const float*)p[11]; a.gw = (const float*)p[12]; a.gb = (const float*)p[13];
+        a.slope = (const float*)p[14]; a.P = n[1]; a.cs = n[2]; a.cout_live = n[3]; a.tile_ctr = (unsigned*)p[15];
+        a.caf_r = (const float*)p[16]; a.caf_att = (const float*)p[17];
+        a.caf_w_key = (const float*)p[18]; a.caf_bn_key = (const float*)p[19]; a.caf_w_val = (const float*)p[20]; a.caf_bn_val = (const float*)p[21];
+        a.caf_T = n[4]; a.caf_F = n[5]; a.caf_Tv = n[6];
+        typedef int (*PwLaunch)(const PwArgs&, int, hipStream_t);
+        static const PwLaunch f32[5] = {launch_pw_audio_bn, launch_pw_gateway_proj, launch_pw_residual, launch_pw_s3, launch_pw_dec_taps};
+        static const PwLaunch f16[5] = {launch_pw16_audio_bn, launch_pw16_gateway_proj, launch_pw16_residual, launch_pw16_s3, launch_pw16_dec_taps};
+        static const PwLaunch pwr[3] = {launch_pwr_audio_bn, launch_pwr_s3, launch_pwr_s3_taps};
+        if (op == 0 || op == 1) {
+            // these two generations read contiguous rows only and check nothing themselves
+            RTFS_RETURN_IF(kind < 0 || kind > 4 || a.cs != 0 || (kind == 4 && (a.cout_live < 1 || a.cout_live > 32)), RTFS_ERR_ARG);
+            rc = (op == 0 ? f32 : f16)[kind](a, B, S(stream));
+        } else if (op == 2) {
+            rc = launch_pws_gateway_proj(a, B, S(stream));
+        } else if (op == 3) {
+            rc = launch_pws_head4(a, B, S(stream));
+        } else if (op == 4) {
+            rc = launch_pws_residual(a, B, S(stream));
+        } else {
+            RTFS_RETURN_IF(kind < 0 || kind > 2 || (kind == 2 && (a.cout_live < 1 || a.cout_live > 32)), RTFS_ERR_ARG);
+            rc = pwr[kind](a, B, S(stream));
+        }
+    } else {
+        return RTFS_ERR_ARG;
+    }
+    const PwRoute& r = pw_route_last();
+    route[0] = r.n;
+    for (int i = 0; i < r.n; ++i) {
+        const PwRouteJob& j = r.job[i];
+        const int v[12] = {j.family, j.cin, j.cout, j.pro, j.epi, j.caf, j.am, j.mode, j.tps, j.ntiles, j.grid, j.counter};
+        for (int k = 0; k < 12; ++k) route[1 + 12 * i + k] = v[k];
+    }
+    return rc;
+}
+
 // ------------------------------------------------------------ self test
 int rtfs_selftest_mfma_f16(const float* A, const float* B, float* D, void* stream) {
     RTFS_RETURN_IF(!A || !B || !D, RTFS_ERR_ARG);

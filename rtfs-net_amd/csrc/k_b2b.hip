@@ -411,6 +411,7 @@ bool launch_pws_b2b4_qualifies(const B2bArgs& a) {
     return (size_t)256 * a.cs * 4 < ((size_t)1 << 31);  // buffer offsets inside one sample: 31 bits
 }
 int launch_pws_b2b4(const B2bArgs& a, int B, unsigned* ctr, hipStream_t st) {
+    pw_route_clear();
     if (!launch_pws_b2b4_qualifies(a)) return RTFS_ERR_ARG;
     const int tps = cdiv(a.P, B4_NT / 64 * 64), ntiles = tps * B;
     const int grid = ntiles < 256 ? ntiles : 256;  // one resident workgroup per CU
@@ -419,6 +420,7 @@ int launch_pws_b2b4(const B2bArgs& a, int B, unsigned* ctr, hipStream_t st) {
 #define B4_LAUNCH(CAF_, AM_)                                                                                                  \
     do {                                                                                                                      \
         if (rtfs_set_max_lds((const void*)pws_b2b4_kernel<CAF_, AM_>, B4_LDS) != RTFS_OK) return RTFS_ERR_LAUNCH;             \
+        pw_route_add(PwRouteJob{PW_FAM_B2B4, 64, 64, 0, 0, CAF_, AM_, 0, tps, ntiles, grid, ctr != nullptr});                 \
         hipLaunchKernelGGL((pws_b2b4_kernel<CAF_, AM_>), dim3(grid), dim3(B4_NT), B4_LDS, st, a, ntiles, tps, ctr);           \
     } while (0)
     if (a.caf_r) {
@@ -439,11 +441,13 @@ int launch_pws_b2b4(const B2bArgs& a, int B, unsigned* ctr, hipStream_t st) {
 
 // block head on padded rows, no second addend, no CAF; RTFS_ERR_ARG = use pws_kernel
 int launch_pws_head4(const PwArgs& a, int B, hipStream_t st) {
+    pw_route_clear();
     if (a.x2 || a.caf_r || a.cs <= 0 || (a.cs & 63) || a.cs < (a.P + 63) / 64 * 64 || a.P < 2) return RTFS_ERR_ARG;
     if ((size_t)256 * a.cs * 4 >= ((size_t)1 << 31)) return RTFS_ERR_ARG;
     if (rtfs_set_max_lds((const void*)pws_head4_kernel, H4_LDS) != RTFS_OK) return RTFS_ERR_LAUNCH;
     const int tps = cdiv(a.P, 256), ntiles = tps * B;
     const int grid = ntiles < 512 ? ntiles : 512;  // two resident workgroups per CU
+    pw_route_add(PwRouteJob{PW_FAM_HEAD4, 256, 64, 2, 0, 0, 0, 0, tps, ntiles, grid, a.tile_ctr != nullptr});
     hipLaunchKernelGGL(pws_head4_kernel, dim3(grid), dim3(256), H4_LDS, st, a, ntiles, tps);
     return rtfs_launch_status();
 }

@@ -361,9 +361,11 @@ bool launch_bn_head_qualifies(const BnHeadArgs& a) {
 
 // RTFS_ERR_ARG = the call does not qualify (contiguous rows, tiny input): the caller runs the separate kernels
 int launch_bn_head(const BnHeadArgs& a, int B, hipStream_t st) {
+    pw_route_clear();
     if (!launch_bn_head_qualifies(a)) return RTFS_ERR_ARG;
     const int tps = cdiv(a.P, N_NT / 64 * 64), ntiles = tps * B;
     const int grid = ntiles < 256 ? ntiles : 256;  // one resident workgroup per CU
+    pw_route_add(PwRouteJob{PW_FAM_BN_HEAD, 256, 64, 0, 0, 0, 0, a.res != nullptr, tps, ntiles, grid, a.tile_ctr != nullptr});
     if (a.res) {
         if (rtfs_set_max_lds((const void*)bn_head_kernel<true>, N_LDS) != RTFS_OK) return RTFS_ERR_LAUNCH;
         hipLaunchKernelGGL(bn_head_kernel<true>, dim3(grid), dim3(N_NT), N_LDS, st, a, ntiles, tps);

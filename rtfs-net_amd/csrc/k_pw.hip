@@ -132,8 +132,18 @@ __global__ __launch_bounds__(256) void pw_kernel(PwArgs a) {
     }
 }
 
+// the route record of the pointwise family (kernels.h): a few host-side integer stores beside each launch, nothing the device sees
+static thread_local PwRoute g_pw_route = {};
+const PwRoute& pw_route_last() { return g_pw_route; }
+void pw_route_clear() { g_pw_route.n = 0; }
+void pw_route_add(const PwRouteJob& j) {
+    if (g_pw_route.n < 2) g_pw_route.job[g_pw_route.n++] = j;
+}
+
 template <int CIN, int COUT, int PT, int WAVES_M, int PRO, int EPI>
 static int launch_pw_t(const PwArgs& a, int B, hipStream_t st) {
+    pw_route_clear();
+    pw_route_add(PwRouteJob{PW_FAM_F32, CIN, COUT, PRO, EPI, 0, 0, 0, cdiv(a.P, PT), cdiv(a.P, PT) * B, cdiv(a.P, PT) * B, 0});
     hipLaunchKernelGGL((pw_kernel<CIN, COUT, PT, WAVES_M, PRO, EPI>), dim3(cdiv(a.P, PT), B), dim3(256), 0, st, a);
     return rtfs_launch_status();
 }

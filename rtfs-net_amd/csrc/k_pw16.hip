@@ -171,6 +171,8 @@ __global__ __launch_bounds__(NT) void pw16_kernel(PwArgs a) {
 
 template <int CIN, int COUT, int PT, int WAVES_M, int PRO, int EPI, int NT = 256>
 static int launch_pw16_t(const PwArgs& a, int B, hipStream_t st) {
+    pw_route_clear();
+    pw_route_add(PwRouteJob{PW_FAM_PW16, CIN, COUT, PRO, EPI, 0, 0, 0, cdiv(a.P, PT), cdiv(a.P, PT) * B, cdiv(a.P, PT) * B, 0});
     hipLaunchKernelGGL((pw16_kernel<CIN, COUT, PT, WAVES_M, PRO, EPI, NT>), dim3(cdiv(a.P, PT), B), dim3(NT), 0, st, a);
     return rtfs_launch_status();
 }

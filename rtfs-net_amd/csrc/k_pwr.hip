@@ -255,6 +255,7 @@ __global__ __launch_bounds__(256, 2) void pwr_kernel(PwArgs a, int ntiles, int t
 
 template <int MODE>
 int launch_pwr_t(const PwArgs& a_, int B, hipStream_t st) {
+    pw_route_clear();
     if (a_.cs && a_.cs < a_.P) return RTFS_ERR_SHAPE;
     PwArgs a = a_;
     if (!a.cs) a.cs = a.P;
@@ -262,6 +263,7 @@ int launch_pwr_t(const PwArgs& a_, int B, hipStream_t st) {
     if (rtfs_set_max_lds((const void*)pwr_kernel<MODE>, PWR_LDS) != RTFS_OK) return RTFS_ERR_LAUNCH;
     const int tps = cdiv(a.P, PWR_PT), ntiles = tps * B;
     const int grid = ntiles < 512 ? ntiles : 512;  // persistent: 2 workgroups per CU
+    pw_route_add(PwRouteJob{PW_FAM_PWR, 256, 256, 0, 0, 0, 0, MODE, tps, ntiles, grid, a.tile_ctr != nullptr});
     hipLaunchKernelGGL((pwr_kernel<MODE>), dim3(grid), dim3(256), PWR_LDS, st, a, ntiles, tps);
     return rtfs_launch_status();
 }
@@ -270,4 +272,8 @@ int launch_pwr_t(const PwArgs& a_, int B, hipStream_t st) {
 
 int launch_pwr_audio_bn(const PwArgs& a, int B, hipStream_t st) { return launch_pwr_t<PWR_BN>(a, B, st); }
 int launch_pwr_s3(const PwArgs& a, int B, hipStream_t st) { return launch_pwr_t<PWR_S3>(a, B, st); }
-int launch_pwr_s3_taps(const PwArgs& a, int B, hipStream_t st) { return a.w16b ? launch_pwr_t<PWR_S3T>(a, B, st) : RTFS_ERR_ARG; }
+int launch_pwr_s3_taps(const PwArgs& a, int B, hipStream_t st) {
+    if (a.w16b) return launch_pwr_t<PWR_S3T>(a, B, st);
+    pw_route_clear();
+    return RTFS_ERR_ARG;
+}

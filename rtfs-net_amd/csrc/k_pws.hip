@@ -2,7 +2,7 @@
 // residual_conv; reference separators/tdanet.py:29-57,106-107,129).  These are HBM-bound (2 KB of activations per
 // pixel against 6 f16 MFMAs per 16 channels), so the kernel is organised around the memory stream:
 //   * the whole f16x3 weight image (64 KB) is loaded into LDS once per workgroup and stays resident;
-//   * workgroups are persistent and walk 128-pixel (64 for COUT 256) tiles; inside a tile every wave owns 32 pixels and needs no
+//   * workgroups are persistent and walk 256-pixel tiles (COUT 64: two pixels per lane; 32 S (4 / CSPLIT) in general); a wave owns 32 S pixels and needs no
 //     barrier: each lane loads the 8 input channels of its MFMA B fragment straight from global memory
 //     (32 consecutive pixels per channel row = full 128-byte segments), applies the prologue, splits to f16 hi/lo
 //     in registers and feeds the matrix cores; each activation is read by exactly one lane;
@@ -206,6 +206,7 @@ __global__ __launch_bounds__(256, 2) void pws_kernel(PwArgs a, int ntiles, int t
 template <int CIN, int COUT, int PRO, int EPI, bool HAS_X2, bool CAF = false>
 static int launch_pws_t(const PwArgs& a_, int B, hipStream_t st) {
     constexpr int S = COUT <= 64 ? 2 : 1;  // two pixels per lane where the accumulators allow it (COUT 64: 64 registers)
+    pw_route_clear();
     if (a_.P < 2 || (a_.cs && a_.cs < a_.P)) return RTFS_ERR_SHAPE;
     PwArgs a = a_;
     if (!a.cs) a.cs = a.P;
@@ -214,11 +215,13 @@ static int launch_pws_t(const PwArgs& a_, int B, hipStream_t st) {
     constexpr int PTB = 32 * S * (4 / (COUT / 32 > 4 ? COUT / 32 / 4 : 1));
     const int tps = cdiv(a.P, PTB), ntiles = tps * B;
     const int grid = ntiles < 512 ? ntiles : 512;  // 2 resident workgroups per CU
+    pw_route_add(PwRouteJob{PW_FAM_PWS, CIN, COUT, PRO, EPI, CAF, 0, HAS_X2, tps, ntiles, grid, a.tile_ctr != nullptr});
     hipLaunchKernelGGL((pws_kernel<CIN, COUT, PRO, EPI, HAS_X2, CAF, S>), dim3(grid), dim3(256), lds, st, a, ntiles, tps);
     return rtfs_launch_status();
 }
 
 int launch_pws_gateway_proj(const PwArgs& a, int B, hipStream_t st) {
+    if (a.caf_r && !a.x2) pw_route_clear();  // (the only refusal of its own; launch_pws_t clears on every other path)
     if (a.caf_r) return a.x2 ? launch_pws_t<256, 64, PRO_GATEWAY, EPI_BIAS, true, true>(a, B, st) : RTFS_ERR_ARG;
     return a.x2 ? launch_pws_t<256, 64, PRO_GATEWAY, EPI_BIAS, true>(a, B, st) : launch_pws_t<256, 64, PRO_GATEWAY, EPI_BIAS, false>(a, B, st);
 }
@@ -323,6 +326,7 @@ __global__ __launch_bounds__(256, 2) void pws_res2_kernel(PwArgs a, int ntiles, 
     pws_res2_body(a, ntiles, tiles_per_sample, a.x, a.aux, a.out);
 }
 static int launch_pws_res2(const PwArgs& a_, int B, hipStream_t st) {
+    pw_route_clear();
     if (a_.P < 2 || (a_.cs && a_.cs < a_.P)) return RTFS_ERR_SHAPE;
     PwArgs a = a_;
     if (!a.cs) a.cs = a.P;
@@ -331,6 +335,7 @@ static int launch_pws_res2(const PwArgs& a_, int B, hipStream_t st) {
     if (rtfs_set_max_lds((const void*)pws_res2_kernel, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
     const int tps = cdiv(a.P, 256), ntiles = tps * B;
     const int grid = ntiles < 512 ? ntiles : 512;  // 2 resident workgroups per CU
+    pw_route_add(PwRouteJob{PW_FAM_RES2, 64, 256, 0, EPI_BIAS_RES, 0, 0, 0, tps, ntiles, grid, a.tile_ctr != nullptr});
     hipLaunchKernelGGL(pws_res2_kernel, dim3(grid), dim3(256), lds, st, a, ntiles, tps);
     return rtfs_launch_status();
 }
@@ -530,6 +535,7 @@ __global__ __launch_bounds__(B2B_NT) void pws_b2b_kernel(B2bArgs a, int ntiles, 
 
 template <bool CAF>
 static int launch_b2b_t(const B2bArgs& a_, int B, hipStream_t st) {
+    pw_route_clear();
     if (a_.cs && a_.cs < a_.P) return RTFS_ERR_SHAPE;
     B2bArgs a = a_;
     if (!a.cs) a.cs = a.P;
@@ -539,6 +545,7 @@ static int launch_b2b_t(const B2bArgs& a_, int B, hipStream_t st) {
     if (a.P < 2) return RTFS_ERR_SHAPE;
     const int tps = cdiv(a.P, B2B_NT / 64 * 64), ntiles = tps * B;
     const int grid = ntiles < 256 ? ntiles : 256;  // one resident 8-wave workgroup per CU
+    pw_route_add(PwRouteJob{PW_FAM_B2B, 64, 64, 0, 0, CAF, 1, 0, tps, ntiles, grid, 0});  // (static stride only)
     hipLaunchKernelGGL((pws_b2b_kernel<CAF>), dim3(grid), dim3(B2B_NT), lds, st, a, ntiles, tps);
     return rtfs_launch_status();
 }

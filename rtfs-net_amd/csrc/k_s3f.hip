@@ -361,11 +361,13 @@ __global__ __launch_bounds__(F_NT) void tail_s3t_kernel(TailS3Args a, int ntiles
 
 // RTFS_ERR_ARG = the call does not qualify (contiguous rows, tiny input): the caller runs the two separate kernels
 int launch_tail_s3t(const TailS3Args& a, int B, hipStream_t st) {
+    pw_route_clear();
     if (a.cs <= 0 || (a.cs & 63) || a.cs < (a.P + 63) / 64 * 64 || a.P < 64 || !a.w16b || a.cout_live > 24 || !a.spec || !a.enc_img || a.T * a.F != a.P) return RTFS_ERR_ARG;
     if ((size_t)256 * a.cs * 4 >= ((size_t)1 << 31)) return RTFS_ERR_ARG;
     if (rtfs_set_max_lds((const void*)tail_s3t_kernel, F_LDS) != RTFS_OK) return RTFS_ERR_LAUNCH;
     const int tps = cdiv(a.P, F_NT / 64 * 64), ntiles = tps * B;
     const int grid = ntiles < 256 ? ntiles : 256;  // one resident workgroup per CU
+    pw_route_add(PwRouteJob{PW_FAM_TAIL, 64, 256, 0, 0, 0, 0, a.K, tps, ntiles, grid, a.tile_ctr != nullptr});
     hipLaunchKernelGGL(tail_s3t_kernel, dim3(grid), dim3(F_NT), F_LDS, st, a, ntiles, tps);
     return rtfs_launch_status();
 }

@@ -33,6 +33,19 @@ struct PwArgs {
     int caf_T = 0, caf_F = 0, caf_Tv = 0;
 };
 
+// What the pointwise launchers (k_pw.hip, k_pw16.hip, k_pwr.hip, k_pws.hip, k_b2b.hip, k_bnh.hip, k_s3f.hip) chose on their last call from
+// this thread (host side only; rtfs_debug_pw_f32 hands it to tests/test_hip_pw_edges.py, which asserts the route every case is meant to take).
+// Every launcher clears the record on entry and appends one job per kernel it launches, so a refusal leaves n == 0.
+enum PwFamily { PW_FAM_F32 = 1, PW_FAM_PW16 = 2, PW_FAM_PWS = 3, PW_FAM_RES2 = 4, PW_FAM_B2B = 5, PW_FAM_B2B4 = 6, PW_FAM_HEAD4 = 7,
+                PW_FAM_PWR = 8, PW_FAM_BN_HEAD = 9, PW_FAM_TAIL = 10 };
+// cin / cout / pro / epi: the template form (0 where the kernel has none); caf: CAF prologue; am: a1_mode (B2B: 1); mode: PWR MODE, PWS HAS_X2,
+// BN_HEAD WRES, TAIL K; tps: tiles per sample; ntiles = tps * B; grid: workgroups launched; counter: 1 = tiles from the counter word, 0 = static stride
+struct PwRouteJob { int family, cin, cout, pro, epi, caf, am, mode, tps, ntiles, grid, counter; };
+struct PwRoute { int n; PwRouteJob job[2]; };
+const PwRoute& pw_route_last();
+void pw_route_clear();
+void pw_route_add(const PwRouteJob& j);
+
 int launch_stft(const float* wav, float* spec, int B, int L, int T, hipStream_t st);
 int launch_enc_conv(const float* spec, const float* w, float* a0, double* stats, int B, int C, int T, int F, size_t cs,
                     size_t bs, hipStream_t st);
