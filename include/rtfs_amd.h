@@ -146,6 +146,11 @@ size_t rtfs_separator_workspace_bytes(int B, int L, int Tv);
  * HBM-bound kernels of one part run beside the latency-bound sweeps of another (batch 32: 14.2 -> 13.0 ms with n = 2).  Results per mixture
  * do not depend on it.  Call it before rtfs_separator_workspace_bytes: the workspace layout follows the setting. */
 int rtfs_set_batch_split(int n);
+/* Route of the RTFS block's steps 15-17 (process-wide).  0 (default): by size - where a 64-channel full-resolution tensor of the call exceeds
+ * the 256 MB memory-side cache (256e6 bytes; batch 31 at 2 s), fusion 0's output xf0 is not written: two launches rebuild it from c0 ("15 + 16": statistics of the concat
+ * layer's local conv, "15 + 17": the apply) in place of the three that write it, read it for the statistic and read it again; 1: always the
+ * three launches; 2: the two passes wherever their launcher takes the shape (tests and A/B runs).  RTFS_ERR_ARG outside 0..2. */
+int rtfs_set_dw_two_pass(int mode);
 /* The same option PER CALL (re-entrant: two host threads can pick different schedules): split = 1 .. 8 parts for this call, 0 = the process
  * default above.  The workspace query and the forward call must be given the same value. */
 size_t rtfs_separator_workspace_bytes_ex(int B, int L, int Tv, int split);
@@ -394,7 +399,9 @@ int rtfs_debug_gemm_f32(int kind, const float* A, const float* B, float* C, int 
  * RTFS_ERR_ARG "not eligible, fall back" answers of the fused launchers stay visible).  It zeroes no statistics: the caller does.
  *   op 0 stride-1 conv (nconv / in_affine / mode), 1 the three-job low-resolution launch (two descriptions: the 4-conv job, the folded
  *   1-conv job), 2 stride-2 + pool beside a MODE 1 statistics pass (two descriptions), 3 stride-2 + pool, 4 g = p0 + gLN(c1),
- *   5 the same-size combine gLN(l) * sigmoid(gLN(gate)) + gLN(emb).
+ *   5 the same-size combine gLN(l) * sigmoid(gLN(gate)) + gLN(emb), 6 / 7 two TFAR layers without the tensor between them (two descriptions:
+ *   the first layer as op 0 takes it with in_affine, mode 2 and no addend - out[] unused; the second as op 0 takes its statistics pass (6:
+ *   w[0], stats_out[0]) or its apply with addend == the first's x (7: w[0], out[0], the folds) - x unused; TH and rev are the second's).
  * One conv description is 35 device pointers, 14 ints and 4 doubles (a second one follows the first in each array):
  *   ptrs  0 x | 1 in_stats 2 in_gamma 3 in_beta | 4-7 w[k] | 8-11 bias[k] | 12-15 out[k] | 16-19 stats_out[k] | 20 loc_stats 21 loc_gamma
  *         22 loc_beta | 23 gate 24 gate_stats 25 gate_gamma 26 gate_beta | 27 emb 28 emb_stats 29 emb_gamma 30 emb_beta | 31 addend
@@ -406,7 +413,8 @@ int rtfs_debug_gemm_f32(int kind, const float* A, const float* B, float* C, int 
  * op 5: ptrs l, gate, emb, l_stats, gate_stats, emb_stats, l_gamma, l_beta, gate_gamma, gate_beta, emb_gamma, emb_beta, out; ints B, C, HW;
  *       dbls inv_count.
  * route (host ints, route_cap >= 33): route[0] = jobs launched (0 after a refusal), then per job family (1 one-column stride-1, 2 packed
- * stride-1, 3 three-job launch, 4 packed stride-2, 5 one-column stride-2, 6 stride-2 + statistics launch, 7 g_form, 8 g_combine), nconv,
+ * stride-1, 3 three-job launch, 4 packed stride-2, 5 one-column stride-2, 6 stride-2 + statistics launch, 7 g_form, 8 g_combine, 9 two
+ * TFAR layers in one launch: nconv 2, mode 1 = statistics pass / 2 = apply pass), nconv,
  * in_affine, mode, var (bit 0 addend, 1 shared gathers, 2 combined input, 3 row mapping, 4 whole-row mapping), effective TH, gx, gy.
  * Refused: RTFS_ERR_ARG (null array, short array, unknown op, B / C / H / W < 1) before any launcher runs. */
 int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, int n_ints, const double* dbls, int n_dbls, int* route,

@@ -374,6 +374,22 @@ int block_head(const BlockPack& p, const float* x, const float* x_res, int B, in
     return RTFS_OK;
 }
 
+// Route of steps 15-17 (block_body): 0 = by size (two passes without xf0 where a 64-channel full-resolution tensor of the call exceeds
+// DW_TWO_PASS_BYTES), 1 = always the three launches, 2 = two passes wherever launch_dw_two_pass takes the shape.  Process-wide
+// (rtfs_set_dw_two_pass); it exists so that tests and A/B runs reach both routes at any size.
+// The size: the two passes trade xf0's write and two re-reads for a second evaluation of fusion 0, so they pay where that traffic goes to
+// DRAM: past the 256 MB memory-side cache (decimal on purpose: batch 32 at 2 s is 265.3e6 bytes per tensor, the case the route was built
+// for, and below 2^28).  Same-process A/B of the two routes, 2 s, forward ms three launches -> two passes: batch 8 (66 MB per tensor)
+// 3.014 -> 3.048, 16 (133 MB) 5.235 -> 5.188, 24 (199 MB) 7.359 -> 7.265, 32 9.551 -> 9.419; but bench.py against the parent commit at
+// batch 16 with the threshold at 128 MB: 5.197-5.205 -> 5.196-5.224, nothing - so the threshold stays at the cache size (NOTES.md).
+static std::atomic<int> g_dw_two_pass{0};
+#ifndef RTFS_DW2P_TH_A  // band heights of the two passes (compile-time switches for A/B builds, as DW1P_RQ in k_dw.hip)
+#define RTFS_DW2P_TH_A 64
+#endif
+#ifndef RTFS_DW2P_TH_B
+#define RTFS_DW2P_TH_B 64
+#endif
+constexpr size_t DW_TWO_PASS_BYTES = 256u * 1000u * 1000u;
 // steps 2-17: everything between the projection (x_enc, residual in the workspace) and `expanded`
 int block_body(const BlockPack& p, int B, int T, int F, const BlockWs& w, hipStream_t st, bool zero_stats = true) {
     const int Tp = T / 2, Fp = F / 2;
@@ -385,6 +401,7 @@ int block_body(const BlockPack& p, int B, int T, int F, const BlockWs& w, hipStr
     // 17 213 -> 204, stride-2 pass 118 -> 103 with 12 output rows; 10.51 -> 10.35 ms per forward).  The statistics passes (one pair of f64 atomics
     // per workgroup) and the low-resolution launches are better off with 64 (measured: 62 -> 65 / 70 us and 122 -> 131 us with shorter bands).
     constexpr int TH_A = 24, TH_B = 24, TH_C = 12, TH_G = 64, TH_S = 64;
+    constexpr int TH_2A = RTFS_DW2P_TH_A, TH_2B = RTFS_DW2P_TH_B;  // the two-pass route of steps 15-17: statistics pass / write pass
     // (the separator gives every block application its own, already zeroed slots: one memset per call instead of one per block - 6 us each on
     // the chain, 1 % of a batch-1 forward)
     if (zero_stats && hipMemsetAsync(w.stats, 0, sizeof(double) * W::NSTAT * w.Bfull * 2, st) != hipSuccess) return RTFS_ERR_LAUNCH;
@@ -520,41 +537,55 @@ int block_body(const BlockPack& p, int B, int T, int F, const BlockWs& w, hipStr
     d0in.x = w.c0;
     d0in.in_stats = w.st(W::S_C0, B); d0in.in_inv_count = icF; d0in.in_gamma = p.ds0_g; d0in.in_beta = p.ds0_be;
     d0in.C = CH; d0in.H = T; d0in.W = F; d0in.TH = 64; d0in.Hg = Tp; d0in.Wg = Fp; d0in.cs = w.cs;
-    {  // 15. xf0 = gLN(conv(d0)) * sigmoid(gLN(G0))^ + gLN(E0)^                              fusion.py:58-67
-        DwArgs a = d0in;
-        a.w[0] = p.fus0.loc_w;
-        a.loc_stats = w.st(W::S_L0, B); a.loc_inv_count = icF; a.loc_gamma = p.fus0.loc_g; a.loc_beta = p.fus0.loc_b;
-        a.gate = w.G0; a.gate_stats = w.st(W::S_G0, B); a.gate_gamma = p.fus0.gate_g; a.gate_beta = p.fus0.gate_b;
-        a.emb = w.E0; a.emb_stats = w.st(W::S_E0, B); a.emb_gamma = p.fus0.emb_g; a.emb_beta = p.fus0.emb_b;
-        a.g_inv_count = icG;
-        a.out[0] = w.xf0;
-        a.TH = TH_B;
-        CHECK(launch_dw_s1(a, 1, true, 2, B, st));
-    }
+    // Steps 15-17.  xf0 = fusion 0's output is only read by the concat layer's local conv: for its statistics (16), then for the apply (17).
+    DwArgs f0 = d0in;  // 15. xf0 = gLN(conv(d0)) * sigmoid(gLN(G0))^ + gLN(E0)^                               fusion.py:58-67
+    f0.w[0] = p.fus0.loc_w;
+    f0.loc_stats = w.st(W::S_L0, B); f0.loc_inv_count = icF; f0.loc_gamma = p.fus0.loc_g; f0.loc_beta = p.fus0.loc_b;
+    f0.gate = w.G0; f0.gate_stats = w.st(W::S_G0, B); f0.gate_gamma = p.fus0.gate_g; f0.gate_beta = p.fus0.gate_b;
+    f0.emb = w.E0; f0.emb_stats = w.st(W::S_E0, B); f0.emb_gamma = p.fus0.emb_g; f0.emb_beta = p.fus0.emb_b;
+    f0.g_inv_count = icG;
     DwArgs xin;  // common: read xf0
     xin.x = w.xf0;
     xin.C = CH; xin.H = T; xin.W = F; xin.TH = 64; xin.Hg = Tp; xin.Wg = Fp; xin.cs = w.cs;
-    {  // 16. concat layer local_embedding conv on xf0: statistics only
-        DwArgs a = xin;
-        a.w[0] = p.cat0.loc_w;
-        a.stats_out[0] = w.st(W::S_L2, B);
-        a.rev = 1;  // xf0 was just written front to back by step 15 (see step 3)
-        a.TH = TH_S;
-        CHECK(launch_dw_s1(a, 1, false, 1, B, st));
+    DwArgs s16 = xin;  // 16. concat layer local_embedding conv on xf0: statistics only
+    s16.w[0] = p.cat0.loc_w;
+    s16.stats_out[0] = w.st(W::S_L2, B);
+    DwArgs s17 = xin;  // 17. expanded = InjectionMultiSum(xf0, xf1) + d0                                      tdanet.py:125
+    s17.w[0] = p.cat0.loc_w;
+    s17.loc_stats = w.st(W::S_L2, B); s17.loc_inv_count = icF; s17.loc_gamma = p.cat0.loc_g; s17.loc_beta = p.cat0.loc_b;
+    s17.gate = w.G2; s17.gate_stats = w.st(W::S_G2, B); s17.gate_gamma = p.cat0.gate_g; s17.gate_beta = p.cat0.gate_b;
+    s17.emb = w.E2; s17.emb_stats = w.st(W::S_E2, B); s17.emb_gamma = p.cat0.emb_g; s17.emb_beta = p.cat0.emb_b;
+    s17.g_inv_count = icG;
+    s17.addend = w.c0; s17.add_stats = w.st(W::S_C0, B); s17.add_inv_count = icF; s17.add_gamma = p.ds0_g; s17.add_beta = p.ds0_be;
+    s17.out[0] = w.expanded;
+    // Two-pass route (large calls: DW_TWO_PASS_BYTES above): both readers rebuild xf0 from c0 instead of reading it (launch_dw_two_pass:
+    // "15 + 16" reads c0 and writes only the statistics, "15 + 17" reads c0 and writes `expanded`; xf0 is not written).  Smaller calls keep
+    // the three launches.  Pass A walks front to back and pass B back to front, so B starts on the tail of c0 that A read last.  Band heights
+    // (same-process A/B at batch 32, forward ms against the three launches' 9.51-9.55): A 64 / B 24 9.45, 64 / 32 9.41, 64 / 48 9.35 (three
+    // launches 9.45 in that run), 64 / 64 9.37 and 9.42, 64 / 84 9.40, 64 / 128 9.49, 128 / 64 9.41, 32 / 24 9.44: the write pass wants long
+    // bands, every band recomputes five xf0 rows of halo.
+    const int two_pass = g_dw_two_pass.load();
+    if (two_pass == 2 || (two_pass == 0 && (size_t)B * CH * w.cs * sizeof(float) > DW_TWO_PASS_BYTES)) {
+        s16.TH = TH_2A;
+        s16.rev = 0;
+        const int rc = launch_dw_two_pass(f0, s16, 0, B, st);
+        if (rc == RTFS_OK) {  // (a shape pass A takes, pass B takes too: the conditions are the same)
+            s17.TH = TH_2B;
+            s17.rev = 1;
+            const int rc2 = launch_dw_two_pass(f0, s17, 1, B, st);
+            return rc2 == RTFS_ERR_ARG ? RTFS_ERR_SHAPE : rc2;
+        }
+        if (rc != RTFS_ERR_ARG) return rc;
     }
-    {  // 17. expanded = InjectionMultiSum(xf0, xf1) + d0                                     tdanet.py:125
-        DwArgs a = xin;
-        a.w[0] = p.cat0.loc_w;
-        a.loc_stats = w.st(W::S_L2, B); a.loc_inv_count = icF; a.loc_gamma = p.cat0.loc_g; a.loc_beta = p.cat0.loc_b;
-        a.gate = w.G2; a.gate_stats = w.st(W::S_G2, B); a.gate_gamma = p.cat0.gate_g; a.gate_beta = p.cat0.gate_b;
-        a.emb = w.E2; a.emb_stats = w.st(W::S_E2, B); a.emb_gamma = p.cat0.emb_g; a.emb_beta = p.cat0.emb_b;
-        a.g_inv_count = icG;
-        a.addend = w.c0; a.add_stats = w.st(W::S_C0, B); a.add_inv_count = icF; a.add_gamma = p.ds0_g; a.add_beta = p.ds0_be;
-        a.out[0] = w.expanded;
-        a.rev = 1;
-        a.TH = TH_B;
-        CHECK(launch_dw_s1(a, 1, false, 2, B, st));
-    }
+    f0.out[0] = w.xf0;
+    f0.TH = TH_B;
+    CHECK(launch_dw_s1(f0, 1, true, 2, B, st));
+    s16.rev = 1;  // xf0 was just written front to back by step 15 (see step 3)
+    s16.TH = TH_S;
+    CHECK(launch_dw_s1(s16, 1, false, 1, B, st));
+    s17.rev = 1;
+    s17.TH = TH_B;
+    CHECK(launch_dw_s1(s17, 1, false, 2, B, st));
     return RTFS_OK;
 }
 
@@ -1132,6 +1163,12 @@ int rtfs_set_batch_split(int n) {
     g_split.store(n);
     return RTFS_OK;
 }
+// route of the RTFS block's steps 15-17 (block_body): 0 by size, 1 always three launches, 2 two passes wherever the launchers qualify
+int rtfs_set_dw_two_pass(int mode) {
+    if (mode < 0 || mode > 2) return RTFS_ERR_ARG;
+    g_dw_two_pass.store(mode);
+    return RTFS_OK;
+}
 static int separator_parts(int B, int split = 0) {  // split > 0: this call's own setting; 0: the process default (setter, else RTFS_SPLIT, else 1)
     static const int env = getenv("RTFS_SPLIT") ? atoi(getenv("RTFS_SPLIT")) : 0;
     int n = split > 0 ? split : g_split.load();
@@ -1349,7 +1386,7 @@ int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, in
                       int route_cap, void* stream) {
     RTFS_RETURN_IF(!ptrs || !ints || !dbls || !route || route_cap < 1 + 8 * 4, RTFS_ERR_ARG);
     route[0] = 0;
-    const int jobs = op == 1 || op == 2 ? 2 : 1;
+    const int jobs = op == 1 || op == 2 || op == 6 || op == 7 ? 2 : 1;
     int rc;
     if (op >= 0 && op <= 3) {
         RTFS_RETURN_IF(n_ptrs < jobs * DW_DBG_PTRS || n_ints < jobs * DW_DBG_INTS || n_dbls < jobs * DW_DBG_DBLS, RTFS_ERR_ARG);
@@ -1364,6 +1401,12 @@ int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, in
             const DwArgs b = dw_debug_args(ptrs + DW_DBG_PTRS, ints + DW_DBG_INTS, dbls + DW_DBG_DBLS);
             rc = op == 1 ? launch_dw_g3(a, b, B, S(stream)) : launch_dw_s2_stats(a, b, B, S(stream));
         }
+    } else if (op == 6 || op == 7) {  // steps 15 + 16 / 15 + 17 without xf0: the first layer's description, then the second's
+        RTFS_RETURN_IF(n_ptrs < 2 * DW_DBG_PTRS || n_ints < 2 * DW_DBG_INTS || n_dbls < 2 * DW_DBG_DBLS, RTFS_ERR_ARG);
+        RTFS_RETURN_IF(ints[0] < 1 || ints[1] < 1 || ints[2] < 1 || ints[3] < 1, RTFS_ERR_ARG);
+        const DwArgs a = dw_debug_args(ptrs, ints, dbls);
+        const DwArgs b = dw_debug_args(ptrs + DW_DBG_PTRS, ints + DW_DBG_INTS, dbls + DW_DBG_DBLS);
+        rc = launch_dw_two_pass(a, b, op - 6, ints[0], S(stream));
     } else if (op == 4) {
         RTFS_RETURN_IF(n_ptrs < 6 || n_ints < 3 || n_dbls < 1 || ints[0] < 1 || ints[1] < 1 || ints[2] < 1, RTFS_ERR_ARG);
         rc = launch_g_form((const float*)ptrs[0], (const float*)ptrs[1], (const double*)ptrs[2], dbls[0], (const float*)ptrs[3],

@@ -587,6 +587,344 @@ __global__ __launch_bounds__(256, 2) void dw_g3_kernel(DwArgs a0, DwArgs a1, DwA
     else dw1p_body<1, true, 0, V>(a2, a2.x, a2.gate, a2.emb, a2.addend, a2.out[0], a2.out[1], a2.out[2], a2.out[3]);
 }
 
+// ---------------------------------------------------------------- two TFAR layers in a row without the tensor between them
+// xf0 = TFAR_0(conv_0(d0)) (dw1p_body MODE 2 on the folded c0) is a pointwise function of conv_0(d0) and two low-resolution gathers, and its
+// only readers are the concat layer's local conv: once for that conv's statistics, once for the apply.  Past the memory-side cache those two
+// reads and the write go to DRAM, so here both readers rebuild xf0 from c0 instead (ROW mapping only: a wave = one 129-column channel row):
+//   PASS 0: c0 -> window 1 -> xf0 rows -> window 2 -> (sum, sumsq) of conv_1(xf0); writes nothing else;
+//   PASS 1: the same up to window 2, then TFAR_1's epilogue with `+ d0` taken from the c0 row the first window held, staged as in dw1p_body.
+// `a` describes the first layer as dw1p_body<1, true, 2, 10> takes it (its out[] is not used), `c2` the second as <1, false, 1> / <1, false, 2, 11>
+// take it (its x is not used; its addend must be a.x: there is no second c0 stream).  Window 1 is dw1p_body's register window, expression by
+// expression, so an xf0 value is the value that kernel stores.  Window 2 lives in a per-wave LDS ring of four xf0 rows (as registers the
+// second window measured 196 VGPRs): a row slot is [0 | columns 0..128 | 0 0], so lane p reads its five tap columns 2p - 1 .. 2p + 3 at
+// floats 2p .. 2p + 4 and the zero columns left and right of the image are stored zeros; xf0 rows above and below the image are stored as
+// zeros too (the second conv pads xf0, not f(0)).  A band of output rows r0 .. r1-1 takes xf0 rows r0-1 .. r1+1, i.e. c0 rows r0-2 .. r1+3.
+template <int PASS>
+__device__ __forceinline__ void dw2p_body(const DwArgs& a, const DwArgs& c2) {
+    __shared__ double red[8];
+    constexpr int W = 129, XR = 132, RING = 2048;
+    constexpr unsigned W4 = W * 4u;
+    __shared__ __attribute__((aligned(16))) float xring_all[4][4 * XR];
+    __shared__ __attribute__((aligned(16))) unsigned char oring_all[PASS ? 4 : 1][PASS ? RING : 16];
+    const int H = a.H, C = a.C;
+    const DwBlk blk = dw_block(a);
+    if (!blk.ok) return;  // block-uniform (padding of the 1-D launch)
+    const int b = blk.z;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blk.x * 4 + wave;  // (the launcher checks C % 4 == 0)
+    const int r0 = blk.y * a.TH, r1 = min(r0 + a.TH, H);
+    const unsigned pa = (unsigned)c * (unsigned)a.cs * 4u;
+    const unsigned vld = pa + 8u * (unsigned)lane;  // this lane's column pair
+    const unsigned vex = pa + 4u * (unsigned)(W - 1);  // column 128 (one address for the whole wave)
+    const size_t sample = (size_t)b * C * (size_t)a.cs;
+    const BufRsrc xs = buf_rsrc(a.x + sample);
+    const BufRsrc os = buf_rsrc(PASS ? c2.out[0] + sample : a.x);
+    // gathers: as dw1p_body's shared form (2 Wg <= W: the pair's second source column is the next lane's first; lane 0 gathers column 128's)
+    const size_t gsample = (size_t)b * C * a.Hg * a.Wg;
+    const BufRsrc gs = buf_rsrc(a.gate + gsample), es = buf_rsrc(a.emb + gsample);
+    const BufRsrc gs2 = buf_rsrc(PASS ? c2.gate + gsample : a.gate), es2 = buf_rsrc(PASS ? c2.emb + gsample : a.emb);
+    const unsigned gpa = (unsigned)c * (unsigned)(a.Hg * a.Wg) * 4u;
+    const unsigned sc0 = min((unsigned)(2 * lane) * (unsigned)a.Wg / (unsigned)W, (unsigned)a.Wg - 1u);
+    const unsigned sc1 = min((unsigned)(2 * lane + 1) * (unsigned)a.Wg / (unsigned)W, (unsigned)a.Wg - 1u);
+    const bool gnext = sc1 != sc0;
+    const unsigned fga = gpa + 4u * (lane == 0 ? min((unsigned)(W - 1) * (unsigned)a.Wg / (unsigned)W, (unsigned)a.Wg - 1u) : sc0);
+    const bool border = r0 < 2 || r1 + 4 > H;  // block-uniform: only these bands ever see an out-of-image c0 row
+    // low-resolution source rows floor(t Hg / H) as incremental quotients, advanced in LOAD order: of xf0 row L - 2 and of output row L - 4
+    const int sA = max(r0 - 1, 0);
+    int qa = (int)(((long long)sA * a.Hg) / H), ra = (int)(((long long)sA * a.Hg) % H);
+    int qb = (int)(((long long)r0 * a.Hg) / H), rb = (int)(((long long)r0 * a.Hg) % H);
+    struct Raw { f32x2 pr; float xe, g0, m0, g2, m2; int tg0, tg2; };  // tg0 / tg2: the gathers' source rows (uniform)
+    auto load_raw = [&](int L) {  // c0 row L with the gathers of xf0 row L - 2 and (PASS 1) of output row L - 4
+        const int tc = L < 0 ? 0 : (L < H ? L : H - 1);
+        Raw r;
+        r.pr = buf_ld2(xs, vld, (unsigned)tc * W4);
+        r.xe = buf_ld1(xs, vex, (unsigned)tc * W4);
+        {
+            const int tg = qa < a.Hg - 1 ? qa : a.Hg - 1;
+            ra += L - 2 >= sA ? a.Hg : 0;
+            const bool wrap = ra >= H;
+            ra -= wrap ? H : 0;
+            qa += wrap ? 1 : 0;
+            const unsigned grow = (unsigned)tg * (unsigned)a.Wg * 4u;
+            r.g0 = buf_ld1(gs, fga, grow);
+            r.m0 = buf_ld1(es, fga, grow);
+            r.tg0 = tg;
+        }
+        r.g2 = r.m2 = 0.f;
+        r.tg2 = 0;
+        if (PASS) {
+            const int tg = qb < a.Hg - 1 ? qb : a.Hg - 1;
+            rb += L - 4 >= r0 ? a.Hg : 0;
+            const bool wrap = rb >= H;
+            rb -= wrap ? H : 0;
+            qb += wrap ? 1 : 0;
+            const unsigned grow = (unsigned)tg * (unsigned)a.Wg * 4u;
+            r.g2 = buf_ld1(gs2, fga, grow);
+            r.m2 = buf_ld1(es2, fga, grow);
+            r.tg2 = tg;
+        }
+        return r;
+    };
+    struct Row { f32x2 p[4]; float xe; };  // a c0 row as the four operand pairs of its taps (dw1p_body)
+    auto complete = [&](int L, const Raw& r) {
+        const float v1 = r.pr.x, v2 = r.pr.y;
+        const float v0 = from_prev_lane(v2), v4 = from_next_lane(v2);
+        float v3 = from_next_lane(v1);
+        v3 = lane == 63 ? r.xe : v3;
+        Row w;
+        w.xe = r.xe;
+        w.p[0] = f32x2{v0, v1};
+        w.p[1] = f32x2{v1, v2};
+        w.p[2] = f32x2{v2, v3};
+        w.p[3] = f32x2{v3, v4};
+        if (border && (L < 0 || L >= H)) {  // uniform
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w.p[j] = f32x2{0.f, 0.f};
+            w.xe = 0.f;
+        }
+        return w;
+    };
+    // ---- start-up: every load the first rows need is requested before the first wait and before the f64 gLN folds below
+    constexpr int RQ = 4;  // rows per trip: the xf0 ring's four slots, so that a row's slot is static
+    constexpr int QD = 2;  // rows in flight per wave
+    Raw st0 = load_raw(r0 - 2), st1 = load_raw(r0 - 1), st2 = load_raw(r0);
+    Raw q[QD];
+#pragma unroll
+    for (int k = 0; k < QD; ++k) q[k] = load_raw(r0 + 1 + k);
+    f32x4 wraw[2][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        wraw[0][i] = *reinterpret_cast<const f32x4*>(a.w[0] + c * 16 + i * 4);
+        wraw[1][i] = *reinterpret_cast<const f32x4*>(c2.w[0] + c * 16 + i * 4);
+    }
+    float isc, ish, lsc, lsh, gsc, gsh, esc, esh;
+    gln_fold(a.in_stats + 2 * b, a.in_inv_count, a.in_gamma[c], a.in_beta[c], isc, ish);
+    gln_fold(a.loc_stats + 2 * b, a.loc_inv_count, a.loc_gamma[c], a.loc_beta[c], lsc, lsh);
+    gln_fold(a.gate_stats + 2 * b, a.g_inv_count, a.gate_gamma[c], a.gate_beta[c], gsc, gsh);
+    gln_fold(a.emb_stats + 2 * b, a.g_inv_count, a.emb_gamma[c], a.emb_beta[c], esc, esh);
+    gsc = first_lane_f(gsc); gsh = first_lane_f(gsh);
+    esc = first_lane_f(esc); esh = first_lane_f(esh);
+    float l2sc = 1.f, l2sh = 0.f, g2sc = 1.f, g2sh = 0.f, e2sc = 1.f, e2sh = 0.f, asc = 1.f, ash = 0.f;
+    if (PASS) {
+        gln_fold(c2.loc_stats + 2 * b, c2.loc_inv_count, c2.loc_gamma[c], c2.loc_beta[c], l2sc, l2sh);
+        gln_fold(c2.gate_stats + 2 * b, c2.g_inv_count, c2.gate_gamma[c], c2.gate_beta[c], g2sc, g2sh);
+        gln_fold(c2.emb_stats + 2 * b, c2.g_inv_count, c2.emb_gamma[c], c2.emb_beta[c], e2sc, e2sh);
+        gln_fold(c2.add_stats + 2 * b, c2.add_inv_count, c2.add_gamma[c], c2.add_beta[c], asc, ash);
+        g2sc = first_lane_f(g2sc); g2sh = first_lane_f(g2sh);
+        e2sc = first_lane_f(e2sc); e2sh = first_lane_f(e2sh);
+        asc = first_lane_f(asc); ash = first_lane_f(ash);
+    }
+    // weight pairs of the first conv: a tap whose column is outside the image has weight 0 (its zero columns are not stored anywhere)
+    f32x2 wp[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int xa = 2 * lane - 1 + j, xb = 2 * lane + j;
+        const bool okA = xa >= 0 && xa < W, okB = xb < W;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            wp[i * 4 + j] = f32x2{okA ? wraw[0][i][j] : 0.f, okB ? wraw[0][i][j] : 0.f};
+            asm volatile("" : "+v"(wp[i * 4 + j]));  // (a pair in registers from here on: summed straight from the selects, the row sums below
+                                                     // become packed adds with op_sel, the form tools/isa_check.py guards against)
+        }
+    }
+    // (the in-image weight sums of a window row: only the border bands take one away from the full sum, so they are formed there, not kept)
+    auto rowsum = [&](int i) { return (wp[i * 4] + wp[i * 4 + 1]) + (wp[i * 4 + 2] + wp[i * 4 + 3]); };
+    const f32x2 wv_full = (rowsum(0) + rowsum(1)) + (rowsum(2) + rowsum(3));
+    const float bv0 = a.bias[0] ? a.bias[0][c] : 0.f, bv1 = c2.bias[0] ? c2.bias[0][c] : 0.f;
+    const f32x2 bias0 = f32x2{bv0, bv0}, bias1 = f32x2{bv1, bv1};
+    const float bias0_e = first_lane_f(bv0), bias1_e = first_lane_f(bv1);
+    // output column 128 meets columns 127 and 128 only (taps 0 and 1 of every window row); its channel is the whole wave's: scalar weights
+    float we0[4], we1[4], rse[4], w2s[4][4];  // (w2s: the second conv's weights, one channel per wave)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        we0[i] = first_lane_f(wraw[0][i][0]);
+        we1[i] = first_lane_f(wraw[0][i][1]);
+        rse[i] = we0[i] + we1[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w2s[i][j] = first_lane_f(wraw[1][i][j]);
+    }
+    const float wve_full = (rse[0] + rse[1]) + (rse[2] + rse[3]);
+    // the xf0 ring: zero columns left and right of every slot once
+    float* const xring = xring_all[wave];
+    if (lane < 4) {
+        xring[lane * XR] = 0.f;
+        xring[lane * XR + W + 1] = 0.f;
+        xring[lane * XR + W + 2] = 0.f;
+    }
+    // PASS 1: the staged store of dw1p_body's row variant (byte positions relative to the channel plane; s0 / s1 = this band's range)
+    unsigned char* const oring = oring_all[PASS ? wave : 0];
+    const unsigned s0 = (unsigned)r0 * W4, s1 = (unsigned)r1 * W4;
+    unsigned chunk = s0 >> 9;  // next 512-byte chunk to leave
+    auto flush = [&](unsigned cidx) {
+        const unsigned cb = cidx << 9, b0 = cb + 8u * (unsigned)lane;
+        const f32x2 v = *reinterpret_cast<const f32x2*>(oring + (cb & (RING - 1)) + 8u * (unsigned)lane);
+        if (cb >= s0 && cb + 512u <= s1) {  // uniform: the whole chunk is this band's
+            buf_st2(os, pa + 8u * (unsigned)lane, cb, v);
+        } else {  // a band's first / last chunk: the other bytes belong to the neighbouring band's wave
+            if (b0 >= s0 && b0 + 4u <= s1) buf_st1(os, pa + 8u * (unsigned)lane, cb, v.x);
+            if (b0 + 4u >= s0 && b0 + 8u <= s1) buf_st1(os, pa + 8u * (unsigned)lane + 4u, cb, v.y);
+        }
+    };
+    auto stage = [&](int t, f32x2 y, float ye) {
+        const unsigned pos = (unsigned)t * W4 + 8u * (unsigned)lane;
+        *reinterpret_cast<float*>(oring + (pos & (RING - 1))) = y.x;
+        *reinterpret_cast<float*>(oring + ((pos + 4u) & (RING - 1))) = y.y;
+        if (lane == 63) *reinterpret_cast<float*>(oring + ((pos + 8u) & (RING - 1))) = ye;  // column 128 follows lane 63's pair
+        const unsigned end = (unsigned)(t + 1) * W4;
+        while (((chunk + 1u) << 9) <= end) {  // uniform
+            flush(chunk);
+            ++chunk;
+        }
+    };
+    // The pair's gate = sigmoid(gLN(G)^) and embedding = gLN(E)^ from the row's gathers, as dw1p_body's shared form builds them.  Two things
+    // that kernel computes again are taken from what is there: column 128's source column is that of column 127 (the launcher checks it), so
+    // its gate and embedding are lane 63's .y, the same expression on the same operands; and a source row serves Hg-to-H consecutive output
+    // rows (two on the block's path), so the pair is rebuilt only when the source row changes - the same values, fewer exp2 / rcp.
+    auto lane63_f = [](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); };
+    auto gate_emb = [&](float gv, float mv, float sc_g, float sh_g, float sc_e, float sh_e, f32x2& gate, f32x2& emb) {
+        float g0 = gv, m0 = mv;
+        float gn = from_next_lane(gv), mn = from_next_lane(mv);
+        const float ge = lane0_f(gv), me = lane0_f(mv);  // column 128's source column, gathered by lane 0
+        g0 = lane == 0 ? gn : g0;  // lane 0's own source column is lane 1's
+        m0 = lane == 0 ? mn : m0;
+        gn = lane == 63 ? ge : gn;  // the last pair's second source column is column 128's
+        mn = lane == 63 ? me : mn;
+        const float g1 = gnext ? gn : g0, m1 = gnext ? mn : m0;
+        gate = f32x2{sigmoidf_(fmaf(g0, sc_g, sh_g)), sigmoidf_(fmaf(g1, sc_g, sh_g))};
+        emb = f32x2{fmaf(m0, sc_e, sh_e), fmaf(m1, sc_e, sh_e)};
+    };
+    f32x2 gateA = {0.f, 0.f}, embA = {0.f, 0.f}, gateB = {0.f, 0.f}, embB = {0.f, 0.f};
+    int rowA = -1, rowB = -1;  // source rows gateA / embA and gateB / embB were built from
+    constexpr bool KEEP_GATES = PASS == 1;  // (the statistics pass sits at its 128 registers: keeping the first layer's pair there spills)
+    // xf0 row u (both columns of the pair, and column 128) from c0 rows u-1 .. u+2: dw1p_body's do_row for <1, true, 2, 10>, stored to the ring
+    auto xf0_row = [&](int u, int slot, const Row& w0, const Row& w1, const Row& w2, const Row& w3, const Raw& e) {
+        f32x2 accA = w0.p[0] * wp[0], accB = w2.p[0] * wp[8];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            accA = w0.p[j] * wp[j] + accA;
+            accB = w2.p[j] * wp[8 + j] + accB;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            accA = w1.p[j] * wp[4 + j] + accA;
+            accB = w3.p[j] * wp[12 + j] + accB;
+        }
+        f32x2 acc = accA + accB;
+        float ea = fmaf(w0.xe, we1[0], w0.p[1].y * we0[0]), eb = fmaf(w2.xe, we1[2], w2.p[1].y * we0[2]);
+        ea = fmaf(w1.xe, we1[1], fmaf(w1.p[1].y, we0[1], ea));
+        eb = fmaf(w3.xe, we1[3], fmaf(w3.p[1].y, we0[3], eb));
+        float acce = ea + eb;
+        f32x2 wv = wv_full;
+        float wve = wve_full;
+        if (border) {
+            if (u - 1 < 0) { wv -= rowsum(0); wve -= rse[0]; }
+            if (u + 1 >= H) { wv -= rowsum(2); wve -= rse[2]; }
+            if (u + 2 >= H) { wv -= rowsum(3); wve -= rse[3]; }
+        }
+        acc = acc * isc + wv * ish;
+        acce = fmaf(acce, isc, wve * ish);
+        acc += bias0;
+        acce += bias0_e;
+        if (!KEEP_GATES || e.tg0 != rowA) {  // uniform
+            gate_emb(e.g0, e.m0, gsc, gsh, esc, esh, gateA, embA);
+            rowA = e.tg0;
+        }
+        f32x2 y = (acc * lsc + lsh) * gateA + embA;
+        float ye = fmaf(fmaf(acce, lsc, lsh), lane63_f(gateA.y), lane63_f(embA.y));
+        if (border && (u < 0 || u >= H)) {  // uniform: the second conv pads xf0 itself
+            y = f32x2{0.f, 0.f};
+            ye = 0.f;
+        }
+        float* const rp = xring + slot * XR + 1 + 2 * lane;
+        rp[0] = y.x;
+        rp[1] = y.y;
+        if (lane == 63) rp[2] = ye;
+    };
+    f32x2 s2 = {0.f, 0.f}, ss2 = {0.f, 0.f};
+    // output row t of the second conv from the ring's four slots (rows t-1 .. t+2 in slots k0 .. k0+3 mod 4); d = c0 row t (PASS 1: + d0)
+    auto out_row = [&](int t, int k0, const Raw& e, f32x2 dpr, float dxe) {
+        // plain FMAs on scalar weights (the ring's zero columns are the padding): the second conv keeps no weight pairs in vector registers
+        float v[4][5];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float* const rp = xring + ((k0 + i) & 3) * XR + 2 * lane;
+            const f32x2 lo = *reinterpret_cast<const f32x2*>(rp), hi = *reinterpret_cast<const f32x2*>(rp + 2);
+            v[i][0] = lo.x; v[i][1] = lo.y; v[i][2] = hi.x; v[i][3] = hi.y; v[i][4] = rp[4];
+        }
+        // four independent chains: window rows 0-1 and 2-3 of either column
+        float a0 = v[0][0] * w2s[0][0], a1 = v[0][1] * w2s[0][0], b0 = v[2][0] * w2s[2][0], b1 = v[2][1] * w2s[2][0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            a0 = fmaf(v[0][j], w2s[0][j], a0); a1 = fmaf(v[0][j + 1], w2s[0][j], a1);
+            b0 = fmaf(v[2][j], w2s[2][j], b0); b1 = fmaf(v[2][j + 1], w2s[2][j], b1);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            a0 = fmaf(v[1][j], w2s[1][j], a0); a1 = fmaf(v[1][j + 1], w2s[1][j], a1);
+            b0 = fmaf(v[3][j], w2s[3][j], b0); b1 = fmaf(v[3][j + 1], w2s[3][j], b1);
+        }
+        f32x2 acc = f32x2{a0 + b0, a1 + b1};
+        // column 128 meets columns 127 and 128: lane 63's v[i][2], v[i][3] (every lane computes it, lane 63's is the one that counts)
+        float ea = fmaf(v[0][3], w2s[0][1], v[0][2] * w2s[0][0]), eb = fmaf(v[2][3], w2s[2][1], v[2][2] * w2s[2][0]);
+        ea = fmaf(v[1][3], w2s[1][1], fmaf(v[1][2], w2s[1][0], ea));
+        eb = fmaf(v[3][3], w2s[3][1], fmaf(v[3][2], w2s[3][0], eb));
+        float acce = ea + eb;
+        acc += bias1;
+        acce += bias1_e;
+        if (!PASS) {
+            s2 += acc;
+            ss2 = acc * acc + ss2;
+            const float em = lane == 63 ? acce : 0.f;
+            s2.x += em;
+            ss2.x = fmaf(em, em, ss2.x);
+            return;
+        }
+        if (e.tg2 != rowB) {  // uniform
+            gate_emb(e.g2, e.m2, g2sc, g2sh, e2sc, e2sh, gateB, embB);
+            rowB = e.tg2;
+        }
+        f32x2 y = (acc * l2sc + l2sh) * gateB + embB;
+        y += f32x2{fmaf(dpr.x, asc, ash), fmaf(dpr.y, asc, ash)};
+        float ye = fmaf(fmaf(acce, l2sc, l2sh), lane63_f(gateB.y), lane63_f(embB.y));
+        ye += fmaf(dxe, asc, ash);
+        stage(t, y, ye);
+    };
+    Row win[3];
+    win[0] = complete(r0 - 2, st0);
+    win[1] = complete(r0 - 1, st1);
+    win[2] = complete(r0, st2);
+    f32x2 dpr = {0.f, 0.f};  // c0 row u - 2 (its own pair and column 128): the `+ d0` of output row u - 2
+    float dxe = 0.f;
+    // RQ xf0 rows per trip, fully unrolled: xf0 row u goes to slot k, and output row u - 2 reads rows u-3 .. u from slots k+1 .. k+4 (mod 4)
+    for (int u = r0 - 1; u < r1 + 2; u += RQ) {
+#pragma unroll
+        for (int k = 0; k < RQ; ++k) {
+            const Raw e = q[k % QD];
+            const Row n = complete(u + k + 2, e);
+            if (u + k < r1 + 2) {  // uniform
+                xf0_row(u + k, k & 3, win[0], win[1], win[2], n, e);
+                __builtin_amdgcn_wave_barrier();  // (a lane reads what its neighbours stored: the stores stay in front of the loads)
+                if (u + k - 2 >= r0) out_row(u + k - 2, (k + 1) & 3, e, dpr, dxe);
+                __builtin_amdgcn_wave_barrier();
+            }
+            q[k % QD] = load_raw(u + k + 2 + QD);
+            dpr = win[0].p[1];
+            dxe = win[0].xe;
+            win[0] = win[1];
+            win[1] = win[2];
+            win[2] = n;
+        }
+    }
+    if (PASS) {
+        if ((chunk << 9) < s1) flush(chunk);  // the band's last, partial chunk
+    } else {
+        block_stats_atomic(s2.x + s2.y, ss2.x + ss2.y, red, c2.stats_out[0] + 2 * b);
+    }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256, PASS ? 3 : 4) void dw2p_kernel(DwArgs a, DwArgs c2) { dw2p_body<PASS>(a, c2); }
+
 // ---------------------------------------------------------------- stride-2 pad-1 4x4 + adaptive average pool
 // Reads d0 = gLN(c0) through the fold; writes c1 (pre-norm conv output, +stats) and p0 = adaptive_avg_pool2d(d0)
 // at the conv's output resolution (Ho = H/2, Wo = W/2).  The pool window of output (i,j) is
@@ -1077,6 +1415,40 @@ int launch_dw_s1(const DwArgs& a_, int nconv, bool in_affine, int mode, int B, h
     if (mode == 2 && nconv == 1 && in_affine) return launch_dw_s1_t<1, true, 2>(a, B, st);
     if (mode == 2 && nconv == 1 && !in_affine) return launch_dw_s1_t<1, false, 2>(a, B, st);
     return RTFS_ERR_ARG;
+}
+
+// Steps 15 + 16 (pass 0) / 15 + 17 (pass 1) of a block without xf0 (dw2p_body).  `first` is step 15's description (out[] unused), `second` step
+// 16's / 17's (x unused); band height and walk direction are the second's.  RTFS_ERR_ARG before any launch = not this launcher's shape: the
+// caller runs the three launches.
+int launch_dw_two_pass(const DwArgs& first, const DwArgs& second, int pass, int B, hipStream_t st) {
+    route_clear();
+    DwArgs a = first;
+    const DwArgs& c = second;
+    if (pass < 0 || pass > 1 || B < 1 || a.W != 129 || a.C < 4 || a.C % 4 != 0 || a.H < 1 || a.Hg < 1 || a.Wg < 1 || c.TH < 1) return RTFS_ERR_ARG;
+    if (c.C != a.C || c.H != a.H || c.W != a.W || c.Hg != a.Hg || c.Wg != a.Wg || c.cs != a.cs) return RTFS_ERR_ARG;
+    if (a.cs && a.cs < a.H * a.W) return RTFS_ERR_ARG;
+    if (!a.cs) a.cs = a.H * a.W;
+    if ((size_t)a.C * a.cs * 4 >= ((size_t)1 << 31)) return RTFS_ERR_ARG;  // 32-bit lane offsets
+    // the gather geometry of launch_dw_s1's row route
+    if (!(nearest_is_integer_quotient(a.Hg, a.H) && nearest_is_integer_quotient(a.Wg, a.W))) return RTFS_ERR_ARG;
+    if (!(2 * a.Wg <= a.W && (a.W - 1) * a.Wg / a.W == (a.W - 2) * a.Wg / a.W && 2 * a.Wg / a.W == 0)) return RTFS_ERR_ARG;
+    if (!a.x || !a.in_stats || !a.in_gamma || !a.in_beta || !a.w[0] || !a.loc_stats || !a.loc_gamma || !a.loc_beta || !a.gate || !a.gate_stats ||
+        !a.gate_gamma || !a.gate_beta || !a.emb || !a.emb_stats || !a.emb_gamma || !a.emb_beta || a.addend || !c.w[0])
+        return RTFS_ERR_ARG;
+    if (pass == 0 && !c.stats_out[0]) return RTFS_ERR_ARG;
+    if (pass == 1 && (!c.out[0] || c.addend != a.x || !c.add_stats || !c.add_gamma || !c.add_beta || !c.loc_stats || !c.loc_gamma || !c.loc_beta ||
+                      !c.gate || !c.gate_stats || !c.gate_gamma || !c.gate_beta || !c.emb || !c.emb_stats || !c.emb_gamma || !c.emb_beta))
+        return RTFS_ERR_ARG;
+    a.gx = a.C / 4;
+    a.TH = band_rows(c.TH, a.H, a.gx, B, pass ? 768 : 320);
+    a.gy = cdiv(a.H, a.TH);
+    a.nblk = a.gx * a.gy * B;
+    a.rev = c.rev;
+    a.blk0 = a.job_stride = a.job_off = 0;
+    route_add(DW_FAM_2P, 2, 1, pass ? 2 : 1, pass ? 11 : 10, a.TH, a.gx, a.gy);
+    if (pass) hipLaunchKernelGGL(dw2p_kernel<1>, dim3((a.nblk + 7) / 8 * 8), dim3(256), 0, st, a, c);
+    else hipLaunchKernelGGL(dw2p_kernel<0>, dim3((a.nblk + 7) / 8 * 8), dim3(256), 0, st, a, c);
+    return rtfs_launch_status();
 }
 
 int launch_dw_g3(const DwArgs& conv4, const DwArgs& aff1, int B, hipStream_t st) {

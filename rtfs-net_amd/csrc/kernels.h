@@ -219,7 +219,7 @@ struct GCombineArgs {
 // the route every case is meant to take: a shape that silently falls to the one-column kernel must not pass for coverage of the packed one).
 // Every launcher clears the record on entry and appends one job per kernel job it launches, so a refusal leaves n == 0.
 enum DwFamily { DW_FAM_S1 = 1, DW_FAM_1P = 2, DW_FAM_G3 = 3, DW_FAM_S2X = 4, DW_FAM_S2_POOL = 5, DW_FAM_S2_STATS = 6, DW_FAM_G_FORM = 7,
-                DW_FAM_G_COMBINE = 8 };
+                DW_FAM_G_COMBINE = 8, DW_FAM_2P = 9 };
 struct DwRouteJob { int family, nconv, in_affine, mode, var, TH, gx, gy; };  // TH, gx, gy: the effective band height and logical grid
 struct DwRoute { int n; DwRouteJob job[4]; };
 const DwRoute& dw_route_last();
@@ -231,6 +231,9 @@ int launch_dw_g3(const DwArgs& conv4, const DwArgs& aff1, int B, hipStream_t st)
 int launch_dw_s2_pool(const DwArgs& a, int B, hipStream_t st);
 // the stride-2 + pool pass and a statistics-only pass (MODE 1, input fold) over the SAME input in one launch; RTFS_ERR_ARG = not eligible
 int launch_dw_s2_stats(const DwArgs& s2, const DwArgs& stats, int B, hipStream_t st);
+// two TFAR layers in a row without the tensor between them (k_dw.hip, dw2p_body): pass 0 = statistics of the second layer's conv, pass 1 = the
+// second layer's apply.  RTFS_ERR_ARG before any launch = the shape is not this launcher's
+int launch_dw_two_pass(const DwArgs& first, const DwArgs& second, int pass, int B, hipStream_t st);
 int launch_g_form(const float* p0, const float* c1, const double* st1, double inv_count, const float* gamma,
                   const float* beta, float* g, int B, int C, int HW, hipStream_t st);
 int launch_g_combine(const GCombineArgs& a, int B, hipStream_t st);
