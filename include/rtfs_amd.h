@@ -448,6 +448,23 @@ int rtfs_debug_dw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, in
 int rtfs_debug_pw_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, int n_ints, const double* dbls, int n_dbls, int* route,
                       int route_cap, void* stream);
 
+/* The inference attention family's three launchers (k_attn.hip) one at a time, exposed for tests (tests/test_hip_attn_edges.py).  It fills
+ * RowCanArgs / AttnArgs from the flat description (the Q/K/V group table by the helper attention() itself uses), calls ONE production
+ * launcher and returns the launcher's status unchanged (launch_attn_core's RTFS_ERR_SHAPE past 512 keys stays visible).
+ *   op 0 launch_row_can_qkv:  x, wt (64, 96), bias (96), slope (12), gamma / beta (96, 64) -> q, k (B,4,T,256), v (B,4,T,1024)
+ *   op 1 launch_attn_core:    q, k, v -> out (B,64,T,64); dbls[0] = score scale, 0 = the 1/16 of the model
+ *   As between the production launches, v holds 64 V (rtfs_debug_attn_vscale(); an exact power of two): op 0 writes it so, op 1 reads it so.
+ *   op 2 launch_row_can_proj: x (the core's output, always channel-major), res, wt (64, 64), bias (64), slope (1), gamma / beta (64, 64) -> out
+ *   ptrs (11)  0 x | 1 res | 2 wt 3 bias 4 slope 5 gamma 6 beta | 7 q 8 k 9 v | 10 out       (a pointer its op does not use is ignored)
+ *   ints (3)   0 B 1 T 2 cl (op 0: x is channel-last (B,T,64 f,64 c); op 2: res is)
+ *   dbls (1)   0 scale (op 1)
+ * route (host ints, route_cap >= 8): route[0] = kernels launched (0 after a refusal), then family (1 Q/K/V rows, 2 core, 3 projection rows),
+ * cl, frames per workgroup (core: 0), grid x, grid y, dynamic LDS bytes (rows: 0), (b, head) pairs (rows: 0).
+ * Refused: RTFS_ERR_ARG (null or short array, a null pointer the op uses, unknown op, B < 1, T < 1) before any launcher runs. */
+int rtfs_debug_attn_f32(int op, void* const* ptrs, int n_ptrs, const int* ints, int n_ints, const double* dbls, int n_dbls, int* route,
+                        int route_cap, void* stream);
+double rtfs_debug_attn_vscale(void);
+
 /* Diagnostic build of the dual-path sweep with s_memtime stamps at phase boundaries (profiling aid only).
  * x, out: (B, 64, R, Ls) with sequences along the last axis; stamps: DEVICE u64 [ceil(B*R/seqs_per_wg)][16]. */
 int rtfs_debug_sweep_stamps(const float* x, const float* pack, float* out, int B, int R, int Ls, unsigned long long* stamps,

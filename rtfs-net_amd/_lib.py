@@ -117,6 +117,8 @@ SIGNATURES = {
     "rtfs_debug_gemm_f32": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "rtfs_debug_dw_f32": (_i, [_i, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
     "rtfs_debug_pw_f32": (_i, [_i, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
+    "rtfs_debug_attn_f32": (_i, [_i, _p, _i, _p, _i, _p, _i, _p, _i, _p]),
+    "rtfs_debug_attn_vscale": (C.c_double, []),
     "rtfs_debug_sweep_stamps": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     "rtfs_selftest_mfma_f16": (_i, [_p, _p, _p, _p]),
     "rtfs_selftest_nearest_index": (_i, [_p, _i, _p, _p, _p, _p]),

@@ -271,6 +271,13 @@ int dualpath(const DpPack& p, const float* x, float* out, int B, int T, int F, i
 
 // ---------------------------------------------------------------- attention
 // x: (B,64,T,64), or channel-last (B,T,64,64) with `cl` (the RTFS block's route from the time sweep); out (B,64,T,64) either way
+// the LayerNorm group table of the Q/K/V rows (also filled by rtfs_debug_attn_f32): channel order Q_h (4 each), K_h (4 each), V_h (16 each)
+static void qkv_groups(RowCanArgs& a) {
+    a.ngroups = 12;
+    for (int g = 0; g <= 12; ++g) a.group_start[g] = g <= 8 ? 4 * g : 32 + 16 * (g - 8);
+    for (int g = 0; g < 12; ++g)
+        for (int o_ = a.group_start[g]; o_ < a.group_start[g + 1]; ++o_) a.group_of[o_] = (unsigned char)g;
+}
 int attention(const AttnPack& p, const float* x, float* out, int B, int T, float* q, float* k, float* v, float* o, hipStream_t st, bool cl = false) {
     RowCanArgs a;
     a.x = x;
@@ -280,11 +287,8 @@ int attention(const AttnPack& p, const float* x, float* out, int B, int T, float
     a.slope = p.qkv_slope;
     a.gamma = p.qkv_gamma;
     a.beta = p.qkv_beta;
-    a.ngroups = 12;
-    // channel order: Q_h (4 each), K_h (4 each), V_h (16 each)
-    for (int g = 0; g <= 12; ++g) a.group_start[g] = g <= 8 ? 4 * g : 32 + 16 * (g - 8);
-    for (int g = 0; g < 12; ++g)
-        for (int o_ = a.group_start[g]; o_ < a.group_start[g + 1]; ++o_) a.group_of[o_] = (unsigned char)g;
+    qkv_groups(a);
+    a.vscale = ATT_VSC;
     a.T = T;
     a.q = q;
     a.k = k;
@@ -297,6 +301,7 @@ int attention(const AttnPack& p, const float* x, float* out, int B, int T, float
     c.out = o;
     c.T = T;
     c.scale = 1.0f / 16.0f;  // 1/sqrt(E*F) = 1/sqrt(4*64)
+    c.vscale = ATT_VSC;
     CHECK(launch_attn_core(c, B, st));
     RowCanArgs r;
     r.x = o;
@@ -1531,6 +1536,63 @@ int rtfs_debug_pw_f32(int op, void* const* p, int n_ptrs, const int* n, int n_in
     }
     return rc;
 }
+
+// The attention family's three launchers (k_attn.hip) by op code, from a flat description (layout: include/rtfs_amd.h).  Tests only: it fills
+// RowCanArgs / AttnArgs, calls one production launcher and hands back its status and route record.
+namespace {
+constexpr int ATT_DBG_PTRS = 11, ATT_DBG_INTS = 3, ATT_DBG_DBLS = 1;
+}  // namespace
+
+int rtfs_debug_attn_f32(int op, void* const* p, int n_ptrs, const int* n, int n_ints, const double* d, int n_dbls, int* route, int route_cap,
+                        void* stream) {
+    RTFS_RETURN_IF(!p || !n || !d || !route || route_cap < 1 + 7, RTFS_ERR_ARG);
+    route[0] = 0;
+    RTFS_RETURN_IF(n_ptrs < ATT_DBG_PTRS || n_ints < ATT_DBG_INTS || n_dbls < ATT_DBG_DBLS, RTFS_ERR_ARG);
+    const int B = n[0], T = n[1];
+    RTFS_RETURN_IF(op < 0 || op > 2 || B < 1 || T < 1, RTFS_ERR_ARG);
+    int rc;
+    if (op == 1) {
+        RTFS_RETURN_IF(!p[7] || !p[8] || !p[9] || !p[10], RTFS_ERR_ARG);
+        AttnArgs c;
+        c.q = (const float*)p[7]; c.k = (const float*)p[8]; c.v = (const float*)p[9]; c.out = (float*)p[10];
+        c.T = T;
+        c.scale = d[0] != 0.0 ? (float)d[0] : 1.0f / 16.0f;
+        c.vscale = ATT_VSC;
+        rc = launch_attn_core(c, B, S(stream));
+    } else {
+        RTFS_RETURN_IF(!p[0] || !p[2] || !p[3] || !p[4] || !p[5] || !p[6], RTFS_ERR_ARG);
+        RowCanArgs a;
+        a.x = (const float*)p[0];
+        a.cl = n[2] != 0;
+        a.wt = (const float*)p[2]; a.bias = (const float*)p[3]; a.slope = (const float*)p[4]; a.gamma = (const float*)p[5]; a.beta = (const float*)p[6];
+        a.T = T;
+        if (op == 0) {
+            RTFS_RETURN_IF(!p[7] || !p[8] || !p[9], RTFS_ERR_ARG);
+            qkv_groups(a);
+            a.vscale = ATT_VSC;
+            a.q = (float*)p[7]; a.k = (float*)p[8]; a.v = (float*)p[9];
+            rc = launch_row_can_qkv(a, B, S(stream));
+        } else {
+            RTFS_RETURN_IF(!p[1] || !p[10], RTFS_ERR_ARG);
+            a.ngroups = 1;
+            a.group_start[0] = 0;
+            a.group_start[1] = 64;
+            a.res = (const float*)p[1];
+            a.out = (float*)p[10];
+            rc = launch_row_can_proj(a, B, S(stream));
+        }
+    }
+    const AttnRoute& r = attn_route_last();
+    route[0] = r.n;
+    for (int i = 0; i < r.n; ++i) {
+        const AttnRouteJob& j = r.job[i];
+        const int v[7] = {j.family, j.cl, j.rpw, j.gx, j.gy, j.lds, j.npairs};
+        for (int k = 0; k < 7; ++k) route[1 + 7 * i + k] = v[k];
+    }
+    return rc;
+}
+
+double rtfs_debug_attn_vscale(void) { return ATT_VSC; }
 
 // ------------------------------------------------------------ self test
 int rtfs_selftest_mfma_f16(const float* A, const float* B, float* D, void* stream) {

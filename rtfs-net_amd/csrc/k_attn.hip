@@ -1,7 +1,7 @@
 // TF-domain self-attention (reference MultiHeadSelfAttention2D, src/models/layers/attention.py:76-189).
 //   row_can_kernel<96>   per (b,t) row: all heads' Q/K/V ConvActNorm = 1x1 conv -> PReLU -> LN over (E,F)
 //                        (conv_layers.py:196-205, normalizations.py:20-41), written head-major
-//                        Q,K (B,H,T,E*F)  V (B,H,T,Cv*F)     (attention.py:156-168)
+//                        Q,K (B,H,T,E*F)  V (B,H,T,Cv*F)     (attention.py:156-168); V is stored times RowCanArgs::vscale (ATT_VSC, kernels.h)
 //   attn_core_kernel     softmax_keys(Q K^T / sqrt(E*F)) V on the f32 matrix cores  (attention.py:171-175)
 //   row_can_kernel<64>   attn_concat_proj ConvActNorm + residual (attention.py:182-184)
 #include "common.h"
@@ -64,8 +64,9 @@ __global__ __launch_bounds__(256, 2) void row_can_kernel(RowCanArgs a) {
     // one workgroup per CU, and every latency of its serial per-frame phases - GEMM, two reductions, stores - was exposed)
     __shared__ float gam_s[NOUT][AF], bet_s[NOUT][AF];
     for (int i = tid; i < NOUT * AF; i += 256) {
-        gam_s[0][i] = a.gamma[i];
-        bet_s[0][i] = a.beta[i];
+        const float vs = NOUT == 96 && i >= 32 * AF ? a.vscale : 1.f;  // V rows: out * vscale = fmaf(y rstd, gamma vscale, beta vscale), exact
+        gam_s[0][i] = a.gamma[i] * vs;
+        bet_s[0][i] = a.beta[i] * vs;
     }
     const int t0 = blockIdx.x * a.rpw;
     const int nrows = min(a.rpw, T - t0);
@@ -279,6 +280,7 @@ __global__ __launch_bounds__(256) void attn_core_kernel(AttnArgs a) {
     }
     __syncthreads();
     // ---- O = P V : 32 column tiles of 32, wave w owns tiles [8w, 8w+8) in two groups of 4
+    const float oscale = 1.f / (ATT_PSC * a.vscale);  // P was scaled by ATT_PSC here, V by vscale where it was written
     for (int grp = 0; grp < 2; ++grp) {
         f32x16 o[4];
 #pragma unroll
@@ -328,7 +330,7 @@ __global__ __launch_bounds__(256) void attn_core_kernel(AttnArgs a) {
                 const int qq = q0 + (q & 3) + 8 * (q >> 2) + 4 * h;
                 if (qq < T)
                     *reinterpret_cast<f32x4*>(a.out + (((size_t)b * 64 + hd * 16 + c) * T + qq) * AF + f) =
-                        f32x4{o[0][q], o[1][q], o[2][q], o[3][q]} * (1.f / ATT_PSC);
+                        f32x4{o[0][q], o[1][q], o[2][q], o[3][q]} * oscale;
             }
         }
     }
@@ -345,10 +347,18 @@ static int rcan_rows(int T, int B) {
     const int r = (int)((long)T * B / 512);
     return r < 1 ? 1 : (r > RCAN_ROWS ? RCAN_ROWS : r);
 }
+static thread_local AttnRoute g_attn_route = {};
+const AttnRoute& attn_route_last() { return g_attn_route; }
+static void attn_route_set(const AttnRouteJob& j) {
+    g_attn_route.job[0] = j;
+    g_attn_route.n = 1;
+}
 int launch_row_can_qkv(const RowCanArgs& a_, int B, hipStream_t st) {
+    g_attn_route.n = 0;
     RowCanArgs a = a_;
     a.rpw = rcan_rows(a.T, B);
     if (a.ngroups != 12 || a.group_start[8] != 32 || a.group_start[12] != 96) return RTFS_ERR_SHAPE;  // Q_h x4, K_h x4 (4 ch), V_h x4 (16 ch)
+    attn_route_set(AttnRouteJob{ATT_FAM_QKV, a.cl != 0, a.rpw, cdiv(a.T, a.rpw), B, 0, 0});
     if (a.cl)
         hipLaunchKernelGGL((row_can_kernel<96, true>), dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
     else
@@ -356,9 +366,11 @@ int launch_row_can_qkv(const RowCanArgs& a_, int B, hipStream_t st) {
     return rtfs_launch_status();
 }
 int launch_row_can_proj(const RowCanArgs& a_, int B, hipStream_t st) {
+    g_attn_route.n = 0;
     RowCanArgs a = a_;
     a.rpw = rcan_rows(a.T, B);
     if (a.ngroups != 1) return RTFS_ERR_SHAPE;
+    attn_route_set(AttnRouteJob{ATT_FAM_PROJ, a.cl != 0, a.rpw, cdiv(a.T, a.rpw), B, 0, 0});
     if (a.cl)
         hipLaunchKernelGGL((row_can_kernel<64, true>), dim3(cdiv(a.T, a.rpw), B), dim3(256), 0, st, a);
     else
@@ -366,11 +378,14 @@ int launch_row_can_proj(const RowCanArgs& a_, int B, hipStream_t st) {
     return rtfs_launch_status();
 }
 int launch_attn_core(const AttnArgs& a, int B, hipStream_t st) {
+    g_attn_route.n = 0;
     if (a.T < 1 || a.T > 512) return RTFS_ERR_SHAPE;  // (the score tile: 66 KB at 512 keys)
     const size_t lds = attn_core_lds_bytes(a.T);
     if (rtfs_set_max_lds((const void*)attn_core_kernel, lds) != RTFS_OK) return RTFS_ERR_LAUNCH;
     AttnArgs a2 = a;
     a2.npairs = B * 4;
-    hipLaunchKernelGGL(attn_core_kernel, dim3(cdiv(a2.npairs, 8) * 8 * cdiv(a.T, 32)), dim3(256), lds, st, a2);
+    const int grid = cdiv(a2.npairs, 8) * 8 * cdiv(a.T, 32);
+    attn_route_set(AttnRouteJob{ATT_FAM_CORE, 0, 0, grid, 1, (int)lds, a2.npairs});
+    hipLaunchKernelGGL(attn_core_kernel, dim3(grid), dim3(256), lds, st, a2);
     return rtfs_launch_status();
 }

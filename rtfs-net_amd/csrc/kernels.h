@@ -278,6 +278,7 @@ struct RowCanArgs {
     unsigned char group_of[96] = {0};
     int T = 0;
     int rpw = 0;  // frames per workgroup (set by the launcher: 8, fewer for small batches)
+    float vscale = 1.f;  // NOUT == 96: V is stored times this power of two, folded into the V modules' LayerNorm affine (exact); see ATT_VSC
     float *q = nullptr, *k = nullptr, *v = nullptr;  // NOUT == 96
     const float* res = nullptr;                       // NOUT == 64: residual
     float* out = nullptr;
@@ -287,12 +288,26 @@ struct AttnArgs {
     float* out = nullptr;  // (B,64,T,64), channel = head*16 + c
     int T = 0;
     float scale = 0.f;
+    float vscale = 1.f;  // v holds vscale * V (a power of two); the output is divided by it
     int npairs = 0;  // B * heads, set by the launcher
 };
 int launch_row_can_qkv(const RowCanArgs& a, int B, hipStream_t st);
 int launch_row_can_proj(const RowCanArgs& a, int B, hipStream_t st);
 int launch_attn_core(const AttnArgs& a, int B, hipStream_t st);
 size_t attn_core_lds_bytes(int T);
+// The power of two attention() stores V times.  The core splits V into f16 hi + lo unscaled otherwise, and the low part of an element
+// below 2^-3 is an f16 subnormal (quantum 2^-24): an absolute floor of 2^-25 that a single-key row (T = 1: the output is V[0]) carries
+// whole - 1.5e-5 of an element of 2e-3 (tests/test_hip_attn_edges.py).  Times 64 the floor is 2^-31; f16 overflows from |V| = 1023 on
+// (a LayerNorm output over 1024 elements is at most 32 |gamma| + |beta|).  P is scaled by 2^12 in the kernel for the same reason.
+constexpr float ATT_VSC = 64.f;
+// What the three attention launchers chose on their last call from this thread (host side only; rtfs_debug_attn_f32 hands it to
+// tests/test_hip_attn_edges.py, which asserts the route every case is meant to take).  Every launcher clears the record on entry and
+// appends one job per kernel it launches, so a refusal leaves n == 0.
+enum AttnFamily { ATT_FAM_QKV = 1, ATT_FAM_CORE = 2, ATT_FAM_PROJ = 3 };
+// cl: channel-last form (rows); rpw: frames per workgroup (rows; core 0); gx, gy: grid; lds: dynamic LDS bytes (core; rows 0); npairs: B * heads (core)
+struct AttnRouteJob { int family, cl, rpw, gx, gy, lds, npairs; };
+struct AttnRoute { int n; AttnRouteJob job[1]; };
+const AttnRoute& attn_route_last();
 
 // CAF
 struct CafArgs {

@@ -27,14 +27,15 @@ if os.environ.get("RTFS_POISON_WS", "") not in ("", "0"):
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FORWARD = ["test_hip_parity.py", "test_hip_sweep_layout.py", "test_hip_long.py", "test_hip_long_separator.py", "test_hip_sizes.py",
-           "test_hip_dw_edges.py", "test_hip_pw_edges.py"]
+           "test_hip_dw_edges.py", "test_hip_pw_edges.py", "test_hip_attn_edges.py"]
 # (test_hip_nearest.py: forward and training cases in one file; its forward cases also run on both patterns in-process)
 TRAINING = ["test_hip_training.py", "test_hip_training_full.py", "test_hip_training_edges.py", "test_hip_training_conv_edges.py",
             "test_hip_nearest.py"]
 # unpoisoned wall time of each file as one child on an MI355X (s; test_hip_training_full.py: its pytest time); the child's limit is
 # about three times that, and at least two minutes
 WALL_S = {"test_hip_parity.py": 48, "test_hip_sweep_layout.py": 41, "test_hip_long.py": 9, "test_hip_long_separator.py": 53,
-          "test_hip_sizes.py": 17, "test_hip_training.py": 28, "test_hip_training_full.py": 190, "test_hip_training_edges.py": 110, "test_hip_training_conv_edges.py": 12, "test_hip_nearest.py": 10, "test_hip_dw_edges.py": 10, "test_hip_pw_edges.py": 26}
+          "test_hip_sizes.py": 17, "test_hip_training.py": 28, "test_hip_training_full.py": 190, "test_hip_training_edges.py": 110, "test_hip_training_conv_edges.py": 12, "test_hip_nearest.py": 10, "test_hip_dw_edges.py": 10, "test_hip_pw_edges.py": 26,
+          "test_hip_attn_edges.py": 47}
 CHILDREN = [("nan", f) for f in FORWARD + TRAINING] + [("big", f) for f in FORWARD]
 ABNORMAL = (124, 134, 137, 139)
 _stopped = []  # the child that ended abnormally, if one did
