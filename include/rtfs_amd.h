@@ -511,6 +511,52 @@ size_t rtfs_stoi_workspace_bytes(int B, int L, int fs);
 int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept_frames,
                   void* stream);
 
+/* Scoring R recordings of different lengths in one pooled pass (metrics.stoi_many / sdr_many, ALLMetricsTracker.update_many): the
+ * scoring half of AVNet.separate_many.  Recording r is L_r samples: mix (L_r), clean and est contiguous (n_src, L_r), each a separate
+ * allocation at any 4-byte alignment, reached through DEVICE arrays of R device pointers (dword loads only, no packing copy).
+ * rtfs_score_many_plan (host only, no device touched; the single place with the arithmetic): L (R lengths, host), n_src 1 .. 4, fs
+ *   16000 | 10000 -> ws_bytes (may be NULL) and the RTFS_SCORE_COLS * (R + 1) int32 words of `table`, column-major: word
+ *   table[c * (R + 1) + r] is column c of recording r, and row R closes the prefix sums.  Columns:
+ *     0 L        the recording's length              row R: n_src   (rows R of columns 0 .. 3 record what the plan was made for;
+ *     1 L10      its length at 10 kHz, ceil(5 L / 8) row R: fs       the launches compare them with their own arguments)
+ *     2 K0       its frames before silence removal   row R: R
+ *     3 Fmax     K0 - 1, the most STFT frames        row R: 0
+ *     4 rs_off   where its 10 kHz copies start in the two resample regions, floats (all 0 at fs = 10000: nothing is resampled)
+ *     5 fr_off   where its K0 frame energies / kept-frame indices start, elements
+ *     6 bd_off   where its (Fmax, 15) band values start, frames
+ *     7 rs0      its first resample chunk  (ceil(L10 / 1024) chunks; 0 at fs = 10000)
+ *     8 bg0      its first band frame group (ceil(Fmax / 4) groups)
+ *     9 cc0      its first correlation chunk = its first STOI partial (ceil(15 (Fmax - 29) / 256) chunks; 0 when Fmax < 30)
+ *    10 mc0      its first moment chunk = its first moment partial (ceil(L / 4096) chunks of 4096 samples from ITS OWN start)
+ *   Columns 4 .. 10 are exclusive prefix sums over the recordings, row R their totals.  The four flat work lists (7 .. 10) are the launch
+ *   grids: workgroup w finds its recording by bisection (the last r with first[r] <= w), so no workgroup exists for padding up to the
+ *   longest recording.  The workspace is RAGGED: nine regions (two resample copies, energies, kept indices, R kept counts, two band
+ *   arrays, STOI partials, moment partials of 2 (2 n_src + 1) + n_src^2 + n_src doubles), each ONE array over all recordings sized by a
+ *   total of row R and rounded up to 256 bytes, so ws_bytes grows with sum(L_r), not R * max(L_r), and stays within the sum of
+ *   rtfs_stoi_workspace_bytes(1, L_r, fs) plus the moment partials (the only padding is 9 * 255 bytes per CALL, none per recording).
+ *   Refused: -4 for a NULL L or table, R < 1, n_src outside 1 .. 4, fs not 16000 / 10000; -1 for a length rtfs_stoi_f32 refuses
+ *   (L < 410 at 16 kHz, < 257 at 10 kHz, > 2^26) or a total past 2^31 - 1.
+ * Both launches below take `table` = the DEVICE copy of those words (4-byte aligned; upload it together with the pointer arrays in ONE
+ *   host-to-device copy) and `plan` = the HOST words the planner wrote, from which they size their grids and verify ws_bytes (-2) and
+ *   that R, n_src and fs are the plan's (-4); NULL pointers are -4.  All refusals come before any launch.  Neither synchronises,
+ *   allocates or calls back; both share one workspace (disjoint regions).  Because of the table upload a call is NOT capturable.
+ * rtfs_stoi_many_f32: classic STOI of the R pairs (cleans[r][0 .. L_r), ests[r][0 .. L_r)): the five stages of rtfs_stoi_f32 with the
+ *   recording's own L, L10, K0 and Fmax -> d (R) float32, kept_frames (R) int32.  A recording's arithmetic, lane assignment and fold
+ *   order are those of rtfs_stoi_f32 with B = 1 (shared device code), so d[r] and kept_frames[r] are BIT-EQUAL to that call.
+ * rtfs_sdr_many_f32: the metrics tracker's four PIT figures.  One pass accumulates in float64 the first and second moments of the
+ *   2 n_src + 1 signals and the cross moments <est_i, clean_j>, <mix, clean_j>, one partial per moment chunk; a second launch folds each
+ *   recording's partials in a fixed order and derives the snr and sisdr pairwise matrices of (est, clean) and (mix stacked n_src times,
+ *   clean) as rtfs_pit_pairwise_sdr_f32 does (zero_mean, take_log, EPS 1e-8), best permutation in itertools order, first minimum.
+ *   -> out (R, 4) float32 in the loss sign [sdr, sdr - baseline, sisnr, sisnr - baseline] and perm (R, n_src) int32 of the (est, clean)
+ *   sisdr search.  The dB figures agree with four rtfs_pit_pairwise_sdr_f32 calls to float64 rounding of the moments, not bit for bit:
+ *   the sums are chunked differently. */
+#define RTFS_SCORE_COLS 11
+int rtfs_score_many_plan(const long long* L, int R, int n_src, int fs, int* table, size_t* ws_bytes);
+int rtfs_stoi_many_f32(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
+                       void* ws, size_t ws_bytes, float* d, int* kept_frames, void* stream);
+int rtfs_sdr_many_f32(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan,
+                      int R, int n_src, int fs, void* ws, size_t ws_bytes, float* out, int* perm, void* stream);
+
 /* Long recordings in overlapping windows on the fused separator (AVNet.separate_long; no reference counterpart: infer_any_video.py:63-86
  * hands a whole track to one forward).  SPF = 640 samples per video frame (16 kHz, 25 fps).  A recording of L samples is cut into N
  * windows of `window` samples every `hop` samples; window n covers samples [n hop, n hop + window) (zeros past L) and video frames

@@ -1627,6 +1627,21 @@ int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, vo
     return launch_stoi(clean, est, B, L, fs, ws, ws_bytes, d, kept_frames, (hipStream_t)stream);
 }
 
+static_assert(SC_COLS == RTFS_SCORE_COLS, "the table columns of kernels.h and rtfs_amd.h");
+int rtfs_score_many_plan(const long long* L, int R, int n_src, int fs, int* table, size_t* ws_bytes) {
+    return score_many_plan(L, R, n_src, fs, table, ws_bytes);
+}
+int rtfs_stoi_many_f32(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
+                       void* ws, size_t ws_bytes, float* d, int* kept_frames, void* stream) {
+    if (!cleans || !ests || !table || !plan || !ws || !d || !kept_frames) return RTFS_ERR_ARG;
+    return launch_stoi_many(cleans, ests, table, plan, R, n_src, fs, ws, ws_bytes, d, kept_frames, (hipStream_t)stream);
+}
+int rtfs_sdr_many_f32(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan,
+                      int R, int n_src, int fs, void* ws, size_t ws_bytes, float* out, int* perm, void* stream) {
+    if (!mixes || !cleans || !ests || !table || !plan || !ws || !out || !perm) return RTFS_ERR_ARG;
+    return launch_sdr_many(mixes, cleans, ests, table, plan, R, n_src, fs, ws, ws_bytes, out, perm, (hipStream_t)stream);
+}
+
 int rtfs_longform_plan(int L, int Tv, int window, int hop, int* N) { return longform_plan(L, Tv, window, hop, N); }
 int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
                             void* stream) {

@@ -16,6 +16,9 @@
 // The DFT runs on the VALU in double, one bin per lane with the twiddle advanced by a complex rotation (no table, no LDS bank conflicts,
 // error ~256 ulp): 212 bins x 256 samples is too small and too oddly shaped (15 unequal bands) for a matrix-core tile to pay, and double
 // keeps weak bands exact next to strong ones.  No atomics: every partial has one writer and is folded in a fixed order.
+// Each stage is a __forceinline__ device body working on ONE row, wrapped twice: by the stoi_*_kernel above for a (B, L) block and by a
+// stoi_many_*_kernel for R recordings of different lengths, whose grid is a flat work list and whose row pointers, L10, K0 and offsets come
+// from score_many_plan's table (rtfs_amd.h).  Same body, same cut of the work, same fold: a recording's result is bit-equal either way.
 #include "common.h"
 #include "kernels.h"
 
@@ -59,11 +62,8 @@ __device__ double bessel_i0(double x) {
     return s;
 }
 
-__global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restrict__ clean, const float* __restrict__ est, int L, int L10,
-                                                            float* __restrict__ xr, float* __restrict__ yr) {
-    __shared__ double taps[2 * RS_HALF + 1];
-    __shared__ double red[4];
-    const int tid = threadIdx.x, b = blockIdx.y;
+// Prologue of the resample kernels: the 581 taps, scaled, into LDS (ends with a barrier).
+__device__ __forceinline__ void resample_taps(double* taps, double* red, int tid) {
     // pystoi _resample_window_oct: kaiser(581, beta) * sinc(t / 8) (its constant factor 2 p fc cancels in h / sum(h))
     const double beta = 0.1102 * (60.0 - 8.7), i0b = bessel_i0(beta);
     double part = 0;
@@ -78,9 +78,12 @@ __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restr
     const double scale = RS_UP / block_sum_256(part, red, tid);  // window = h / sum(h); resample_poly multiplies it by up
     for (int i = tid; i < 2 * RS_HALF + 1; i += 256) taps[i] *= scale;
     __syncthreads();
-    const float* src = (blockIdx.z ? est : clean) + (size_t)b * L;
-    float* dst = (blockIdx.z ? yr : xr) + (size_t)b * L10;
-    const long long n0 = (long long)blockIdx.x * (256 * RS_OUT);
+}
+
+// Outputs [1024 chunk, 1024 chunk + 1024) of one row: src (L) -> dst (L10).
+__device__ __forceinline__ void resample_chunk(const float* __restrict__ src, float* __restrict__ dst, int L, int L10, int chunk,
+                                               const double* taps, int tid) {
+    const long long n0 = (long long)chunk * (256 * RS_OUT);
 #pragma unroll
     for (int r = 0; r < RS_OUT; ++r) {
         const long long n = n0 + r * 256 + tid;
@@ -96,14 +99,19 @@ __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restr
     }
 }
 
-// One workgroup per row: clean frame energies, maximum, mask, kept index list (ascending) and its length.
-__global__ __launch_bounds__(256) void stoi_mask_kernel(const float* __restrict__ xr, int L10, int K0, double* __restrict__ energy,
-                                                        int* __restrict__ kidx, int* __restrict__ kcount) {
+__global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restrict__ clean, const float* __restrict__ est, int L, int L10,
+                                                            float* __restrict__ xr, float* __restrict__ yr) {
+    __shared__ double taps[2 * RS_HALF + 1];
     __shared__ double red[4];
-    __shared__ int wcount[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
-    const float* x = xr + (size_t)b * L10;
-    double* e = energy + (size_t)b * K0;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    resample_taps(taps, red, tid);
+    resample_chunk((blockIdx.z ? est : clean) + (size_t)b * L, (blockIdx.z ? yr : xr) + (size_t)b * L10, L, L10, blockIdx.x, taps, tid);
+}
+
+// One workgroup per row: clean frame energies, maximum, mask, kept index list (ascending) and its length.
+__device__ __forceinline__ void mask_row(const float* __restrict__ x, int K0, double* __restrict__ e, int* __restrict__ ki,
+                                         int* __restrict__ kcount, double* red, int* wcount, int tid) {
+    const int lane = tid & 63, wv = tid >> 6;
     double w[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) w[r] = hann258(lane + 64 * r);
@@ -125,7 +133,6 @@ __global__ __launch_bounds__(256) void stoi_mask_kernel(const float* __restrict_
     if (lane == 0) red[wv] = mx;
     __syncthreads();  // also orders the energy writes above before the reads below (same workgroup)
     mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-    int* ki = kidx + (size_t)b * K0;
     int base = 0;
     for (int f0 = 0; f0 < K0; f0 += 256) {
         const int f = f0 + tid;
@@ -139,26 +146,34 @@ __global__ __launch_bounds__(256) void stoi_mask_kernel(const float* __restrict_
         base += wcount[0] + wcount[1] + wcount[2] + wcount[3];
         __syncthreads();
     }
-    if (tid == 0) kcount[b] = base;
+    if (tid == 0) *kcount = base;
 }
 
-// Band values of reduced frames j = BAND_FPW * blockIdx.x + 0 .. BAND_FPW - 1 of row blockIdx.y (frames j < K - 1 exist).
-__global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict__ xr, const float* __restrict__ yr, int L10, int K0, int Fmax,
-                                                         const int* __restrict__ kidx, const int* __restrict__ kcount,
-                                                         double* __restrict__ xb, double* __restrict__ yb) {
-    __shared__ double sx[SF], sy[SF];
-    __shared__ double px[NBIN], py[NBIN];
-    const int tid = threadIdx.x, b = blockIdx.y;
-    const int F = kcount[b] - 1;
-    const float* x = xr + (size_t)b * L10;
-    const float* y = yr + (size_t)b * L10;
-    const int* ki = kidx + (size_t)b * K0;
+__global__ __launch_bounds__(256) void stoi_mask_kernel(const float* __restrict__ xr, int L10, int K0, double* __restrict__ energy,
+                                                        int* __restrict__ kidx, int* __restrict__ kcount) {
+    __shared__ double red[4];
+    __shared__ int wcount[4];
+    const int b = blockIdx.x;
+    mask_row(xr + (size_t)b * L10, K0, energy + (size_t)b * K0, kidx + (size_t)b * K0, kcount + b, red, wcount, threadIdx.x);
+}
+
+// LDS of a bands workgroup
+struct BandsLds {
+    double sx[SF], sy[SF];
+    double px[NBIN], py[NBIN];
+};
+
+// Band values of reduced frames j = BAND_FPW * group + 0 .. BAND_FPW - 1 of one row (frames j < F = K - 1 exist): x, y the row's 10 kHz
+// signals, ki its kept-frame list, xb / yb its (Fmax, 15) band values.
+__device__ __forceinline__ void bands_group(const float* __restrict__ x, const float* __restrict__ y, const int* __restrict__ ki, int F,
+                                            int group, double* __restrict__ xb, double* __restrict__ yb, BandsLds& lds, int tid) {
+    double *sx = lds.sx, *sy = lds.sy, *px = lds.px, *py = lds.py;
     const double wn = hann258(tid);
     const double wo = hann258(tid < SHOP ? tid + SHOP : tid - SHOP);  // window at the position the neighbouring frame contributes
     double cr = 1, ci = 0, sr = 1, si = 0;
     if (tid < NBIN) sincospi(2.0 * (BIN0 + tid) / 512.0, &si, &sr);  // rotation by -2 pi k / 512 (sign of |X| is irrelevant)
     for (int q = 0; q < BAND_FPW; ++q) {
-        const int j = blockIdx.x * BAND_FPW + q;
+        const int j = group * BAND_FPW + q;
         if (j >= F) break;  // uniform over the workgroup
         // overlap-added reduced signal over [128 j, 128 j + 256): kept frames j - 1 (first half), j, j + 1 (second half)
         const size_t self = (size_t)ki[j] * SHOP + tid;
@@ -201,23 +216,31 @@ __global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict
             const double* p = tid < NBAND ? px : py;
             double s = 0;
             for (int k = kBandEdge[band]; k < kBandEdge[band + 1]; ++k) s += p[k];
-            (tid < NBAND ? xb : yb)[((size_t)b * Fmax + j) * NBAND + band] = sqrt(s);
+            (tid < NBAND ? xb : yb)[(size_t)j * NBAND + band] = sqrt(s);
         }
     }
 }
 
-// One lane per (segment s, band): frames s .. s + 29 of the row's band values; partial sums per workgroup in double.
-__global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict__ xb, const double* __restrict__ yb, int Fmax,
-                                                        const int* __restrict__ kcount, int nchunk, double* __restrict__ partial) {
-    __shared__ double red[4];
-    const int tid = threadIdx.x, b = blockIdx.y;
-    const int J = kcount[b] - 1 - (SEG - 1);  // segments m = 30 .. F'
-    const int p = blockIdx.x * 256 + tid;
+__global__ __launch_bounds__(256) void stoi_bands_kernel(const float* __restrict__ xr, const float* __restrict__ yr, int L10, int K0, int Fmax,
+                                                         const int* __restrict__ kidx, const int* __restrict__ kcount,
+                                                         double* __restrict__ xb, double* __restrict__ yb) {
+    __shared__ BandsLds lds;
+    const int b = blockIdx.y;
+    bands_group(xr + (size_t)b * L10, yr + (size_t)b * L10, kidx + (size_t)b * K0, kcount[b] - 1, blockIdx.x,
+                xb + (size_t)b * Fmax * NBAND, yb + (size_t)b * Fmax * NBAND, lds, threadIdx.x);
+}
+
+// One lane per (segment s, band): frames s .. s + 29 of the row's (Fmax, 15) band values, K kept frames; the sum over the 256 lanes of
+// work-list chunk `chunk` (exact zero past the row's own segments).
+__device__ __forceinline__ double corr_chunk(const double* __restrict__ xb, const double* __restrict__ yb, int K, int chunk, double* red,
+                                             int tid) {
+    const int J = K - 1 - (SEG - 1);  // segments m = 30 .. F'
+    const int p = chunk * 256 + tid;
     double corr = 0;
     if (J > 0 && p < J * NBAND) {
         const int s = p / NBAND, band = p % NBAND;
-        const double* xs = xb + ((size_t)b * Fmax + s) * NBAND + band;
-        const double* ys = yb + ((size_t)b * Fmax + s) * NBAND + band;
+        const double* xs = xb + (size_t)s * NBAND + band;
+        const double* ys = yb + (size_t)s * NBAND + band;
         double xv[SEG], yv[SEG];
         double nx = 0, ny = 0;
 #pragma unroll
@@ -249,23 +272,113 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict
         }
         corr = sxy / ((sqrt(sxx) + eps) * (sqrt(syy) + eps));
     }
-    corr = block_sum_256(corr, red, tid);
+    return block_sum_256(corr, red, tid);
+}
+
+__global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict__ xb, const double* __restrict__ yb, int Fmax,
+                                                        const int* __restrict__ kcount, int nchunk, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const double corr = corr_chunk(xb + (size_t)b * Fmax * NBAND, yb + (size_t)b * Fmax * NBAND, kcount[b], blockIdx.x, red, tid);
     if (tid == 0) partial[(size_t)b * nchunk + blockIdx.x] = corr;
+}
+
+// Folds a row's nchunk partials (lane c % 256 takes partial c, then the block sum): read only when the row has a segment.
+__device__ __forceinline__ void final_row(const double* __restrict__ partial, int nchunk, int K, float* __restrict__ d, int* __restrict__ kept,
+                                          double* red, int tid) {
+    const int J = K - 1 - (SEG - 1);
+    double s = 0;
+    if (J > 0)
+        for (int c = tid; c < nchunk; c += 256) s += partial[c];
+    s = block_sum_256(s, red, tid);
+    if (tid == 0) {
+        *d = J > 0 ? (float)(s / ((double)J * NBAND)) : 1e-5f;  // pystoi returns 1e-5 below 30 frames
+        *kept = K;
+    }
 }
 
 __global__ __launch_bounds__(256) void stoi_final_kernel(const double* __restrict__ partial, int nchunk, const int* __restrict__ kcount,
                                                          float* __restrict__ d, int* __restrict__ kept) {
     __shared__ double red[4];
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const int K = kcount[b], J = K - 1 - (SEG - 1);
-    double s = 0;
-    if (J > 0)
-        for (int c = tid; c < nchunk; c += 256) s += partial[(size_t)b * nchunk + c];
-    s = block_sum_256(s, red, tid);
-    if (tid == 0) {
-        d[b] = J > 0 ? (float)(s / ((double)J * NBAND)) : 1e-5f;  // pystoi returns 1e-5 below 30 frames
-        kept[b] = K;
+    const int b = blockIdx.x;
+    final_row(partial + (size_t)b * nchunk, nchunk, kcount[b], d + b, kept + b, red, threadIdx.x);
+}
+
+// ---------------------------------------------------------------- many recordings of different lengths (score_many_plan's table)
+// Column c of the table is table[c * (R + 1) + r]; row R holds the totals of the offset and work-list columns (rtfs_amd.h).
+
+struct ScoreRec {
+    int r, item;  // recording and the work item's index inside it
+};
+
+// Recording of entry w of a flat work list: the last r with first[r] <= w (first = a work-list column, ascending, first[R] = the total).
+__device__ __forceinline__ ScoreRec score_find(const int* __restrict__ first, int R, int w) {
+    int lo = 0, hi = R;  // invariant: first[lo] <= w < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= w) lo = mid; else hi = mid;
     }
+    return {lo, w - first[lo]};
+}
+
+__global__ __launch_bounds__(256) void stoi_many_resample_kernel(const float* const* __restrict__ cleans, const float* const* __restrict__ ests,
+                                                                 const int* __restrict__ table, int R, float* __restrict__ xr,
+                                                                 float* __restrict__ yr) {
+    __shared__ double taps[2 * RS_HALF + 1];
+    __shared__ double red[4];
+    const int tid = threadIdx.x, R1 = R + 1;
+    resample_taps(taps, red, tid);
+    const ScoreRec w = score_find(table + SC_RS0 * R1, R, blockIdx.x);
+    const size_t off = (size_t)table[SC_RS_OFF * R1 + w.r];
+    resample_chunk((blockIdx.y ? ests : cleans)[w.r], (blockIdx.y ? yr : xr) + off, table[SC_L * R1 + w.r], table[SC_L10 * R1 + w.r], w.item,
+                   taps, tid);
+}
+
+// x / y of recording r at 10 kHz: the resampled copy, or the recording itself at fs = 10000
+__device__ __forceinline__ const float* score_row10(const float* const* __restrict__ rows, const float* __restrict__ res, const int* table,
+                                                    int R1, int r) {
+    return res ? res + (size_t)table[SC_RS_OFF * R1 + r] : rows[r];
+}
+
+__global__ __launch_bounds__(256) void stoi_many_mask_kernel(const float* const* __restrict__ cleans, const float* __restrict__ xr,
+                                                             const int* __restrict__ table, int R, double* __restrict__ energy,
+                                                             int* __restrict__ kidx, int* __restrict__ kcount) {
+    __shared__ double red[4];
+    __shared__ int wcount[4];
+    const int r = blockIdx.x, R1 = R + 1;
+    const size_t fo = (size_t)table[SC_FR_OFF * R1 + r];
+    mask_row(score_row10(cleans, xr, table, R1, r), table[SC_K0 * R1 + r], energy + fo, kidx + fo, kcount + r, red, wcount, threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void stoi_many_bands_kernel(const float* const* __restrict__ cleans, const float* const* __restrict__ ests,
+                                                              const float* __restrict__ xr, const float* __restrict__ yr,
+                                                              const int* __restrict__ table, int R, const int* __restrict__ kidx,
+                                                              const int* __restrict__ kcount, double* __restrict__ xb, double* __restrict__ yb) {
+    __shared__ BandsLds lds;
+    const int R1 = R + 1;
+    const ScoreRec w = score_find(table + SC_BG0 * R1, R, blockIdx.x);
+    const size_t bo = (size_t)table[SC_BD_OFF * R1 + w.r] * NBAND;
+    bands_group(score_row10(cleans, xr, table, R1, w.r), score_row10(ests, yr, table, R1, w.r), kidx + table[SC_FR_OFF * R1 + w.r],
+                kcount[w.r] - 1, w.item, xb + bo, yb + bo, lds, threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void stoi_many_corr_kernel(const double* __restrict__ xb, const double* __restrict__ yb,
+                                                             const int* __restrict__ table, int R, const int* __restrict__ kcount,
+                                                             double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x, R1 = R + 1;
+    const ScoreRec w = score_find(table + SC_CC0 * R1, R, blockIdx.x);
+    const size_t bo = (size_t)table[SC_BD_OFF * R1 + w.r] * NBAND;
+    const double corr = corr_chunk(xb + bo, yb + bo, kcount[w.r], w.item, red, tid);
+    if (tid == 0) partial[blockIdx.x] = corr;
+}
+
+__global__ __launch_bounds__(256) void stoi_many_final_kernel(const double* __restrict__ partial, const int* __restrict__ table, int R,
+                                                              const int* __restrict__ kcount, float* __restrict__ d, int* __restrict__ kept) {
+    __shared__ double red[4];
+    const int r = blockIdx.x, R1 = R + 1;
+    const int c0 = table[SC_CC0 * R1 + r];
+    final_row(partial + c0, table[SC_CC0 * R1 + r + 1] - c0, kcount[r], d + r, kept + r, red, threadIdx.x);
 }
 
 struct StoiDims {
@@ -353,5 +466,109 @@ int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void
         if ((r = rtfs_launch_status()) != RTFS_OK) return r;
     }
     hipLaunchKernelGGL(stoi_final_kernel, dim3(B), dim3(256), 0, st, w.partial, s.nchunk, w.kcount, d, kept);
+    return rtfs_launch_status();
+}
+
+// ---------------------------------------------------------------- many recordings: planner, ragged workspace, launches
+namespace {
+
+// The nine regions of the pooled workspace, sized by the totals in row R of the plan: each region is ONE array over all recordings
+// (recording r's slice starts at its *_OFF / first-entry column), so the size grows with the sums, not with R times the longest.
+size_t score_carve(const int* plan, int R, int n_src, char* base, ScoreManyWs* w) {
+    const int R1 = R + 1;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        off = align_up(off, 256);
+        char* r = base ? base + off : nullptr;
+        off += bytes;
+        return r;
+    };
+    const size_t rs = (size_t)plan[SC_RS_OFF * R1 + R], fr = (size_t)plan[SC_FR_OFF * R1 + R], bd = (size_t)plan[SC_BD_OFF * R1 + R];
+    w->xr = (float*)take(rs * sizeof(float));
+    w->yr = (float*)take(rs * sizeof(float));
+    w->energy = (double*)take(fr * sizeof(double));
+    w->kidx = (int*)take(fr * sizeof(int));
+    w->kcount = (int*)take((size_t)R * sizeof(int));
+    w->xb = (double*)take(bd * NBAND * sizeof(double));
+    w->yb = (double*)take(bd * NBAND * sizeof(double));
+    w->partial = (double*)take((size_t)plan[SC_CC0 * R1 + R] * sizeof(double));
+    w->mom = (double*)take((size_t)plan[SC_MC0 * R1 + R] * score_moments(n_src) * sizeof(double));
+    return off;
+}
+
+}  // namespace
+
+int score_many_plan(const long long* L, int R, int n_src, int fs, int* table, size_t* ws_bytes) {
+    if (!L || !table || R < 1 || n_src < 1 || n_src > 4 || (fs != 16000 && fs != 10000)) return RTFS_ERR_ARG;
+    for (int r = 0; r < R; ++r)
+        if (L[r] < 1 || L[r] > (1 << 26) || stoi_check_args(1, (int)L[r], fs) != RTFS_OK) return RTFS_ERR_SHAPE;
+    const int R1 = R + 1;
+    long long rs_off = 0, fr_off = 0, bd_off = 0, rs0 = 0, bg0 = 0, cc0 = 0, mc0 = 0;
+    for (int r = 0; r <= R; ++r) {
+        const long long tot[7] = {rs_off, fr_off, bd_off, rs0, bg0, cc0, mc0};
+        for (int c = 0; c < 7; ++c) {
+            if (tot[c] > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+            table[(SC_RS_OFF + c) * R1 + r] = (int)tot[c];
+        }
+        if (r == R) break;
+        const StoiDims s = stoi_dims((int)L[r], fs);
+        table[SC_L * R1 + r] = (int)L[r];
+        table[SC_L10 * R1 + r] = s.L10;
+        table[SC_K0 * R1 + r] = s.K0;
+        table[SC_FMAX * R1 + r] = s.Fmax;
+        rs_off += s.resample ? s.L10 : 0;
+        fr_off += s.K0;
+        bd_off += s.Fmax;
+        rs0 += s.resample ? cdiv(s.L10, 256 * RS_OUT) : 0;
+        bg0 += cdiv(s.Fmax, BAND_FPW);
+        cc0 += s.Fmax >= SEG ? s.nchunk : 0;  // below 30 frames the row takes the 1e-5 path and has no correlation chunk
+        mc0 += cdiv((int)L[r], SCORE_MOM_CHUNK);
+    }
+    if (mc0 * score_moments(n_src) > 0x7fffffffLL || bd_off * NBAND > 0x7fffffffLL) return RTFS_ERR_SHAPE;
+    table[SC_L * R1 + R] = n_src;  // row R of the four per-recording columns records what the plan was made for
+    table[SC_L10 * R1 + R] = fs;
+    table[SC_K0 * R1 + R] = R;
+    table[SC_FMAX * R1 + R] = 0;
+    if (ws_bytes) {
+        ScoreManyWs w;
+        *ws_bytes = score_carve(table, R, n_src, nullptr, &w);
+    }
+    return RTFS_OK;
+}
+
+int score_many_carve(const int* plan, int R, int n_src, int fs, void* ws, size_t ws_bytes, ScoreManyWs* w) {
+    if (!plan || !ws || R < 1 || n_src < 1 || n_src > 4 || (fs != 16000 && fs != 10000)) return RTFS_ERR_ARG;
+    const int R1 = R + 1;
+    if (plan[SC_L * R1 + R] != n_src || plan[SC_L10 * R1 + R] != fs || plan[SC_K0 * R1 + R] != R) return RTFS_ERR_ARG;
+    if (score_carve(plan, R, n_src, nullptr, w) > ws_bytes) return RTFS_ERR_WORKSPACE;
+    score_carve(plan, R, n_src, (char*)ws, w);
+    return RTFS_OK;
+}
+
+int launch_stoi_many(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs, void* ws,
+                     size_t ws_bytes, float* d, int* kept, hipStream_t st) {
+    ScoreManyWs w;
+    int r = score_many_carve(plan, R, n_src, fs, ws, ws_bytes, &w);
+    if (r != RTFS_OK) return r;
+    const int R1 = R + 1;
+    const int n_rs = plan[SC_RS0 * R1 + R], n_bg = plan[SC_BG0 * R1 + R], n_cc = plan[SC_CC0 * R1 + R];
+    const float *xr = nullptr, *yr = nullptr;  // fs = 10000: the stages read the recordings themselves
+    if (n_rs > 0) {
+        hipLaunchKernelGGL(stoi_many_resample_kernel, dim3(n_rs, 2), dim3(256), 0, st, cleans, ests, table, R, w.xr, w.yr);
+        if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+        xr = w.xr;
+        yr = w.yr;
+    }
+    hipLaunchKernelGGL(stoi_many_mask_kernel, dim3(R), dim3(256), 0, st, cleans, xr, table, R, w.energy, w.kidx, w.kcount);
+    if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+    if (n_bg > 0) {
+        hipLaunchKernelGGL(stoi_many_bands_kernel, dim3(n_bg), dim3(256), 0, st, cleans, ests, xr, yr, table, R, w.kidx, w.kcount, w.xb, w.yb);
+        if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+    }
+    if (n_cc > 0) {
+        hipLaunchKernelGGL(stoi_many_corr_kernel, dim3(n_cc), dim3(256), 0, st, w.xb, w.yb, table, R, w.kcount, w.partial);
+        if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+    }
+    hipLaunchKernelGGL(stoi_many_final_kernel, dim3(R), dim3(256), 0, st, w.partial, table, R, w.kcount, d, kept);
     return rtfs_launch_status();
 }

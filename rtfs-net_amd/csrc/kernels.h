@@ -374,6 +374,26 @@ int launch_pit_pairwise(const float* est, const float* tgt, int B, int n, int L,
 size_t stoi_workspace_bytes(int B, int L, int fs);
 int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept, hipStream_t st);
 
+// scoring many recordings of different lengths in one pooled pass (k_stoi.hip: planner, workspace, STOI; k_score.hip: the four PIT
+// figures from float64 moments).  `plan` is the HOST table score_many_plan wrote, `table` its device copy (layout: rtfs_amd.h).
+// column c of the table is table[c * (R + 1) + r]; row R holds the totals of the offset and work-list columns
+enum { SC_L, SC_L10, SC_K0, SC_FMAX, SC_RS_OFF, SC_FR_OFF, SC_BD_OFF, SC_RS0, SC_BG0, SC_CC0, SC_MC0, SC_COLS };
+constexpr int SCORE_MOM_CHUNK = 4096;  // samples per moment workgroup, counted from the recording's own start
+// moments of the 2 n + 1 signals (mix, n clean, n estimates): sums, sums of squares, <est_i, clean_j>, <mix, clean_j>
+constexpr int score_moments(int n) { return 2 * (2 * n + 1) + n * n + n; }
+struct ScoreManyWs {
+    float *xr, *yr;
+    double *energy, *xb, *yb, *partial, *mom;
+    int *kidx, *kcount;
+};
+int score_many_plan(const long long* L, int R, int n_src, int fs, int* table, size_t* ws_bytes);
+// checks the plan's own record of (R, n_src, fs) against the call's and the workspace size, then carves: RTFS_ERR_ARG / RTFS_ERR_WORKSPACE
+int score_many_carve(const int* plan, int R, int n_src, int fs, void* ws, size_t ws_bytes, ScoreManyWs* w);
+int launch_stoi_many(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs, void* ws,
+                     size_t ws_bytes, float* d, int* kept, hipStream_t st);
+int launch_sdr_many(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R,
+                    int n_src, int fs, void* ws, size_t ws_bytes, float* out, int* perm, hipStream_t st);
+
 // long recordings in overlapping windows (k_longform.hip): window plan (host), framing of audio + video in one launch, cross-faded overlap-add
 int longform_plan(int L, int Tv, int window, int hop, int* N);
 // K lip tracks per recording (one track: K = 1): the audio window once, video_win (B*N*K, 512, window / SPF), target row (b*N + n)*K + k

@@ -1,18 +1,23 @@
 """Evaluation metrics of the reference on the device: ``pystoi.stoi`` (classic STOI, the version 0.4.1 the reference pins) and
 ``src/metrics/allwrapper.py`` ``ALLMetricsTracker``, same class name, constructor, methods and CSV.  STOI runs in ``librtfs_amd.so``
 (``rtfs_stoi_f32``, ``csrc/k_stoi.hip``); SI-SNR and SNR are the PIT loss kernel the losses use (``rtfs_pit_pairwise_sdr_f32``).
+``stoi_many``, ``sdr_many`` and ``ALLMetricsTracker.update_many`` score R recordings of different lengths in one pooled pass
+(``rtfs_score_many_plan``, ``rtfs_stoi_many_f32``, ``rtfs_sdr_many_f32``; DESIGN.md, "Scoring many recordings of different lengths").
 There is no CPU fallback.  PESQ (ITU-T P.862) is not implemented here: pass a host callable as ``pesq_fn`` (called as the reference
 calls ``pypesq.pesq``: ``pesq_fn(estimate, clean, 16000)`` on numpy rows) or the ``pesq`` column is NaN (and so are its mean and std).
 """
 from __future__ import annotations
 
 import csv
+import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
 from .losses import _pairwise
+
+SCORE_COLS = 11  # RTFS_SCORE_COLS: columns of rtfs_score_many_plan's table (include/rtfs_amd.h)
 
 
 def stoi(clean, estimate, fs=16000, extended=False, return_kept=False):
@@ -41,6 +46,115 @@ def stoi(clean, estimate, fs=16000, extended=False, return_kept=False):
     if one:
         d, kept = d[0], kept[0]
     return (d, kept) if return_kept else d
+
+
+class _ScorePool:
+    """R recordings of different lengths, validated and planned for ``rtfs_stoi_many_f32`` / ``rtfs_sdr_many_f32``: everything that can
+    be refused is refused here, as ValueError naming the recording, before any upload or launch.  ``mixes`` None: STOI only, clean and
+    estimate rows (L_r)|(1,L_r).  Otherwise mix (L_r)|(1,L_r) and clean / estimate (n_src,L_r)."""
+
+    def __init__(self, what, mixes, cleans, estimates, fs, keys=None):
+        try:
+            cleans, estimates = list(cleans), list(estimates)
+            mixes = None if mixes is None else list(mixes)
+            keys = None if keys is None else list(keys)
+        except TypeError:
+            raise ValueError(f"{what}: the recordings must come as sequences of tensors") from None
+        R = len(cleans)
+        counts = [len(s) for s in (mixes, cleans, estimates, keys) if s is not None]
+        if R < 1 or any(c != R for c in counts):
+            raise ValueError(f"{what}: sequences of {counts} entries; need the same number in each, at least 1")
+        if fs not in (16000, 10000):
+            raise ValueError(f"{what}: fs must be 16000 or 10000, got {fs}")
+        n = None
+        for r in range(R):
+            row = (cleans[r], estimates[r]) if mixes is None else (mixes[r], cleans[r], estimates[r])
+            if not all(isinstance(t, torch.Tensor) for t in row):
+                raise ValueError(f"{what}: recording {r} is not made of tensors")
+            if mixes is None:
+                flat = [t for t in row if t.ndim == 1 or (t.ndim == 2 and t.shape[0] == 1)]
+                if len(flat) != 2:
+                    raise ValueError(f"{what}: clean and estimate {r} must be (L) or (1,L); got {[tuple(t.shape) for t in row]}")
+                cleans[r], estimates[r] = (t.reshape(1, -1) for t in row)
+            else:
+                m, c, e = row
+                if not (m.ndim == 1 or (m.ndim == 2 and m.shape[0] == 1)) or c.ndim != 2 or e.ndim != 2:
+                    raise ValueError(f"{what}: recording {r} must be mix (L)|(1,L), clean and estimate (n_src,L); "
+                                     f"got {[tuple(t.shape) for t in row]}")
+                mixes[r] = m.reshape(-1)
+            c, e = cleans[r], estimates[r]
+            n = c.shape[0] if n is None else n
+            if c.shape[0] != n or e.shape[0] != n or not 1 <= n <= 4:
+                raise ValueError(f"{what}: recording {r} has {c.shape[0]} clean and {e.shape[0]} estimated source(s); "
+                                 f"recording 0 has {n} (n_src 1 .. 4, the same everywhere)")
+            if e.shape[1] != c.shape[1] or (mixes is not None and mixes[r].shape[0] != c.shape[1]):
+                lens = [int(t.shape[-1]) for t in row]
+                raise ValueError(f"{what}: recording {r} has lengths {lens}; mix, clean and estimate must be equally long")
+            if any(t.dtype != torch.float32 for t in row):
+                raise ValueError(f"{what}: recording {r} is {[str(t.dtype) for t in row]}; the kernels are float32")
+        lib = _lib.load()
+        lens = [int(c.shape[1]) for c in cleans]
+        self.plan = (C.c_int * (SCORE_COLS * (R + 1)))()
+        nbytes = C.c_size_t(0)
+        if lib.rtfs_score_many_plan((C.c_longlong * R)(*lens), R, n, fs, self.plan, C.byref(nbytes)) != 0:
+            one, scratch = C.c_size_t(0), (C.c_int * (SCORE_COLS * 2))()
+            for r, L in enumerate(lens):
+                if lib.rtfs_score_many_plan((C.c_longlong * 1)(L), 1, n, fs, scratch, C.byref(one)) != 0:
+                    raise ValueError(f"{what}: recording {r} has {L} samples; STOI at fs = {fs} needs "
+                                     f"{410 if fs == 16000 else 257} .. 2^26")
+            raise ValueError(f"{what}: {R} recordings of {sum(lens)} samples need a workspace offset past 2^31 - 1")
+        device = cleans[0].device
+        for r in range(R):
+            row = (cleans[r], estimates[r]) if mixes is None else (mixes[r], cleans[r], estimates[r])
+            if any(t.device != device for t in row):
+                raise ValueError(f"{what}: recording {r} lies on {[str(t.device) for t in row]}, recording 0 on {device}")
+        if device.type != "cuda":
+            raise ValueError(f"{what}: the recordings lie on {device}; the kernels run on the MI355X only (there is no CPU fallback)")
+        self.lib, self.R, self.n, self.fs, self.device, self.keys = lib, R, n, fs, device, keys
+        self.cleans, self.estimates = [c.contiguous() for c in cleans], [e.contiguous() for e in estimates]
+        self.mixes = None if mixes is None else [m.contiguous() for m in mixes]
+        groups = [self.cleans, self.estimates] + ([] if mixes is None else [self.mixes])
+        ptrs = np.array([t.data_ptr() for g in groups for t in g], dtype=np.int64)
+        host = np.concatenate([ptrs.view(np.uint8), np.ctypeslib.as_array(self.plan).view(np.uint8)])
+        self.tab = torch.from_numpy(host).to(device)  # the one host-to-device copy: 2 R | 3 R pointers, then the plan's table
+        base = self.tab.data_ptr()
+        self.p_clean, self.p_est, self.p_mix = (C.c_void_p(base + 8 * R * k) for k in range(3))
+        self.p_table = C.c_void_p(base + 8 * R * len(groups))
+        self.ws = _lib.workspace(nbytes.value, device)
+        self.stream = _lib.stream_of(self.tab)
+
+    def stoi(self):
+        d = _lib.empty(self.R, device=self.device, dtype=torch.float32)
+        kept = _lib.empty(self.R, device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.rtfs_stoi_many_f32(self.p_clean, self.p_est, self.p_table, self.plan, self.R, self.n, self.fs, _lib.ptr(self.ws),
+                                               self.ws.numel(), _lib.ptr(d), _lib.ptr(kept), self.stream), "rtfs_stoi_many_f32")
+        return d, kept
+
+    def sdr(self):
+        out = _lib.empty(self.R, 4, device=self.device, dtype=torch.float32)
+        perm = _lib.empty(self.R, self.n, device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.rtfs_sdr_many_f32(self.p_mix, self.p_clean, self.p_est, self.p_table, self.plan, self.R, self.n, self.fs,
+                                              _lib.ptr(self.ws), self.ws.numel(), _lib.ptr(out), _lib.ptr(perm), self.stream),
+                   "rtfs_sdr_many_f32")
+        return out, perm
+
+
+def stoi_many(cleans, estimates, fs=16000, return_kept=False):
+    """``stoi`` for R recordings of different lengths in one pooled pass: two sequences of R float32 device tensors (L_r)|(1,L_r) -> (R,)
+    float32, and with ``return_kept`` the kept frames (R,) int32.  Entry r is bit-equal to ``stoi(cleans[r], estimates[r], fs)``.  The
+    rows are read where they lie (separate allocations, any 4-byte alignment); one planner call, ONE host-to-device copy of the table
+    and the 2 R row pointers, five launches whose grids are flat work lists, a workspace that grows with sum(L_r).  Because of the
+    upload a call is not capturable in a HIP graph.  ValueError, before the upload, names the offending recording."""
+    d, kept = _ScorePool("stoi_many", None, cleans, estimates, fs).stoi()
+    return (d, kept) if return_kept else d
+
+
+def sdr_many(mixes, cleans, estimates):
+    """The tracker's four PIT figures for R mixtures of different lengths in one pass over the samples: mixes R tensors (L_r)|(1,L_r),
+    cleans / estimates R tensors (n_src,L_r) -> (R,4) float32 in the loss sign [sdr, sdr - baseline, sisnr, sisnr - baseline] (baseline =
+    the mixture stacked n_src times against the clean sources) and the (R,n_src) int32 permutation of the estimate-vs-clean SI-SDR search.
+    Float64 moments, so the figures agree with ``losses._pairwise`` to rounding, not bit for bit.  Not capturable (table upload)."""
+    return _ScorePool("sdr_many", mixes, cleans, estimates, 16000).sdr()
 
 
 class ALLMetricsTracker:
@@ -84,6 +198,21 @@ class ALLMetricsTracker:
         else:
             pesqs = [float("nan")] * B
         self.record(keys, vals, pesqs)
+
+    def update_many(self, mixes, cleans, estimates, keys):
+        """R mixtures of different lengths in one pooled pass (the scoring half of ``separate_many``): mixes R tensors (L_r)|(1,L_r),
+        cleans / estimates R tensors (n_src,L_r), keys R row ids.  One planner call, one table upload, the launches of
+        ``rtfs_sdr_many_f32`` and ``rtfs_stoi_many_f32`` on one workspace, ONE device-to-host copy of an (R,5) array, then ``record``:
+        the CSV and the accumulators come out as R calls of ``__call__`` leave them, rows in input order (the stoi column identical,
+        the dB columns to float64 rounding of the moments).  STOI scores source 0 against target 0, ``pesq_fn`` is called per recording.
+        ValueError, before the upload, names the offending recording."""
+        pool = _ScorePool("update_many", mixes, cleans, estimates, self.fs, keys)
+        vals = torch.cat([pool.sdr()[0], pool.stoi()[0][:, None]], 1).cpu().numpy()  # the one device -> host copy
+        if self.pesq_fn is not None:
+            pesqs = [float(self.pesq_fn(e[0].cpu().numpy(), c[0].cpu().numpy(), self.fs)) for e, c in zip(pool.estimates, pool.cleans)]
+        else:
+            pesqs = [float("nan")] * pool.R
+        self.record(pool.keys, vals, pesqs)
 
     def record(self, keys, vals, pesqs):
         """Write and accumulate rows from host values: vals (B, 5) = the losses (sdr, sdr - baseline, sisnr, sisnr - baseline) in the

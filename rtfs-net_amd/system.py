@@ -168,6 +168,15 @@ class System(nn.Module):
                     embs[r] = emb[g]
         return self.audio_model.separate_many(wavs, embs, **kw)
 
+    def evaluate_many(self, wavs, cleans, mouths, keys, tracker, **kw):
+        """The reference's test loop (``test.py:51-62``) for a pool: ``separate_many(wavs, mouths, **kw)``, then
+        ``tracker.update_many(wavs, cleans, estimates, keys)`` (an ``ALLMetricsTracker``; cleans = R tensors (n_src,L_r)) scores the R
+        estimates in one pooled pass.  Returns the estimates, the list ``separate_many`` returns."""
+        wavs = list(wavs)
+        estimates = self.separate_many(wavs, mouths, **kw)
+        tracker.update_many(wavs, cleans, estimates, keys)
+        return estimates
+
     def separate_many_speakers(self, wavs, mouths, **kw):
         """Many recordings, each with its own number of faces, in one pooled pass (inference): wavs = R tensors (L_r)|(1,L_r), mouths = R
         tensors (K_r,1,Tv_r,88,88) at 25 fps -> a list of R tensors (K_r,L_r).  The video front-end runs under no_grad ONCE PER GROUP of
