@@ -557,6 +557,38 @@ int rtfs_stoi_many_f32(const float* const* cleans, const float* const* ests, con
 int rtfs_sdr_many_f32(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan,
                       int R, int n_src, int fs, void* ws, size_t ws_bytes, float* out, int* perm, void* stream);
 
+/* Extended STOI (ESTOI, Jensen & Taal 2016) as pystoi 0.4.1 computes stoi(clean, estimate, fs, extended=True), with two deliberate
+ * differences (below).  Stages 1 .. 3 are those of rtfs_stoi_f32 (resampling to 10 kHz, silence removal, band values x, y of shape
+ * (15, F)).  With F < 30 d_ext = 1e-5.  Otherwise each of the J = F - 29 segments (15 bands x 30 frames, one per m = 30 .. F) of x and of
+ * y is normalised twice -- per band: minus its mean over the 30 frames, divided by its Euclidean norm; then per frame: minus its mean
+ * over the 15 bands, divided by its norm -- and d_ext = sum(x_n * y_n) / 30 / J, in double, stored as float32.
+ *   Noise: pystoi adds eps * standard_normal before each of the two normalisations; this library does not (on the test signals the
+ *     terms move d by about 1e-16), so the result is deterministic.
+ *   Zero norms: a norm of exactly zero gives the inverse 0 (inv = n > 0 ? 1 / n : 0), so a silent estimate and an all-zero clean signal
+ *     score exactly 0.0 and nothing is ever NaN (pystoi's answer there is whatever its noise happens to be).
+ *   pystoi is not installed where this project is developed: agreement with the package itself is not measured; the definition is
+ *   tests/estoi_oracle.py.
+ * Work cut: the correlation stage runs on the classic stage's work list, ceil(15 J / 256) chunks per row (column 9 of the pooled table);
+ *   chunk c owns the segments s with floor(15 s / 256) == c (at most 18; a planned chunk may own none and then writes the partial 0.0).
+ *   One writer per partial, fixed fold order, no atomics: a row's result does not depend on the batch or the pool.
+ * rtfs_estoi_f32: clean, est (B, L) -> d_ext (B) float32, kept_frames (B) int32 and, when d_classic is not NULL, d_classic (B) = classic
+ *   STOI from the same band values, BIT-EQUAL to rtfs_stoi_f32.  The workspace is that of rtfs_stoi_f32, plus one more region of B *
+ *   nchunk partials when with_classic != 0 (pass with_classic = 1 to the size query exactly when d_classic is not NULL; a workspace sized
+ *   with it also serves a call without).  Refusals as rtfs_stoi_f32, all before any launch: -4 for fs other than 16000 / 10000 or a NULL
+ *   pointer (d_classic excepted), -1 for rows too short for one frame, -2 for a small workspace.  Capturable in a graph.
+ * rtfs_estoi_many_f32: the same for R recordings of different lengths on rtfs_score_many_plan's table (arguments, checks and codes as
+ *   rtfs_stoi_many_f32).  ESTOI alone fits the plan's own workspace (its partials take the STOI partial region).  With d_classic the
+ *   ESTOI partials take a TENTH region of 8 * (total of column 9) bytes appended after the nine, starting at the next multiple of 256:
+ *   rtfs_estoi_many_workspace_bytes(plan, R, 1) (0 for a NULL plan or one not made for R recordings); the nine existing offsets,
+ *   those rtfs_sdr_many_f32 uses included, do not move.  d_ext[r] and d_classic[r] are BIT-EQUAL to rtfs_estoi_f32 on recording r alone
+ *   (shared device code).  Not capturable (table upload). */
+size_t rtfs_estoi_workspace_bytes(int B, int L, int fs, int with_classic);
+int rtfs_estoi_f32(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d_ext,
+                   float* d_classic /* NULL: not wanted */, int* kept_frames, void* stream);
+size_t rtfs_estoi_many_workspace_bytes(const int* plan, int R, int with_classic);
+int rtfs_estoi_many_f32(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
+                        void* ws, size_t ws_bytes, float* d_ext, float* d_classic /* NULL: not wanted */, int* kept_frames, void* stream);
+
 /* Long recordings in overlapping windows on the fused separator (AVNet.separate_long; no reference counterpart: infer_any_video.py:63-86
  * hands a whole track to one forward).  SPF = 640 samples per video frame (16 kHz, 25 fps).  A recording of L samples is cut into N
  * windows of `window` samples every `hop` samples; window n covers samples [n hop, n hop + window) (zeros past L) and video frames

@@ -130,6 +130,10 @@ SIGNATURES = {
     "rtfs_score_many_plan": (_i, [_p, _i, _i, _i, _p, C.POINTER(C.c_size_t)]),
     "rtfs_stoi_many_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p]),
     "rtfs_sdr_many_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p]),
+    "rtfs_estoi_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "rtfs_estoi_f32": (_i, [_p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _p]),
+    "rtfs_estoi_many_workspace_bytes": (_z, [_p, _i, _i]),
+    "rtfs_estoi_many_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _p]),
     "rtfs_longform_plan": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "rtfs_longform_frame_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rtfs_longform_frame_speakers_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

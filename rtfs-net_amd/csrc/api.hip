@@ -1627,6 +1627,14 @@ int rtfs_stoi_f32(const float* clean, const float* est, int B, int L, int fs, vo
     return launch_stoi(clean, est, B, L, fs, ws, ws_bytes, d, kept_frames, (hipStream_t)stream);
 }
 
+size_t rtfs_estoi_workspace_bytes(int B, int L, int fs, int with_classic) { return estoi_workspace_bytes(B, L, fs, with_classic); }
+int rtfs_estoi_f32(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d_ext, float* d_classic,
+                   int* kept_frames, void* stream) {
+    if (fs != 16000 && fs != 10000) return RTFS_ERR_ARG;
+    if (!clean || !est || !ws || !d_ext || !kept_frames) return RTFS_ERR_ARG;
+    return launch_estoi(clean, est, B, L, fs, ws, ws_bytes, d_ext, d_classic, kept_frames, (hipStream_t)stream);
+}
+
 static_assert(SC_COLS == RTFS_SCORE_COLS, "the table columns of kernels.h and rtfs_amd.h");
 int rtfs_score_many_plan(const long long* L, int R, int n_src, int fs, int* table, size_t* ws_bytes) {
     return score_many_plan(L, R, n_src, fs, table, ws_bytes);
@@ -1635,6 +1643,12 @@ int rtfs_stoi_many_f32(const float* const* cleans, const float* const* ests, con
                        void* ws, size_t ws_bytes, float* d, int* kept_frames, void* stream) {
     if (!cleans || !ests || !table || !plan || !ws || !d || !kept_frames) return RTFS_ERR_ARG;
     return launch_stoi_many(cleans, ests, table, plan, R, n_src, fs, ws, ws_bytes, d, kept_frames, (hipStream_t)stream);
+}
+size_t rtfs_estoi_many_workspace_bytes(const int* plan, int R, int with_classic) { return estoi_many_workspace_bytes(plan, R, with_classic); }
+int rtfs_estoi_many_f32(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
+                        void* ws, size_t ws_bytes, float* d_ext, float* d_classic, int* kept_frames, void* stream) {
+    if (!cleans || !ests || !table || !plan || !ws || !d_ext || !kept_frames) return RTFS_ERR_ARG;
+    return launch_estoi_many(cleans, ests, table, plan, R, n_src, fs, ws, ws_bytes, d_ext, d_classic, kept_frames, (hipStream_t)stream);
 }
 int rtfs_sdr_many_f32(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan,
                       int R, int n_src, int fs, void* ws, size_t ws_bytes, float* out, int* perm, void* stream) {

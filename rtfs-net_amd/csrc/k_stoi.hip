@@ -13,6 +13,9 @@
 //                         j is built from the at most three kept frames it overlaps.  (frame group, row)
 //   stoi_corr_kernel      intermediate intelligibility per (30-frame segment, band) in double, folded to one partial sum per workgroup.
 //   stoi_final_kernel     folds a row's partials in a fixed order: d = sum / (segments * 15), or 1e-5 when fewer than 30 frames remain.
+//   estoi_corr_kernel     extended STOI (Jensen & Taal 2016) on the same band values and the same work list: per 30-frame segment the
+//   estoi_final_kernel    15 x 30 matrices of x and y normalised per band, then per frame, and correlated (further down; DESIGN.md,
+//                         "Extended STOI"); the final stage folds its partials and, when asked, the classic ones in one launch.
 // The DFT runs on the VALU in double, one bin per lane with the twiddle advanced by a complex rotation (no table, no LDS bank conflicts,
 // error ~256 ulp): 212 bins x 256 samples is too small and too oddly shaped (15 unequal bands) for a matrix-core tile to pay, and double
 // keeps weak bands exact next to strong ones.  No atomics: every partial has one writer and is folded in a fixed order.
@@ -283,16 +286,17 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const double* __restrict
     if (tid == 0) partial[(size_t)b * nchunk + blockIdx.x] = corr;
 }
 
-// Folds a row's nchunk partials (lane c % 256 takes partial c, then the block sum): read only when the row has a segment.
-__device__ __forceinline__ void final_row(const double* __restrict__ partial, int nchunk, int K, float* __restrict__ d, int* __restrict__ kept,
-                                          double* red, int tid) {
+// Folds a row's nchunk partials (lane c % 256 takes partial c, then the block sum): read only when the row has a segment.  `per` = terms
+// per segment the mean runs over: NBAND for classic STOI, SEG for extended STOI.
+__device__ __forceinline__ void final_row(const double* __restrict__ partial, int nchunk, int K, int per, float* __restrict__ d,
+                                          int* __restrict__ kept, double* red, int tid) {
     const int J = K - 1 - (SEG - 1);
     double s = 0;
     if (J > 0)
         for (int c = tid; c < nchunk; c += 256) s += partial[c];
     s = block_sum_256(s, red, tid);
     if (tid == 0) {
-        *d = J > 0 ? (float)(s / ((double)J * NBAND)) : 1e-5f;  // pystoi returns 1e-5 below 30 frames
+        *d = J > 0 ? (float)(s / ((double)J * per)) : 1e-5f;  // pystoi returns 1e-5 below 30 frames
         *kept = K;
     }
 }
@@ -301,7 +305,115 @@ __global__ __launch_bounds__(256) void stoi_final_kernel(const double* __restric
                                                          float* __restrict__ d, int* __restrict__ kept) {
     __shared__ double red[4];
     const int b = blockIdx.x;
-    final_row(partial + (size_t)b * nchunk, nchunk, kcount[b], d + b, kept + b, red, threadIdx.x);
+    final_row(partial + (size_t)b * nchunk, nchunk, kcount[b], NBAND, d + b, kept + b, red, threadIdx.x);
+}
+
+// ---------------------------------------------------------------- extended STOI (Jensen & Taal 2016; pystoi 0.4.1 extended=True)
+// Same stages up to the band values; then each 30-frame segment's 15 x 30 matrix of x and of y is normalised per band (minus the mean
+// over the 30 frames, divided by the Euclidean norm) and then per frame (minus the mean over the 15 bands, divided by the norm), and
+// d = sum(x_n * y_n) / 30 / J.  Two deliberate differences from pystoi (tests/estoi_oracle.py): its eps * standard_normal
+// noise terms are left out (they move d by ~1e-16), and a norm of exactly zero gives the inverse 0, so silent rows score exactly 0.0 and
+// nothing is ever NaN.  The stage runs on the classic correlation work list: chunk c owns the segments s with floor(15 s / 256) == c,
+// at most 18 of them and possibly none (its partial is then an exact 0.0, written all the same).
+
+// v + (v of the lane a DPP row pattern pairs this lane with); every lane of the wave must be active
+template <int CTRL>
+__device__ __forceinline__ double dpp_pair_sum(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return v + __hiloint2double(hi, lo);
+}
+
+// Sum over the 16 lanes of a segment's group = one DPP row: the xor butterfly 1, 2, 4, 8 written as quad_perm [1,0,3,2], quad_perm
+// [2,3,0,1], row_half_mirror (lane i <-> 7 - i: the other quad, whose four lanes agree by then) and row_mirror (i <-> 15 - i: the
+// other half).  Register moves, no LDS round trip as with ds_bpermute; each step pairs two lanes that hold a + b and b + a, so every
+// lane ends with the same bits.
+__device__ __forceinline__ double group16_sum(double v) {
+    v = dpp_pair_sum<0xB1>(v);
+    v = dpp_pair_sum<0x4E>(v);
+    v = dpp_pair_sum<0x141>(v);
+    return dpp_pair_sum<0x140>(v);
+}
+
+__device__ __forceinline__ double inv_or_zero(double sumsq) {
+    const double n = sqrt(sumsq);
+    return n > 0 ? 1.0 / n : 0.0;
+}
+
+// One segment per 16-lane group, lane = band (lane 15 and the lanes of a group without a segment carry zeros and load nothing): frames
+// s .. s + 29 of the row's (Fmax, 15) band values -> this lane's share of sum(x_n * y_n).  Executed by whole waves (shuffles).
+__device__ __forceinline__ double estoi_segment(const double* __restrict__ xb, const double* __restrict__ yb, int s, int band, bool live) {
+    double xv[SEG], yv[SEG];
+    double mx = 0, my = 0;
+#pragma unroll
+    for (int t = 0; t < SEG; ++t) {
+        xv[t] = live ? xb[(size_t)(s + t) * NBAND + band] : 0.0;
+        yv[t] = live ? yb[(size_t)(s + t) * NBAND + band] : 0.0;
+        mx += xv[t];
+        my += yv[t];
+    }
+    mx /= SEG;
+    my /= SEG;
+    double nx = 0, ny = 0;
+#pragma unroll
+    for (int t = 0; t < SEG; ++t) {  // per band: centre over the 30 frames
+        xv[t] -= mx;
+        yv[t] -= my;
+        nx += xv[t] * xv[t];
+        ny += yv[t] * yv[t];
+    }
+    const double ix = inv_or_zero(nx), iy = inv_or_zero(ny);
+    const bool isband = band < NBAND;
+    double acc = 0;
+#pragma unroll
+    for (int t = 0; t < SEG; ++t) {  // per frame: centre over the 15 bands (mean first, then the squares of the centred values)
+        const double u = xv[t] * ix, v = yv[t] * iy;
+        const double mu = group16_sum(u) / NBAND, mv = group16_sum(v) / NBAND;  // by all 16 lanes: no shuffle under a lane condition
+        const double cu = isband ? u - mu : 0.0;
+        const double cv = isband ? v - mv : 0.0;
+        const double iu = inv_or_zero(group16_sum(cu * cu)), iv = inv_or_zero(group16_sum(cv * cv));
+        acc += (cu * iu) * (cv * iv);
+    }
+    return acc;
+}
+
+// Sum over the segments work-list chunk `chunk` owns (K kept frames): groups 0 .. 15 take its slots 0 .. 15, groups 0 and 1 of wave 0
+// its slots 16 and 17 in a second trip.
+__device__ __forceinline__ double estoi_corr_chunk(const double* __restrict__ xb, const double* __restrict__ yb, int K, int chunk,
+                                                   double* red, int tid) {
+    const int J = K - 1 - (SEG - 1);
+    const int s_lo = cdiv(chunk * 256, NBAND);
+    int s_hi = cdiv((chunk + 1) * 256, NBAND);  // s_hi - s_lo <= 18
+    s_hi = s_hi < J ? s_hi : J;
+    const int g = tid >> 4, band = tid & 15;
+    double acc = estoi_segment(xb, yb, s_lo + g, band, band < NBAND && s_lo + g < s_hi);
+    if (tid < 64 && s_lo + 16 < s_hi)  // uniform over wave 0
+        acc += estoi_segment(xb, yb, s_lo + 16 + g, band, band < NBAND && g < 2 && s_lo + 16 + g < s_hi);
+    return block_sum_256(acc, red, tid);
+}
+
+__global__ __launch_bounds__(256) void estoi_corr_kernel(const double* __restrict__ xb, const double* __restrict__ yb, int Fmax,
+                                                         const int* __restrict__ kcount, int nchunk, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const double corr = estoi_corr_chunk(xb + (size_t)b * Fmax * NBAND, yb + (size_t)b * Fmax * NBAND, kcount[b], blockIdx.x, red, tid);
+    if (tid == 0) partial[(size_t)b * nchunk + blockIdx.x] = corr;
+}
+
+// Extended STOI of one row from its partials pe and, with dc, classic STOI from its partials pc (final_row twice, uniform branch).
+__device__ __forceinline__ void estoi_final_row(const double* __restrict__ pe, const double* __restrict__ pc, int nchunk, int K,
+                                                float* __restrict__ de, float* __restrict__ dc, int* __restrict__ kept, double* red, int tid) {
+    final_row(pe, nchunk, K, SEG, de, kept, red, tid);
+    if (dc) final_row(pc, nchunk, K, NBAND, dc, kept, red, tid);  // block_sum_256 opens with a barrier: the reads of red above are done
+}
+
+__global__ __launch_bounds__(256) void estoi_final_kernel(const double* __restrict__ pe, const double* __restrict__ pc, int nchunk,
+                                                          const int* __restrict__ kcount, float* __restrict__ de, float* __restrict__ dc,
+                                                          int* __restrict__ kept) {
+    __shared__ double red[4];
+    const int b = blockIdx.x;
+    estoi_final_row(pe + (size_t)b * nchunk, dc ? pc + (size_t)b * nchunk : nullptr, nchunk, kcount[b], de + b, dc ? dc + b : nullptr,
+                    kept + b, red, threadIdx.x);
 }
 
 // ---------------------------------------------------------------- many recordings of different lengths (score_many_plan's table)
@@ -378,7 +490,28 @@ __global__ __launch_bounds__(256) void stoi_many_final_kernel(const double* __re
     __shared__ double red[4];
     const int r = blockIdx.x, R1 = R + 1;
     const int c0 = table[SC_CC0 * R1 + r];
-    final_row(partial + c0, table[SC_CC0 * R1 + r + 1] - c0, kcount[r], d + r, kept + r, red, threadIdx.x);
+    final_row(partial + c0, table[SC_CC0 * R1 + r + 1] - c0, kcount[r], NBAND, d + r, kept + r, red, threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void estoi_many_corr_kernel(const double* __restrict__ xb, const double* __restrict__ yb,
+                                                              const int* __restrict__ table, int R, const int* __restrict__ kcount,
+                                                              double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x, R1 = R + 1;
+    const ScoreRec w = score_find(table + SC_CC0 * R1, R, blockIdx.x);
+    const size_t bo = (size_t)table[SC_BD_OFF * R1 + w.r] * NBAND;
+    const double corr = estoi_corr_chunk(xb + bo, yb + bo, kcount[w.r], w.item, red, tid);
+    if (tid == 0) partial[blockIdx.x] = corr;
+}
+
+__global__ __launch_bounds__(256) void estoi_many_final_kernel(const double* __restrict__ pe, const double* __restrict__ pc,
+                                                               const int* __restrict__ table, int R, const int* __restrict__ kcount,
+                                                               float* __restrict__ de, float* __restrict__ dc, int* __restrict__ kept) {
+    __shared__ double red[4];
+    const int r = blockIdx.x, R1 = R + 1;
+    const int c0 = table[SC_CC0 * R1 + r];
+    estoi_final_row(pe + c0, dc ? pc + c0 : nullptr, table[SC_CC0 * R1 + r + 1] - c0, kcount[r], de + r, dc ? dc + r : nullptr, kept + r, red,
+                    threadIdx.x);
 }
 
 struct StoiDims {
@@ -399,11 +532,12 @@ StoiDims stoi_dims(int L, int fs) {
 
 struct StoiWs {
     float *xr, *yr;
-    double *energy, *xb, *yb, *partial;
+    double *energy, *xb, *yb, *partial, *partial2;
     int *kidx, *kcount;
 };
 
-size_t stoi_carve(const StoiDims& s, int B, char* base, StoiWs* w) {
+// `extra`: one more region of B * nchunk partials after the classic layout (extended STOI together with classic STOI)
+size_t stoi_carve(const StoiDims& s, int B, char* base, StoiWs* w, bool extra = false) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
         off = align_up(off, 256);
@@ -420,6 +554,7 @@ size_t stoi_carve(const StoiDims& s, int B, char* base, StoiWs* w) {
     w->xb = (double*)take((size_t)B * s.Fmax * NBAND * sizeof(double));
     w->yb = (double*)take((size_t)B * s.Fmax * NBAND * sizeof(double));
     w->partial = (double*)take((size_t)B * s.nchunk * sizeof(double));
+    w->partial2 = extra ? (double*)take((size_t)B * s.nchunk * sizeof(double)) : nullptr;
     return off;
 }
 
@@ -438,13 +573,8 @@ size_t stoi_workspace_bytes(int B, int L, int fs) {
     return stoi_carve(stoi_dims(L, fs), B, nullptr, &w);
 }
 
-int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept, hipStream_t st) {
-    const int e = stoi_check_args(B, L, fs);
-    if (e != RTFS_OK) return e;
-    const StoiDims s = stoi_dims(L, fs);
-    StoiWs w;
-    if (stoi_carve(s, B, nullptr, &w) > ws_bytes) return RTFS_ERR_WORKSPACE;
-    stoi_carve(s, B, (char*)ws, &w);
+// Stages 1 .. 3 of a (B, L) block, shared by classic and extended STOI: resample, mask, band values.
+static int launch_stoi_bands(const float* clean, const float* est, int B, int L, const StoiDims& s, const StoiWs& w, hipStream_t st) {
     const float *xr = clean, *yr = est;
     if (s.resample) {
         hipLaunchKernelGGL(stoi_resample_kernel, dim3(cdiv(s.L10, 256 * RS_OUT), B, 2), dim3(256), 0, st, clean, est, L, s.L10, w.xr, w.yr);
@@ -461,11 +591,53 @@ int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void
                            w.xb, w.yb);
         if ((r = rtfs_launch_status()) != RTFS_OK) return r;
     }
+    return RTFS_OK;
+}
+
+int launch_stoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d, int* kept, hipStream_t st) {
+    const int e = stoi_check_args(B, L, fs);
+    if (e != RTFS_OK) return e;
+    const StoiDims s = stoi_dims(L, fs);
+    StoiWs w;
+    if (stoi_carve(s, B, nullptr, &w) > ws_bytes) return RTFS_ERR_WORKSPACE;
+    stoi_carve(s, B, (char*)ws, &w);
+    int r = launch_stoi_bands(clean, est, B, L, s, w, st);
+    if (r != RTFS_OK) return r;
     if (s.Fmax >= SEG) {  // otherwise every row takes the 1e-5 path and the partials are never read
         hipLaunchKernelGGL(stoi_corr_kernel, dim3(s.nchunk, B), dim3(256), 0, st, w.xb, w.yb, s.Fmax, w.kcount, s.nchunk, w.partial);
         if ((r = rtfs_launch_status()) != RTFS_OK) return r;
     }
     hipLaunchKernelGGL(stoi_final_kernel, dim3(B), dim3(256), 0, st, w.partial, s.nchunk, w.kcount, d, kept);
+    return rtfs_launch_status();
+}
+
+size_t estoi_workspace_bytes(int B, int L, int fs, int with_classic) {
+    if (stoi_check_args(B, L, fs) != RTFS_OK) return 0;
+    StoiWs w;
+    return stoi_carve(stoi_dims(L, fs), B, nullptr, &w, with_classic != 0);
+}
+
+int launch_estoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d_ext, float* d_classic,
+                 int* kept, hipStream_t st) {
+    const int e = stoi_check_args(B, L, fs);
+    if (e != RTFS_OK) return e;
+    const StoiDims s = stoi_dims(L, fs);
+    const bool both = d_classic != nullptr;
+    StoiWs w;
+    if (stoi_carve(s, B, nullptr, &w, both) > ws_bytes) return RTFS_ERR_WORKSPACE;
+    stoi_carve(s, B, (char*)ws, &w, both);
+    int r = launch_stoi_bands(clean, est, B, L, s, w, st);
+    if (r != RTFS_OK) return r;
+    double* pe = both ? w.partial2 : w.partial;  // the classic partials stay where launch_stoi keeps them
+    if (s.Fmax >= SEG) {
+        if (both) {
+            hipLaunchKernelGGL(stoi_corr_kernel, dim3(s.nchunk, B), dim3(256), 0, st, w.xb, w.yb, s.Fmax, w.kcount, s.nchunk, w.partial);
+            if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+        }
+        hipLaunchKernelGGL(estoi_corr_kernel, dim3(s.nchunk, B), dim3(256), 0, st, w.xb, w.yb, s.Fmax, w.kcount, s.nchunk, pe);
+        if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+    }
+    hipLaunchKernelGGL(estoi_final_kernel, dim3(B), dim3(256), 0, st, pe, w.partial, s.nchunk, w.kcount, d_ext, d_classic, kept);
     return rtfs_launch_status();
 }
 
@@ -545,13 +717,12 @@ int score_many_carve(const int* plan, int R, int n_src, int fs, void* ws, size_t
     return RTFS_OK;
 }
 
-int launch_stoi_many(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs, void* ws,
-                     size_t ws_bytes, float* d, int* kept, hipStream_t st) {
-    ScoreManyWs w;
-    int r = score_many_carve(plan, R, n_src, fs, ws, ws_bytes, &w);
-    if (r != RTFS_OK) return r;
+// Stages 1 .. 3 of the pooled pass, shared by classic and extended STOI: resample, mask, band values.
+static int launch_stoi_many_bands(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R,
+                                  const ScoreManyWs& w, hipStream_t st) {
     const int R1 = R + 1;
-    const int n_rs = plan[SC_RS0 * R1 + R], n_bg = plan[SC_BG0 * R1 + R], n_cc = plan[SC_CC0 * R1 + R];
+    const int n_rs = plan[SC_RS0 * R1 + R], n_bg = plan[SC_BG0 * R1 + R];
+    int r;
     const float *xr = nullptr, *yr = nullptr;  // fs = 10000: the stages read the recordings themselves
     if (n_rs > 0) {
         hipLaunchKernelGGL(stoi_many_resample_kernel, dim3(n_rs, 2), dim3(256), 0, st, cleans, ests, table, R, w.xr, w.yr);
@@ -565,10 +736,56 @@ int launch_stoi_many(const float* const* cleans, const float* const* ests, const
         hipLaunchKernelGGL(stoi_many_bands_kernel, dim3(n_bg), dim3(256), 0, st, cleans, ests, xr, yr, table, R, w.kidx, w.kcount, w.xb, w.yb);
         if ((r = rtfs_launch_status()) != RTFS_OK) return r;
     }
+    return RTFS_OK;
+}
+
+int launch_stoi_many(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs, void* ws,
+                     size_t ws_bytes, float* d, int* kept, hipStream_t st) {
+    ScoreManyWs w;
+    int r = score_many_carve(plan, R, n_src, fs, ws, ws_bytes, &w);
+    if (r != RTFS_OK) return r;
+    const int n_cc = plan[SC_CC0 * (R + 1) + R];
+    if ((r = launch_stoi_many_bands(cleans, ests, table, plan, R, w, st)) != RTFS_OK) return r;
     if (n_cc > 0) {
         hipLaunchKernelGGL(stoi_many_corr_kernel, dim3(n_cc), dim3(256), 0, st, w.xb, w.yb, table, R, w.kcount, w.partial);
         if ((r = rtfs_launch_status()) != RTFS_OK) return r;
     }
     hipLaunchKernelGGL(stoi_many_final_kernel, dim3(R), dim3(256), 0, st, w.partial, table, R, w.kcount, d, kept);
+    return rtfs_launch_status();
+}
+
+// The pooled workspace for extended STOI: the plan's nine regions and, with classic STOI as well, a tenth of (total of column 9) partials
+// appended at the next multiple of 256 (no existing offset moves).  0 for a plan that is not one of R recordings.
+size_t estoi_many_workspace_bytes(const int* plan, int R, int with_classic) {
+    if (!plan || R < 1) return 0;
+    const int R1 = R + 1, n_src = plan[SC_L * R1 + R];
+    if (plan[SC_K0 * R1 + R] != R || n_src < 1 || n_src > 4) return 0;
+    ScoreManyWs w;
+    const size_t nine = score_carve(plan, R, n_src, nullptr, &w);
+    return with_classic ? align_up(nine, 256) + (size_t)plan[SC_CC0 * R1 + R] * sizeof(double) : nine;
+}
+
+int launch_estoi_many(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
+                      void* ws, size_t ws_bytes, float* d_ext, float* d_classic, int* kept, hipStream_t st) {
+    const bool both = d_classic != nullptr;
+    ScoreManyWs w;
+    int r = score_many_carve(plan, R, n_src, fs, ws, ws_bytes, &w);  // the plan / argument checks of launch_stoi_many
+    if (r != RTFS_OK) return r;
+    if (both && estoi_many_workspace_bytes(plan, R, 1) > ws_bytes) return RTFS_ERR_WORKSPACE;
+    const int n_cc = plan[SC_CC0 * (R + 1) + R];
+    // the classic partials stay where launch_stoi_many keeps them; with both, the extended ones take the tenth region
+    double* pe = both ? (double*)((char*)ws + align_up(score_carve(plan, R, n_src, nullptr, &w), 256)) : nullptr;
+    score_carve(plan, R, n_src, (char*)ws, &w);
+    if (!both) pe = w.partial;
+    if ((r = launch_stoi_many_bands(cleans, ests, table, plan, R, w, st)) != RTFS_OK) return r;
+    if (n_cc > 0) {
+        if (both) {
+            hipLaunchKernelGGL(stoi_many_corr_kernel, dim3(n_cc), dim3(256), 0, st, w.xb, w.yb, table, R, w.kcount, w.partial);
+            if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+        }
+        hipLaunchKernelGGL(estoi_many_corr_kernel, dim3(n_cc), dim3(256), 0, st, w.xb, w.yb, table, R, w.kcount, pe);
+        if ((r = rtfs_launch_status()) != RTFS_OK) return r;
+    }
+    hipLaunchKernelGGL(estoi_many_final_kernel, dim3(R), dim3(256), 0, st, pe, w.partial, table, R, w.kcount, d_ext, d_classic, kept);
     return rtfs_launch_status();
 }

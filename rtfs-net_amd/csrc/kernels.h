@@ -394,6 +394,16 @@ int launch_stoi_many(const float* const* cleans, const float* const* ests, const
 int launch_sdr_many(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R,
                     int n_src, int fs, void* ws, size_t ws_bytes, float* out, int* perm, hipStream_t st);
 
+// extended STOI (k_stoi.hip; Jensen & Taal 2016 as pystoi 0.4.1's extended=True branch without its noise terms): stages 1-3 of classic
+// STOI, then per 30-frame segment the 15 x 30 band matrix normalised along both axes and correlated.  d_classic non-NULL: classic STOI
+// on the same band values as well (bit-equal to launch_stoi / launch_stoi_many), one more partial region (with_classic).
+size_t estoi_workspace_bytes(int B, int L, int fs, int with_classic);
+int launch_estoi(const float* clean, const float* est, int B, int L, int fs, void* ws, size_t ws_bytes, float* d_ext, float* d_classic,
+                 int* kept, hipStream_t st);
+size_t estoi_many_workspace_bytes(const int* plan, int R, int with_classic);
+int launch_estoi_many(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
+                      void* ws, size_t ws_bytes, float* d_ext, float* d_classic, int* kept, hipStream_t st);
+
 // long recordings in overlapping windows (k_longform.hip): window plan (host), framing of audio + video in one launch, cross-faded overlap-add
 int longform_plan(int L, int Tv, int window, int hop, int* N);
 // K lip tracks per recording (one track: K = 1): the audio window once, video_win (B*N*K, 512, window / SPF), target row (b*N + n)*K + k

@@ -3,6 +3,8 @@
 (``rtfs_stoi_f32``, ``csrc/k_stoi.hip``); SI-SNR and SNR are the PIT loss kernel the losses use (``rtfs_pit_pairwise_sdr_f32``).
 ``stoi_many``, ``sdr_many`` and ``ALLMetricsTracker.update_many`` score R recordings of different lengths in one pooled pass
 (``rtfs_score_many_plan``, ``rtfs_stoi_many_f32``, ``rtfs_sdr_many_f32``; DESIGN.md, "Scoring many recordings of different lengths").
+``estoi`` / ``estoi_many`` are extended STOI (``rtfs_estoi_f32`` / ``rtfs_estoi_many_f32``; DESIGN.md, "Extended STOI"), alone or
+together with classic STOI from the same band values; ``ALLMetricsTracker(..., estoi=True)`` adds it as a seventh column.
 There is no CPU fallback.  PESQ (ITU-T P.862) is not implemented here: pass a host callable as ``pesq_fn`` (called as the reference
 calls ``pypesq.pesq``: ``pesq_fn(estimate, clean, 16000)`` on numpy rows) or the ``pesq`` column is NaN (and so are its mean and std).
 """
@@ -25,7 +27,7 @@ def stoi(clean, estimate, fs=16000, extended=False, return_kept=False):
     fs 16000 (resampled to 10 kHz on the device) or 10000.  ``return_kept`` also returns the frames silence removal kept (int32), a
     speech-activity count.  Below 30 remaining STFT frames the score is 1e-5, as pystoi returns."""
     if extended:
-        raise ValueError("extended STOI is not supported (the reference scores with extended=False)")
+        raise ValueError("stoi scores classic STOI only (the reference scores with extended=False); extended STOI is metrics.estoi")
     if fs not in (16000, 10000):
         raise ValueError(f"stoi: fs must be 16000 or 10000, got {fs}")
     if clean.shape != estimate.shape or clean.ndim not in (1, 2):
@@ -48,12 +50,43 @@ def stoi(clean, estimate, fs=16000, extended=False, return_kept=False):
     return (d, kept) if return_kept else d
 
 
+def estoi(clean, estimate, fs=16000, return_kept=False, with_classic=False):
+    """Extended STOI (Jensen & Taal 2016; pystoi ``stoi(x, y, fs_sig, extended=True)`` without its noise terms and with the inverse of
+    a zero norm taken as 0: DESIGN.md, "Extended STOI") for (B, L) or (L,) device tensors -> (B,) float32, shapes, rates and refusals
+    as ``stoi``.  ``with_classic`` also returns classic STOI computed from the same band values in the same call, bit-equal to
+    ``stoi``: ``(estoi, stoi)``; ``return_kept`` appends the kept-frame counts.  Below 30 remaining STFT frames both are 1e-5."""
+    if fs not in (16000, 10000):
+        raise ValueError(f"estoi: fs must be 16000 or 10000, got {fs}")
+    if clean.shape != estimate.shape or clean.ndim not in (1, 2):
+        raise ValueError(f"estoi: clean and estimate must have the same (B, L) or (L,) shape, got {tuple(clean.shape)} and {tuple(estimate.shape)}")
+    _lib.need_gpu(clean, estimate)
+    lib = _lib.load()
+    one = clean.ndim == 1
+    x = clean.reshape(1, -1) if one else clean
+    y = estimate.reshape(1, -1) if one else estimate
+    x, y = x.contiguous(), y.contiguous()
+    B, L = x.shape
+    d = _lib.empty(B, device=x.device, dtype=torch.float32)
+    dc = _lib.empty(B, device=x.device, dtype=torch.float32) if with_classic else None
+    kept = _lib.empty(B, device=x.device, dtype=torch.int32)
+    ws = _lib.workspace(lib.rtfs_estoi_workspace_bytes(B, L, fs, int(bool(with_classic))), x.device)
+    _lib.check(lib.rtfs_estoi_f32(_lib.ptr(x), _lib.ptr(y), B, L, fs, _lib.ptr(ws), ws.numel(), _lib.ptr(d), _lib.ptr(dc), _lib.ptr(kept),
+                                  _lib.stream_of(x)), "rtfs_estoi_f32")
+    out = (d, dc) if with_classic else (d,)
+    if return_kept:
+        out += (kept,)
+    if one:
+        out = tuple(t[0] for t in out)
+    return out if len(out) > 1 else out[0]
+
+
 class _ScorePool:
     """R recordings of different lengths, validated and planned for ``rtfs_stoi_many_f32`` / ``rtfs_sdr_many_f32``: everything that can
     be refused is refused here, as ValueError naming the recording, before any upload or launch.  ``mixes`` None: STOI only, clean and
-    estimate rows (L_r)|(1,L_r).  Otherwise mix (L_r)|(1,L_r) and clean / estimate (n_src,L_r)."""
+    estimate rows (L_r)|(1,L_r).  Otherwise mix (L_r)|(1,L_r) and clean / estimate (n_src,L_r).  ``both``: the workspace also holds the
+    tenth region ``estoi(with_classic=True)`` needs."""
 
-    def __init__(self, what, mixes, cleans, estimates, fs, keys=None):
+    def __init__(self, what, mixes, cleans, estimates, fs, keys=None, both=False):
         try:
             cleans, estimates = list(cleans), list(estimates)
             mixes = None if mixes is None else list(mixes)
@@ -120,7 +153,8 @@ class _ScorePool:
         base = self.tab.data_ptr()
         self.p_clean, self.p_est, self.p_mix = (C.c_void_p(base + 8 * R * k) for k in range(3))
         self.p_table = C.c_void_p(base + 8 * R * len(groups))
-        self.ws = _lib.workspace(nbytes.value, device)
+        self.both = bool(both)
+        self.ws = _lib.workspace(lib.rtfs_estoi_many_workspace_bytes(self.plan, R, 1) if both else nbytes.value, device)
         self.stream = _lib.stream_of(self.tab)
 
     def stoi(self):
@@ -129,6 +163,18 @@ class _ScorePool:
         _lib.check(self.lib.rtfs_stoi_many_f32(self.p_clean, self.p_est, self.p_table, self.plan, self.R, self.n, self.fs, _lib.ptr(self.ws),
                                                self.ws.numel(), _lib.ptr(d), _lib.ptr(kept), self.stream), "rtfs_stoi_many_f32")
         return d, kept
+
+    def estoi(self, with_classic=False):
+        """-> (estoi, stoi | None, kept)"""
+        if with_classic and not self.both:
+            raise ValueError("this pool's workspace was not sized for extended and classic STOI together")
+        d = _lib.empty(self.R, device=self.device, dtype=torch.float32)
+        dc = _lib.empty(self.R, device=self.device, dtype=torch.float32) if with_classic else None
+        kept = _lib.empty(self.R, device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.rtfs_estoi_many_f32(self.p_clean, self.p_est, self.p_table, self.plan, self.R, self.n, self.fs,
+                                                _lib.ptr(self.ws), self.ws.numel(), _lib.ptr(d), _lib.ptr(dc), _lib.ptr(kept), self.stream),
+                   "rtfs_estoi_many_f32")
+        return d, dc, kept
 
     def sdr(self):
         out = _lib.empty(self.R, 4, device=self.device, dtype=torch.float32)
@@ -149,6 +195,17 @@ def stoi_many(cleans, estimates, fs=16000, return_kept=False):
     return (d, kept) if return_kept else d
 
 
+def estoi_many(cleans, estimates, fs=16000, return_kept=False, with_classic=False):
+    """``estoi`` for R recordings of different lengths in one pooled pass, inputs and refusals as ``stoi_many`` -> (R,) float32; with
+    ``with_classic`` ``(estoi, stoi)`` from the same band values, with ``return_kept`` the kept frames (R,) int32 appended.  Entry r is
+    bit-equal to ``estoi(cleans[r], estimates[r], fs, with_classic=...)``.  Not capturable (table upload)."""
+    d, dc, kept = _ScorePool("estoi_many", None, cleans, estimates, fs, both=with_classic).estoi(with_classic)
+    out = (d, dc) if with_classic else (d,)
+    if return_kept:
+        out += (kept,)
+    return out if len(out) > 1 else out[0]
+
+
 def sdr_many(mixes, cleans, estimates):
     """The tracker's four PIT figures for R mixtures of different lengths in one pass over the samples: mixes R tensors (L_r)|(1,L_r),
     cleans / estimates R tensors (n_src,L_r) -> (R,4) float32 in the loss sign [sdr, sdr - baseline, sisnr, sisnr - baseline] (baseline =
@@ -161,15 +218,20 @@ class ALLMetricsTracker:
     """reference allwrapper.py:19-134.  Per mixture: SI-SNR, SI-SNRi, SDR, SDRi, PESQ and STOI; ``final()`` adds ``avg`` and ``std``
     rows and closes the CSV.  Signs as the reference: the CSV holds ``si-snr = -loss``, ``si-snr_i = -(loss - baseline)`` but
     ``sdr = loss`` and ``sdr_i = loss - baseline`` (negative dB); the accumulated means / stds are positive dB for all four.
-    ``update_batch`` scores a whole batch in one set of launches and moves one small host array."""
+    ``update_batch`` scores a whole batch in one set of launches and moves one small host array.  ``estoi=True`` (not in the
+    reference) adds extended STOI as a seventh metric ``"estoi"`` after ``"stoi"`` everywhere -- rows, ``avg`` / ``std``, ``get_mean`` /
+    ``get_std``, ``all_estois`` -- computed with classic STOI in one combined call; without it the tracker is the reference's."""
 
     COLUMNS = ["snt_id", "sdr", "sdr_i", "si-snr", "si-snr_i", "pesq", "stoi"]
 
-    def __init__(self, save_file: str = "", pesq_fn=None, fs: int = 16000):
+    def __init__(self, save_file: str = "", pesq_fn=None, fs: int = 16000, estoi: bool = False):
         self.all_sdrs, self.all_sdrs_i, self.all_sisnrs, self.all_sisnrs_i, self.all_pesqs, self.all_stois = [], [], [], [], [], []
-        self.pesq_fn, self.fs = pesq_fn, fs
+        self.pesq_fn, self.fs, self.estoi = pesq_fn, fs, bool(estoi)
+        self.columns = self.COLUMNS + (["estoi"] if self.estoi else [])
+        if self.estoi:
+            self.all_estois = []
         self.results_csv = open(save_file, "w")
-        self.writer = csv.DictWriter(self.results_csv, fieldnames=self.COLUMNS)
+        self.writer = csv.DictWriter(self.results_csv, fieldnames=self.columns)
         self.writer.writeheader()
 
     def __call__(self, mix, clean, estimate, key):
@@ -190,8 +252,12 @@ class ALLMetricsTracker:
         sisnr_b = _pairwise(mixs, clean, "sisdr", True, True)[1]
         sdr = _pairwise(estimate, clean, "snr", True, True)[1]
         sdr_b = _pairwise(mixs, clean, "snr", True, True)[1]
-        st = stoi(clean[:, 0], estimate[:, 0], self.fs)
-        vals = torch.stack([sdr, sdr - sdr_b, sisnr, sisnr - sisnr_b, st], 1).cpu().numpy()  # the one device -> host copy
+        if self.estoi:  # stages 1-3 once: (estoi, stoi) from the same band values
+            est, st = estoi(clean[:, 0], estimate[:, 0], self.fs, with_classic=True)
+            cols = [sdr, sdr - sdr_b, sisnr, sisnr - sisnr_b, st, est]
+        else:
+            cols = [sdr, sdr - sdr_b, sisnr, sisnr - sisnr_b, stoi(clean[:, 0], estimate[:, 0], self.fs)]
+        vals = torch.stack(cols, 1).cpu().numpy()  # the one device -> host copy
         if self.pesq_fn is not None:
             est_h, cl_h = estimate[:, 0].cpu().numpy(), clean[:, 0].cpu().numpy()
             pesqs = [float(self.pesq_fn(est_h[b], cl_h[b], self.fs)) for b in range(B)]
@@ -206,8 +272,13 @@ class ALLMetricsTracker:
         the CSV and the accumulators come out as R calls of ``__call__`` leave them, rows in input order (the stoi column identical,
         the dB columns to float64 rounding of the moments).  STOI scores source 0 against target 0, ``pesq_fn`` is called per recording.
         ValueError, before the upload, names the offending recording."""
-        pool = _ScorePool("update_many", mixes, cleans, estimates, self.fs, keys)
-        vals = torch.cat([pool.sdr()[0], pool.stoi()[0][:, None]], 1).cpu().numpy()  # the one device -> host copy
+        pool = _ScorePool("update_many", mixes, cleans, estimates, self.fs, keys, both=self.estoi)
+        if self.estoi:  # (R,6): stages 1-3 once, (estoi, stoi) from the same band values
+            est, st, _ = pool.estoi(with_classic=True)
+            cols = [pool.sdr()[0], st[:, None], est[:, None]]
+        else:
+            cols = [pool.sdr()[0], pool.stoi()[0][:, None]]
+        vals = torch.cat(cols, 1).cpu().numpy()  # the one device -> host copy
         if self.pesq_fn is not None:
             pesqs = [float(self.pesq_fn(e[0].cpu().numpy(), c[0].cpu().numpy(), self.fs)) for e, c in zip(pool.estimates, pool.cleans)]
         else:
@@ -216,12 +287,18 @@ class ALLMetricsTracker:
 
     def record(self, keys, vals, pesqs):
         """Write and accumulate rows from host values: vals (B, 5) = the losses (sdr, sdr - baseline, sisnr, sisnr - baseline) in the
-        loss sign, then stoi; pesqs: B floats."""
+        loss sign, then stoi; with ``estoi=True`` (B, 6): estoi last; pesqs: B floats."""
         for b in range(len(keys)):
-            l_sdr, l_sdr_i, l_sisnr, l_sisnr_i, s = (float(v) for v in vals[b])
+            l_sdr, l_sdr_i, l_sisnr, l_sisnr_i, s, *ext = (float(v) for v in vals[b])
+            if len(ext) != int(self.estoi):
+                raise ValueError(f"record: {len(vals[b])} values per row; this tracker takes {6 if self.estoi else 5}")
             self.key = keys[b]
-            self.writer.writerow({"snt_id": keys[b], "sdr": l_sdr, "sdr_i": l_sdr_i, "si-snr": -l_sisnr, "si-snr_i": -l_sisnr_i,
-                                  "pesq": pesqs[b], "stoi": s})
+            row = {"snt_id": keys[b], "sdr": l_sdr, "sdr_i": l_sdr_i, "si-snr": -l_sisnr, "si-snr_i": -l_sisnr_i,
+                   "pesq": pesqs[b], "stoi": s}
+            if self.estoi:
+                row["estoi"] = ext[0]
+                self.all_estois.append(ext[0])
+            self.writer.writerow(row)
             self.all_sdrs.append(-l_sdr)
             self.all_sdrs_i.append(-l_sdr_i)
             self.all_sisnrs.append(-l_sisnr)
@@ -230,8 +307,11 @@ class ALLMetricsTracker:
             self.all_stois.append(s)
 
     def _lists(self):
-        return {"sdr": self.all_sdrs, "sdr_i": self.all_sdrs_i, "si-snr": self.all_sisnrs, "si-snr_i": self.all_sisnrs_i,
-                "pesq": self.all_pesqs, "stoi": self.all_stois}
+        lists = {"sdr": self.all_sdrs, "sdr_i": self.all_sdrs_i, "si-snr": self.all_sisnrs, "si-snr_i": self.all_sisnrs_i,
+                 "pesq": self.all_pesqs, "stoi": self.all_stois}
+        if self.estoi:
+            lists["estoi"] = self.all_estois
+        return lists
 
     def get_mean(self):
         return {k: np.mean(v) for k, v in self._lists().items()}

@@ -13,7 +13,9 @@ set, ALL figures come from ONE child process, on the same tensors:
   separate+loop    separate_many, then the loop
   separate_many    alone, for scale
 Times are HIP events around the call (the trackers' device-to-host copies block, so the host time is inside), min / median / max over the
-steps after warm-up calls of the same shapes.  No ratio is asserted.  Each child runs under its own time limit; after a child that ends
+steps after warm-up calls of the same shapes.  No ratio is asserted.  With --estoi each child times only ``update_many`` on a tracker
+without and with ``estoi=True`` (a seventh column, one combined STOI + ESTOI call), alternating the two in --rounds rounds; per variant
+the median / min / max over the rounds' medians, and the added cost per round.  Each child runs under its own time limit; after a child that ends
 abnormally (signal, abort, time limit) no further child is started.  Prints one JSON line (and writes it to --out)."""
 import argparse
 import json
@@ -28,7 +30,7 @@ sys.path.insert(0, ROOT)
 from tools.bench_many import ABNORMAL, FS, HOP, MAX_BATCH, SETS, SPF, WINDOW, lengths  # noqa: E402
 
 
-def child(name, steps, warmup):
+def child(name, steps, warmup, estoi_rounds=0):
     import numpy as np
     import torch
 
@@ -36,9 +38,10 @@ def child(name, steps, warmup):
     from oracle.params import load_spec, make_state_dict
     from rtfs_net_amd.configs import audionet_config
     from tests import metrics_oracle as M
-    m = R.AVNet(print_macs=False, **audionet_config(4))
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in make_state_dict(load_spec("state_spec_R4.json"), 0).items()})
-    system = R.System(audio_model=m.cuda().eval()).eval()
+    if not estoi_rounds:  # the separator is not part of the --estoi comparison
+        m = R.AVNet(print_macs=False, **audionet_config(4))
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in make_state_dict(load_spec("state_spec_R4.json"), 0).items()})
+        system = R.System(audio_model=m.cuda().eval()).eval()
     Ls = lengths(name)
     rng = np.random.default_rng(2)
     cleans_h = [M.speech_like(rng, L, FS, gaps=[(0.3 * L / FS, 0.4 * L / FS)]) * 0.05 for L in Ls]
@@ -72,6 +75,22 @@ def child(name, steps, warmup):
 
     res = {"set": name, "recordings": len(Ls), "seconds_of_audio": round(sum(Ls) / FS, 2), "steps": steps, "warmup": warmup,
            "device": torch.cuda.get_device_name(0)}
+    if estoi_rounds:
+        with tempfile.TemporaryDirectory() as td, torch.no_grad():
+            t5, t6 = R.ALLMetricsTracker(os.path.join(td, "five.csv")), R.ALLMetricsTracker(os.path.join(td, "six.csv"), estoi=True)
+            ms = {"update_many": [], "update_many_estoi": []}
+            for _ in range(estoi_rounds):
+                ms["update_many"].append(timed(lambda: t5.update_many(wavs, cleans, ests, keys))["ms_median"])
+                ms["update_many_estoi"].append(timed(lambda: t6.update_many(wavs, cleans, ests, keys))["ms_median"])
+            t5.final()
+            t6.final()
+        res["rounds"] = estoi_rounds
+        for k, v in ms.items():
+            res[k] = {"ms_median": round(float(np.median(v)), 3), "ms_min": round(min(v), 3), "ms_max": round(max(v), 3)}
+        add = [b - a for a, b in zip(ms["update_many"], ms["update_many_estoi"])]
+        res["estoi_adds_ms"] = {"median": round(float(np.median(add)), 3), "min": round(min(add), 3), "max": round(max(add), 3)}
+        print(json.dumps(res))
+        return
     with tempfile.TemporaryDirectory() as td, torch.no_grad():
         t = R.ALLMetricsTracker(os.path.join(td, "m.csv"))
         res["update_many"] = timed(lambda: t.update_many(wavs, cleans, ests, keys))
@@ -96,16 +115,23 @@ def main():
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--estoi", action="store_true", help="time update_many without and with the extended-STOI column only")
+    ap.add_argument("--rounds", type=int, default=7)
     args = ap.parse_args()
     if args.child:
-        return child(args.sets[0], args.steps, args.warmup)
+        return child(args.sets[0], args.steps, args.warmup, args.rounds if args.estoi else 0)
     out = {"metric": "scoring 64 recordings (SDR, SDRi, SI-SNR, SI-SNRi, STOI; n_src 1, 16 kHz): one pooled update_many against the loop of "
                      "tracker(...) per recording, and the same behind separate_many (RTFS-Net-4 SRU, window 2 s, hop 1 s, max_batch 32); "
                      "HIP events, min / median / max ms per call, one process per set",
            "sets": {name: lengths(name) for name in args.sets}, "cases": []}
+    if args.estoi:
+        out["metric"] = ("ALLMetricsTracker.update_many on 64 recordings without and with estoi=True (n_src 1, 16 kHz), alternating in "
+                         "rounds of one process per set; HIP events, median / min / max of the rounds' medians, ms per call")
     stopped = None
     for name in args.sets:
         cmd = [sys.executable, os.path.abspath(__file__), "--child", "--sets", name, "--steps", str(args.steps), "--warmup", str(args.warmup)]
+        if args.estoi:
+            cmd += ["--estoi", "--rounds", str(args.rounds)]
         try:
             pr = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=args.child_timeout)
         except subprocess.TimeoutExpired:
