@@ -1024,6 +1024,61 @@ int rtfs_mouth_affine(const double* eyes, const double* lips, long long n, int o
                       long long* refused);
 int rtfs_mouth_rois_u8(const long long* jobs, const long long* host_jobs, int J, int out_h, int out_w, void* stream);
 
+/* Training mixtures on the device (datas.mix_batch, System.online_mixing_collate / System.mix_batch; DESIGN.md "Training mixtures";
+ * csrc/k_mix.hip): the reference's online mixing (src/system/core.py:183-202) and the target-speaker form (a target plus interferers at
+ * a drawn SNR, each at a drawn crop of its utterance) as a host recipe, one table upload and TWO launches.
+ * A recipe has B rows of J = RTFS_MIX_MAX_SOURCES slots.  Slot (b, j) names a segment of L samples of a source allocation, a factor a
+ * (float64) and optionally a reference segment; a slot may be empty.  Sources are separate device allocations read where they lie:
+ * float32 at any 4-byte alignment or int16 PCM at any 2-byte alignment, which enters as (float)s / 32768; both may appear in one call
+ * and an allocation or segment may appear in any number of slots and rows.  With x_j the slot's segment and E(x) = sum x^2 (raw, no
+ * mean removal, as the reference), everything in float64:
+ *   g_j = a_j without a reference, a_j sqrt(E(ref_j) / E(x_j)) with one (no eps: a silent segment gives inf / NaN as core.py:197),
+ *   0 for an empty slot, which reads nothing;  m[t] = sum_j g_j x_j[t] over the non-empty slots in the order j = 0, 1, ..., multiply
+ *   then add, never fused;  without normalisation mixture[b,t] = (float)m[t], sources[b,j,t] = (float)(g_j x_j[t]) for j < n_out;
+ *   with it (avspeech_dataset.py:145-148, the rule of rtfs_wav_normalize_f32) s = the unbiased standard deviation of m,
+ *   inv = 1 / (s + eps), mixture = (float)((m - mean(m)) inv), sources[j] = (float)((g_j x_j - g_j (sum x_j / L)) inv); L = 1 gives NaN.
+ *   A source row of an empty slot is (float)0, or (float)((0 - 0) inv).
+ *   stats (B, J + 2) float64 on the device = [g_0 .. g_{J-1} | mean(m) | inv]; always written, never read back by the library.
+ * rtfs_mix_plan (host only, no device call, the single place with the arithmetic): slots = B * J records of RTFS_MIX_RECIPE_WORDS = 8
+ *   int64 words, row-major [source address (0: an empty slot) | source length in samples | dtype RTFS_MIX_F32 / RTFS_MIX_I16 | start
+ *   sample | reference source address (0: none) | its length | its dtype | its start sample], a = B * J factors -> *ws_bytes and, when
+ *   table is not NULL, the B * J * RTFS_MIX_TABLE_WORDS = 4 int64 words rtfs_mix_f32 reads FROM DEVICE MEMORY (the caller uploads them
+ *   once), per slot [address of the segment's first sample (0: empty) | address of the reference's first sample (0: none) | the bits
+ *   of a | (segment is int16) + 2 (reference is int16)].  Refusals return -4, write nothing else and name themselves in
+ *   refused[2] = [row * J + slot or -1 | RTFS_MIX_* reason]: B < 1, a missing array, a grid that would not fit (BAD_ARGUMENT); L outside
+ *   [1, RTFS_MIX_MAX_LENGTH] (BAD_LENGTH); n_out outside [0, J] (BAD_N_OUT); a segment or reference that leaves its source
+ *   (SEGMENT_RANGE / REFERENCE_RANGE); a row whose slots are all empty (EMPTY_ROW, slot 0 of the row); an address that is misaligned
+ *   for its dtype (MISALIGNED); an unknown dtype (BAD_DTYPE).  table, ws_bytes, refused may be NULL.
+ * rtfs_mix_workspace_bytes: B * ceil(L / RTFS_MIX_CHUNK) * RTFS_MIX_MOMENTS doubles; 0 for sizes the plan refuses.
+ * rtfs_mix_f32 (two launches): pass 1, one workgroup per (row, chunk of RTFS_MIX_CHUNK samples), writes the chunk's RTFS_MIX_MOMENTS
+ *   float64 partial moments into ws: [sum x_j (J) | E(ref_j) (J) | sum x_i x_j, i <= j, row-major (the diagonal is E(x_j))]; the square
+ *   or product of two float32 values is exact in double.  Pass 2 re-reduces its row's partials in a fixed order (L is bounded so that
+ *   a row has at most 256 chunks, one per thread), forms the gains and sum m = sum_j g_j sum x_j, sum m^2 = g^T G g, hence mean and
+ *   deviation without a pass over m, and writes the outputs: 16-byte stores on each output row's own 16-byte grid, scalar head and
+ *   tail.  mixture (B,L), sources (B,n_out,L) (may be NULL with n_out = 0) 4-byte aligned; stats, ws, table 8-byte aligned (-4);
+ *   ws_bytes below the query: -2; sizes the plan refuses: -1; all before any launch.  Caller's stream, no allocation, nothing read
+ *   back, no atomics: the same inputs give the same bits.  The launches trust the device table: pass what rtfs_mix_plan wrote. */
+#define RTFS_MIX_MAX_SOURCES 4
+#define RTFS_MIX_CHUNK 4096
+#define RTFS_MIX_MAX_LENGTH (1 << 20)
+#define RTFS_MIX_RECIPE_WORDS 8
+#define RTFS_MIX_TABLE_WORDS 4
+#define RTFS_MIX_MOMENTS 18
+#define RTFS_MIX_F32 0
+#define RTFS_MIX_I16 1
+#define RTFS_MIX_BAD_ARGUMENT 1
+#define RTFS_MIX_BAD_LENGTH 2
+#define RTFS_MIX_BAD_N_OUT 3
+#define RTFS_MIX_SEGMENT_RANGE 4
+#define RTFS_MIX_REFERENCE_RANGE 5
+#define RTFS_MIX_EMPTY_ROW 6
+#define RTFS_MIX_MISALIGNED 7
+#define RTFS_MIX_BAD_DTYPE 8
+size_t rtfs_mix_workspace_bytes(int B, int L);
+int rtfs_mix_plan(const long long* slots, const double* a, int B, int L, int n_out, long long* table, size_t* ws_bytes, int* refused);
+int rtfs_mix_f32(const long long* table, float* mixture, float* sources, double* stats, int B, int L, int n_out, int normalize, double eps,
+                 void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

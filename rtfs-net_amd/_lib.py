@@ -189,6 +189,9 @@ SIGNATURES = {
     "rtfs_live_resample_f32": (_i, [_p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _p]),
     "rtfs_live_resample_i16": (_i, [_p, _p, _p, _p, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _p]),
     "rtfs_live_resample_reset": (_i, [_p, _p, _i, _i, _i, _p]),
+    "rtfs_mix_workspace_bytes": (_z, [_i, _i]),
+    "rtfs_mix_plan": (_i, [_p, _p, _i, _i, _i, _p, C.POINTER(C.c_size_t), _p]),
+    "rtfs_mix_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_double, _p, _z, _p]),
 }
 
 _lib = None

@@ -6,6 +6,9 @@
                                      ``src/datas/transform.py``: on ``uint8`` device ROIs a pipeline is ONE ``rtfs_lips_prepare_u8`` launch
 * ``mouth_affine`` / ``mouth_rois``  ``RTFSNet_file.py:20-73, 111-118`` (``align_face``, lip box, ``cv2.resize``, grey) as one affine map per
                                      (frame, face) and ONE ``rtfs_mouth_rois_u8`` launch on whole camera frames (``csrc/k_mouth.hip``)
+* ``MixRecipe`` / ``draw_mix_recipe`` / ``mix_batch``   training mixtures formed on the device: ``System.online_mixing_collate``
+                                     (``src/system/core.py:183-202``) and target + interferers at a drawn SNR, a host plan and TWO launches
+                                     of ``rtfs_mix_f32`` (``csrc/k_mix.hip``)
 
 All arithmetic runs in ``librtfs_amd.so`` (``csrc/k_prep.hip``); there is no host fallback.  ``tests/prep_oracle.py`` restates the three
 in float64 numpy."""
@@ -22,7 +25,7 @@ from . import _lib
 
 __all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
            "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams", "frame_rate_of", "frame_rate_map",
-           "timestamp_map", "mouth_affine", "mouth_rois"]
+           "timestamp_map", "mouth_affine", "mouth_rois", "MixRecipe", "draw_mix_recipe", "mix_batch"]
 
 CROP = 88
 MAX_RATIO = 640
@@ -399,6 +402,152 @@ def normalize_tensor_wav(wav_tensor, eps=1e-8, std=None):
         s = s.expand(*wav_tensor.shape[:-1], 1).reshape(-1).contiguous()
     out, _ = _normalize(rows, None, s, eps)
     return out.reshape(wav_tensor.shape)
+
+
+# ---------------------------------------------------------------- training mixtures (DESIGN.md "Training mixtures")
+MIX_MAX_SOURCES, MIX_CHUNK, MIX_MAX_LENGTH = 4, 4096, 1 << 20  # RTFS_MIX_MAX_SOURCES, RTFS_MIX_CHUNK, RTFS_MIX_MAX_LENGTH
+MIX_RECIPE_WORDS, MIX_TABLE_WORDS = 8, 4                        # RTFS_MIX_RECIPE_WORDS, RTFS_MIX_TABLE_WORDS
+MIX_REASONS = {1: "a bad argument", 2: f"length outside [1, {MIX_MAX_LENGTH}]", 3: f"n_out outside [0, {MIX_MAX_SOURCES}]",
+               4: "a segment that leaves its source", 5: "a reference segment that leaves its source", 6: "a row whose slots are all empty",
+               7: "a source address that is misaligned for its dtype", 8: "an unknown dtype"}
+
+
+class MixRecipe:
+    """Which segments make up every row of a batch of mixtures: plain host arrays (B, J), J <= 4, per (row, slot).
+    ``src``: index into the list of sources, -1 for an empty slot; ``start``: first sample of the segment; ``a``: the slot's factor
+    (float64); ``ref_src`` / ``ref_start``: the reference segment whose energy the slot is scaled to, -1 / 0 for none.  The gain of a
+    slot is a, or a sqrt(E(ref) / E(segment)) with a reference (``rtfs_mix_plan``)."""
+
+    def __init__(self, src, start, a, ref_src=None, ref_start=None):
+        import numpy as np
+        try:
+            self.src = np.array(src, dtype=np.int64)
+            self.start = np.array(start, dtype=np.int64)
+            self.a = np.array(a, dtype=np.float64)
+            self.ref_src = np.full(self.src.shape, -1, np.int64) if ref_src is None else np.array(ref_src, dtype=np.int64)
+            self.ref_start = np.zeros(self.src.shape, np.int64) if ref_start is None else np.array(ref_start, dtype=np.int64)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("MixRecipe: src, start, ref_src, ref_start are integer arrays (B, J) and a a float array (B, J)") from None
+        if self.src.ndim != 2 or self.src.shape[0] < 1 or not 1 <= self.src.shape[1] <= MIX_MAX_SOURCES or \
+                any(v.shape != self.src.shape for v in (self.start, self.a, self.ref_src, self.ref_start)):
+            raise ValueError(f"MixRecipe: five arrays of one shape (B, J) with B >= 1 and 1 <= J <= {MIX_MAX_SOURCES}; got "
+                             f"{[tuple(v.shape) for v in (self.src, self.start, self.a, self.ref_src, self.ref_start)]}")
+
+    @property
+    def shape(self):
+        return tuple(int(v) for v in self.src.shape)
+
+    def __repr__(self):
+        return f"MixRecipe(B={self.shape[0]}, J={self.shape[1]})"
+
+    @classmethod
+    def snr(cls, targets, interferers, starts, snr_db):
+        """The target-speaker recipe.  targets (B) source indices, interferers (B, K) source indices (-1: none), starts (B, 1 + K),
+        snr_db a scalar, (B) or (B, K).  Slot 0 is the target with a = 1 and no reference; slot j >= 1 an interferer whose reference
+        is the row's target segment, with a = 10^(-snr_db / 20): the target lies snr_db above that interferer."""
+        import numpy as np
+        try:
+            t = np.array(targets, dtype=np.int64).reshape(-1)
+            k = np.array(interferers, dtype=np.int64).reshape(t.shape[0], -1)
+            s = np.array(starts, dtype=np.int64).reshape(t.shape[0], -1)
+            db = np.array(snr_db, dtype=np.float64)
+            db = np.broadcast_to(db[:, None] if db.ndim == 1 else db, k.shape)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("MixRecipe.snr: targets (B), interferers (B, K), starts (B, 1 + K), snr_db a scalar, (B) or (B, K)") from None
+        if s.shape != (t.shape[0], 1 + k.shape[1]):
+            raise ValueError(f"MixRecipe.snr: starts must be {(t.shape[0], 1 + k.shape[1])}; got {s.shape}")
+        src = np.concatenate([t[:, None], k], axis=1)
+        a = np.concatenate([np.ones((t.shape[0], 1)), 10.0 ** (-db / 20.0)], axis=1)
+        ref = np.concatenate([np.full((t.shape[0], 1), -1, np.int64), np.where(k >= 0, t[:, None], -1)], axis=1)
+        ref_start = np.concatenate([np.zeros((t.shape[0], 1), np.int64), np.where(k >= 0, s[:, :1], 0)], axis=1)
+        return cls(src, s, a, ref, ref_start)
+
+
+def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1, rng=None):
+    """A drawn target-speaker recipe (``MixRecipe.snr``) for ``batch`` rows of ``length`` samples out of utterances of ``lengths``
+    samples: per row ``n_src`` distinct utterances (the first is the target), per utterance a uniform start that is a multiple of
+    ``align``, per interferer a uniform SNR in ``snr_db`` = (low, high).  Draws come from ``rng`` (a ``random.Random``) or the ``random``
+    module, per row in the order utterances, starts, SNRs.  An utterance shorter than ``length`` is never drawn; ValueError if fewer
+    than ``n_src`` are long enough."""
+    r = random if rng is None else rng
+    batch, length, n_src, align = operator.index(batch), operator.index(length), operator.index(n_src), operator.index(align)
+    lengths = [operator.index(n) for n in lengths]
+    lo, hi = (float(v) for v in snr_db)
+    if batch < 1 or length < 1 or align < 1 or not 1 <= n_src <= MIX_MAX_SOURCES:
+        raise ValueError(f"draw_mix_recipe: batch, length, align >= 1 and 1 <= n_src <= {MIX_MAX_SOURCES}")
+    pool = [i for i, n in enumerate(lengths) if n >= length]
+    if len(pool) < n_src:
+        raise ValueError(f"draw_mix_recipe: {len(pool)} of {len(lengths)} utterance(s) hold {length} samples; a row needs {n_src} distinct ones")
+    rows, starts, dbs = [], [], []
+    for _ in range(batch):
+        row = r.sample(pool, n_src)
+        rows.append(row)
+        starts.append([align * r.randint(0, (lengths[i] - length) // align) for i in row])
+        dbs.append([r.uniform(lo, hi) for _ in row[1:]])
+    return MixRecipe.snr([row[0] for row in rows], [row[1:] for row in rows], starts, dbs)
+
+
+def _mix_plan(sources, recipe, length, n_out):
+    """Everything of a ``mix_batch`` call that needs no launch -> (host table (B*J*4) int64, workspace bytes, B, n_out, device)."""
+    import numpy as np
+    if not isinstance(recipe, MixRecipe):
+        raise ValueError(f"mix_batch: recipe must be a MixRecipe; got {type(recipe).__name__}")
+    sources = list(sources)
+    device = None
+    for i, s in enumerate(sources):
+        if not isinstance(s, torch.Tensor) or not s.is_cuda or s.ndim != 1 or s.dtype not in (torch.float32, torch.int16) or \
+                (s.numel() > 1 and s.stride(0) != 1):
+            raise ValueError(f"mix_batch: source {i} must be a 1-D float32 or int16 tensor on the device with adjacent samples (there is "
+                             f"no CPU fallback); got {(tuple(s.shape), s.dtype, s.device) if isinstance(s, torch.Tensor) else type(s).__name__}")
+        device = s.device if device is None else device
+        if s.device != device:
+            raise ValueError(f"mix_batch: source {i} lies on {s.device}, source 0 on {device}")
+    if not sources:
+        raise ValueError("mix_batch: no sources")
+    B, Jr = recipe.shape
+    L = operator.index(length)
+    n_out = Jr if n_out is None else operator.index(n_out)
+    if max(int(recipe.src.max()), int(recipe.ref_src.max())) >= len(sources) or min(int(recipe.src.min()), int(recipe.ref_src.min())) < -1:
+        raise ValueError(f"mix_batch: the recipe names a source outside [-1, {len(sources)})")
+    addr = np.array([s.data_ptr() for s in sources] + [0], dtype=np.int64)  # index -1: the empty slot
+    size = np.array([s.numel() for s in sources] + [0], dtype=np.int64)
+    kind = np.array([1 if s.dtype == torch.int16 else 0 for s in sources] + [0], dtype=np.int64)
+    slots = np.zeros((B, MIX_MAX_SOURCES, MIX_RECIPE_WORDS), np.int64)
+    a = np.zeros((B, MIX_MAX_SOURCES), np.float64)
+    for w, (idx, start) in enumerate(((recipe.src, recipe.start), (recipe.ref_src, recipe.ref_start))):
+        slots[:, :Jr, 4 * w], slots[:, :Jr, 4 * w + 1], slots[:, :Jr, 4 * w + 2] = addr[idx], size[idx], kind[idx]
+        slots[:, :Jr, 4 * w + 3] = start
+    a[:, :Jr] = recipe.a
+    table = _lib.empty(B * MIX_MAX_SOURCES * MIX_TABLE_WORDS, device="cpu", dtype=torch.int64)  # host table, every word written by the plan
+    ws, refused = C.c_size_t(0), (C.c_int * 2)(-1, 0)
+    code = _lib.load().rtfs_mix_plan(C.c_void_p(slots.ctypes.data), C.c_void_p(a.ctypes.data), B, min(max(L, -1), 1 << 30),
+                                     min(max(n_out, -1), 1 << 30), _lib.ptr(table), C.byref(ws), refused)
+    if code != 0:
+        where = "" if refused[0] < 0 else f" at row {refused[0] // MIX_MAX_SOURCES}, slot {refused[0] % MIX_MAX_SOURCES}"
+        raise ValueError(f"mix_batch: {MIX_REASONS.get(refused[1], 'refused')}{where} (B {B}, length {L}, n_out {n_out})")
+    return table, int(ws.value), B, n_out, device
+
+
+def mix_batch(sources, recipe, length, n_out=None, normalize=False, eps=1e-8, return_stats=False):
+    """Training mixtures formed on the device (``rtfs_mix_f32``; DESIGN.md "Training mixtures"): a host plan, one table upload and TWO
+    launches, nothing read back.  ``sources``: a list of 1-D device tensors, float32 or int16 PCM (taken as s / 32768), of any lengths;
+    views at any offset are read where they lie, nothing is copied.  ``recipe``: a ``MixRecipe`` (B, J).  Returns mixture (B, length) and
+    sources (B, n_out, length), the first ``n_out`` (default J) scaled slots of every row, plus ``stats`` (B, 6) float64
+    [the four gains | the mixture's mean | 1 / (std + eps)] with ``return_stats``.  ``normalize``: the dataset's joint normalisation
+    (``normalize_mixture``) in the same two launches.  There is no CPU fallback; what ``rtfs_mix_plan`` refuses (a segment that leaves
+    its source, an empty row, length outside [1, 2^20], n_out outside [0, 4]) and sources that are not float32 / int16 device vectors
+    raise ValueError before anything is launched."""
+    table, nbytes, B, n_out, dev = _mix_plan(sources, recipe, length, n_out)
+    L, lib = int(length), _lib.load()
+    tab = table.to(dev)  # the one host-to-device copy of the call
+    mixture = _lib.empty(B, L, device=dev)
+    out = _lib.empty(B, n_out, L, device=dev)
+    stats = _lib.empty(B, MIX_MAX_SOURCES + 2, device=dev, dtype=torch.float64)
+    ws = _lib.workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rtfs_mix_f32(_lib.ptr(tab), _lib.ptr(mixture), _lib.ptr(out) if n_out else None, _lib.ptr(stats), B, L, n_out,
+                                    1 if normalize else 0, float(eps), _lib.ptr(ws), nbytes, _lib.stream_of(tab)), "rtfs_mix_f32")
+    return (mixture, out, stats) if return_stats else (mixture, out)
 
 
 # ---------------------------------------------------------------- mouth-ROI transforms (src/datas/transform.py)

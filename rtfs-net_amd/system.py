@@ -309,6 +309,68 @@ class System(nn.Module):
                 out[1] = t.reshape(targets.shape)
         return type(batch)(out) if isinstance(batch, (list, tuple)) else out
 
+    @staticmethod
+    def online_mixing_collate(batch, perms=None, generator=None):
+        """core.py:183-202 on the device: batch = (inputs, targets (B,n_src,L)) -> (inputs, targets).  For every source index i in the
+        order 0 .. n_src - 1 a permutation p_i of the batch is taken from ``perms[i]`` or drawn with ``torch.randperm(B,
+        generator=generator)`` on the CPU - the reference's call and order, so the same ``torch.manual_seed`` gives the same
+        permutations.  New source i of row b is ``targets[p_i[b], i]`` scaled to the energy of ``targets[b, i]`` (no eps: a silent
+        source gives inf / NaN, as there), the new input their sum.  ONE ``datas.mix_batch`` call: the segments are rows of ``targets``
+        addressed where they lie, the references the rows they replace.  n_src <= 4, L <= 2^20, float32 on the device (ValueError)."""
+        from . import datas
+        _, targets = batch
+        if not isinstance(targets, torch.Tensor) or targets.ndim != 3 or not targets.is_cuda or targets.dtype != torch.float32:
+            raise ValueError("System.online_mixing_collate: targets must be a float32 device tensor (B,n_src,L); there is no CPU fallback")
+        B, n_src, L = (int(v) for v in targets.shape)
+        if perms is not None and len(perms) != n_src:
+            raise ValueError(f"System.online_mixing_collate: {len(perms)} permutation(s) for {n_src} source(s)")
+        src, ref = [], []
+        for i in range(n_src):
+            p = [int(v) for v in (torch.randperm(B, generator=generator) if perms is None else perms[i])]
+            if sorted(p) != list(range(B)):
+                raise ValueError(f"System.online_mixing_collate: perms[{i}] is no permutation of 0 .. {B - 1}")
+            src.append([(q * n_src + i) * L for q in p])
+            ref.append([(b * n_src + i) * L for b in range(B)])
+        zeros = [[0] * n_src for _ in range(B)]
+        recipe = datas.MixRecipe(zeros, [list(r) for r in zip(*src)], [[1.0] * n_src for _ in range(B)], zeros, [list(r) for r in zip(*ref)])
+        return datas.mix_batch([targets.contiguous().reshape(-1)], recipe, L, n_out=n_src)
+
+    def mix_batch(self, sources, mouth_rois, length=32000, n_src=2, snr_db=(-5.0, 5.0), normalize_audio=False, train=True, rng=None,
+                  recipe=None):
+        """A fresh target-speaker training batch from a pool of utterances, formed on the device: sources = R 1-D device tensors
+        (float32 or int16 PCM at 16 kHz), mouth_rois = their R uint8 ROI tracks (Tv_r,H,W) at 25 fps -> the reference-shaped batch
+        (inputs (B,L), targets (B,L), target_mouths (B,1,Tv,88,88), keys) that ``common_step`` and ``optimization_step`` take as is.
+        ``recipe``: a ``datas.MixRecipe``, or None to draw one (``datas.draw_mix_recipe(..., align=640)``, so every start lies on a video
+        frame) from ``rng`` or ``random``: ``config["training"]["batch_size"]`` rows (default 4), per row a target and ``n_src - 1``
+        interferers at SNRs uniform in ``snr_db``.  Mixture and target come from ONE ``datas.mix_batch`` (``n_out`` 1;
+        ``normalize_audio``: the dataset's joint normalisation in the same two
+        launches).  The target's ROI track is sliced at start / 640 for length // 640 frames (ValueError if it is too short), the
+        slices are stacked and prepared by the ``"train"`` / ``"val"`` pipeline with the same ``rng``.  ``keys``: the target indices."""
+        from . import datas
+        sources, mouth_rois = list(sources), list(mouth_rois)
+        if len(mouth_rois) != len(sources):
+            raise ValueError(f"System.mix_batch: {len(sources)} utterance(s) and {len(mouth_rois)} ROI track(s)")
+        if recipe is None:
+            B = int(self.config.get("training", {}).get("batch_size", 4))  # the yaml's training.batch_size
+            recipe = datas.draw_mix_recipe([int(s.shape[0]) for s in sources], B, length, n_src=n_src, snr_db=snr_db, align=640, rng=rng)
+        Tv = int(length) // 640
+        keys = [int(t) for t in recipe.src[:, 0]]
+        if Tv < 1:
+            raise ValueError(f"System.mix_batch: length {length} holds no video frame")
+        tracks = []
+        for b, t in enumerate(keys):
+            if t < 0:
+                raise ValueError(f"System.mix_batch: row {b} has no target in slot 0")
+            roi, f0 = mouth_rois[t], int(recipe.start[b, 0]) // 640
+            if not isinstance(roi, torch.Tensor) or roi.dtype != torch.uint8 or roi.ndim != 3 or roi.shape[0] < f0 + Tv:
+                raise ValueError(f"System.mix_batch: ROI track {t} must be uint8 (Tv,H,W) with at least {f0 + Tv} frames for a segment "
+                                 f"that starts at sample {int(recipe.start[b, 0])}; got "
+                                 f"{(tuple(roi.shape), roi.dtype) if isinstance(roi, torch.Tensor) else type(roi).__name__}")
+            tracks.append(roi[f0:f0 + Tv])
+        inputs, targets = datas.mix_batch(sources, recipe, length, n_out=1, normalize=normalize_audio)
+        lips = datas.get_preprocessing_pipelines()["train" if train else "val"](torch.stack(tracks), rng=rng)
+        return inputs, targets[:, 0], lips, keys
+
     def forward_grouped(self, wav, mouth=None):
         """``forward`` for a batch that may list each mixture once per target speaker, as the reference's test batches do (test.py:128-140,
         avspeech_dataset.py:81-84: n_src 1, no shuffling, the entries of one mixture side by side).  wav (N,L) or (N,1,L) -> (N,1,L) in
@@ -340,6 +402,8 @@ class System(nn.Module):
             est_targets = self.audio_model(inputs, mouth_emb)
         elif self.video_model is None:
             inputs, targets, _ = batch
+            if self.config.get("training", {}).get("online_mix"):  # core.py:96-97
+                inputs, targets = self.online_mixing_collate((batch[0], batch[1]))
             est_targets = self(inputs)
         else:
             inputs, targets, target_mouths, _ = batch

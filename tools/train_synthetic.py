@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--optimizer", choices=["torch", "fused"], default="torch", help="fused: rtfs_net_amd.optimizers.AdamW (gather, one "
                     "all-reduce on its flat buffer, clip + update in two launches)")
+    ap.add_argument("--online-mix", action="store_true", help="every step's batch is formed on the device by System.mix_batch from a "
+                    "synthetic pool of utterances and ROI tracks (target + one interferer at a drawn SNR and crop; needs the video model)")
     a = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -40,13 +42,28 @@ def main():
     model = R.AVNet(print_macs=False, **conf).cuda().train()
     loss = R.losses.PITLossWrapper(R.losses.PairwiseNegSDR("snr"), pit_from="pw_mtx")
     opt = (R.optimizers.AdamW if a.optimizer == "fused" else torch.optim.AdamW)(model.parameters(), lr=a.lr, weight_decay=0.1)
-    system = R.System(audio_model=model, loss_func={"train": loss, "val": loss}, optimizer=opt)
+    video = R.FRCNNVideoModel(print_macs=False).cuda().eval() if a.online_mix else None
+    system = R.System(audio_model=model, video_model=video, loss_func={"train": loss, "val": loss}, optimizer=opt,
+                      config={"training": {"batch_size": a.batch}})
     if world > 1:
         system.convert_sync_batchnorm()  # train.py:145 sync_batchnorm=True
     g = torch.Generator().manual_seed(1234 + rank)  # every rank its own shard
     L, Tv = int(16000 * a.seconds), int(25 * a.seconds)
+    if a.online_mix:  # 16 utterances of 3 .. 12 s with their 25 fps ROI tracks; the draws of every rank come from its own seed
+        import random
+        rng = random.Random(1234 + rank)
+        secs = [3 + (9 * i) // 15 for i in range(16)]
+        pool = [(0.05 * torch.randn(16000 * s, generator=g)).cuda() for s in secs]
+        rois = [torch.randint(0, 256, (25 * s, 96, 96), generator=g, dtype=torch.uint8).cuda() for s in secs]
     t0 = time.time()
     for step in range(a.steps):
+        if a.online_mix:
+            value = system.optimization_step(system.mix_batch(pool, rois, length=L - L % 640, rng=rng), step)
+            if rank == 0 and (step % 5 == 0 or step == a.steps - 1):
+                torch.cuda.synchronize()
+                print(f"step {step:4d}  loss {float(value):8.4f}  {(time.time() - t0) / (step + 1) * 1e3:7.1f} ms/step  world {world}  "
+                      f"online mix", flush=True)
+            continue
         s1, s2 = 0.05 * torch.randn(a.batch, L, generator=g), 0.05 * torch.randn(a.batch, L, generator=g)
         batch = ((s1 + s2).cuda(), s1.unsqueeze(1).cuda(), torch.randn(a.batch, 512, Tv, generator=g).cuda(), None)
         value = system.optimization_step(batch, step)
