@@ -589,6 +589,50 @@ size_t rtfs_estoi_many_workspace_bytes(const int* plan, int R, int with_classic)
 int rtfs_estoi_many_f32(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
                         void* ws, size_t ws_bytes, float* d_ext, float* d_classic /* NULL: not wanted */, int* kept_frames, void* stream);
 
+/* BSS-eval SDR: the SDR column of mir_eval.separation.bss_eval_sources / fast_bss_eval, the ratio after the estimate has been projected
+ * onto the F = 512 delayed copies of the true source, so that a fixed delay or a short linear distortion is allowed (the "sdr" figure
+ * of rtfs_sdr_many_f32 and of the reference's tracker is plain SNR: one sample of delay ruins it).  Definition, for a reference s and
+ * an estimate e of L >= 1 float32 samples, ALL arithmetic in float64, F = 512 fixed (mir_eval's default), no mean removal:
+ *     r[k] = sum_t s[t] s[t+k],  d[k] = sum_t s[t] e[t+k],  k = 0 .. 511 (terms past the end are absent; the products are exact)
+ *     G = Toeplitz(r),  G c = d,  num = c'd,  ee = sum e^2,  den = max(ee - num, 0),  SDR = 10 log10(num / den)
+ *   IEEE as it comes: +inf for den = 0 < num, -inf for num = 0 < den, NaN for 0 / 0.  This equals mir_eval's
+ *   |s_target|^2 / |e_pad - s_target|^2 with s_target = s * c, the full convolution of length L + 511, and e zero-padded to that length.
+ *   Solver: Levinson-Durbin.  Stop rule: when the prediction error at order k is <= r[0] 2^-46, or r[0] = 0, the recursion stops and taps
+ *   k .. 511 are 0 (a silent reference gives c = 0: -inf, or NaN for a silent estimate as well).  It is a guard, not a measurement.
+ *   Sources: with n_src = n <= 4 all n^2 values SDR(e_i, s_j) are formed (the estimates scored against s_j share G_j); the permutation
+ *   maximises the mean SDR over the sources, scanned in itertools order, first maximum (fast_bss_eval's rule; mir_eval chooses by SIR,
+ *   which needs the joint projection and is not computed here).  perm[b][j] = the estimate assigned to clean source j, the convention of
+ *   rtfs_pit_pairwise_sdr_f32; sdr[b][j] = SDR(e_perm[b][j], s_j) in positive dB.  With a mixture the baseline of source j is
+ *   SDR(mix, s_j) and sdr_i[b][j] = sdr[b][j] - baseline[j] (subtracted in float64, stored as float32).
+ *   Agreement with the mir_eval package itself is not measured (it is not installed where this project is developed); the definition
+ *   is tests/bss_oracle.py.
+ * Work cut (three launches): correlation partials per (chunk of 4096 samples from the recording's own start, clean source, 256 lags),
+ *   one writer each; per (recording, clean source) a fold of the partials in chunk order and the recursion for all right-hand sides at
+ *   once; per recording the matrix, the search and the outputs.  No atomics: a row's bits depend on neither batch, pool nor scheduling.
+ * rtfs_bss_sdr_f32: clean, est (B, n_src, L), mix (B, L) or NULL -> sdr (B, n_src) float32, sdr_i (B, n_src) float32 (required with mix,
+ *   untouched without), perm (B, n_src) int32.  It allocates, uploads and reads back nothing: capturable in a graph.  Refused before any
+ *   launch: -4 for a NULL pointer (mix excepted; sdr_i only with mix), B < 1, L < 1 or n_src outside 1 .. 4; -1 when B * ceil(L / 4096) *
+ *   n_src * 2 workgroups exceed 2^31 - 1; -2 for a workspace below rtfs_bss_sdr_workspace_bytes(B, n_src, L, mix != NULL) (0 for
+ *   arguments the call refuses; a workspace sized with_mix = 1 also serves a call without).
+ * rtfs_bss_sdr_many_f32: the same for R recordings of different lengths on rtfs_score_many_plan's table, of which it uses columns 0 and
+ *   10 only; arguments, checks and codes as rtfs_stoi_many_f32 (mixes may be NULL, then sdr_i is untouched).  The workspace is its own,
+ *   rtfs_bss_sdr_many_workspace_bytes(plan, R, with_mix) (0 for a NULL plan or one not made for R recordings): RTFS_SCORE_COLS and the
+ *   regions of the plan's workspace do not move.  The kernels are those of rtfs_bss_sdr_f32, so row r is BIT-EQUAL to that call on
+ *   recording r alone.  Not capturable (table upload).
+ * rtfs_debug_bss_f64: rtfs_bss_sdr_f32 that also copies out, per (row b, clean source j) at index b n_src + j, the folded r_j (512
+ *   doubles), the d rows (NR = n_src + (mix != NULL) rows of 512: the estimates, then the mixture), the ee values (NR) and the order
+ *   the recursion reached (int32; 512 = the guard did not fire).  form: 0 = the production solver, 512 = one thread per tap (two
+ *   barriers per order), 64 = a single wave with 8 taps per lane; -4 for another value or a NULL debug pointer. */
+size_t rtfs_bss_sdr_workspace_bytes(int B, int n_src, int L, int with_mix);
+int rtfs_bss_sdr_f32(const float* clean, const float* est, const float* mix /* NULL: no baseline */, int B, int n_src, int L, void* ws,
+                     size_t ws_bytes, float* sdr, float* sdr_i, int* perm, void* stream);
+size_t rtfs_bss_sdr_many_workspace_bytes(const int* plan, int R, int with_mix);
+int rtfs_bss_sdr_many_f32(const float* const* mixes /* NULL: no baseline */, const float* const* cleans, const float* const* ests,
+                          const int* table, const int* plan, int R, int n_src, int fs, void* ws, size_t ws_bytes, float* sdr, float* sdr_i,
+                          int* perm, void* stream);
+int rtfs_debug_bss_f64(const float* clean, const float* est, const float* mix, int B, int n_src, int L, void* ws, size_t ws_bytes, float* sdr,
+                       float* sdr_i, int* perm, int form, double* r_out, double* d_out, double* ee_out, int* order_out, void* stream);
+
 /* Long recordings in overlapping windows on the fused separator (AVNet.separate_long; no reference counterpart: infer_any_video.py:63-86
  * hands a whole track to one forward).  SPF = 640 samples per video frame (16 kHz, 25 fps).  A recording of L samples is cut into N
  * windows of `window` samples every `hop` samples; window n covers samples [n hop, n hop + window) (zeros past L) and video frames

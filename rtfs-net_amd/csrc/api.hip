@@ -1656,6 +1656,25 @@ int rtfs_sdr_many_f32(const float* const* mixes, const float* const* cleans, con
     return launch_sdr_many(mixes, cleans, ests, table, plan, R, n_src, fs, ws, ws_bytes, out, perm, (hipStream_t)stream);
 }
 
+size_t rtfs_bss_sdr_workspace_bytes(int B, int n_src, int L, int with_mix) { return bss_sdr_workspace_bytes(B, n_src, L, with_mix); }
+int rtfs_bss_sdr_f32(const float* clean, const float* est, const float* mix, int B, int n_src, int L, void* ws, size_t ws_bytes, float* sdr,
+                     float* sdr_i, int* perm, void* stream) {
+    return launch_bss_sdr(clean, est, mix, B, n_src, L, ws, ws_bytes, sdr, sdr_i, perm, BssDebug{nullptr, nullptr, nullptr, nullptr, 0},
+                          (hipStream_t)stream);
+}
+size_t rtfs_bss_sdr_many_workspace_bytes(const int* plan, int R, int with_mix) { return bss_sdr_many_workspace_bytes(plan, R, with_mix); }
+int rtfs_bss_sdr_many_f32(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan,
+                          int R, int n_src, int fs, void* ws, size_t ws_bytes, float* sdr, float* sdr_i, int* perm, void* stream) {
+    return launch_bss_sdr_many(mixes, cleans, ests, table, plan, R, n_src, fs, ws, ws_bytes, sdr, sdr_i, perm,
+                               BssDebug{nullptr, nullptr, nullptr, nullptr, 0}, (hipStream_t)stream);
+}
+int rtfs_debug_bss_f64(const float* clean, const float* est, const float* mix, int B, int n_src, int L, void* ws, size_t ws_bytes, float* sdr,
+                       float* sdr_i, int* perm, int form, double* r_out, double* d_out, double* ee_out, int* order_out, void* stream) {
+    if (!r_out || !d_out || !ee_out || !order_out) return RTFS_ERR_ARG;
+    return launch_bss_sdr(clean, est, mix, B, n_src, L, ws, ws_bytes, sdr, sdr_i, perm, BssDebug{r_out, d_out, ee_out, order_out, form},
+                          (hipStream_t)stream);
+}
+
 int rtfs_longform_plan(int L, int Tv, int window, int hop, int* N) { return longform_plan(L, Tv, window, hop, N); }
 int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
                             void* stream) {

@@ -404,6 +404,24 @@ size_t estoi_many_workspace_bytes(const int* plan, int R, int with_classic);
 int launch_estoi_many(const float* const* cleans, const float* const* ests, const int* table, const int* plan, int R, int n_src, int fs,
                       void* ws, size_t ws_bytes, float* d_ext, float* d_classic, int* kept, hipStream_t st);
 
+// BSS-eval SDR (k_bss.hip): 512-tap projection of every estimate (and the mixture) onto every clean source from float64 correlations,
+// Levinson-Durbin per clean source, permutation by the largest mean.  The pooled entry works on score_many_plan's table (columns 0 and
+// 10) with a workspace of its own.  BssDebug: optional copies of the folded r (rows n, 512), d (rows n, NR, 512), ee (rows n, NR) and the
+// order reached (rows n); form 0 = the production solver, 64 | 512 = that many threads per (recording, clean source).
+constexpr int BSS_TAPS = 512, BSS_CHUNK = 4096;
+struct BssDebug {
+    double *r, *d, *ee;
+    int* order;
+    int form;
+};
+size_t bss_sdr_workspace_bytes(int B, int n_src, int L, int with_mix);
+int launch_bss_sdr(const float* clean, const float* est, const float* mix, int B, int n_src, int L, void* ws, size_t ws_bytes, float* sdr,
+                   float* sdr_i, int* perm, const BssDebug& dbg, hipStream_t st);
+size_t bss_sdr_many_workspace_bytes(const int* plan, int R, int with_mix);
+int launch_bss_sdr_many(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan,
+                        int R, int n_src, int fs, void* ws, size_t ws_bytes, float* sdr, float* sdr_i, int* perm, const BssDebug& dbg,
+                        hipStream_t st);
+
 // long recordings in overlapping windows (k_longform.hip): window plan (host), framing of audio + video in one launch, cross-faded overlap-add
 int longform_plan(int L, int Tv, int window, int hop, int* N);
 // K lip tracks per recording (one track: K = 1): the audio window once, video_win (B*N*K, 512, window / SPF), target row (b*N + n)*K + k

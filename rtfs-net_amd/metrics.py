@@ -5,6 +5,8 @@
 (``rtfs_score_many_plan``, ``rtfs_stoi_many_f32``, ``rtfs_sdr_many_f32``; DESIGN.md, "Scoring many recordings of different lengths").
 ``estoi`` / ``estoi_many`` are extended STOI (``rtfs_estoi_f32`` / ``rtfs_estoi_many_f32``; DESIGN.md, "Extended STOI"), alone or
 together with classic STOI from the same band values; ``ALLMetricsTracker(..., estoi=True)`` adds it as a seventh column.
+``bss_sdr`` / ``bss_sdr_many`` are the SDR of BSS-eval (``rtfs_bss_sdr_f32`` / ``rtfs_bss_sdr_many_f32``, ``csrc/k_bss.hip``; DESIGN.md,
+"BSS-eval SDR"): the 512-tap projection in float64; ``ALLMetricsTracker(..., bss_sdr=True)`` adds it and its improvement as two columns.
 There is no CPU fallback.  PESQ (ITU-T P.862) is not implemented here: pass a host callable as ``pesq_fn`` (called as the reference
 calls ``pypesq.pesq``: ``pesq_fn(estimate, clean, 16000)`` on numpy rows) or the ``pesq`` column is NaN (and so are its mean and std).
 """
@@ -80,13 +82,62 @@ def estoi(clean, estimate, fs=16000, return_kept=False, with_classic=False):
     return out if len(out) > 1 else out[0]
 
 
+def _mirror(one, flat, *ts):
+    """(B,n) results in the rank the inputs came in: (B,) for (B,L) inputs, 0-d for (L,) inputs."""
+    if one:
+        return tuple(t[0, 0] for t in ts)
+    return tuple(t[:, 0] for t in ts) if flat else ts
+
+
+def bss_sdr(clean, estimate, mix=None, return_perm=False):
+    """BSS-eval SDR (the SDR of ``mir_eval.separation.bss_eval_sources`` with ``fast_bss_eval``'s permutation rule; definition:
+    include/rtfs_amd.h and DESIGN.md, "BSS-eval SDR") in positive dB: each estimate is projected onto the 512 delayed copies of each
+    clean source in float64, so a fixed delay or a short linear distortion is allowed.  clean / estimate float32 device tensors
+    (B,n_src,L), (B,L) or (L,), n_src <= 4; mix (B,L) or (L,) -> ``sdr`` float32 (B,n_src) in clean-source order after the permutation
+    that maximises the mean SDR (itertools order, first maximum); the input rank is mirrored as ``stoi`` does ((B,) and 0-d).  With
+    ``mix`` it returns ``(sdr, sdr_i)``, ``sdr_i = sdr - SDR(mix, clean)``; ``return_perm`` appends ``perm`` int32 (``perm[b][j]`` = the
+    estimate assigned to clean source j).  +inf, -inf and NaN come as IEEE gives them (a perfect estimate, a silent reference, a silent
+    estimate).  Three launches, no host copy: capturable in a graph.  ValueError before any launch for shape or dtype mismatches."""
+    ts = (clean, estimate) + (() if mix is None else (mix,))
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("bss_sdr: clean, estimate and mix must be tensors")
+    if clean.shape != estimate.shape or clean.ndim not in (1, 2, 3):
+        raise ValueError(f"bss_sdr: clean and estimate must have the same (B, n_src, L), (B, L) or (L,) shape, got {tuple(clean.shape)} "
+                         f"and {tuple(estimate.shape)}")
+    one, flat = clean.ndim == 1, clean.ndim < 3
+    B, n, L = (1, 1, clean.shape[0]) if one else (clean.shape[0], 1, clean.shape[1]) if flat else clean.shape
+    if mix is not None and tuple(mix.shape) != ((L,) if one else (B, L)):
+        raise ValueError(f"bss_sdr: mix must be {'(L,)' if one else '(B, L)'} = {(L,) if one else (B, L)}, got {tuple(mix.shape)}")
+    if not 1 <= n <= 4:
+        raise ValueError(f"bss_sdr: n_src must be 1 .. 4, got {n}")
+    if B < 1 or L < 1:
+        raise ValueError(f"bss_sdr: empty input {tuple(clean.shape)}")
+    if any(t.dtype != torch.float32 for t in ts):
+        raise ValueError(f"bss_sdr: the kernels are float32, got {[str(t.dtype) for t in ts]}")
+    if any(t.device != clean.device for t in ts):
+        raise ValueError(f"bss_sdr: the tensors lie on {[str(t.device) for t in ts]}")
+    _lib.need_gpu(*ts)
+    lib = _lib.load()
+    c, e = clean.reshape(B, n, L).contiguous(), estimate.reshape(B, n, L).contiguous()
+    m = None if mix is None else mix.reshape(B, L).contiguous()
+    sdr = _lib.empty(B, n, device=c.device, dtype=torch.float32)
+    sdr_i = None if m is None else _lib.empty(B, n, device=c.device, dtype=torch.float32)
+    perm = _lib.empty(B, n, device=c.device, dtype=torch.int32)
+    ws = _lib.workspace(lib.rtfs_bss_sdr_workspace_bytes(B, n, L, int(m is not None)), c.device)
+    _lib.check(lib.rtfs_bss_sdr_f32(_lib.ptr(c), _lib.ptr(e), _lib.ptr(m), B, n, L, _lib.ptr(ws), ws.numel(), _lib.ptr(sdr), _lib.ptr(sdr_i),
+                                    _lib.ptr(perm), _lib.stream_of(c)), "rtfs_bss_sdr_f32")
+    out = (sdr,) + (() if m is None else (sdr_i,)) + ((perm,) if return_perm else ())
+    out = _mirror(one, flat, *out)
+    return out if len(out) > 1 else out[0]
+
+
 class _ScorePool:
     """R recordings of different lengths, validated and planned for ``rtfs_stoi_many_f32`` / ``rtfs_sdr_many_f32``: everything that can
     be refused is refused here, as ValueError naming the recording, before any upload or launch.  ``mixes`` None: STOI only, clean and
-    estimate rows (L_r)|(1,L_r).  Otherwise mix (L_r)|(1,L_r) and clean / estimate (n_src,L_r).  ``both``: the workspace also holds the
-    tenth region ``estoi(with_classic=True)`` needs."""
+    estimate rows (L_r)|(1,L_r) -- with ``multi`` (BSS-eval SDR without a baseline) (L_r)|(n_src,L_r).  Otherwise mix (L_r)|(1,L_r) and
+    clean / estimate (n_src,L_r).  ``both``: the workspace also holds the tenth region ``estoi(with_classic=True)`` needs."""
 
-    def __init__(self, what, mixes, cleans, estimates, fs, keys=None, both=False):
+    def __init__(self, what, mixes, cleans, estimates, fs, keys=None, both=False, multi=False):
         try:
             cleans, estimates = list(cleans), list(estimates)
             mixes = None if mixes is None else list(mixes)
@@ -104,7 +155,11 @@ class _ScorePool:
             row = (cleans[r], estimates[r]) if mixes is None else (mixes[r], cleans[r], estimates[r])
             if not all(isinstance(t, torch.Tensor) for t in row):
                 raise ValueError(f"{what}: recording {r} is not made of tensors")
-            if mixes is None:
+            if mixes is None and multi:
+                if any(t.ndim not in (1, 2) for t in row):
+                    raise ValueError(f"{what}: clean and estimate {r} must be (L) or (n_src,L); got {[tuple(t.shape) for t in row]}")
+                cleans[r], estimates[r] = (t.reshape(1, -1) if t.ndim == 1 else t for t in row)
+            elif mixes is None:
                 flat = [t for t in row if t.ndim == 1 or (t.ndim == 2 and t.shape[0] == 1)]
                 if len(flat) != 2:
                     raise ValueError(f"{what}: clean and estimate {r} must be (L) or (1,L); got {[tuple(t.shape) for t in row]}")
@@ -184,6 +239,33 @@ class _ScorePool:
                    "rtfs_sdr_many_f32")
         return out, perm
 
+    def bss(self):
+        """-> (sdr (R,n), sdr_i (R,n) | None without mixtures, perm (R,n)); a workspace of its own, the pool's table (columns 0 and 10)"""
+        with_mix = self.mixes is not None
+        sdr = _lib.empty(self.R, self.n, device=self.device, dtype=torch.float32)
+        sdr_i = _lib.empty(self.R, self.n, device=self.device, dtype=torch.float32) if with_mix else None
+        perm = _lib.empty(self.R, self.n, device=self.device, dtype=torch.int32)
+        ws = _lib.workspace(self.lib.rtfs_bss_sdr_many_workspace_bytes(self.plan, self.R, int(with_mix)), self.device)
+        _lib.check(self.lib.rtfs_bss_sdr_many_f32(self.p_mix if with_mix else None, self.p_clean, self.p_est, self.p_table, self.plan, self.R,
+                                                  self.n, self.fs, _lib.ptr(ws), ws.numel(), _lib.ptr(sdr), _lib.ptr(sdr_i), _lib.ptr(perm),
+                                                  self.stream), "rtfs_bss_sdr_many_f32")
+        return sdr, sdr_i, perm
+
+
+def bss_sdr_many(cleans, estimates, mixes=None, return_perm=False):
+    """``bss_sdr`` for R recordings of different lengths in one pooled pass: cleans / estimates R float32 device tensors (n_src,L_r) or
+    (L_r), mixes None or R tensors (L_r)|(1,L_r) -> ``sdr`` (R,n_src) float32, with mixes ``(sdr, sdr_i)``, with ``return_perm`` ``perm``
+    (R,n_src) int32 appended.  Entry r is bit-equal to ``bss_sdr`` on recording r (the same kernels).  The pool is the one of
+    ``stoi_many`` (one planner call, one table upload, rows read where they lie), so STOI's length limits apply, 410 .. 2^26 samples,
+    and are named in the error; the workspace is the call's own.  Not capturable (table upload)."""
+    try:
+        cleans, estimates = ([t.reshape(1, -1) if isinstance(t, torch.Tensor) and t.ndim == 1 else t for t in s] for s in (cleans, estimates))
+    except TypeError:
+        raise ValueError("bss_sdr_many: the recordings must come as sequences of tensors") from None
+    sdr, sdr_i, perm = _ScorePool("bss_sdr_many", mixes, cleans, estimates, 16000, multi=True).bss()
+    out = (sdr,) + (() if mixes is None else (sdr_i,)) + ((perm,) if return_perm else ())
+    return out if len(out) > 1 else out[0]
+
 
 def stoi_many(cleans, estimates, fs=16000, return_kept=False):
     """``stoi`` for R recordings of different lengths in one pooled pass: two sequences of R float32 device tensors (L_r)|(1,L_r) -> (R,)
@@ -220,16 +302,22 @@ class ALLMetricsTracker:
     ``sdr = loss`` and ``sdr_i = loss - baseline`` (negative dB); the accumulated means / stds are positive dB for all four.
     ``update_batch`` scores a whole batch in one set of launches and moves one small host array.  ``estoi=True`` (not in the
     reference) adds extended STOI as a seventh metric ``"estoi"`` after ``"stoi"`` everywhere -- rows, ``avg`` / ``std``, ``get_mean`` /
-    ``get_std``, ``all_estois`` -- computed with classic STOI in one combined call; without it the tracker is the reference's."""
+    ``get_std``, ``all_estois`` -- computed with classic STOI in one combined call; without it the tracker is the reference's.
+    ``bss_sdr=True`` (not in the reference either) adds BSS-eval SDR (``metrics.bss_sdr``) as the columns ``"bss_sdr"`` and
+    ``"bss_sdr_i"`` after ``"stoi"`` (after ``"estoi"`` when both options are on), each the mean over the sources, in POSITIVE dB in
+    the CSV and in ``all_bss_sdrs`` / ``all_bss_sdrs_i`` alike -- unlike the reference's ``sdr`` / ``sdr_i`` next to them, which the
+    CSV holds as negative dB and which are plain SNR: one sample of delay ruins those, a delay of up to 511 samples leaves these."""
 
     COLUMNS = ["snt_id", "sdr", "sdr_i", "si-snr", "si-snr_i", "pesq", "stoi"]
 
-    def __init__(self, save_file: str = "", pesq_fn=None, fs: int = 16000, estoi: bool = False):
+    def __init__(self, save_file: str = "", pesq_fn=None, fs: int = 16000, estoi: bool = False, bss_sdr: bool = False):
         self.all_sdrs, self.all_sdrs_i, self.all_sisnrs, self.all_sisnrs_i, self.all_pesqs, self.all_stois = [], [], [], [], [], []
-        self.pesq_fn, self.fs, self.estoi = pesq_fn, fs, bool(estoi)
-        self.columns = self.COLUMNS + (["estoi"] if self.estoi else [])
+        self.pesq_fn, self.fs, self.estoi, self.bss_sdr = pesq_fn, fs, bool(estoi), bool(bss_sdr)
+        self.columns = self.COLUMNS + (["estoi"] if self.estoi else []) + (["bss_sdr", "bss_sdr_i"] if self.bss_sdr else [])
         if self.estoi:
             self.all_estois = []
+        if self.bss_sdr:
+            self.all_bss_sdrs, self.all_bss_sdrs_i = [], []
         self.results_csv = open(save_file, "w")
         self.writer = csv.DictWriter(self.results_csv, fieldnames=self.columns)
         self.writer.writeheader()
@@ -257,6 +345,8 @@ class ALLMetricsTracker:
             cols = [sdr, sdr - sdr_b, sisnr, sisnr - sisnr_b, st, est]
         else:
             cols = [sdr, sdr - sdr_b, sisnr, sisnr - sisnr_b, stoi(clean[:, 0], estimate[:, 0], self.fs)]
+        if self.bss_sdr:  # each the mean over the sources, positive dB
+            cols += [v.mean(1) for v in bss_sdr(clean, estimate, mix)]
         vals = torch.stack(cols, 1).cpu().numpy()  # the one device -> host copy
         if self.pesq_fn is not None:
             est_h, cl_h = estimate[:, 0].cpu().numpy(), clean[:, 0].cpu().numpy()
@@ -278,6 +368,8 @@ class ALLMetricsTracker:
             cols = [pool.sdr()[0], st[:, None], est[:, None]]
         else:
             cols = [pool.sdr()[0], pool.stoi()[0][:, None]]
+        if self.bss_sdr:
+            cols += [v.mean(1, keepdim=True) for v in pool.bss()[:2]]
         vals = torch.cat(cols, 1).cpu().numpy()  # the one device -> host copy
         if self.pesq_fn is not None:
             pesqs = [float(self.pesq_fn(e[0].cpu().numpy(), c[0].cpu().numpy(), self.fs)) for e, c in zip(pool.estimates, pool.cleans)]
@@ -287,17 +379,22 @@ class ALLMetricsTracker:
 
     def record(self, keys, vals, pesqs):
         """Write and accumulate rows from host values: vals (B, 5) = the losses (sdr, sdr - baseline, sisnr, sisnr - baseline) in the
-        loss sign, then stoi; with ``estoi=True`` (B, 6): estoi last; pesqs: B floats."""
+        loss sign, then stoi; with ``estoi=True`` estoi follows; with ``bss_sdr=True`` bss_sdr and bss_sdr_i (positive dB, the means over the
+        sources) come last: 5 + estoi + 2 values per row; pesqs: B floats."""
         for b in range(len(keys)):
             l_sdr, l_sdr_i, l_sisnr, l_sisnr_i, s, *ext = (float(v) for v in vals[b])
-            if len(ext) != int(self.estoi):
-                raise ValueError(f"record: {len(vals[b])} values per row; this tracker takes {6 if self.estoi else 5}")
+            if len(ext) != int(self.estoi) + 2 * int(self.bss_sdr):
+                raise ValueError(f"record: {len(vals[b])} values per row; this tracker takes {5 + int(self.estoi) + 2 * int(self.bss_sdr)}")
             self.key = keys[b]
             row = {"snt_id": keys[b], "sdr": l_sdr, "sdr_i": l_sdr_i, "si-snr": -l_sisnr, "si-snr_i": -l_sisnr_i,
                    "pesq": pesqs[b], "stoi": s}
             if self.estoi:
                 row["estoi"] = ext[0]
                 self.all_estois.append(ext[0])
+            if self.bss_sdr:
+                row["bss_sdr"], row["bss_sdr_i"] = ext[-2], ext[-1]
+                self.all_bss_sdrs.append(ext[-2])
+                self.all_bss_sdrs_i.append(ext[-1])
             self.writer.writerow(row)
             self.all_sdrs.append(-l_sdr)
             self.all_sdrs_i.append(-l_sdr_i)
@@ -311,6 +408,8 @@ class ALLMetricsTracker:
                  "pesq": self.all_pesqs, "stoi": self.all_stois}
         if self.estoi:
             lists["estoi"] = self.all_estois
+        if self.bss_sdr:
+            lists["bss_sdr"], lists["bss_sdr_i"] = self.all_bss_sdrs, self.all_bss_sdrs_i
         return lists
 
     def get_mean(self):
