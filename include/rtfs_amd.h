@@ -601,7 +601,7 @@ int rtfs_estoi_many_f32(const float* const* cleans, const float* const* ests, co
  *   k .. 511 are 0 (a silent reference gives c = 0: -inf, or NaN for a silent estimate as well).  It is a guard, not a measurement.
  *   Sources: with n_src = n <= 4 all n^2 values SDR(e_i, s_j) are formed (the estimates scored against s_j share G_j); the permutation
  *   maximises the mean SDR over the sources, scanned in itertools order, first maximum (fast_bss_eval's rule; mir_eval chooses by SIR,
- *   which needs the joint projection and is not computed here).  perm[b][j] = the estimate assigned to clean source j, the convention of
+ *   which needs the joint projection: see "BSS-eval SIR and SAR" below).  perm[b][j] = the estimate assigned to clean source j, the convention of
  *   rtfs_pit_pairwise_sdr_f32; sdr[b][j] = SDR(e_perm[b][j], s_j) in positive dB.  With a mixture the baseline of source j is
  *   SDR(mix, s_j) and sdr_i[b][j] = sdr[b][j] - baseline[j] (subtracted in float64, stored as float32).
  *   Agreement with the mir_eval package itself is not measured (it is not installed where this project is developed); the definition
@@ -632,6 +632,67 @@ int rtfs_bss_sdr_many_f32(const float* const* mixes /* NULL: no baseline */, con
                           int* perm, void* stream);
 int rtfs_debug_bss_f64(const float* clean, const float* est, const float* mix, int B, int n_src, int L, void* ws, size_t ws_bytes, float* sdr,
                        float* sdr_i, int* perm, int form, double* r_out, double* d_out, double* ee_out, int* order_out, void* stream);
+
+/* BSS-eval SIR and SAR: the other two time-domain ratios of mir_eval.separation.bss_eval_sources, which need the projection of the
+ * estimate onto the delayed copies of ALL true sources at once.  True sources s_0 .. s_{J-1}: the n = n_src clean sources that the
+ * estimates are scored against, then m = n_other "other" sources (an interfering talker, noise) that belong to the span but are not
+ * scored; J = n + m, 1 <= n, J <= 4.  Estimate e, L float32 samples, ALL arithmetic in float64, F = 512, no mean removal:
+ *     r_ij[k] = sum_t s_i[t] s_j[t+k],  k = -511 .. 511   (r_ij[-k] = r_ji[k]; terms past the end are absent)
+ *     d_i[k]  = sum_t s_i[t] e[t+k],    k = 0 .. 511,     ee = sum e^2
+ *     G_all   = the (J 512)^2 matrix with G[(i,a),(j,b)] = r_ij[a-b],  G_all C = D_all,  p_all = C'D_all   (|P_all e|^2)
+ *     p_j     = c_j'd_j with Toeplitz(r_jj) c_j = d_j                 (|s_target|^2, the num of "BSS-eval SDR")
+ *     SDR_j = 10 log10(p_j / max(ee - p_j, 0))       (the value of rtfs_bss_sdr_f32, bit for bit)
+ *     SIR_j = 10 log10(p_j / max(p_all - p_j, 0))
+ *     SAR   = 10 log10(p_all / max(ee - p_all, 0))
+ *   These are mir_eval's |s_target|^2 / |e_interf|^2 and |s_target + e_interf|^2 / |e_artif|^2 with s_target = s_j * c_j, e_interf =
+ *   P_all e - s_target and e_artif = e_pad - P_all e on the zero-padded length L + 511 (e_interf is orthogonal to s_target, so the closed
+ *   forms hold).  IEEE as it comes (+-inf, NaN for 0/0), as for the SDR.
+ *   Solver: block Levinson with J x J blocks over the 512 orders (tap-major ordering: G_all is block-Toeplitz with blocks M[k][i][j] =
+ *   r_ij[k], M[-k] = M[k]'), forward and backward block predictors, the error blocks E_f and E_b of every order inverted by Gauss-Jordan
+ *   without pivoting.  Stop rule, the scalar one generalised: the recursion ends at order m, taps m .. 511 stay 0, when a pivot of the
+ *   order's E_f or E_b is <= 2^-46 r_ii[0] of its source i (order 0: the block M[0]; two identical sources stop there, p_all = 0).  It is
+ *   a guard, not a measurement.  A source with r_jj[0] = 0 (silent) is left out of the joint set and its taps are 0.  When the joint set
+ *   is one scored source, P_all is that source's scalar projection and p_all is taken from the scalar solve: SIR = +inf and SAR = SDR
+ *   bit for bit, for J = 1 and for n = 1 with silent others alike (a single-talker segment does not turn into NaN).  An empty joint set
+ *   has p_all = 0.  G_all is the Gram matrix of 512 J vectors in R^(L + 511): rows shorter than 512 J + 512 samples are rank-deficient or
+ *   close to it and belong with the degenerate rows (the call finishes; the figures are whatever the stop rule leaves).
+ *   Permutation, perm_by: RTFS_BSS_PERM_BY_SDR (0) the rule of rtfs_bss_sdr_f32 -- then sdr, sdr_i and perm ARE that call's, bit for bit
+ *   -- or RTFS_BSS_PERM_BY_SIR (1) mir_eval's rule: the largest mean over the sources of SIR(e_perm[j], s_j), itertools order, first
+ *   maximum.  sir[b][j] = SIR(e_perm[b][j], s_j); sar[b][j] = SAR(e_perm[b][j]).
+ *   Agreement with the mir_eval package itself is not measured (it is not installed where this project is developed); the definition
+ *   is tests/bss_eval_oracle.py.
+ * Work cut (four launches): the correlation partials of "BSS-eval SDR" with every one of the J sources staged and the J sources and n
+ *   estimates (for a scored source also the mixture) as right-hand signals; the scalar solves, unchanged; one workgroup per recording
+ *   for the fold in chunk order and the block recursion for all n estimates at once; one thread per recording for the matrices, the
+ *   search and the outputs.  No atomics: a row's bits depend on neither batch, pool nor scheduling.
+ * rtfs_bss_eval_f32: clean, est (B, n_src, L), mix (B, L) or NULL, other (B, n_other, L) or NULL -> sdr, sir, sar (B, n_src) float32,
+ *   sdr_i (B, n_src) (required with mix, untouched without), perm (B, n_src) int32.  It allocates, uploads and reads back nothing:
+ *   capturable in a graph.  Refused before any launch: -4 for a NULL pointer (mix excepted; sdr_i only with mix; other only with n_other
+ *   > 0), B < 1, L < 1, n_src < 1, n_other < 0, n_src + n_other > 4 or an unknown perm_by; -1 when B * ceil(L / 4096) * J * 2 workgroups
+ *   exceed 2^31 - 1; -2 for a workspace below rtfs_bss_eval_workspace_bytes (0 for arguments the call refuses).
+ * rtfs_bss_eval_many_f32: the same for R recordings of different lengths on rtfs_score_many_plan's table, of which it uses columns 0
+ *   and 10 only (RTFS_SCORE_COLS does not move); arguments, checks and codes as rtfs_bss_sdr_many_f32.  others: R * n_other device
+ *   pointers, recording r's rows at [r n_other, (r + 1) n_other), each L_r samples; NULL with n_other = 0.  The workspace is its own,
+ *   rtfs_bss_eval_many_workspace_bytes(plan, R, n_other, with_mix).  The kernels are those of rtfs_bss_eval_f32: row r is BIT-EQUAL to
+ *   that call on recording r alone.  Not capturable (table upload).
+ * rtfs_debug_bss_eval_f64: rtfs_bss_eval_f32 that also copies out, per row b, the folded r_ij at all lags (J, J, 1023 doubles: lag k at
+ *   index 511 + k), D_all (n_src, J, 512: d_i of estimate q at [q][i]), p_all (n_src), p_j (n_src estimates x n_src sources) and the
+ *   order the joint recursion reached (int32; 512 = the guard did not fire, also reported when the scalar solve stood in; 0 for an
+ *   empty joint set); -4 for a NULL debug pointer. */
+#define RTFS_BSS_PERM_BY_SDR 0
+#define RTFS_BSS_PERM_BY_SIR 1
+size_t rtfs_bss_eval_workspace_bytes(int B, int n_src, int n_other, int L, int with_mix);
+int rtfs_bss_eval_f32(const float* clean, const float* est, const float* mix /* NULL: no baseline */, const float* other /* NULL: none */,
+                      int B, int n_src, int n_other, int L, void* ws, size_t ws_bytes, float* sdr, float* sir, float* sar, float* sdr_i,
+                      int* perm, int perm_by, void* stream);
+size_t rtfs_bss_eval_many_workspace_bytes(const int* plan, int R, int n_other, int with_mix);
+int rtfs_bss_eval_many_f32(const float* const* mixes /* NULL: no baseline */, const float* const* cleans, const float* const* ests,
+                           const float* const* others /* NULL: none */, const int* table, const int* plan, int R, int n_src, int n_other,
+                           int fs, void* ws, size_t ws_bytes, float* sdr, float* sir, float* sar, float* sdr_i, int* perm, int perm_by,
+                           void* stream);
+int rtfs_debug_bss_eval_f64(const float* clean, const float* est, const float* mix, const float* other, int B, int n_src, int n_other, int L,
+                            void* ws, size_t ws_bytes, float* sdr, float* sir, float* sar, float* sdr_i, int* perm, int perm_by, double* r_out,
+                            double* d_out, double* pall_out, double* pj_out, int* order_out, void* stream);
 
 /* Long recordings in overlapping windows on the fused separator (AVNet.separate_long; no reference counterpart: infer_any_video.py:63-86
  * hands a whole track to one forward).  SPF = 640 samples per video frame (16 kHz, 25 fps).  A recording of L samples is cut into N

@@ -10,7 +10,7 @@ from .system import System  # noqa: F401
 from .streaming import (CameraStreamPool, FaceCameraStreamPool, FaceStreamPool, LipStreamPool, RateLipStreamPool, RateStreamPool,  # noqa: F401
                         ResampleStreamPool, SpeakerCameraStreamPool, SpeakerStreamPool, StampLipStreamPool, StreamPool)
 from .optimizers import make_optimizer  # noqa: F401
-from .metrics import ALLMetricsTracker, bss_sdr, bss_sdr_many, estoi, estoi_many, sdr_many, stoi, stoi_many  # noqa: F401
+from .metrics import ALLMetricsTracker, bss_eval, bss_eval_many, bss_sdr, bss_sdr_many, estoi, estoi_many, sdr_many, stoi, stoi_many  # noqa: F401
 from .datas import (Compose, Normalize, CenterCrop, RandomCrop, HorizontalFlip, get_preprocessing_pipelines, normalize_mixture,  # noqa: F401
                     normalize_tensor_wav, resample, mouth_affine, mouth_rois)
 from .videomodels import FRCNNVideoModel  # noqa: F401

@@ -139,6 +139,11 @@ SIGNATURES = {
     "rtfs_bss_sdr_many_workspace_bytes": (_z, [_p, _i, _i]),
     "rtfs_bss_sdr_many_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _p]),
     "rtfs_debug_bss_f64": (_i, [_p, _p, _p, _i, _i, _i, _p, _z, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "rtfs_bss_eval_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "rtfs_bss_eval_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p, _p, _p, _p, _p, _i, _p]),
+    "rtfs_bss_eval_many_workspace_bytes": (_z, [_p, _i, _i, _i]),
+    "rtfs_bss_eval_many_f32": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p, _p, _p, _p, _p, _i, _p]),
+    "rtfs_debug_bss_eval_f64": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _z, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
     "rtfs_longform_plan": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "rtfs_longform_frame_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "rtfs_longform_frame_speakers_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

@@ -1675,6 +1675,31 @@ int rtfs_debug_bss_f64(const float* clean, const float* est, const float* mix, i
                           (hipStream_t)stream);
 }
 
+size_t rtfs_bss_eval_workspace_bytes(int B, int n_src, int n_other, int L, int with_mix) {
+    return bss_eval_workspace_bytes(B, n_src, n_other, L, with_mix);
+}
+int rtfs_bss_eval_f32(const float* clean, const float* est, const float* mix, const float* other, int B, int n_src, int n_other, int L, void* ws,
+                      size_t ws_bytes, float* sdr, float* sir, float* sar, float* sdr_i, int* perm, int perm_by, void* stream) {
+    return launch_bss_eval(clean, est, mix, other, B, n_src, n_other, L, ws, ws_bytes, sdr, sir, sar, sdr_i, perm, perm_by,
+                           BssEvalDebug{nullptr, nullptr, nullptr, nullptr, nullptr}, (hipStream_t)stream);
+}
+size_t rtfs_bss_eval_many_workspace_bytes(const int* plan, int R, int n_other, int with_mix) {
+    return bss_eval_many_workspace_bytes(plan, R, n_other, with_mix);
+}
+int rtfs_bss_eval_many_f32(const float* const* mixes, const float* const* cleans, const float* const* ests, const float* const* others,
+                           const int* table, const int* plan, int R, int n_src, int n_other, int fs, void* ws, size_t ws_bytes, float* sdr,
+                           float* sir, float* sar, float* sdr_i, int* perm, int perm_by, void* stream) {
+    return launch_bss_eval_many(mixes, cleans, ests, others, table, plan, R, n_src, n_other, fs, ws, ws_bytes, sdr, sir, sar, sdr_i, perm,
+                                perm_by, (hipStream_t)stream);
+}
+int rtfs_debug_bss_eval_f64(const float* clean, const float* est, const float* mix, const float* other, int B, int n_src, int n_other, int L,
+                            void* ws, size_t ws_bytes, float* sdr, float* sir, float* sar, float* sdr_i, int* perm, int perm_by, double* r_out,
+                            double* d_out, double* pall_out, double* pj_out, int* order_out, void* stream) {
+    if (!r_out || !d_out || !pall_out || !pj_out || !order_out) return RTFS_ERR_ARG;
+    return launch_bss_eval(clean, est, mix, other, B, n_src, n_other, L, ws, ws_bytes, sdr, sir, sar, sdr_i, perm, perm_by,
+                           BssEvalDebug{r_out, d_out, pall_out, pj_out, order_out}, (hipStream_t)stream);
+}
+
 int rtfs_longform_plan(int L, int Tv, int window, int hop, int* N) { return longform_plan(L, Tv, window, hop, N); }
 int rtfs_longform_frame_f32(const float* wav, const float* video, float* wav_win, float* video_win, int B, int L, int Tv, int window, int hop,
                             void* stream) {

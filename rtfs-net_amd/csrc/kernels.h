@@ -421,6 +421,22 @@ size_t bss_sdr_many_workspace_bytes(const int* plan, int R, int with_mix);
 int launch_bss_sdr_many(const float* const* mixes, const float* const* cleans, const float* const* ests, const int* table, const int* plan,
                         int R, int n_src, int fs, void* ws, size_t ws_bytes, float* sdr, float* sdr_i, int* perm, const BssDebug& dbg,
                         hipStream_t st);
+// BSS-eval SIR and SAR (k_bss.hip): the joint projection onto all J = n_src + n_other true sources (block Levinson, J x J blocks) next
+// to the scalar ones; four launches.  BssEvalDebug: optional copies of the folded r_ij (rows, J, J, 1023: lag k at 511 + k), D_all (rows,
+// n_src, J, 512), p_all (rows, n_src), p_j (rows, n_src[estimate], n_src[source]) and the joint order reached (rows).
+constexpr int BSS_PERM_BY_SDR = 0, BSS_PERM_BY_SIR = 1;
+struct BssEvalDebug {
+    double *r, *d, *pall, *pj;
+    int* order;
+};
+size_t bss_eval_workspace_bytes(int B, int n_src, int n_other, int L, int with_mix);
+int launch_bss_eval(const float* clean, const float* est, const float* mix, const float* other, int B, int n_src, int n_other, int L, void* ws,
+                    size_t ws_bytes, float* sdr, float* sir, float* sar, float* sdr_i, int* perm, int perm_by, const BssEvalDebug& dbg,
+                    hipStream_t st);
+size_t bss_eval_many_workspace_bytes(const int* plan, int R, int n_other, int with_mix);
+int launch_bss_eval_many(const float* const* mixes, const float* const* cleans, const float* const* ests, const float* const* others,
+                         const int* table, const int* plan, int R, int n_src, int n_other, int fs, void* ws, size_t ws_bytes, float* sdr,
+                         float* sir, float* sar, float* sdr_i, int* perm, int perm_by, hipStream_t st);
 
 // long recordings in overlapping windows (k_longform.hip): window plan (host), framing of audio + video in one launch, cross-faded overlap-add
 int longform_plan(int L, int Tv, int window, int hop, int* N);
