@@ -1184,6 +1184,68 @@ int rtfs_mix_plan(const long long* slots, const double* a, int B, int L, int n_o
 int rtfs_mix_f32(const long long* table, float* mixture, float* sources, double* stats, int B, int L, int n_out, int normalize, double eps,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* Reverberant mixtures (datas.reverberate, datas.mix_batch(rirs=...), System.mix_batch(rirs=...); DESIGN.md "Reverberant mixtures";
+ * csrc/k_reverb.hip): every source convolved with its own room impulse response (RIR) before the mix, the WHAMR! / SMS-WSJ recipe.
+ * A job names a source x of n_x samples (float32 at any 4-byte alignment, or int16 PCM at any 2-byte alignment entering as
+ * (float)s / 32768, read where it lies), a segment start p with 0 <= p, p + L <= n_x, an RIR h of N float32 taps on the device at any
+ * 4-byte alignment, 1 <= N <= RTFS_REVERB_MAX_TAPS, and an offset o, 0 <= o < N.  With x~[i] = x[i] for 0 <= i < n_x and 0 elsewhere,
+ * the image is
+ *   r[t] = (float) sum_{k=0}^{N-1} h[k] x~[p + t + o - k],  t = 0 .. L-1.
+ * The sum is in float64, where the product of two float32 values is exact; its terms are added one by one in the order k = 0, 1, ...
+ * (fused multiply-add on the converted operands, which rounds once per term as add after an exact multiply does), so the same inputs
+ * give the same bits whatever the batch or the scheduling.  Exactly the N terms of the sum enter: no tap and no sample is padded in,
+ * and a sample outside [max(0, p + o - N + 1), min(n_x, p + o + L)) never reaches an output.  History before the segment is read from
+ * the utterance itself (a crop of a reverberant utterance, not a reverberated crop); before sample 0 and past the last sample the
+ * room is silent.  o lets a caller cancel the direct-path delay (o = argmax |h|): the image then stays sample-aligned with the dry
+ * segment.
+ * A reverberant mixture is the mixture definition above applied to images: a slot with an RIR contributes its image r_j wherever the
+ * definition says x_j, a reference with an RIR contributes E(r_ref); the energy rule, the SNRs (now between images), the order of the
+ * sum, the normalisation and stats are unchanged, and a slot without an RIR is read dry from its source as before.
+ * rtfs_reverb_plan (host only, no device call): jobs = S records of RTFS_REVERB_RECIPE_WORDS = 7 int64 words [source address | source
+ *   length in samples | dtype RTFS_MIX_F32 / RTFS_MIX_I16 | start p | RIR address | taps N | offset o] -> when table is not NULL, the
+ *   S * RTFS_REVERB_JOB_WORDS = 6 int64 words rtfs_reverb_f32 reads FROM DEVICE MEMORY, per job [source address | n_x | p + o | RIR
+ *   address | N | source is int16].  Refusals return -4, write nothing else and name themselves in refused[2] = [job or -1 | reason],
+ *   with the RTFS_MIX_* reasons and two more: S < 1, a missing array, a work list of S * ceil(L / RTFS_REVERB_TILE) past 2^31 - 1
+ *   (BAD_ARGUMENT, -1); L outside [1, RTFS_MIX_MAX_LENGTH] (BAD_LENGTH, -1); per job, in this order: a null source or RIR address
+ *   (BAD_ARGUMENT); an unknown dtype (BAD_DTYPE); a source address misaligned for its dtype or an RIR address off the 4-byte grid
+ *   (MISALIGNED); a segment that leaves its source (SEGMENT_RANGE); taps outside [1, RTFS_REVERB_MAX_TAPS] (RTFS_REVERB_BAD_TAPS); an
+ *   offset outside [0, taps) (RTFS_REVERB_BAD_OFFSET).  table and refused may be NULL.
+ * rtfs_reverb_f32 (one launch): images (S, L) float32, 4-byte aligned, row s = the image of job s; table 8-byte aligned (-4); sizes
+ *   the plan refuses: -1.  One workgroup per (image, tile of RTFS_REVERB_TILE outputs) walks the taps in chunks of
+ *   RTFS_REVERB_TAP_CHUNK, staging the chunk's taps and the TILE + CHUNK - 1 samples they touch in LDS (int16 converted, zeros outside
+ *   the utterance); each thread keeps 8 consecutive outputs in float64 registers.  16-byte stores on the row's own 16-byte grid,
+ *   scalar head and tail.  Caller's stream, no allocation, no workspace, nothing read back, no atomics, one writer per cell.  The
+ *   launch trusts the device table: pass what rtfs_reverb_plan wrote.
+ * rtfs_mix_reverb_plan (host only): rtfs_mix_plan's slots and a, plus rirs = B * J records of RTFS_MIX_RIR_WORDS = 6 int64 words [RIR
+ *   address of the slot's segment (0: dry) | its taps | its offset | RIR address of the slot's reference (0: dry) | its taps | its
+ *   offset].  Every distinct (source address, dtype, start, RIR address, taps, offset) gets ONE image row, numbered in the order the
+ *   slots name them (row-major; a slot's segment before its reference): a target's image that is also its interferers' reference is
+ *   computed once.  -> *n_images = S, *ws_bytes = rtfs_mix_workspace_bytes(B, L) and, when table is not NULL, ONE table of
+ *   S * RTFS_REVERB_JOB_WORDS + B * J * RTFS_MIX_TABLE_WORDS words: the reverb jobs, then rtfs_mix_plan's table of the recipe in which
+ *   every reverberant segment or reference is the float32 row `images + 4 L row` (images: the device address of the (S, L) buffer the
+ *   caller allocates after a first call with table = NULL; it may be 0 while table is NULL or S is 0).  Refusals (-4, refused as
+ *   above with row * J + slot, nothing else written): a missing array and everything rtfs_mix_plan refuses, first; then images off
+ *   the 4-byte grid (MISALIGNED, -1); then per slot in row-major order what rtfs_reverb_plan refuses of a job; then S * tiles past
+ *   2^31 - 1 or a table asked for with S > 0 and images = 0 (BAD_ARGUMENT, -1).  With no RIR anywhere S = 0 and the table is
+ *   rtfs_mix_plan's.
+ * rtfs_mix_reverb_f32 (THREE launches; two with n_images = 0, then it is rtfs_mix_f32 on the same table): the reverb launch on the
+ *   first n_images jobs of the table, then rtfs_mix_f32 on the words behind them.  Arguments and error codes as rtfs_mix_f32; images
+ *   4-byte aligned and not NULL when n_images > 0.  All checks before any launch. */
+#define RTFS_REVERB_TILE 1024
+#define RTFS_REVERB_TAP_CHUNK 768
+#define RTFS_REVERB_MAX_TAPS 16384
+#define RTFS_REVERB_RECIPE_WORDS 7
+#define RTFS_REVERB_JOB_WORDS 6
+#define RTFS_MIX_RIR_WORDS 6
+#define RTFS_REVERB_BAD_TAPS 9
+#define RTFS_REVERB_BAD_OFFSET 10
+int rtfs_reverb_plan(const long long* jobs, int S, int L, long long* table, int* refused);
+int rtfs_reverb_f32(const long long* table, float* images, int S, int L, void* stream);
+int rtfs_mix_reverb_plan(const long long* slots, const double* a, const long long* rirs, int B, int L, int n_out, long long images,
+                         long long* table, int* n_images, size_t* ws_bytes, int* refused);
+int rtfs_mix_reverb_f32(const long long* table, int n_images, float* images, float* mixture, float* sources, double* stats, int B, int L,
+                        int n_out, int normalize, double eps, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,10 @@ SIGNATURES = {
     "rtfs_mix_workspace_bytes": (_z, [_i, _i]),
     "rtfs_mix_plan": (_i, [_p, _p, _i, _i, _i, _p, C.POINTER(C.c_size_t), _p]),
     "rtfs_mix_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_double, _p, _z, _p]),
+    "rtfs_reverb_plan": (_i, [_p, _i, _i, _p, _p]),
+    "rtfs_reverb_f32": (_i, [_p, _p, _i, _i, _p]),
+    "rtfs_mix_reverb_plan": (_i, [_p, _p, _p, _i, _i, _i, C.c_longlong, _p, C.POINTER(_i), C.POINTER(C.c_size_t), _p]),
+    "rtfs_mix_reverb_f32": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, C.c_double, _p, _z, _p]),
 }
 
 _lib = None

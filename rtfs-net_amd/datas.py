@@ -9,6 +9,9 @@
 * ``MixRecipe`` / ``draw_mix_recipe`` / ``mix_batch``   training mixtures formed on the device: ``System.online_mixing_collate``
                                      (``src/system/core.py:183-202``) and target + interferers at a drawn SNR, a host plan and TWO launches
                                      of ``rtfs_mix_f32`` (``csrc/k_mix.hip``)
+* ``reverberate`` / ``load_rirs`` / ``synthetic_rir``   reverberant training mixtures: every source convolved with its own room impulse
+                                     response on the device (``csrc/k_reverb.hip``), alone or in front of the two mix launches
+                                     (``mix_batch(..., rirs=...)``)
 
 All arithmetic runs in ``librtfs_amd.so`` (``csrc/k_prep.hip``); there is no host fallback.  ``tests/prep_oracle.py`` restates the three
 in float64 numpy."""
@@ -25,7 +28,8 @@ from . import _lib
 
 __all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
            "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams", "frame_rate_of", "frame_rate_map",
-           "timestamp_map", "mouth_affine", "mouth_rois", "MixRecipe", "draw_mix_recipe", "mix_batch"]
+           "timestamp_map", "mouth_affine", "mouth_rois", "MixRecipe", "draw_mix_recipe", "mix_batch", "reverberate", "load_rirs",
+           "synthetic_rir"]
 
 CROP = 88
 MAX_RATIO = 640
@@ -410,15 +414,22 @@ MIX_RECIPE_WORDS, MIX_TABLE_WORDS = 8, 4                        # RTFS_MIX_RECIP
 MIX_REASONS = {1: "a bad argument", 2: f"length outside [1, {MIX_MAX_LENGTH}]", 3: f"n_out outside [0, {MIX_MAX_SOURCES}]",
                4: "a segment that leaves its source", 5: "a reference segment that leaves its source", 6: "a row whose slots are all empty",
                7: "a source address that is misaligned for its dtype", 8: "an unknown dtype"}
+REVERB_TILE, REVERB_TAP_CHUNK, REVERB_MAX_TAPS = 1024, 768, 16384  # RTFS_REVERB_TILE, RTFS_REVERB_TAP_CHUNK, RTFS_REVERB_MAX_TAPS
+REVERB_RECIPE_WORDS, REVERB_JOB_WORDS, MIX_RIR_WORDS = 7, 6, 6     # RTFS_REVERB_RECIPE_WORDS, RTFS_REVERB_JOB_WORDS, RTFS_MIX_RIR_WORDS
+REVERB_REASONS = {**MIX_REASONS, 7: "a source or RIR address that is misaligned for its dtype", 9: f"taps outside [1, {REVERB_MAX_TAPS}]",
+                  10: "an offset outside [0, taps)"}
 
 
 class MixRecipe:
     """Which segments make up every row of a batch of mixtures: plain host arrays (B, J), J <= 4, per (row, slot).
     ``src``: index into the list of sources, -1 for an empty slot; ``start``: first sample of the segment; ``a``: the slot's factor
     (float64); ``ref_src`` / ``ref_start``: the reference segment whose energy the slot is scaled to, -1 / 0 for none.  The gain of a
-    slot is a, or a sqrt(E(ref) / E(segment)) with a reference (``rtfs_mix_plan``)."""
+    slot is a, or a sqrt(E(ref) / E(segment)) with a reference (``rtfs_mix_plan``).
+    Reverberant mixtures (``mix_batch(..., rirs=...)``): ``rir`` / ``ref_rir`` index the list of room impulse responses the slot's
+    segment / its reference is convolved with (-1, the default: dry), ``rir_offset`` / ``ref_offset`` the sample of that response the
+    image is aligned to (default 0; ``argmax |h|`` cancels the direct-path delay)."""
 
-    def __init__(self, src, start, a, ref_src=None, ref_start=None):
+    def __init__(self, src, start, a, ref_src=None, ref_start=None, rir=None, ref_rir=None, rir_offset=None, ref_offset=None):
         import numpy as np
         try:
             self.src = np.array(src, dtype=np.int64)
@@ -426,12 +437,25 @@ class MixRecipe:
             self.a = np.array(a, dtype=np.float64)
             self.ref_src = np.full(self.src.shape, -1, np.int64) if ref_src is None else np.array(ref_src, dtype=np.int64)
             self.ref_start = np.zeros(self.src.shape, np.int64) if ref_start is None else np.array(ref_start, dtype=np.int64)
+            self.rir = np.full(self.src.shape, -1, np.int64) if rir is None else np.array(rir, dtype=np.int64)
+            self.ref_rir = np.full(self.src.shape, -1, np.int64) if ref_rir is None else np.array(ref_rir, dtype=np.int64)
+            self.rir_offset = np.zeros(self.src.shape, np.int64) if rir_offset is None else np.array(rir_offset, dtype=np.int64)
+            self.ref_offset = np.zeros(self.src.shape, np.int64) if ref_offset is None else np.array(ref_offset, dtype=np.int64)
         except (TypeError, ValueError, OverflowError):
-            raise ValueError("MixRecipe: src, start, ref_src, ref_start are integer arrays (B, J) and a a float array (B, J)") from None
+            raise ValueError("MixRecipe: src, start, ref_src, ref_start (and rir, ref_rir, rir_offset, ref_offset) are integer arrays "
+                             "(B, J) and a a float array (B, J)") from None
         if self.src.ndim != 2 or self.src.shape[0] < 1 or not 1 <= self.src.shape[1] <= MIX_MAX_SOURCES or \
                 any(v.shape != self.src.shape for v in (self.start, self.a, self.ref_src, self.ref_start)):
             raise ValueError(f"MixRecipe: five arrays of one shape (B, J) with B >= 1 and 1 <= J <= {MIX_MAX_SOURCES}; got "
                              f"{[tuple(v.shape) for v in (self.src, self.start, self.a, self.ref_src, self.ref_start)]}")
+        if any(v.shape != self.src.shape for v in (self.rir, self.ref_rir, self.rir_offset, self.ref_offset)):
+            raise ValueError(f"MixRecipe: rir, ref_rir, rir_offset, ref_offset must have the recipe's shape {tuple(self.src.shape)}; got "
+                             f"{[tuple(v.shape) for v in (self.rir, self.ref_rir, self.rir_offset, self.ref_offset)]}")
+
+    @property
+    def reverberant(self):
+        """True if any slot or reference names an RIR."""
+        return bool((self.rir >= 0).any() or (self.ref_rir >= 0).any())
 
     @property
     def shape(self):
@@ -441,10 +465,12 @@ class MixRecipe:
         return f"MixRecipe(B={self.shape[0]}, J={self.shape[1]})"
 
     @classmethod
-    def snr(cls, targets, interferers, starts, snr_db):
+    def snr(cls, targets, interferers, starts, snr_db, rirs=None, offsets=None):
         """The target-speaker recipe.  targets (B) source indices, interferers (B, K) source indices (-1: none), starts (B, 1 + K),
         snr_db a scalar, (B) or (B, K).  Slot 0 is the target with a = 1 and no reference; slot j >= 1 an interferer whose reference
-        is the row's target segment, with a = 10^(-snr_db / 20): the target lies snr_db above that interferer."""
+        is the row's target segment, with a = 10^(-snr_db / 20): the target lies snr_db above that interferer.
+        ``rirs`` (B, 1 + K): the RIR index of every slot (-1: dry), ``offsets`` (B, 1 + K) its alignment sample (default 0); every
+        interferer's reference gets the target's RIR and offset, so the SNR holds between the reverberant images."""
         import numpy as np
         try:
             t = np.array(targets, dtype=np.int64).reshape(-1)
@@ -460,15 +486,30 @@ class MixRecipe:
         a = np.concatenate([np.ones((t.shape[0], 1)), 10.0 ** (-db / 20.0)], axis=1)
         ref = np.concatenate([np.full((t.shape[0], 1), -1, np.int64), np.where(k >= 0, t[:, None], -1)], axis=1)
         ref_start = np.concatenate([np.zeros((t.shape[0], 1), np.int64), np.where(k >= 0, s[:, :1], 0)], axis=1)
-        return cls(src, s, a, ref, ref_start)
+        if rirs is None and offsets is None:
+            return cls(src, s, a, ref, ref_start)
+        try:
+            rr = np.full(src.shape, -1, np.int64) if rirs is None else np.array(rirs, dtype=np.int64).reshape(t.shape[0], -1)
+            oo = np.zeros(src.shape, np.int64) if offsets is None else np.array(offsets, dtype=np.int64).reshape(t.shape[0], -1)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("MixRecipe.snr: rirs and offsets are integer arrays (B, 1 + K)") from None
+        if rr.shape != src.shape or oo.shape != src.shape:
+            raise ValueError(f"MixRecipe.snr: rirs and offsets must be {src.shape}; got {rr.shape}, {oo.shape}")
+        rr = np.where(src >= 0, rr, -1)
+        oo = np.where(rr >= 0, oo, 0)
+        ref_rir = np.where(ref >= 0, rr[:, :1], -1)
+        return cls(src, s, a, ref, ref_start, rr, ref_rir, oo, np.where(ref_rir >= 0, oo[:, :1], 0))
 
 
-def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1, rng=None):
+def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1, rng=None, n_rirs=None, rir_prob=1.0, rir_offsets=None):
     """A drawn target-speaker recipe (``MixRecipe.snr``) for ``batch`` rows of ``length`` samples out of utterances of ``lengths``
     samples: per row ``n_src`` distinct utterances (the first is the target), per utterance a uniform start that is a multiple of
     ``align``, per interferer a uniform SNR in ``snr_db`` = (low, high).  Draws come from ``rng`` (a ``random.Random``) or the ``random``
     module, per row in the order utterances, starts, SNRs.  An utterance shorter than ``length`` is never drawn; ValueError if fewer
-    than ``n_src`` are long enough."""
+    than ``n_src`` are long enough.
+    ``n_rirs``: additionally draw, per row after that row's SNRs and per slot, ``rng.random() < rir_prob`` and, if so, an RIR index
+    ``rng.randrange(n_rirs)`` (otherwise the slot stays dry); ``rir_offsets``: the alignment sample of every RIR (``load_rirs``'s second
+    result; default 0).  Without ``n_rirs`` nothing more is drawn: a seed gives the dry recipe it always gave."""
     r = random if rng is None else rng
     batch, length, n_src, align = operator.index(batch), operator.index(length), operator.index(n_src), operator.index(align)
     lengths = [operator.index(n) for n in lengths]
@@ -478,17 +519,28 @@ def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1
     pool = [i for i, n in enumerate(lengths) if n >= length]
     if len(pool) < n_src:
         raise ValueError(f"draw_mix_recipe: {len(pool)} of {len(lengths)} utterance(s) hold {length} samples; a row needs {n_src} distinct ones")
-    rows, starts, dbs = [], [], []
+    if n_rirs is not None:
+        n_rirs = operator.index(n_rirs)
+        rir_offsets = [0] * n_rirs if rir_offsets is None else [operator.index(o) for o in rir_offsets]
+        if n_rirs < 1 or len(rir_offsets) != n_rirs:
+            raise ValueError(f"draw_mix_recipe: n_rirs >= 1 and one offset per RIR; got n_rirs {n_rirs}, {len(rir_offsets)} offset(s)")
+    rows, starts, dbs, rirs = [], [], [], []
     for _ in range(batch):
         row = r.sample(pool, n_src)
         rows.append(row)
         starts.append([align * r.randint(0, (lengths[i] - length) // align) for i in row])
         dbs.append([r.uniform(lo, hi) for _ in row[1:]])
-    return MixRecipe.snr([row[0] for row in rows], [row[1:] for row in rows], starts, dbs)
+        if n_rirs is not None:
+            rirs.append([r.randrange(n_rirs) if r.random() < rir_prob else -1 for _ in row])
+    if n_rirs is None:
+        return MixRecipe.snr([row[0] for row in rows], [row[1:] for row in rows], starts, dbs)
+    return MixRecipe.snr([row[0] for row in rows], [row[1:] for row in rows], starts, dbs, rirs=rirs,
+                         offsets=[[rir_offsets[i] if i >= 0 else 0 for i in row] for row in rirs])
 
 
-def _mix_plan(sources, recipe, length, n_out):
-    """Everything of a ``mix_batch`` call that needs no launch -> (host table (B*J*4) int64, workspace bytes, B, n_out, device)."""
+def _mix_slots(sources, recipe, length, n_out):
+    """The checks of ``mix_batch`` that need no library call and the recipe as ``rtfs_mix_plan`` takes it
+    -> (slots (B, 4, 8) int64, a (B, 4) float64, B, L, n_out, device)."""
     import numpy as np
     if not isinstance(recipe, MixRecipe):
         raise ValueError(f"mix_batch: recipe must be a MixRecipe; got {type(recipe).__name__}")
@@ -518,6 +570,12 @@ def _mix_plan(sources, recipe, length, n_out):
         slots[:, :Jr, 4 * w], slots[:, :Jr, 4 * w + 1], slots[:, :Jr, 4 * w + 2] = addr[idx], size[idx], kind[idx]
         slots[:, :Jr, 4 * w + 3] = start
     a[:, :Jr] = recipe.a
+    return slots, a, B, L, n_out, device
+
+
+def _mix_plan(sources, recipe, length, n_out):
+    """Everything of a ``mix_batch`` call that needs no launch -> (host table (B*J*4) int64, workspace bytes, B, n_out, device)."""
+    slots, a, B, L, n_out, device = _mix_slots(sources, recipe, length, n_out)
     table = _lib.empty(B * MIX_MAX_SOURCES * MIX_TABLE_WORDS, device="cpu", dtype=torch.int64)  # host table, every word written by the plan
     ws, refused = C.c_size_t(0), (C.c_int * 2)(-1, 0)
     code = _lib.load().rtfs_mix_plan(C.c_void_p(slots.ctypes.data), C.c_void_p(a.ctypes.data), B, min(max(L, -1), 1 << 30),
@@ -528,7 +586,101 @@ def _mix_plan(sources, recipe, length, n_out):
     return table, int(ws.value), B, n_out, device
 
 
-def mix_batch(sources, recipe, length, n_out=None, normalize=False, eps=1e-8, return_stats=False):
+def _check_rirs(rirs, device, what):
+    """-> (addresses + [0], taps + [0]) of a list of 1-D float32 device RIRs; index -1 is the dry slot."""
+    import numpy as np
+    rirs = list(rirs)
+    for i, h in enumerate(rirs):
+        if not isinstance(h, torch.Tensor) or not h.is_cuda or h.ndim != 1 or h.dtype != torch.float32 or \
+                (h.numel() > 1 and h.stride(0) != 1) or (device is not None and h.device != device):
+            raise ValueError(f"{what}: RIR {i} must be a 1-D float32 tensor with adjacent taps on the sources' device (there is no CPU "
+                             f"fallback); got {(tuple(h.shape), h.dtype, h.device) if isinstance(h, torch.Tensor) else type(h).__name__}")
+    return (np.array([h.data_ptr() for h in rirs] + [0], dtype=np.int64), np.array([h.numel() for h in rirs] + [0], dtype=np.int64))
+
+
+def _refused(what, refused, rows, detail):
+    where = "" if refused[0] < 0 else (f" at row {refused[0] // MIX_MAX_SOURCES}, slot {refused[0] % MIX_MAX_SOURCES}" if rows
+                                       else f" at job {refused[0]}")
+    return ValueError(f"{what}: {REVERB_REASONS.get(refused[1], 'refused')}{where} ({detail})")
+
+
+def reverberate(sources, rirs, src, start, rir, length, offset=None):
+    """Reverberant images on the device (``rtfs_reverb_f32``; DESIGN.md "Reverberant mixtures"): a host plan, one table upload and ONE
+    launch, nothing read back.  Job s convolves ``sources[src[s]]`` (1-D device tensors, float32 or int16 PCM taken as s / 32768, read
+    where they lie) with ``rirs[rir[s]]`` (1-D float32 device tensors of 1 .. 16384 taps) and returns, as row s of the (S, length)
+    float32 result, r[t] = sum_k h[k] x[start[s] + t + offset[s] - k], t = 0 .. length - 1, summed in float64 and rounded once.  The
+    history in front of the segment is the utterance's own; before its first and past its last sample the room is silent.
+    ``offset`` (default 0, within [0, taps)): ``argmax |h|`` keeps the image aligned with the dry segment.  There is no CPU fallback;
+    what ``rtfs_reverb_plan`` refuses raises ValueError before anything is launched."""
+    import numpy as np
+    try:
+        src, start, rir = (np.array(v, dtype=np.int64).reshape(-1) for v in (src, start, rir))
+        offset = np.zeros(src.shape, np.int64) if offset is None else np.array(offset, dtype=np.int64).reshape(-1)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("reverberate: src, start, rir and offset are integer arrays (S)") from None
+    S, L = int(src.shape[0]), operator.index(length)
+    if S < 1 or any(v.shape != src.shape for v in (start, rir, offset)):
+        raise ValueError(f"reverberate: src, start, rir, offset must be four arrays of one length S >= 1; got "
+                         f"{[int(v.shape[0]) for v in (src, start, rir, offset)]}")
+    recipe = MixRecipe(src[:, None], start[:, None], np.ones((S, 1)))  # the source checks of mix_batch, no library call
+    slots, _, _, _, _, dev = _mix_slots(sources, recipe, max(L, 1), 0)
+    addr, taps = _check_rirs(rirs, dev, "reverberate")
+    if src.min() < 0 or rir.min() < 0 or rir.max() >= len(addr) - 1:
+        raise ValueError(f"reverberate: a job names a source outside [0, {len(list(sources))}) or an RIR outside [0, {len(addr) - 1})")
+    jobs = np.zeros((S, REVERB_RECIPE_WORDS), np.int64)
+    jobs[:, :4] = slots[:, 0, :4]
+    jobs[:, 4], jobs[:, 5], jobs[:, 6] = addr[rir], taps[rir], offset
+    table = _lib.empty(S * REVERB_JOB_WORDS, device="cpu", dtype=torch.int64)
+    refused = (C.c_int * 2)(-1, 0)
+    if _lib.load().rtfs_reverb_plan(C.c_void_p(jobs.ctypes.data), S, min(max(L, -1), 1 << 30), _lib.ptr(table), refused) != 0:
+        raise _refused("reverberate", refused, False, f"S {S}, length {L}")
+    tab = table.to(dev)  # the one host-to-device copy of the call
+    images = _lib.empty(S, L, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().rtfs_reverb_f32(_lib.ptr(tab), _lib.ptr(images), S, L, _lib.stream_of(tab)), "rtfs_reverb_f32")
+    return images
+
+
+def _mix_reverb(sources, recipe, length, n_out, normalize, eps, rirs):
+    """``mix_batch`` with RIRs: two host plans (count the images, then write the one table), one upload, THREE launches
+    -> (mixture, out, stats, images (S, L), image_map (B, Jr) int64 on the host)."""
+    import numpy as np
+    slots, a, B, L, n_out, dev = _mix_slots(sources, recipe, length, n_out)
+    Jr = recipe.shape[1]
+    addr, taps = _check_rirs([] if rirs is None else rirs, dev, "mix_batch")
+    n = len(addr) - 1
+    if max(int(recipe.rir.max()), int(recipe.ref_rir.max())) >= n or min(int(recipe.rir.min()), int(recipe.ref_rir.min())) < -1:
+        raise ValueError(f"mix_batch: the recipe names an RIR outside [-1, {n})")
+    rr = np.zeros((B, MIX_MAX_SOURCES, MIX_RIR_WORDS), np.int64)
+    for w, (idx, off) in enumerate(((recipe.rir, recipe.rir_offset), (recipe.ref_rir, recipe.ref_offset))):
+        rr[:, :Jr, 3 * w], rr[:, :Jr, 3 * w + 1], rr[:, :Jr, 3 * w + 2] = addr[idx], taps[idx], off
+    lib = _lib.load()
+    S, ws, refused = C.c_int(0), C.c_size_t(0), (C.c_int * 2)(-1, 0)
+    args = (C.c_void_p(slots.ctypes.data), C.c_void_p(a.ctypes.data), C.c_void_p(rr.ctypes.data), B, min(max(L, -1), 1 << 30),
+            min(max(n_out, -1), 1 << 30))
+    if lib.rtfs_mix_reverb_plan(*args, 0, None, C.byref(S), C.byref(ws), refused) != 0:
+        raise _refused("mix_batch", refused, True, f"B {B}, length {L}, n_out {n_out}")
+    S, nbytes = int(S.value), int(ws.value)
+    images = _lib.empty(S, L, device=dev)
+    table = _lib.empty(S * REVERB_JOB_WORDS + B * MIX_MAX_SOURCES * MIX_TABLE_WORDS, device="cpu", dtype=torch.int64)
+    if lib.rtfs_mix_reverb_plan(*args, images.data_ptr() if S else 0, _lib.ptr(table), None, None, refused) != 0:
+        raise _refused("mix_batch", refused, True, f"B {B}, length {L}, n_out {n_out}")
+    tab = table.to(dev)  # the one host-to-device copy of the call
+    mixture = _lib.empty(B, L, device=dev)
+    out = _lib.empty(B, n_out, L, device=dev)
+    stats = _lib.empty(B, MIX_MAX_SOURCES + 2, device=dev, dtype=torch.float64)
+    work = _lib.workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.rtfs_mix_reverb_f32(_lib.ptr(tab), S, _lib.ptr(images) if S else None, _lib.ptr(mixture), _lib.ptr(out) if n_out else None,
+                                           _lib.ptr(stats), B, L, n_out, 1 if normalize else 0, float(eps), _lib.ptr(work), nbytes,
+                                           _lib.stream_of(tab)), "rtfs_mix_reverb_f32")
+    # which image row a slot reads: the address the plan put into the slot's table entry (host arithmetic on the host table)
+    seg = table[S * REVERB_JOB_WORDS:].numpy().reshape(B, MIX_MAX_SOURCES, MIX_TABLE_WORDS)[:, :Jr, 0]
+    image_map = np.where((recipe.rir >= 0) & (recipe.src >= 0), (seg - images.data_ptr()) // (4 * L), -1).astype(np.int64)
+    return mixture, out, stats, images, image_map
+
+
+def mix_batch(sources, recipe, length, n_out=None, normalize=False, eps=1e-8, return_stats=False, rirs=None, return_images=False):
     """Training mixtures formed on the device (``rtfs_mix_f32``; DESIGN.md "Training mixtures"): a host plan, one table upload and TWO
     launches, nothing read back.  ``sources``: a list of 1-D device tensors, float32 or int16 PCM (taken as s / 32768), of any lengths;
     views at any offset are read where they lie, nothing is copied.  ``recipe``: a ``MixRecipe`` (B, J).  Returns mixture (B, length) and
@@ -536,7 +688,16 @@ def mix_batch(sources, recipe, length, n_out=None, normalize=False, eps=1e-8, re
     [the four gains | the mixture's mean | 1 / (std + eps)] with ``return_stats``.  ``normalize``: the dataset's joint normalisation
     (``normalize_mixture``) in the same two launches.  There is no CPU fallback; what ``rtfs_mix_plan`` refuses (a segment that leaves
     its source, an empty row, length outside [1, 2^20], n_out outside [0, 4]) and sources that are not float32 / int16 device vectors
-    raise ValueError before anything is launched."""
+    raise ValueError before anything is launched.
+    Reverberant mixtures (DESIGN.md "Reverberant mixtures"): ``rirs``, a list of 1-D float32 device tensors that the recipe's ``rir`` /
+    ``ref_rir`` index.  Every distinct (source, start, RIR, offset) is convolved once (``rtfs_reverb_f32``, one more launch in front:
+    THREE in all, still one upload) and the mixture definition is applied to the images: gains, SNRs and normalisation are between
+    what the room makes of the sources; a slot without an RIR is read dry.  With ``rirs=None`` and a recipe without RIR indices the
+    call is the dry one, unchanged.  ``return_images``: also return the (S, length) image tensor and the (B, J) host array of each
+    slot's image row, -1 where the slot is dry."""
+    if rirs is not None or (isinstance(recipe, MixRecipe) and recipe.reverberant):
+        mixture, out, stats, images, image_map = _mix_reverb(sources, recipe, length, n_out, normalize, eps, rirs)
+        return (mixture, out) + ((stats,) if return_stats else ()) + ((images, image_map) if return_images else ())
     table, nbytes, B, n_out, dev = _mix_plan(sources, recipe, length, n_out)
     L, lib = int(length), _lib.load()
     tab = table.to(dev)  # the one host-to-device copy of the call
@@ -547,7 +708,56 @@ def mix_batch(sources, recipe, length, n_out=None, normalize=False, eps=1e-8, re
     with torch.cuda.device(dev):
         _lib.check(lib.rtfs_mix_f32(_lib.ptr(tab), _lib.ptr(mixture), _lib.ptr(out) if n_out else None, _lib.ptr(stats), B, L, n_out,
                                     1 if normalize else 0, float(eps), _lib.ptr(ws), nbytes, _lib.stream_of(tab)), "rtfs_mix_f32")
+    if return_images:
+        import numpy as np
+        return (mixture, out) + ((stats,) if return_stats else ()) + (_lib.empty(0, L, device=dev), np.full(recipe.shape, -1, np.int64))
     return (mixture, out, stats) if return_stats else (mixture, out)
+
+
+def load_rirs(rirs, device="cuda"):
+    """Room impulse responses for ``reverberate`` / ``mix_batch``: a list of 1-D float32 host arrays (numpy or torch, 1 .. 16384 taps)
+    -> (a list of device views into ONE allocation, uploaded with one copy, and the list of ``argmax |h|``, the direct-path sample of
+    each, for ``offset`` / ``rir_offsets``).  A host helper: run it once when the RIR set is loaded, not per batch."""
+    hs = []
+    for i, h in enumerate(rirs):
+        t = torch.as_tensor(h)
+        if t.ndim != 1 or t.dtype != torch.float32 or t.is_cuda or not 1 <= t.numel() <= REVERB_MAX_TAPS:
+            raise ValueError(f"load_rirs: RIR {i} must be a 1-D float32 host array of 1 .. {REVERB_MAX_TAPS} taps; got "
+                             f"{(tuple(t.shape), t.dtype, t.device)}")
+        hs.append(t)
+    if not hs:
+        raise ValueError("load_rirs: no RIRs")
+    flat = torch.cat(hs).to(device)
+    views, at = [], 0
+    for t in hs:
+        views.append(flat[at:at + t.numel()])
+        at += t.numel()
+    return views, [int(t.abs().argmax()) for t in hs]
+
+
+def synthetic_rir(n_taps, t60, sample_rate=16000, delay=0, drr_db=0.0, rng=None):
+    """A stand-in RIR for tests, the benchmark and ``tools/train_synthetic.py --reverb``; NOT a room simulation.  -> float32 numpy
+    array (n_taps): a unit direct path at sample ``delay`` plus, behind it, Gaussian noise under an exponential envelope that falls by
+    60 dB in ``t60`` seconds, scaled so that the direct-to-reverberant energy ratio is ``drr_db``.  ``rng``: a ``numpy.random.RandomState``
+    (default: seed 0).  The tail is scaled below the direct path where needed, so ``argmax |h|`` is ``delay``."""
+    import numpy as np
+    n_taps, delay = operator.index(n_taps), operator.index(delay)
+    if not 1 <= n_taps <= REVERB_MAX_TAPS or not 0 <= delay < n_taps or not float(t60) > 0 or not float(sample_rate) > 0:
+        raise ValueError(f"synthetic_rir: 1 <= n_taps <= {REVERB_MAX_TAPS}, 0 <= delay < n_taps, t60 > 0, sample_rate > 0")
+    rng = np.random.RandomState(0) if rng is None else rng
+    h = np.zeros(n_taps, np.float64)
+    n = n_taps - delay - 1
+    if n > 0:
+        tail = rng.randn(n) * np.exp(-3.0 * np.log(10.0) * np.arange(1, n + 1) / (float(t60) * float(sample_rate)))
+        e = float(tail @ tail)
+        if e > 0:
+            tail *= np.sqrt(10.0 ** (-float(drr_db) / 10.0) / e)
+            peak = float(np.abs(tail).max())
+            if peak > 0.99:
+                tail *= 0.99 / peak
+        h[delay + 1:] = tail
+    h[delay] = 1.0
+    return h.astype(np.float32)
 
 
 # ---------------------------------------------------------------- mouth-ROI transforms (src/datas/transform.py)

@@ -336,7 +336,7 @@ class System(nn.Module):
         return datas.mix_batch([targets.contiguous().reshape(-1)], recipe, L, n_out=n_src)
 
     def mix_batch(self, sources, mouth_rois, length=32000, n_src=2, snr_db=(-5.0, 5.0), normalize_audio=False, train=True, rng=None,
-                  recipe=None):
+                  recipe=None, rirs=None, rir_prob=1.0):
         """A fresh target-speaker training batch from a pool of utterances, formed on the device: sources = R 1-D device tensors
         (float32 or int16 PCM at 16 kHz), mouth_rois = their R uint8 ROI tracks (Tv_r,H,W) at 25 fps -> the reference-shaped batch
         (inputs (B,L), targets (B,L), target_mouths (B,1,Tv,88,88), keys) that ``common_step`` and ``optimization_step`` take as is.
@@ -345,14 +345,19 @@ class System(nn.Module):
         interferers at SNRs uniform in ``snr_db``.  Mixture and target come from ONE ``datas.mix_batch`` (``n_out`` 1;
         ``normalize_audio``: the dataset's joint normalisation in the same two
         launches).  The target's ROI track is sliced at start / 640 for length // 640 frames (ValueError if it is too short), the
-        slices are stacked and prepared by the ``"train"`` / ``"val"`` pipeline with the same ``rng``.  ``keys``: the target indices."""
+        slices are stacked and prepared by the ``"train"`` / ``"val"`` pipeline with the same ``rng``.  ``keys``: the target indices.
+        ``rirs``: device room impulse responses (``datas.load_rirs``) for reverberant mixtures (DESIGN.md "Reverberant mixtures"): a
+        drawn recipe gives every slot an RIR with probability ``rir_prob`` (offset 0: the room's delay stays in the audio), a given
+        ``recipe`` carries its own indices; the SNR holds between the images and the target returned is the target's image scaled as
+        slot 0, as in the dry call.  One more launch in front of the two."""
         from . import datas
         sources, mouth_rois = list(sources), list(mouth_rois)
         if len(mouth_rois) != len(sources):
             raise ValueError(f"System.mix_batch: {len(sources)} utterance(s) and {len(mouth_rois)} ROI track(s)")
         if recipe is None:
             B = int(self.config.get("training", {}).get("batch_size", 4))  # the yaml's training.batch_size
-            recipe = datas.draw_mix_recipe([int(s.shape[0]) for s in sources], B, length, n_src=n_src, snr_db=snr_db, align=640, rng=rng)
+            recipe = datas.draw_mix_recipe([int(s.shape[0]) for s in sources], B, length, n_src=n_src, snr_db=snr_db, align=640, rng=rng,
+                                           n_rirs=None if rirs is None else len(rirs), rir_prob=rir_prob)
         Tv = int(length) // 640
         keys = [int(t) for t in recipe.src[:, 0]]
         if Tv < 1:
@@ -367,7 +372,7 @@ class System(nn.Module):
                                  f"that starts at sample {int(recipe.start[b, 0])}; got "
                                  f"{(tuple(roi.shape), roi.dtype) if isinstance(roi, torch.Tensor) else type(roi).__name__}")
             tracks.append(roi[f0:f0 + Tv])
-        inputs, targets = datas.mix_batch(sources, recipe, length, n_out=1, normalize=normalize_audio)
+        inputs, targets = datas.mix_batch(sources, recipe, length, n_out=1, normalize=normalize_audio, rirs=rirs)
         lips = datas.get_preprocessing_pipelines()["train" if train else "val"](torch.stack(tracks), rng=rng)
         return inputs, targets[:, 0], lips, keys
 

@@ -30,6 +30,8 @@ def main():
                     "all-reduce on its flat buffer, clip + update in two launches)")
     ap.add_argument("--online-mix", action="store_true", help="every step's batch is formed on the device by System.mix_batch from a "
                     "synthetic pool of utterances and ROI tracks (target + one interferer at a drawn SNR and crop; needs the video model)")
+    ap.add_argument("--reverb", action="store_true", help="with --online-mix: every source is convolved with one of 8 synthetic room impulse "
+                    "responses of 4096 taps (datas.synthetic_rir, a stand-in, not a room simulation) before the mix")
     a = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -55,10 +57,15 @@ def main():
         secs = [3 + (9 * i) // 15 for i in range(16)]
         pool = [(0.05 * torch.randn(16000 * s, generator=g)).cuda() for s in secs]
         rois = [torch.randint(0, 256, (25 * s, 96, 96), generator=g, dtype=torch.uint8).cuda() for s in secs]
+        rirs = None
+        if a.reverb:
+            import numpy as np
+            nrng = np.random.RandomState(1234 + rank)
+            rirs, _ = R.datas.load_rirs([R.datas.synthetic_rir(4096, 0.2 + 0.05 * i, delay=16, rng=nrng) for i in range(8)])
     t0 = time.time()
     for step in range(a.steps):
         if a.online_mix:
-            value = system.optimization_step(system.mix_batch(pool, rois, length=L - L % 640, rng=rng), step)
+            value = system.optimization_step(system.mix_batch(pool, rois, length=L - L % 640, rng=rng, rirs=rirs), step)
             if rank == 0 and (step % 5 == 0 or step == a.steps - 1):
                 torch.cuda.synchronize()
                 print(f"step {step:4d}  loss {float(value):8.4f}  {(time.time() - t0) / (step + 1) * 1e3:7.1f} ms/step  world {world}  "
