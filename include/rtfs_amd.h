@@ -1246,6 +1246,72 @@ int rtfs_mix_reverb_plan(const long long* slots, const double* a, const long lon
 int rtfs_mix_reverb_f32(const long long* table, int n_images, float* images, float* mixture, float* sources, double* stats, int B, int L,
                         int n_out, int normalize, double eps, void* ws, size_t ws_bytes, void* stream);
 
+/* Loudness (datas.loudness / loudness_many / loudness_normalize, MixRecipe.lufs, System.mix_batch(loudness=...); DESIGN.md "Loudness";
+ * csrc/k_loudness.hip, csrc/loudness.h): ITU-R BS.1770 integrated loudness of mono recordings, float64 throughout.
+ * Sample rate: fs an integer, RTFS_LOUD_MIN_RATE = 8000 <= fs <= RTFS_LOUD_MAX_RATE = 192000, fs % 10 == 0.  H = fs / 10 is one hop
+ *   of 100 ms, a block is 4 H samples.
+ * Input: float32 at any 4-byte alignment, or int16 PCM at any 2-byte alignment entering as (float)s / 32768; read where it lies.
+ * K-weighting: two biquads in series with zero initial state; coefficients from the design formulas in float64 on the host
+ *   (csrc/loudness.h, the single place):
+ *   shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196;  K = tan(pi f0 / fs), Vh = 10^(G/20),
+ *              Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2;  b = [Vh + Vb K/Q + K^2, 2 (K^2 - Vh), Vh - Vb K/Q + K^2] / a0,
+ *              a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0]
+ *   high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773;  b = [1, -2, 1], a formed as above from its own K.
+ *   At 48 kHz these are the standard's table (shelf b 1.53512485958697, -2.69169618940638, 1.19839281085285, a -1.69065929318241,
+ *   0.73248077421585; high-pass a -1.99004745483398, 0.99007225036621).
+ * Hop and block energies: with y the filtered signal of a recording of L samples, E_h = sum of y[n]^2 over n in [h H, (h + 1) H) for
+ *   h < floor(L / H); the L mod H samples behind the last whole hop are never read.  Block j has
+ *   z_j = (E_j + E_{j+1} + E_{j+2} + E_{j+3}) / (4 H) for j < nb = floor(L / H) - 3: complete blocks only, as the standard says
+ *   (pyloudnorm rounds the block count instead; agreement with that package is not measured).
+ * Gates, applied to z (no logarithm decides a gate): absolute z_j > 10^((-70 + 0.691) / 10); relative z_j > 0.1 x the mean of z over
+ *   the absolutely gated blocks.  lufs = -0.691 + 10 log10(mean of z over the blocks passing both), kept = the number of such blocks.
+ *   No surviving block: lufs = -inf, kept = 0.  Any non-finite z_j: lufs = NaN (kept = 0).
+ * The cascade is the linear system s' = A s + B x, y = C s + D x over the four states of two transposed direct form II biquads.  A
+ *   wave takes a hop and gives lane l the piece [min(l p, H), min((l + 1) p, H)), p = ceil(H / RTFS_LOUD_LANES); every lane runs its
+ *   piece from zero state, the piece end states are combined across the lanes with A^p (A^(H mod p) behind the one ragged piece), the
+ *   hop end states along the recording with A^H in a per-recording scan, and a second sweep over the samples accumulates the
+ *   energies from the true start states.  The powers are multiplied out on the host in long double and rounded once.
+ * rtfs_loudness_design (host only): the eight doubles [shelf b0 b1 b2 a1 a2 | high-pass a1 a2 | the absolute gate] for fs; -4 for a
+ *   rate the definition does not cover.
+ * rtfs_loudness_plan (host only, no device call): recs = R records of RTFS_LOUD_RECORD_WORDS = 3 int64 words [address | length in
+ *   samples | dtype RTFS_MIX_F32 / RTFS_MIX_I16] -> *ws_bytes, totals[4] = [hops | blocks | samples | gain chunks] of the pool and,
+ *   when table is not NULL, the RTFS_LOUD_HEADER_WORDS + R * RTFS_LOUD_TABLE_WORDS int64 words the launches read FROM DEVICE MEMORY
+ *   (one upload): the header [fs | H | p | R | hops | blocks | samples | chunks | the eight doubles of rtfs_loudness_design | A^p |
+ *   A^(H mod p) | A^H, row-major], then per recording [address | L | is int16 | hops | first hop | first sample | first gain chunk |
+ *   first block], the last four being the recording's offsets in the flat work lists and buffers.  Refusals return -4, write nothing
+ *   else and name themselves in refused[2] = [recording or -1 | RTFS_LOUD_* reason]: R < 1, a missing array, a work list past
+ *   2^31 - 1 (BAD_ARGUMENT, -1); a rate outside the definition (BAD_RATE, -1); per recording in this order a null address
+ *   (BAD_ARGUMENT), an unknown dtype (BAD_DTYPE), an address misaligned for its dtype (MISALIGNED), L < 4 H (TOO_SHORT),
+ *   L > RTFS_LOUD_MAX_LENGTH = 2^26 (TOO_LONG).  table, ws_bytes, totals, refused may be NULL.
+ * rtfs_loudness_f32 (FOUR launches): out (R, 2) float64 = [lufs | kept]; z, if not NULL, the flat float64 buffer of totals[1] block
+ *   energies, recording r at its first-block offset.  Flat work lists over (recording, hop), one wave each, for the two sweeps; one
+ *   thread per recording for the scan; one workgroup per recording for the gates.  host_table: the host copy of the table, of which
+ *   only the header's sizes are read.  table, out, z, ws 8-byte aligned (-4); ws_bytes below the plan's: -2; a header no plan
+ *   writes: -1; all before any launch.  Caller's stream, no allocation, nothing read back, no atomics, fixed reduction orders: the
+ *   same inputs give the same bits, and entry r of a pool is bit-equal to recording r measured alone.
+ * rtfs_loudness_gain_f32 (one launch): out, flat float32 of totals[2] samples, recording r at its first-sample offset:
+ *   out = (float)(x g) with g = 10^((target - lufs) / 20) formed on the device in float64 from loud (R, 2) as rtfs_loudness_f32 wrote
+ *   it, g = 1 where lufs is not finite; stats (R) float64 = g.  One workgroup per (recording, chunk of RTFS_LOUD_CHUNK samples). */
+#define RTFS_LOUD_LANES 64
+#define RTFS_LOUD_CHUNK 4096
+#define RTFS_LOUD_MAX_LENGTH (1 << 26)
+#define RTFS_LOUD_MIN_RATE 8000
+#define RTFS_LOUD_MAX_RATE 192000
+#define RTFS_LOUD_RECORD_WORDS 3
+#define RTFS_LOUD_HEADER_WORDS 64
+#define RTFS_LOUD_TABLE_WORDS 8
+#define RTFS_LOUD_BAD_ARGUMENT 1
+#define RTFS_LOUD_BAD_RATE 2
+#define RTFS_LOUD_TOO_SHORT 3
+#define RTFS_LOUD_TOO_LONG 4
+#define RTFS_LOUD_MISALIGNED 5
+#define RTFS_LOUD_BAD_DTYPE 6
+int rtfs_loudness_design(int fs, double* coef);
+int rtfs_loudness_plan(const long long* recs, int R, int fs, long long* table, size_t* ws_bytes, long long* totals, int* refused);
+int rtfs_loudness_f32(const long long* table, const long long* host_table, double* out, double* z, void* ws, size_t ws_bytes, void* stream);
+int rtfs_loudness_gain_f32(const long long* table, const long long* host_table, const double* loud, double target, float* out, double* stats,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,10 @@ SIGNATURES = {
     "rtfs_reverb_f32": (_i, [_p, _p, _i, _i, _p]),
     "rtfs_mix_reverb_plan": (_i, [_p, _p, _p, _i, _i, _i, C.c_longlong, _p, C.POINTER(_i), C.POINTER(C.c_size_t), _p]),
     "rtfs_mix_reverb_f32": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, C.c_double, _p, _z, _p]),
+    "rtfs_loudness_design": (_i, [_i, _p]),
+    "rtfs_loudness_plan": (_i, [_p, _i, _i, _p, C.POINTER(C.c_size_t), _p, _p]),
+    "rtfs_loudness_f32": (_i, [_p, _p, _p, _p, _p, _z, _p]),
+    "rtfs_loudness_gain_f32": (_i, [_p, _p, _p, C.c_double, _p, _p, _p]),
 }
 
 _lib = None

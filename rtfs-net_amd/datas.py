@@ -12,6 +12,8 @@
 * ``reverberate`` / ``load_rirs`` / ``synthetic_rir``   reverberant training mixtures: every source convolved with its own room impulse
                                      response on the device (``csrc/k_reverb.hip``), alone or in front of the two mix launches
                                      (``mix_batch(..., rirs=...)``)
+* ``loudness`` / ``loudness_many`` / ``loudness_normalize`` / ``MixRecipe.lufs``   ITU-R BS.1770 integrated loudness on the device
+                                     (K-weighting, 400 ms blocks, two gates; ``csrc/k_loudness.hip``) and levels set by it
 
 All arithmetic runs in ``librtfs_amd.so`` (``csrc/k_prep.hip``); there is no host fallback.  ``tests/prep_oracle.py`` restates the three
 in float64 numpy."""
@@ -29,7 +31,7 @@ from . import _lib
 __all__ = ["Compose", "Normalize", "CenterCrop", "RandomCrop", "HorizontalFlip", "get_preprocessing_pipelines", "resample",
            "normalize_tensor_wav", "normalize_mixture", "resample_plan", "resample_bank", "open_resample_streams", "frame_rate_of", "frame_rate_map",
            "timestamp_map", "mouth_affine", "mouth_rois", "MixRecipe", "draw_mix_recipe", "mix_batch", "reverberate", "load_rirs",
-           "synthetic_rir"]
+           "synthetic_rir", "loudness", "loudness_many", "loudness_normalize"]
 
 CROP = 88
 MAX_RATIO = 640
@@ -500,8 +502,47 @@ class MixRecipe:
         ref_rir = np.where(ref >= 0, rr[:, :1], -1)
         return cls(src, s, a, ref, ref_start, rr, ref_rir, oo, np.where(ref_rir >= 0, oo[:, :1], 0))
 
+    @classmethod
+    def lufs(cls, srcs, starts, target_lufs, utter_lufs, rirs=None, offsets=None):
+        """Levels by loudness (DESIGN.md "Loudness"): srcs (B, J) source indices (-1: an empty slot), starts (B, J), target_lufs a
+        scalar, (B) or (B, J), utter_lufs a host sequence with the integrated loudness of every WHOLE utterance (``loudness_many``,
+        measured once per dataset).  Every slot has the fixed gain a = 10^((target - utter_lufs[src]) / 20) and no reference segment:
+        the level does not move with the crop.  ``rirs`` / ``offsets`` (B, J) as in ``snr``; the level is that of the dry utterance.
+        ValueError naming the source for an utterance whose loudness is not finite (silence reads -inf)."""
+        import numpy as np
+        try:
+            src = np.array(srcs, dtype=np.int64)
+            s = np.array(starts, dtype=np.int64)
+            tg = np.array(target_lufs, dtype=np.float64)
+            tg = np.broadcast_to(tg[:, None] if tg.ndim == 1 else tg, src.shape)
+            ul = np.array(utter_lufs, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("MixRecipe.lufs: srcs and starts (B, J), target_lufs a scalar, (B) or (B, J), utter_lufs one value per source") from None
+        if src.ndim != 2 or s.shape != src.shape:
+            raise ValueError(f"MixRecipe.lufs: srcs and starts must be one shape (B, J); got {src.shape}, {s.shape}")
+        if src.size and (src.max() >= ul.shape[0] or src.min() < -1):
+            raise ValueError(f"MixRecipe.lufs: srcs names a source outside [-1, {ul.shape[0]})")
+        for i in np.unique(src[src >= 0]):
+            if not np.isfinite(ul[i]):
+                raise ValueError(f"MixRecipe.lufs: source {int(i)} has loudness {ul[i]}; a level by loudness needs a finite one")
+        if not np.isfinite(tg[src >= 0]).all():
+            raise ValueError("MixRecipe.lufs: target_lufs must be finite")
+        a = np.where(src >= 0, 10.0 ** ((tg - ul[np.maximum(src, 0)]) / 20.0), 0.0)
+        if rirs is None and offsets is None:
+            return cls(src, s, a)
+        try:
+            rr = np.full(src.shape, -1, np.int64) if rirs is None else np.array(rirs, dtype=np.int64).reshape(src.shape[0], -1)
+            oo = np.zeros(src.shape, np.int64) if offsets is None else np.array(offsets, dtype=np.int64).reshape(src.shape[0], -1)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError("MixRecipe.lufs: rirs and offsets are integer arrays (B, J)") from None
+        if rr.shape != src.shape or oo.shape != src.shape:
+            raise ValueError(f"MixRecipe.lufs: rirs and offsets must be {src.shape}; got {rr.shape}, {oo.shape}")
+        rr = np.where(src >= 0, rr, -1)
+        return cls(src, s, a, rir=rr, rir_offset=np.where(rr >= 0, oo, 0))
 
-def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1, rng=None, n_rirs=None, rir_prob=1.0, rir_offsets=None):
+
+def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1, rng=None, n_rirs=None, rir_prob=1.0, rir_offsets=None,
+                    loudness=None, utter_lufs=None):
     """A drawn target-speaker recipe (``MixRecipe.snr``) for ``batch`` rows of ``length`` samples out of utterances of ``lengths``
     samples: per row ``n_src`` distinct utterances (the first is the target), per utterance a uniform start that is a multiple of
     ``align``, per interferer a uniform SNR in ``snr_db`` = (low, high).  Draws come from ``rng`` (a ``random.Random``) or the ``random``
@@ -509,8 +550,18 @@ def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1
     than ``n_src`` are long enough.
     ``n_rirs``: additionally draw, per row after that row's SNRs and per slot, ``rng.random() < rir_prob`` and, if so, an RIR index
     ``rng.randrange(n_rirs)`` (otherwise the slot stays dry); ``rir_offsets``: the alignment sample of every RIR (``load_rirs``'s second
-    result; default 0).  Without ``n_rirs`` nothing more is drawn: a seed gives the dry recipe it always gave."""
+    result; default 0).  Without ``n_rirs`` nothing more is drawn: a seed gives the dry recipe it always gave.
+    ``loudness`` = (low, high) with ``utter_lufs`` (the loudness of every whole utterance, ``loudness_many``): levels by loudness
+    (``MixRecipe.lufs``) instead of SNRs: in place of the row's SNRs a uniform target in LUFS is drawn per slot, the target speaker's
+    included (``n_src`` draws where the SNR form makes ``n_src - 1``).  Without it the draws are the ones above, unchanged."""
     r = random if rng is None else rng
+    if (loudness is None) != (utter_lufs is None):
+        raise ValueError("draw_mix_recipe: loudness=(low, high) and utter_lufs go together")
+    if loudness is not None:
+        llo, lhi = (float(v) for v in loudness)
+        utter_lufs = [float(v) for v in utter_lufs]
+        if len(utter_lufs) != len(lengths):
+            raise ValueError(f"draw_mix_recipe: {len(utter_lufs)} loudness value(s) for {len(lengths)} utterance(s)")
     batch, length, n_src, align = operator.index(batch), operator.index(length), operator.index(n_src), operator.index(align)
     lengths = [operator.index(n) for n in lengths]
     lo, hi = (float(v) for v in snr_db)
@@ -529,9 +580,13 @@ def draw_mix_recipe(lengths, batch, length, n_src=2, snr_db=(-5.0, 5.0), align=1
         row = r.sample(pool, n_src)
         rows.append(row)
         starts.append([align * r.randint(0, (lengths[i] - length) // align) for i in row])
-        dbs.append([r.uniform(lo, hi) for _ in row[1:]])
+        dbs.append([r.uniform(lo, hi) for _ in row[1:]] if loudness is None else [r.uniform(llo, lhi) for _ in row])
         if n_rirs is not None:
             rirs.append([r.randrange(n_rirs) if r.random() < rir_prob else -1 for _ in row])
+    if loudness is not None:
+        if n_rirs is None:
+            return MixRecipe.lufs(rows, starts, dbs, utter_lufs)
+        return MixRecipe.lufs(rows, starts, dbs, utter_lufs, rirs=rirs, offsets=[[rir_offsets[i] if i >= 0 else 0 for i in row] for row in rirs])
     if n_rirs is None:
         return MixRecipe.snr([row[0] for row in rows], [row[1:] for row in rows], starts, dbs)
     return MixRecipe.snr([row[0] for row in rows], [row[1:] for row in rows], starts, dbs, rirs=rirs,
@@ -758,6 +813,107 @@ def synthetic_rir(n_taps, t60, sample_rate=16000, delay=0, drr_db=0.0, rng=None)
         h[delay + 1:] = tail
     h[delay] = 1.0
     return h.astype(np.float32)
+
+
+# ---------------------------------------------------------------- loudness (DESIGN.md "Loudness")
+LOUD_MAX_LENGTH, LOUD_MIN_RATE, LOUD_MAX_RATE = 1 << 26, 8000, 192000  # RTFS_LOUD_MAX_LENGTH, RTFS_LOUD_MIN_RATE, RTFS_LOUD_MAX_RATE
+LOUD_RECORD_WORDS, LOUD_HEADER_WORDS, LOUD_TABLE_WORDS = 3, 64, 8      # RTFS_LOUD_RECORD_WORDS, RTFS_LOUD_HEADER_WORDS, RTFS_LOUD_TABLE_WORDS
+LOUD_REASONS = {1: "a bad argument", 2: f"a sample rate outside [{LOUD_MIN_RATE}, {LOUD_MAX_RATE}] or no multiple of 10",
+                3: "a recording shorter than one 400 ms block", 4: f"a recording longer than {LOUD_MAX_LENGTH} samples",
+                5: "an address that is misaligned for its dtype", 6: "an unknown dtype"}
+
+
+def _loud_plan(wavs, sample_rate, who):
+    """Everything of a loudness call that needs no launch: checks the recordings and runs the host planner
+    -> (host table int64, (hops, blocks, samples, chunks), workspace bytes, lengths, device)."""
+    import numpy as np
+    wavs = list(wavs)
+    device = None
+    for i, w in enumerate(wavs):
+        if not isinstance(w, torch.Tensor) or not w.is_cuda or w.ndim != 1 or w.dtype not in (torch.float32, torch.int16) or \
+                (w.numel() > 1 and w.stride(0) != 1):
+            raise ValueError(f"{who}: recording {i} must be a 1-D float32 or int16 tensor on the device with adjacent samples (there is no "
+                             f"CPU fallback); got {(tuple(w.shape), w.dtype, w.device) if isinstance(w, torch.Tensor) else type(w).__name__}")
+        device = w.device if device is None else device
+        if w.device != device:
+            raise ValueError(f"{who}: recording {i} lies on {w.device}, recording 0 on {device}")
+    if not wavs:
+        raise ValueError(f"{who}: no recordings")
+    fs = operator.index(sample_rate)
+    R = len(wavs)
+    recs = np.array([[w.data_ptr(), w.numel(), 1 if w.dtype == torch.int16 else 0] for w in wavs], dtype=np.int64)
+    table = _lib.empty(LOUD_HEADER_WORDS + R * LOUD_TABLE_WORDS, device="cpu", dtype=torch.int64)  # host table, every word written by the plan
+    ws, totals, refused = C.c_size_t(0), (C.c_longlong * 4)(), (C.c_int * 2)(-1, 0)
+    if _lib.load().rtfs_loudness_plan(C.c_void_p(recs.ctypes.data), R, min(max(fs, -1), 1 << 30), _lib.ptr(table), C.byref(ws), totals, refused) != 0:
+        where = "" if refused[0] < 0 else f" at recording {refused[0]} ({int(recs[refused[0], 1])} samples)"
+        raise ValueError(f"{who}: {LOUD_REASONS.get(refused[1], 'refused')}{where} (R {R}, sample_rate {fs})")
+    return table, tuple(int(v) for v in totals), int(ws.value), [int(n) for n in recs[:, 1]], device
+
+
+def _loud_measure(table, tab, totals, nbytes, dev, blocks):
+    """The four launches -> (out (R, 2) float64 [lufs | kept], z flat float64 or None)."""
+    R = (int(table.numel()) - LOUD_HEADER_WORDS) // LOUD_TABLE_WORDS
+    out = _lib.empty(R, 2, device=dev, dtype=torch.float64)
+    z = _lib.empty(totals[1], device=dev, dtype=torch.float64) if blocks else None
+    ws = _lib.workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().rtfs_loudness_f32(_lib.ptr(tab), _lib.ptr(table), _lib.ptr(out), _lib.ptr(z), _lib.ptr(ws), nbytes,
+                                                 _lib.stream_of(tab)), "rtfs_loudness_f32")
+    return out, z
+
+
+def loudness_many(wavs, sample_rate, return_kept=False, return_blocks=False):
+    """ITU-R BS.1770 integrated loudness of R mono recordings of different lengths in ONE pooled call (``rtfs_loudness_f32``; DESIGN.md
+    "Loudness"): a host plan, one table upload and FOUR launches, nothing read back.  ``wavs``: 1-D device tensors, float32 or int16 PCM
+    (taken as s / 32768), views at any offset read where they lie; ``sample_rate``: an integer in [8000, 192000] that 10 divides.
+    Returns lufs (R,) float64 on the device; with ``return_kept`` also the (R,) int64 count of blocks that passed both gates, with
+    ``return_blocks`` also a list of R float64 views, the mean squares z of every recording's 400 ms blocks.  Silence (no block
+    passes) reads -inf, a non-finite sample NaN.  Entry r is bit-equal to recording r measured alone.  There is no CPU fallback;
+    what ``rtfs_loudness_plan`` refuses (a recording under 400 ms or over 2^26 samples, a rate outside the definition) raises
+    ValueError before anything is launched.  Agreement with pyloudnorm or torchaudio is not measured (neither is a dependency; they
+    round the block count where this counts complete blocks)."""
+    table, totals, nbytes, lengths, dev = _loud_plan(wavs, sample_rate, "loudness_many")
+    tab = table.to(dev)  # the one host-to-device copy of the call
+    out, z = _loud_measure(table, tab, totals, nbytes, dev, return_blocks)
+    res = (out[:, 0],)
+    if return_kept:
+        res += (out[:, 1].to(torch.int64),)
+    if return_blocks:
+        H = int(sample_rate) // 10
+        res += (list(z.split([n // H - 3 for n in lengths])),)
+    return res[0] if len(res) == 1 else res
+
+
+def _loud_rows(wav, who):
+    if not isinstance(wav, torch.Tensor) or wav.ndim not in (1, 2) or (wav.ndim == 2 and wav.shape[0] < 1):
+        raise ValueError(f"{who}: wav must be a tensor (L) or (B,L); got {tuple(wav.shape) if isinstance(wav, torch.Tensor) else type(wav).__name__}")
+    return [wav] if wav.ndim == 1 else list(wav.unbind(0))
+
+
+def loudness(wav, sample_rate):
+    """Integrated loudness of wav (L) | (B,L), float32 or int16 on the device -> (B,) float64 on the device ((1,) for (L)); the rows
+    are the recordings of one ``loudness_many`` call."""
+    return loudness_many(_loud_rows(wav, "loudness"), sample_rate)
+
+
+def loudness_normalize(wav, sample_rate, target=-23.0, return_stats=False):
+    """Scale recordings to ``target`` LUFS on the device: the four launches of ``loudness_many`` and ONE more
+    (``rtfs_loudness_gain_f32``), out = (float)(x g) with g = 10^((target - lufs) / 20) formed on the device in float64 from the
+    device's own lufs: no readback.  ``wav``: a tensor (L) | (B,L) -> a float32 tensor of that shape, or a sequence of 1-D tensors
+    of different lengths -> a list of float32 views of one allocation.  A recording whose loudness is not finite (silence, a
+    non-finite sample) is copied with g = 1.  ``return_stats``: also (lufs (R,), g (R,)) float64 on the device."""
+    single = isinstance(wav, torch.Tensor)
+    rows = _loud_rows(wav, "loudness_normalize") if single else list(wav)
+    table, totals, nbytes, lengths, dev = _loud_plan(rows, sample_rate, "loudness_normalize")
+    tab = table.to(dev)  # the one host-to-device copy of the call
+    loud, _ = _loud_measure(table, tab, totals, nbytes, dev, False)
+    flat = _lib.empty(totals[2], device=dev)
+    g = _lib.empty(len(rows), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().rtfs_loudness_gain_f32(_lib.ptr(tab), _lib.ptr(table), _lib.ptr(loud), float(target), _lib.ptr(flat), _lib.ptr(g),
+                                                      _lib.stream_of(tab)), "rtfs_loudness_gain_f32")
+    out = flat.view(wav.shape) if single else list(flat.split(lengths))
+    return (out, (loud[:, 0], g)) if return_stats else out
 
 
 # ---------------------------------------------------------------- mouth-ROI transforms (src/datas/transform.py)

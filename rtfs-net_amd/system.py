@@ -336,7 +336,7 @@ class System(nn.Module):
         return datas.mix_batch([targets.contiguous().reshape(-1)], recipe, L, n_out=n_src)
 
     def mix_batch(self, sources, mouth_rois, length=32000, n_src=2, snr_db=(-5.0, 5.0), normalize_audio=False, train=True, rng=None,
-                  recipe=None, rirs=None, rir_prob=1.0):
+                  recipe=None, rirs=None, rir_prob=1.0, loudness=None, utter_lufs=None):
         """A fresh target-speaker training batch from a pool of utterances, formed on the device: sources = R 1-D device tensors
         (float32 or int16 PCM at 16 kHz), mouth_rois = their R uint8 ROI tracks (Tv_r,H,W) at 25 fps -> the reference-shaped batch
         (inputs (B,L), targets (B,L), target_mouths (B,1,Tv,88,88), keys) that ``common_step`` and ``optimization_step`` take as is.
@@ -349,7 +349,11 @@ class System(nn.Module):
         ``rirs``: device room impulse responses (``datas.load_rirs``) for reverberant mixtures (DESIGN.md "Reverberant mixtures"): a
         drawn recipe gives every slot an RIR with probability ``rir_prob`` (offset 0: the room's delay stays in the audio), a given
         ``recipe`` carries its own indices; the SNR holds between the images and the target returned is the target's image scaled as
-        slot 0, as in the dry call.  One more launch in front of the two."""
+        slot 0, as in the dry call.  One more launch in front of the two.
+        ``loudness`` = (low, high) with ``utter_lufs`` (the integrated loudness of every whole utterance, measured once per dataset with
+        ``datas.loudness_many``; a host sequence): a drawn recipe sets every slot to a target in LUFS uniform in ``loudness`` with the
+        fixed gain 10^((target - utter_lufs) / 20) instead of an SNR (``datas.MixRecipe.lufs``; DESIGN.md "Loudness"); with RIRs the
+        level is that of the dry utterance.  Without the two arguments the call draws and returns what it always did."""
         from . import datas
         sources, mouth_rois = list(sources), list(mouth_rois)
         if len(mouth_rois) != len(sources):
@@ -357,7 +361,8 @@ class System(nn.Module):
         if recipe is None:
             B = int(self.config.get("training", {}).get("batch_size", 4))  # the yaml's training.batch_size
             recipe = datas.draw_mix_recipe([int(s.shape[0]) for s in sources], B, length, n_src=n_src, snr_db=snr_db, align=640, rng=rng,
-                                           n_rirs=None if rirs is None else len(rirs), rir_prob=rir_prob)
+                                           n_rirs=None if rirs is None else len(rirs), rir_prob=rir_prob, loudness=loudness,
+                                           utter_lufs=utter_lufs)
         Tv = int(length) // 640
         keys = [int(t) for t in recipe.src[:, 0]]
         if Tv < 1:
